@@ -2,7 +2,7 @@
 """Headline benchmark: utterances/sec, FastGRNN forward+backward, T=99 feat=32
 hidden=128, bs=4096 per GPU (BASELINE.json `metric`), fp32, synthetic MFCC frames.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 is launched by the driver with torch.distributed.run (one rank per GPU, RCCL);
 batch shards data-parallel (weak scaling: 4096 utterances per GPU) and the parameter
@@ -19,6 +19,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -183,15 +184,20 @@ def extra_configs(dev, B):
     return res
 
 
-def make_step(model, x, G, params, bucket, ar_events=None, sample_allreduce=lambda: False):
+def make_step(model, x, G, params, bucket, ar_events=None, sample_allreduce=lambda: False, keep=None):
     """The benchmark's step: zero the gradients, module forward over [T,B,F], backward with the dense grad_hs, and -- data
     parallel -- ONE all-reduce of the flat gradient bucket (kws_amd.dp.GradBucket).  `ar_events` collects (start, end)
-    events around the collective on the steps for which `sample_allreduce()` says so.  (A function of its own so that
-    tests/test_dp_gloo.py can run exactly this on CPU over gloo.)"""
+    events around the collective on the steps for which `sample_allreduce()` says so.  A dict `keep` receives the
+    step's hs, detached, as keep["hs"] (--dump-outputs).  (A function of its own so that tests/test_dp_gloo.py can
+    run exactly this on CPU over gloo.)"""
     def step():
         for p in params:
             p.grad = None
         hs = model(x)
+        if keep is not None:
+            # detached: a kept grad_fn holds the step's AccumulateGrad nodes alive into GraphedStep's side-stream
+            # warmup and capture, where backward meets them on the wrong stream (torch warns; the run segfaulted)
+            keep["hs"] = hs.detach()
         hs.backward(G)                            # L = sum(hs*G): dL/dhs = G
         if bucket is not None:
             if ar_events is not None and sample_allreduce():
@@ -203,6 +209,21 @@ def make_step(model, x, G, params, bucket, ar_events=None, sample_allreduce=lamb
             else:
                 bucket.all_reduce_()
     return step
+
+
+DUMP_HS_UTTERANCES, DUMP_SEED = 768, 2024     # hs sample: [T, 768, H] fp32 = 38.9 MB of the 64 MB a dump may hold
+
+
+def snapshot_outputs(hs, model):
+    """What the step hands its caller, copied on the device right after the timed region: hs for a fixed, seeded
+    sample of DUMP_HS_UTTERANCES utterances (whole sequences; the same batch indices on every run with the same
+    --batch) and every parameter gradient, as fp32."""
+    B = hs.shape[1]
+    idx = torch.randperm(B, generator=torch.Generator().manual_seed(DUMP_SEED))[:min(B, DUMP_HS_UTTERANCES)]
+    out = {"hs_sample": hs.index_select(1, idx.sort().values.to(hs.device)).float()}
+    for n, p in model.named_parameters():
+        out["grad_" + n] = p.grad.detach().float().clone()
+    return out
 
 
 def agree_on_count(n, world, device):
@@ -234,7 +255,12 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-extra-configs", action="store_true",
                     help="skip the other BASELINE configurations (fwd-only, bf16, low-rank, 2-layer stack) at N=1")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, "
+                         "fp32: hs_sample [T, 768, H] (a fixed, seeded sample of the batch) and grad_<parameter>")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -261,7 +287,9 @@ def main():
     bucket = GradBucket(params, world) if world > 1 else None
 
     ar_events = []                                # (start, end) around the gradient all-reduce, every fourth step
-    step = make_step(model, x, G, params, bucket, ar_events, lambda: fastgrnn_cuda._timing is not None)
+    dump = args.dump_outputs and rank == 0
+    kept = {} if dump else None
+    step = make_step(model, x, G, params, bucket, ar_events, lambda: fastgrnn_cuda._timing is not None, kept)
 
     eager_step = step
     if args.graph:
@@ -314,6 +342,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     timing, fastgrnn_cuda._timing = samples, None
+    outputs = snapshot_outputs(kept["hs"], model) if dump else None
     if args.graph:                  # events cannot be recorded inside a replay: sample the kernel durations on eager steps
         torch.cuda.synchronize()
         for i in range(8):
@@ -473,6 +502,11 @@ def main():
                                            "sample": "B=64 (BASELINE config 1, README.md:54), same step"},
                                    "b64_one_thread": {"value": r1["utt_per_s"], "cores": 1, "iters": r1["iters"]}}
             out["speedup_vs_cpu"] = value / r["utt_per_s"]
+        if outputs is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, t in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy())
+            print("[bench] wrote %s to %s" % (", ".join(sorted(outputs)), args.dump_outputs), file=sys.stderr, flush=True)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -247,6 +247,37 @@ def _worker_bench_step(rank, world, port, q):
         dist.destroy_process_group()
 
 
+def test_bench_dump_snapshot_is_the_last_step_and_a_fixed_sample():
+    """bench.py --dump-outputs: make_step hands its hs to `keep`, snapshot_outputs takes the same seeded utterances of
+    it on every call plus every parameter gradient, fp32; at the benchmark's own shape the dump stays under 64 MB."""
+    sys.path.insert(0, ROOT)
+    import bench
+    T, B, F, H = 7, 1000, 5, 12
+    torch.manual_seed(0)
+    model = _PortModule(F, H)
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(T, B, F, generator=g)
+    G = torch.randn(T, B, H, generator=g)
+    params = list(model.parameters())
+    kept = {}
+    step = bench.make_step(model, x, G, params, None, keep=kept)
+    step()
+    hs = kept["hs"]
+    assert hs.grad_fn is None              # the step's autograd graph is not kept alive past its backward
+    assert torch.equal(hs, model(x))
+    a, b = bench.snapshot_outputs(hs, model), bench.snapshot_outputs(hs, model)
+    assert sorted(a) == sorted(["hs_sample"] + ["grad_" + n for n, _ in model.named_parameters()])
+    assert all(v.dtype == torch.float32 and torch.equal(v, b[k]) for k, v in a.items())
+    assert a["hs_sample"].shape == (T, bench.DUMP_HS_UTTERANCES, H)
+    cols = [next(j for j in range(B) if torch.equal(hs[:, j], a["hs_sample"][:, i])) for i in range(0, 768, 97)]
+    assert cols == sorted(set(cols))
+    for n, p in model.named_parameters():
+        assert torch.equal(a["grad_" + n], p.grad)
+    assert bench.snapshot_outputs(hs[:, :10], model)["hs_sample"].shape == (T, 10, H)
+    n_grads = bench.F * bench.H + bench.H * bench.H + 2 * bench.H + 2
+    assert 4 * (bench.T * bench.DUMP_HS_UTTERANCES * bench.H + n_grads) <= 64 * 2 ** 20
+
+
 def test_bench_step_over_gloo_equals_the_single_process_average_bit_for_bit():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
