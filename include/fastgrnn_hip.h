@@ -110,6 +110,14 @@ typedef enum fastgrnn_nonlinearity {
  * FASTGRNN_ERR_UNSUPPORTED otherwise. */
 #define FASTGRNN_FLAG_GRAD_LAST 256u
 #define FASTGRNN_FLAG_HS_LAST 512u
+/* Eval-mode BatchNorm cell (the reference's FastGRNNBatchNorm, rnn.py:316-452, with its running statistics): a
+ * per-unit scale of the pre-activation in front of each nonlinearity,
+ *   z = gate(gate_scale . pre + bias_gate),  h' = update(update_scale . pre + bias_update),  pre = w.x + u.h
+ * (elementwise scales, the four BatchNorm1d layers folded into w, u and the biases by the caller).  Only
+ * fastgrnn_hip_forward_unroll_affine runs it; with this flag set fastgrnn_hip_kernel_path(d, 0) and
+ * fastgrnn_hip_forward_workspace_bytes answer for that call, fastgrnn_hip_kernel_path(d, 1) is -1 (there is no
+ * backward) and every other entry point answers FASTGRNN_ERR_UNSUPPORTED. */
+#define FASTGRNN_FLAG_PREACT_AFFINE 1024u
 
 /* Problem descriptor.  T = 1 for the single-step operators. */
 typedef struct fastgrnn_desc {
@@ -188,6 +196,10 @@ const char *fastgrnn_hip_status_string(int status);
  *                                 projected onto the factors (as the reference's CUDA operator does for every
  *                                 low-rank cell, .cu:353-362,546-555); the dense shape's limits and flags apply.
  *                                 No rank-space vector is saved (c_s is ignored under FASTGRNN_FLAG_SAVE_PREACT).
+ *   FASTGRNN_FLAG_PREACT_AFFINE (forward only): fp32 sequences, gates sigmoid / relu / tanh, update tanh, dense
+ *                                 H=128 with F=32/64/128/256 and dense H=256 with F=32/64/128; time- or batch-major,
+ *                                 FASTGRNN_FLAG_HS_LAST.  Every other fp32 / fp64 cell (other shapes, quantised
+ *                                 nonlinearity codes) runs on path 0, time-major without FASTGRNN_FLAG_HS_LAST.
  * Under FASTGRNN_FLAG_SAVE_PREACT a factorised forward with both ranks in 1..16 also writes, through c_s, the rank-space vector
  * [U1.h_{t-1} | W1.x_t] as a time-major fp32 [T*B, 32] tensor (each half zero-extended to 16 columns) that the
  * backward takes back through c_s (with z_s, the pre-activation): its factor gradients are contracted inside the
@@ -210,6 +222,17 @@ int fastgrnn_hip_forward_unroll(const fastgrnn_desc *d, const fastgrnn_params *p
                                 const void *x, const void *h0,
                                 void *hs, void *z_s, void *c_s,
                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/* forward_unroll_affine -- inference forward of the eval-mode BatchNorm cell (FASTGRNN_FLAG_PREACT_AFFINE above,
+ * which d->flags must carry).  gate_scale, update_scale: [H] in the parameter dtype; p->bias_gate / p->bias_update
+ * hold the folded biases, p->w / p->u the folded (dense) matrices.  x:[T,B,F], h0:[B,H] -> hs:[T,B,H] (or the
+ * layouts of FASTGRNN_FLAG_BATCH_MAJOR / FASTGRNN_FLAG_HS_LAST on kernel path 2).  No z_s / h_prime_s: nothing is
+ * saved for a backward.  fp32 or fp64; bf16 sequences, FASTGRNN_FLAG_X_BFT, FASTGRNN_FLAG_SAVE_PREACT, factorised
+ * operands and the layout flags off path 2 answer FASTGRNN_ERR_UNSUPPORTED. */
+int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc *d, const fastgrnn_params *p,
+                                       const void *gate_scale, const void *update_scale,
+                                       const void *x, const void *h0, void *hs,
+                                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* backward_unroll -- replaces fastgrnn_unroll_backward (fastgrnn_cuda.cpp:182-232 ->
  * .cu:417-557).  grad_hs:[T,B,H] is dL/d(hs[t]) for every t; z_s,c_s are the

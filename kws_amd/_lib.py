@@ -25,6 +25,7 @@ FLAG_X_BFT = 128              # x / d_x are the trainer's [B,F,T]
 FLAG_GRAD_LAST = 256          # backward_unroll: grad_h is [B,H], the gradient of the last state alone (model.py:227)
 FLAG_HS_LAST = 512            # forward_unroll (inference, no saved tensors): hs is [B,H] = h_T
 FLAG_BATCH_MAJOR = 16         # sequences are [B,T,.] (batch_first) instead of [T,B,.]
+FLAG_PREACT_AFFINE = 1024     # fastgrnn_hip_forward_unroll_affine: per-unit pre-activation scales (eval-mode BatchNorm)
 
 # include/fastgrnn_hip.h: fastgrnn_nonlinearity.  0..2 are the reference's table
 # (rnn.py:478,751); 3..5 the CPU cell's quantised family (rnn.py:53-60).
@@ -36,7 +37,7 @@ EXPORTS = (
     "fastgrnn_hip_forward_unroll", "fastgrnn_hip_backward_unroll",
     "fastgrnn_hip_forward", "fastgrnn_hip_backward",
     "fastgrnn_hip_head_workspace_bytes", "fastgrnn_hip_head_xent", "fastgrnn_hip_debug_poison_cu_state",
-    "fastgrnn_hip_frame_gemm",
+    "fastgrnn_hip_frame_gemm", "fastgrnn_hip_forward_unroll_affine",
 )
 
 
@@ -91,6 +92,8 @@ def load():
         f.argtypes = [DP]
     lib.fastgrnn_hip_forward_unroll.restype = i32
     lib.fastgrnn_hip_forward_unroll.argtypes = [DP, PP, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.fastgrnn_hip_forward_unroll_affine.restype = i32
+    lib.fastgrnn_hip_forward_unroll_affine.argtypes = [DP, PP, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.fastgrnn_hip_backward_unroll.restype = i32
     lib.fastgrnn_hip_backward_unroll.argtypes = [DP, PP, vp, vp, vp, vp, vp, vp, GP, vp, sz, vp]
     lib.fastgrnn_hip_forward.restype = i32

@@ -36,6 +36,8 @@ int check_ws(void* ws, size_t have, size_t need) {
 
 // 0 = generic scan, 1 = fp32-MFMA scan, 2 = split-precision scan on the bf16 matrix pipe
 int pick_path(const fastgrnn_desc* d, int direction) {
+  if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE)        // the scaled forward: split-precision scans or the generic one
+    return (!(d->flags & (FASTGRNN_FLAG_FORCE_GENERIC | FASTGRNN_FLAG_FORCE_F32_MFMA)) && affine_supported(*d)) ? 2 : 0;
   if (d->flags & FASTGRNN_FLAG_FORCE_GENERIC) return 0;
   if (!(d->flags & FASTGRNN_FLAG_FORCE_F32_MFMA) && split_supported(*d, direction)) return 2;
   return mfma_supported(*d, direction) ? 1 : 0;
@@ -63,6 +65,7 @@ const char* fastgrnn_hip_status_string(int status) {
 
 int fastgrnn_hip_kernel_path(const fastgrnn_desc* d, int direction) {
   if (check_desc(d) != FASTGRNN_OK) return -1;
+  if ((d->flags & FASTGRNN_FLAG_PREACT_AFFINE) && direction != 0) return -1;   // inference only
   return pick_path(d, direction);
 }
 
@@ -76,7 +79,7 @@ size_t fastgrnn_hip_forward_workspace_bytes(const fastgrnn_desc* d) {
 }
 
 size_t fastgrnn_hip_backward_workspace_bytes(const fastgrnn_desc* d) {
-  if (check_desc(d) != FASTGRNN_OK) return 0;
+  if (check_desc(d) != FASTGRNN_OK || (d->flags & FASTGRNN_FLAG_PREACT_AFFINE)) return 0;
   switch (pick_path(d, 1)) {
     case 2: return split_backward_ws(*d);
     case 1: return mfma_backward_ws(*d);
@@ -91,6 +94,7 @@ int fastgrnn_hip_forward_unroll(const fastgrnn_desc* d, const fastgrnn_params* p
   if (st) return st;
   if ((st = check_params(d, p))) return st;
   if (!x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
+  if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // fastgrnn_hip_forward_unroll_affine
   if (((d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST)) ||
        d->dtype == FASTGRNN_BF16_IO) && pick_path(d, 0) != 2)
     return FASTGRNN_ERR_UNSUPPORTED;
@@ -106,12 +110,31 @@ int fastgrnn_hip_forward_unroll(const fastgrnn_desc* d, const fastgrnn_params* p
   }
 }
 
+int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc* d, const fastgrnn_params* p, const void* gate_scale,
+                                       const void* update_scale, const void* x, const void* h0, void* hs,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  int st = check_desc(d);
+  if (st) return st;
+  if ((st = check_params(d, p))) return st;
+  if (!gate_scale || !update_scale || !x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
+  if (!(d->flags & FASTGRNN_FLAG_PREACT_AFFINE) || d->dtype == FASTGRNN_BF16_IO || d->w_rank || d->u_rank ||
+      (d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)))
+    return FASTGRNN_ERR_UNSUPPORTED;
+  const int path = pick_path(d, 0);
+  if ((d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_HS_LAST)) && path != 2) return FASTGRNN_ERR_UNSUPPORTED;
+  if ((st = check_ws(workspace, workspace_bytes, fastgrnn_hip_forward_workspace_bytes(d)))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (path == 2) return split_forward(*d, *p, x, h0, hs, nullptr, nullptr, workspace, s, gate_scale, update_scale);
+  return generic_forward(*d, *p, x, h0, hs, nullptr, nullptr, workspace, s, gate_scale, update_scale);
+}
+
 int fastgrnn_hip_backward_unroll(const fastgrnn_desc* d, const fastgrnn_params* p, const void* grad_hs,
                                  const void* x, const void* hs, const void* z_s, const void* c_s, const void* h0,
                                  const fastgrnn_grads* g, void* workspace, size_t workspace_bytes, void* stream) {
   int st = check_desc(d);
   if (st) return st;
   if ((st = check_params(d, p))) return st;
+  if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // inference only
   const bool preact = (d->flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
   if ((preact || (d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)) || d->dtype == FASTGRNN_BF16_IO) && pick_path(d, 1) != 2)
     return FASTGRNN_ERR_UNSUPPORTED;

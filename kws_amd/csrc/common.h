@@ -46,8 +46,11 @@ static inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 // ---- internal launchers (implemented in kernels_generic.hip / kernels_mfma.hip) ---------
 size_t generic_forward_ws(const fastgrnn_desc& d);
 size_t generic_backward_ws(const fastgrnn_desc& d);
+// sg, sc (FASTGRNN_FLAG_PREACT_AFFINE): [H] per-unit scales of the pre-activation in front of the gate and the
+// update nonlinearity, in the parameter dtype; NULL for the plain cell
 int generic_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0,
-                    void* hs, void* zs, void* cs, void* ws, hipStream_t s);
+                    void* hs, void* zs, void* cs, void* ws, hipStream_t s, const void* sg = nullptr,
+                    const void* sc = nullptr);
 int generic_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x,
                      const void* hs, const void* zs, const void* cs, const void* h0,
                      const fastgrnn_grads& g, void* ws, hipStream_t s);
@@ -73,8 +76,11 @@ size_t split_forward_ws(const fastgrnn_desc& d);
 size_t split_backward_ws(const fastgrnn_desc& d);
 bool split_forward_ws_optional(const fastgrnn_desc& d);   // the forward workspace is only used when z_s is NULL
 bool split_dx_optional(const fastgrnn_desc& d);           // the backward accepts d_x == NULL (no input gradient)
+// the per-unit scaled forward (sg, sc non-NULL, zs = cs = NULL) on the shapes affine_supported() admits
+bool affine_supported(const fastgrnn_desc& d);
 int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0,
-                  void* hs, void* zs, void* cs, void* ws, hipStream_t s);
+                  void* hs, void* zs, void* cs, void* ws, hipStream_t s, const void* sg = nullptr,
+                  const void* sc = nullptr);
 int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x,
                    const void* hs, const void* zs, const void* cs, const void* h0,
                    const fastgrnn_grads& g, void* ws, hipStream_t s);
@@ -100,7 +106,7 @@ bool h256_supported(const fastgrnn_desc& d, int direction);
 size_t h256_forward_ws(const fastgrnn_desc& d);
 size_t h256_backward_ws(const fastgrnn_desc& d);
 int h256_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                 void* cs, void* ws, hipStream_t s);
+                 void* cs, void* ws, hipStream_t s, const float* sg = nullptr, const float* sc = nullptr);
 int h256_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
                   const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s);
 

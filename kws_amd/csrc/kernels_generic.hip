@@ -24,7 +24,10 @@ __global__ void transpose_kernel(const T* __restrict__ src, T* __restrict__ dst,
   }
 }
 
-template <typename T>
+// AFF: per-unit pre-activation scales (FASTGRNN_FLAG_PREACT_AFFINE): z = gate(sg*pre + bz), c = update(sc*pre + bh),
+// with bz, bh pointing at [H] biases followed by the [H] scales (packed by the launcher: the kernel's argument list,
+// and with it the offsets of the implicit arguments that blockDim is read from, stays that of the plain kernel)
+template <typename T, bool AFF = false>
 __global__ __launch_bounds__(NTHREADS) void fwd_scan_generic(
     int Tn, int B, int F, int H, int rw, int ru, int gate, int upd,
     const T* __restrict__ x, const T* __restrict__ h0,
@@ -109,11 +112,12 @@ __global__ __launch_bounds__(NTHREADS) void fwd_scan_generic(
         }
       }
       const T bzn = bz[n], bhn = bh[n];
+      const T sgn = AFF ? bz[H + n] : T(1), scn = AFF ? bh[H + n] : T(1);
 #pragma unroll
       for (int b = 0; b < BT; ++b) {
         T pre = accw[b] + accu[b];                       // rnn.py:289
-        T z = act<T>(pre + bzn, gate);                   // rnn.py:290
-        T c = act<T>(pre + bhn, upd);                    // rnn.py:292
+        T z = act<T>(AFF ? sgn * pre + bzn : pre + bzn, gate);   // rnn.py:290
+        T c = act<T>(AFF ? scn * pre + bhn : pre + bhn, upd);    // rnn.py:292
         T hv = z * hc[b * H + n] + (sz * (T(1) - z) + sn) * c;   // rnn.py:294-295
         if (b0 + b < B) {
           size_t o = ((size_t)t * B + b0 + b) * H + n;
@@ -440,7 +444,7 @@ void launch_tn(size_t R, int M, int N, const T* A, const T* B0, const T* B1, siz
 
 template <typename T>
 int generic_forward_t(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                      void* zs, void* cs, void* ws, hipStream_t s) {
+                      void* zs, void* cs, void* ws, hipStream_t s, const void* sg, const void* sc) {
   const int F = d.F, H = d.H, rw = d.w_rank, ru = d.u_rank;
   T* wA = reinterpret_cast<T*>(ws);
   size_t wA_n = (size_t)(rw ? rw : F) * H;
@@ -457,14 +461,25 @@ int generic_forward_t(const fastgrnn_desc& d, const fastgrnn_params& p, const vo
   if (lds > 160 * 1024) return FASTGRNN_ERR_UNSUPPORTED;
   int nth = H >= NTHREADS ? NTHREADS : ((H + 63) / 64) * 64;
   unsigned nwg = (unsigned)((d.B + BT - 1) / BT);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_scan_generic<T>),
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(fwd_scan_generic<T>, dim3(nwg), dim3(nth), lds, s, d.T, d.B, F, H, rw, ru, d.gate_nl,
-                     d.update_nl, reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(h0), wA,
-                     reinterpret_cast<const T*>(p.w1), uA, reinterpret_cast<const T*>(p.u1),
-                     reinterpret_cast<const T*>(p.bias_gate), reinterpret_cast<const T*>(p.bias_update),
-                     reinterpret_cast<const T*>(p.zeta), reinterpret_cast<const T*>(p.nu),
-                     reinterpret_cast<T*>(hs), reinterpret_cast<T*>(zs), reinterpret_cast<T*>(cs));
+  const T* bz = reinterpret_cast<const T*>(p.bias_gate);
+  const T* bh = reinterpret_cast<const T*>(p.bias_update);
+  if (sg) {                                      // [bias_gate | gate_scale | bias_update | update_scale]
+    T* pack = reinterpret_cast<T*>(reinterpret_cast<char*>(uA) + align256(uA_n * sizeof(T)));
+    const size_t hb = (size_t)H * sizeof(T);
+    const void* src[4] = {p.bias_gate, sg, p.bias_update, sc};
+    for (int k = 0; k < 4; ++k)
+      if (hipMemcpyAsync(pack + (size_t)k * H, src[k], hb, hipMemcpyDeviceToDevice, s) != hipSuccess) return FASTGRNN_ERR_LAUNCH;
+    bz = pack; bh = pack + 2 * (size_t)H;
+  }
+  auto go = [&](auto kern) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3(nwg), dim3(nth), lds, s, d.T, d.B, F, H, rw, ru, d.gate_nl,
+                       d.update_nl, reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(h0), wA,
+                       reinterpret_cast<const T*>(p.w1), uA, reinterpret_cast<const T*>(p.u1), bz, bh,
+                       reinterpret_cast<const T*>(p.zeta), reinterpret_cast<const T*>(p.nu),
+                       reinterpret_cast<T*>(hs), reinterpret_cast<T*>(zs), reinterpret_cast<T*>(cs));
+  };
+  if (sg) go(fwd_scan_generic<T, true>); else go(fwd_scan_generic<T, false>);
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 
@@ -544,14 +559,15 @@ void tn_gemm_f32(size_t R, int M, int N, const float* A, int lda, const float* B
 size_t generic_forward_ws(const fastgrnn_desc& d) {
   size_t es = d.dtype == FASTGRNN_F64 ? 8 : 4;
   return align256((size_t)(d.w_rank ? d.w_rank : d.F) * d.H * es) +
-         align256((size_t)(d.u_rank ? d.u_rank : d.H) * d.H * es);
+         align256((size_t)(d.u_rank ? d.u_rank : d.H) * d.H * es) +
+         ((d.flags & FASTGRNN_FLAG_PREACT_AFFINE) ? align256((size_t)4 * d.H * es) : 0);   // the packed biases / scales
 }
 size_t generic_backward_ws(const fastgrnn_desc& d) { return bwd_layout(d).total; }
 
 int generic_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                    void* zs, void* cs, void* ws, hipStream_t s) {
-  return d.dtype == FASTGRNN_F64 ? generic_forward_t<double>(d, p, x, h0, hs, zs, cs, ws, s)
-                                 : generic_forward_t<float>(d, p, x, h0, hs, zs, cs, ws, s);
+                    void* zs, void* cs, void* ws, hipStream_t s, const void* sg, const void* sc) {
+  return d.dtype == FASTGRNN_F64 ? generic_forward_t<double>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc)
+                                 : generic_forward_t<float>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc);
 }
 int generic_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x,
                      const void* hs, const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g,

@@ -44,14 +44,21 @@ constexpr int SLAB2 = 576;                      // floats per workgroup: d_bz[25
 // has no recurrence in it: `x` is then P[T*B, 256] = X . W^T, written by the batched frame GEMM (kernels_gemm.hip) in
 // front of this launch, and the scan reads P(t) where it otherwise runs its W.x MFMAs (as the H = 128 wide layers do).
 // BF: FASTGRNN_BF16_IO -- x and hs are bf16 in HBM (P, the saved pre-activation, h0 and the state itself stay fp32).
-template <int GATE, int AUX, bool RAGGED, int MODE, bool PREIN = false, bool BF = false>
+// AFF: per-unit pre-activation scales (FASTGRNN_FLAG_PREACT_AFFINE, an eval-mode BatchNorm cell folded into w, u and
+// the biases): z = gate(sg*pre + bz), c = tanh(sc*pre + bh); fp32, AUX 0 / 3.  The scales are staged beside the
+// biases in sbias.  The bf16 path's planes leave 1.5 KB of LDS beside sbias (160 256 B + 2 KB of 163 840), and its
+// registers hold no 16 more per lane without scratch (tools/resource_usage.py), so an AFF kernel sizes `smem` for
+// the path its MODE runs: MODE 1 (the fp16 path's 90 624 B) stages both scales in sbias; MODE 0 / 2 stage the update
+// scales there (1 KB) and keep the lane's eight gate scales in registers (loaded once).
+template <int GATE, int AUX, bool RAGGED, int MODE, bool PREIN = false, bool BF = false, bool AFF = false>
 __global__ __launch_bounds__(512) void fwd_scan_h256(
     int Tn, int B, unsigned hsT, unsigned hsB, unsigned xsT, unsigned xsB,
     const float* __restrict__ x, const float* __restrict__ h0,
     const float* __restrict__ w, const float* __restrict__ u,
     const float* __restrict__ bz, const float* __restrict__ bh,
     const float* __restrict__ zeta, const float* __restrict__ nu,
-    float* __restrict__ hs, float* __restrict__ zs, float* __restrict__ cs, unsigned* __restrict__ flags) {
+    float* __restrict__ hs, float* __restrict__ zs, float* __restrict__ cs, unsigned* __restrict__ flags,
+    const float* __restrict__ sg = nullptr, const float* __restrict__ sc = nullptr) {
   // hsT / hsB: element strides of one step / one utterance in hs, zs, cs (and in P under PREIN, whose rows follow the
   // frames' order); xsT / xsB: the same for x.  Time-major: (B*256, 256) and (B*32, 32); FASTGRNN_FLAG_BATCH_MAJOR:
   // (256, T*256) and (32, T*32) -- rnn.py:812-813 transposes instead.
@@ -62,8 +69,11 @@ __global__ __launch_bounds__(512) void fwd_scan_h256(
   //               128 registers of U planes per lane the 24 of W's are re-read each step instead of kept)
   //   bf16 path:  U plane 2 (fragment order) | state planes [1][3] | feature planes [1][3]   (single-buffered: two
   //               barriers per step; 160 256 bytes, the CU has 163 840)
-  __shared__ __attribute__((aligned(16))) unsigned char smem[U2L + 3 * PLH2 + 3 * PLX2];
-  __shared__ __attribute__((aligned(16))) float sbias[2][H2];
+  constexpr bool SG_LDS = AFF && MODE == 1;         // gate scales in sbias[3] (fp16 path only: see above)
+  __shared__ __attribute__((aligned(16))) unsigned char smem[SG_LDS ? 2 * 2 * PLH2 + 2 * 3 * PLX2 + 2 * 8 * 3 * 64 * 16
+                                                                    : U2L + 3 * PLH2 + 3 * PLX2];
+  // bias_gate | bias_update [| update scales [| gate scales]]
+  __shared__ __attribute__((aligned(16))) float sbias[!AFF ? 2 : (SG_LDS ? 4 : 3)][H2];
   __shared__ float hmax_s[8];
 
   const int tid = threadIdx.x;
@@ -79,6 +89,15 @@ __global__ __launch_bounds__(512) void fwd_scan_h256(
   const int xbc = (!RAGGED || xb < B) ? xb : B - 1;
 
   if (tid < H2) { sbias[0][tid] = bz[tid]; sbias[1][tid] = bh[tid]; }
+  if constexpr (AFF) {
+    if (tid < H2) sbias[AFF ? 2 : 0][tid] = sc[tid];
+  }
+  if constexpr (SG_LDS) {
+    if (tid < H2) sbias[SG_LDS ? 3 : 0][tid] = sg[tid];
+  }
+  f32x4 sgr[2];                                    // AFF, MODE 0 / 2: the lane's gate scales
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) sgr[mt] = (AFF && !SG_LDS) ? ld4(sg + n0 + 16 * mt) : f32x4{1.f, 1.f, 1.f, 1.f};
   f32x4 hown[2];
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt) hown[mt] = ld4(h0 + (size_t)bc * H2 + n0 + 16 * mt);
@@ -338,11 +357,13 @@ __global__ __launch_bounds__(512) void fwd_scan_h256(
       const f32x4 pre = H16 ? a[mt] + (ah[mt] + ahl[mt]) * u_unscale : a[mt] + alo[mt];
       const f32x4 bzq = *reinterpret_cast<const f32x4*>(&sbias[0][n0 + 16 * mt]);
       const f32x4 bhq = *reinterpret_cast<const f32x4*>(&sbias[1][n0 + 16 * mt]);
+      const f32x4 sgq = SG_LDS ? *reinterpret_cast<const f32x4*>(&sbias[SG_LDS ? 3 : 0][n0 + 16 * mt]) : sgr[mt];
+      const f32x4 scq = AFF ? *reinterpret_cast<const f32x4*>(&sbias[AFF ? 2 : 0][n0 + 16 * mt]) : sgr[mt];
       f32x4 zq, cq;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float z = gate_act<GATE>(pre[r] + bzq[r]);
-        const float c = ftanh(pre[r] + bhq[r]);
+        const float z = gate_act<GATE>(AFF ? fmaf(pre[r], sgq[r], bzq[r]) : pre[r] + bzq[r]);
+        const float c = ftanh(AFF ? fmaf(pre[r], scq[r], bhq[r]) : pre[r] + bhq[r]);
         hown[mt][r] = (sz * (1.0f - z) + sn) * c + hown[mt][r] * z;
         zq[r] = z; cq[r] = c;
       }
@@ -772,7 +793,7 @@ H256BwdWs h256_bwd_layout(const fastgrnn_desc& d) {
 
 template <int GATE>
 void launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                void* cs, void* ws, hipStream_t s) {
+                void* cs, void* ws, hipStream_t s, const float* sg, const float* sc) {
   dim3 grid((d.B + 15) / 16), block(512);
   const bool ragged = (d.B % 16) != 0;
   const int aux = (d.flags & FASTGRNN_FLAG_HS_LAST) ? 3 : (zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1));
@@ -799,11 +820,32 @@ void launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
   auto go = [&](auto kern) __attribute__((always_inline)) {
     hipLaunchKernelGGL(kern, grid, block, 0, s, d.T, d.B, hsT, hsB, xsT, xsB, (const float*)x, (const float*)h0, (const float*)p.w,
                        (const float*)p.u, (const float*)p.bias_gate, (const float*)p.bias_update, (const float*)p.zeta,
-                       (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, flags);
+                       (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, flags, sg, sc);
   };
   // fp16 two-plane state product only for gates that keep z in [0,1] (see fwd_scan_split_w8); FWD_BF16X3: A/B
   constexpr bool BOUNDED = GATE == FASTGRNN_NL_SIGMOID || GATE == FASTGRNN_NL_QUANT_SIGM || GATE == FASTGRNN_NL_QUANT_SIGM4;
   const bool h16 = BOUNDED && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3);
+  if constexpr (GATE <= FASTGRNN_NL_TANH) {
+    if (sg) {                                        // FASTGRNN_FLAG_PREACT_AFFINE (affine_supported: fp32, AUX 0 / 3)
+      auto aff = [&](auto aux_tag, auto prein_tag) __attribute__((always_inline)) {
+        constexpr int A = decltype(aux_tag)::value;
+        constexpr bool PI = decltype(prein_tag)::value;
+        if constexpr (BOUNDED) {
+          if (h16) {
+            if (ragged) { go(fwd_scan_h256<GATE, A, true, 1, PI, false, true>); go(fwd_scan_h256<GATE, A, true, 2, PI, false, true>); }
+            else        { go(fwd_scan_h256<GATE, A, false, 1, PI, false, true>); go(fwd_scan_h256<GATE, A, false, 2, PI, false, true>); }
+            return;
+          }
+        }
+        if (ragged) go(fwd_scan_h256<GATE, A, true, 0, PI, false, true>); else go(fwd_scan_h256<GATE, A, false, 0, PI, false, true>);
+      };
+      auto aff_in = [&](auto aux_tag) __attribute__((always_inline)) {
+        if (prein) aff(aux_tag, std::true_type{}); else aff(aux_tag, std::false_type{});
+      };
+      if (aux == 3) aff_in(std::integral_constant<int, 3>{}); else aff_in(std::integral_constant<int, 0>{});
+      return;
+    }
+  }
   auto pick = [&](auto aux_tag) __attribute__((always_inline)) {
     constexpr int A = decltype(aux_tag)::value;
     auto with = [&](auto prein_tag, auto bf_tag) __attribute__((always_inline)) {
@@ -919,15 +961,15 @@ size_t h256_forward_ws(const fastgrnn_desc& d) {
 }
 
 int h256_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                 void* cs, void* ws, hipStream_t s) {
+                 void* cs, void* ws, hipStream_t s, const float* sg, const float* sc) {
   if (!ws) return FASTGRNN_ERR_WORKSPACE;
   switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: launch_fwd<FASTGRNN_NL_SIGMOID>(d, p, x, h0, hs, zs, cs, ws, s); break;
-    case FASTGRNN_NL_RELU: launch_fwd<FASTGRNN_NL_RELU>(d, p, x, h0, hs, zs, cs, ws, s); break;
-    case FASTGRNN_NL_TANH: launch_fwd<FASTGRNN_NL_TANH>(d, p, x, h0, hs, zs, cs, ws, s); break;
-    case FASTGRNN_NL_QUANT_TANH: launch_fwd<FASTGRNN_NL_QUANT_TANH>(d, p, x, h0, hs, zs, cs, ws, s); break;
-    case FASTGRNN_NL_QUANT_SIGM: launch_fwd<FASTGRNN_NL_QUANT_SIGM>(d, p, x, h0, hs, zs, cs, ws, s); break;
-    default: launch_fwd<FASTGRNN_NL_QUANT_SIGM4>(d, p, x, h0, hs, zs, cs, ws, s); break;
+    case FASTGRNN_NL_SIGMOID: launch_fwd<FASTGRNN_NL_SIGMOID>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
+    case FASTGRNN_NL_RELU: launch_fwd<FASTGRNN_NL_RELU>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
+    case FASTGRNN_NL_TANH: launch_fwd<FASTGRNN_NL_TANH>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
+    case FASTGRNN_NL_QUANT_TANH: launch_fwd<FASTGRNN_NL_QUANT_TANH>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
+    case FASTGRNN_NL_QUANT_SIGM: launch_fwd<FASTGRNN_NL_QUANT_SIGM>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
+    default: launch_fwd<FASTGRNN_NL_QUANT_SIGM4>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
   }
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }

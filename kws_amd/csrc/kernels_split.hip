@@ -230,13 +230,20 @@ constexpr int W8_ROWX = 80;             // bytes per utterance row of a 32-wide 
 // UQ: the update nonlinearity is quantTanh = clip(a, -1, 1) instead of tanh (the CPU cell allows it, rnn.py:57-58,
 // 292-293; the reference's CUDA classes fix tanh).  Instantiated for fp32 time- or batch-major sequences without
 // PREIN; hs only or the one-saved-tensor contract.
-template <int GATE, int AUX, bool RAGGED, bool BF = false, bool F16H = true, bool PREIN = false, bool UQ = false>
+// AFF: per-unit pre-activation scales (FASTGRNN_FLAG_PREACT_AFFINE: an eval-mode BatchNorm cell folded into w, u and
+// the biases): z = gate(sg*pre + bz), c = tanh(sc*pre + bh).  fp32 sequences, hs only or h_T alone (AUX 0 / 3); sg,
+// sc are read only here (two more f32x4 beside bzv / bhv).  The fp16 state product stays eligible: the gate is still
+// z in [0,1] for the gates F16H is instantiated for, so the bound on h above holds, and the rows of u carry the BN
+// scales, which the per-wave power-of-two pre-scale of U absorbs like any other row magnitude.
+template <int GATE, int AUX, bool RAGGED, bool BF = false, bool F16H = true, bool PREIN = false, bool UQ = false,
+          bool AFF = false>
 __global__ __launch_bounds__(512) void fwd_scan_split_w8(
     int Tn, int B, int rsT, int rsB, int mode, const float* __restrict__ x, const float* __restrict__ h0,
     const float* __restrict__ w, const float* __restrict__ u,
     const float* __restrict__ bz, const float* __restrict__ bh,
     const float* __restrict__ zeta, const float* __restrict__ nu,
-    float* __restrict__ hs, float* __restrict__ zs, float* __restrict__ cs) {
+    float* __restrict__ hs, float* __restrict__ zs, float* __restrict__ cs,
+    const float* __restrict__ sg = nullptr, const float* __restrict__ sc = nullptr) {
   constexpr int H = 128, F = 32, KS = H / 32;
   __shared__ __attribute__((aligned(16))) unsigned char hpl[2][3][16 * W8_ROWH];
   __shared__ __attribute__((aligned(16))) unsigned char xpl[PREIN ? 1 : 2][3][PREIN ? 16 : 16 * W8_ROWX];
@@ -259,6 +266,7 @@ __global__ __launch_bounds__(512) void fwd_scan_split_w8(
   const int xbc = (!RAGGED || xb < B) ? xb : B - 1;
 
   const f32x4 bzv = ld4(bz + n0), bhv = ld4(bh + n0);
+  const f32x4 sgv = AFF ? ld4(sg + n0) : f32x4{1.f, 1.f, 1.f, 1.f}, scv = AFF ? ld4(sc + n0) : f32x4{1.f, 1.f, 1.f, 1.f};
   f32x4 hown = ld4(h0 + (size_t)bc * H + n0);
   const float sz = fsigmoid(zeta[0]), sn = fsigmoid(nu[0]);
 
@@ -439,8 +447,9 @@ __global__ __launch_bounds__(512) void fwd_scan_split_w8(
     SPLIT_STAMP(2)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {                                                        // .cu:55-58
-      const float z = gate_act<GATE>(a[r] + bzv[r]);
-      const float c = UQ ? fminf(fmaxf(a[r] + bhv[r], -1.0f), 1.0f) : ftanh(a[r] + bhv[r]);
+      const float z = gate_act<GATE>(AFF ? fmaf(a[r], sgv[r], bzv[r]) : a[r] + bzv[r]);
+      const float c = UQ ? fminf(fmaxf(a[r] + bhv[r], -1.0f), 1.0f)
+                         : ftanh(AFF ? fmaf(a[r], scv[r], bhv[r]) : a[r] + bhv[r]);
       hown[r] = (sz * (1.0f - z) + sn) * c + hown[r] * z;
       zq[r] = z; cq[r] = c;
     }
@@ -1077,9 +1086,11 @@ void launch_bwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
 
 // pws != nullptr: PREIN -- the frame product P = X.W^T has been written by rows_gemm to zs (SAVE_PREACT), cs (the
 // reference's outputs) or, when the caller wants no auxiliary tensor, to the workspace pws
+// sg, sc: FASTGRNN_FLAG_PREACT_AFFINE -- the AFF variants (gates sigmoid / relu / tanh, fp32, hs only or h_T alone)
 template <int GATE>
 void launch_fwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                     void* zs, void* cs, hipStream_t s, void* pws = nullptr) {
+                     void* zs, void* cs, hipStream_t s, void* pws = nullptr, const float* sg = nullptr,
+                     const float* sc = nullptr) {
   dim3 grid((d.B + 15) / 16), block(256);
   const bool ragged = (d.B % 16) != 0;
   const int aux = zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1);
@@ -1095,7 +1106,7 @@ void launch_fwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
     hipLaunchKernelGGL(kern, grid, dim3(512), 0, s, d.T, d.B, row_stride_t(d), row_stride_b(d),
                        (d.flags & FASTGRNN_FLAG_X_BFT) ? 1 : 0, (const float*)x, (const float*)h0, (const float*)p.w,
                        (const float*)p.u, (const float*)p.bias_gate, (const float*)p.bias_update,
-                       (const float*)p.zeta, (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs);
+                       (const float*)p.zeta, (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, sg, sc);
   };
   // fp16 two-plane state product (F16H) only for gates that keep z in [0,1] -- they bound the growth of h to
   // sigma(nu) per step, and the kernel itself checks h0 (see fwd_scan_split_w8); relu / tanh / quantTanh gates
@@ -1103,6 +1114,29 @@ void launch_fwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
   constexpr bool BOUNDED = GATE == FASTGRNN_NL_SIGMOID || GATE == FASTGRNN_NL_QUANT_SIGM || GATE == FASTGRNN_NL_QUANT_SIGM4;
   const bool h16 = BOUNDED && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3);
   const bool bf = d.dtype == FASTGRNN_BF16_IO;
+  if constexpr (GATE <= FASTGRNN_NL_TANH) {
+    if (sg) {                                        // affine_supported(): fp32, no saved tensors
+      auto aff = [&](auto aux_tag, auto prein_tag) __attribute__((always_inline)) {
+        constexpr int A = decltype(aux_tag)::value;
+        constexpr bool PI = decltype(prein_tag)::value;
+        if constexpr (BOUNDED) {
+          if (h16) {
+            if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, true, PI, false, true>);
+            else        go8(fwd_scan_split_w8<GATE, A, false, false, true, PI, false, true>);
+            return;
+          }
+        }
+        if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, false, PI, false, true>);
+        else        go8(fwd_scan_split_w8<GATE, A, false, false, false, PI, false, true>);
+      };
+      auto aff_in = [&](auto aux_tag) __attribute__((always_inline)) {
+        if (prein) aff(aux_tag, std::true_type{}); else aff(aux_tag, std::false_type{});
+      };
+      if (d.flags & FASTGRNN_FLAG_HS_LAST) aff_in(std::integral_constant<int, 3>{});
+      else aff_in(std::integral_constant<int, 0>{});
+      return;
+    }
+  }
   auto pick8 = [&](auto aux_tag) __attribute__((always_inline)) {
     constexpr int A = decltype(aux_tag)::value;
     if constexpr (A == 0 || A == 2) {
@@ -1214,6 +1248,16 @@ bool split_supported(const fastgrnn_desc& d, int direction) {
   return dense;
 }
 
+// FASTGRNN_FLAG_PREACT_AFFINE on kernel path 2: fp32 sequences, gates sigmoid / relu / tanh, update tanh, dense
+// H = 128 (F = 32 / 64 / 128 / 256) and H = 256 (F = 32 / 64 / 128); time- or batch-major, hs or h_T alone
+bool affine_supported(const fastgrnn_desc& d) {
+  if (d.dtype != FASTGRNN_F32 || d.gate_nl > FASTGRNN_NL_TANH || d.update_nl != FASTGRNN_NL_TANH) return false;
+  if (d.flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)) return false;
+  if (h256_shape(d)) return h256_supported(d, 0);
+  const bool fits32 = (double)d.T * d.B * (d.H > d.F ? d.H : d.F) * 4.0 < 4294967296.0;
+  return (d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && fits32) || dense_wide_shape(d);
+}
+
 size_t split_forward_ws(const fastgrnn_desc& d) {
   // wide layers: the frame product P = X.W^T goes to the auxiliary output the caller passes (z_s under SAVE_PREACT,
   // c_s otherwise); a forward without auxiliary outputs needs room for it.  The query cannot see the pointers, so
@@ -1255,10 +1299,13 @@ int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
 }
 
 int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                  void* zs, void* cs, void* ws, hipStream_t s) {
+                  void* zs, void* cs, void* ws, hipStream_t s, const void* sg_, const void* sc_) {
   if (!(d.flags & FASTGRNN_FLAG_SAVE_PREACT) && (zs == nullptr) != (cs == nullptr)) return FASTGRNN_ERR_NULL_POINTER;
   if (d.dtype == FASTGRNN_BF16_IO && zs && !(d.flags & FASTGRNN_FLAG_SAVE_PREACT)) return FASTGRNN_ERR_UNSUPPORTED;
-  if (h256_shape(d)) return h256_forward(d, p, x, h0, hs, zs, cs, ws, s);
+  const float* sg = reinterpret_cast<const float*>(sg_);
+  const float* sc = reinterpret_cast<const float*>(sc_);
+  if (sg && (zs || !affine_supported(d))) return FASTGRNN_ERR_UNSUPPORTED;
+  if (h256_shape(d)) return h256_forward(d, p, x, h0, hs, zs, cs, ws, s, sg, sc);
   if (lowrank_shape(d)) return lowrank_forward(d, p, x, h0, hs, zs, cs, ws, s);
   if (densified_shape(d)) return densified_forward(d, p, x, h0, hs, zs, cs, ws, s);
   void* pws = nullptr;
@@ -1272,12 +1319,12 @@ int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
     if (st != FASTGRNN_OK) return st;
   }
   switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: launch_fwd_gate<FASTGRNN_NL_SIGMOID>(d, p, x, h0, hs, zs, cs, s, pws); break;
-    case FASTGRNN_NL_RELU: launch_fwd_gate<FASTGRNN_NL_RELU>(d, p, x, h0, hs, zs, cs, s, pws); break;
-    case FASTGRNN_NL_TANH: launch_fwd_gate<FASTGRNN_NL_TANH>(d, p, x, h0, hs, zs, cs, s, pws); break;
-    case FASTGRNN_NL_QUANT_TANH: launch_fwd_gate<FASTGRNN_NL_QUANT_TANH>(d, p, x, h0, hs, zs, cs, s, pws); break;
-    case FASTGRNN_NL_QUANT_SIGM: launch_fwd_gate<FASTGRNN_NL_QUANT_SIGM>(d, p, x, h0, hs, zs, cs, s, pws); break;
-    default: launch_fwd_gate<FASTGRNN_NL_QUANT_SIGM4>(d, p, x, h0, hs, zs, cs, s, pws); break;
+    case FASTGRNN_NL_SIGMOID: launch_fwd_gate<FASTGRNN_NL_SIGMOID>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
+    case FASTGRNN_NL_RELU: launch_fwd_gate<FASTGRNN_NL_RELU>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
+    case FASTGRNN_NL_TANH: launch_fwd_gate<FASTGRNN_NL_TANH>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
+    case FASTGRNN_NL_QUANT_TANH: launch_fwd_gate<FASTGRNN_NL_QUANT_TANH>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
+    case FASTGRNN_NL_QUANT_SIGM: launch_fwd_gate<FASTGRNN_NL_QUANT_SIGM>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
+    default: launch_fwd_gate<FASTGRNN_NL_QUANT_SIGM4>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
   }
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }

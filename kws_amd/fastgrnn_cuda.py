@@ -475,6 +475,52 @@ def forward_unroll(input, w, u, bias_gate, bias_update, zeta, nu, initial_h, z_n
                          w1, w2, u1, u2, True, update_non_linearity, want_gates, flags)
 
 
+def forward_unroll_affine(input, w, u, bias_gate, bias_update, zeta, nu, gate_scale, update_scale, initial_h,
+                          z_non_linearity, update_non_linearity=2, flags=0):
+    """Inference forward of the cell with per-unit pre-activation scales (include/fastgrnn_hip.h,
+    ``fastgrnn_hip_forward_unroll_affine``): ``z = gate(gate_scale*pre + bias_gate)``, ``h' = update(update_scale*pre
+    + bias_update)``, ``pre = w.x + u.h`` -- an eval-mode BatchNorm cell after folding.  Dense operands in the
+    ``[out,in]`` layout, fp32 or fp64.  Returns hs (``[T,B,H]``, ``[B,T,H]`` under FLAG_BATCH_MAJOR, ``[B,H]`` under
+    FLAG_HS_LAST).  Nothing is saved for a backward."""
+    lib = _lib.load()
+    flags = int(flags) | _lib.FLAG_PREACT_AFFINE
+    for t, n in ((input, "input"), (initial_h, "initial_h"), (bias_gate, "bias_gate"), (bias_update, "bias_update"),
+                 (gate_scale, "gate_scale"), (update_scale, "update_scale")):
+        _check_input(t, n)
+    if input.dim() != 3:
+        raise RuntimeError("input must be [timesteps, batch, features]")
+    if flags & _lib.FLAG_BATCH_MAJOR:
+        B, T, F = input.shape
+    else:
+        T, B, F = input.shape
+    H = initial_h.shape[-1]
+    _expect(initial_h, (B, H), "initial_h")
+    for t, n in ((bias_gate, "bias_gate"), (bias_update, "bias_update"), (gate_scale, "gate_scale"),
+                 (update_scale, "update_scale")):
+        if t.numel() != H:
+            raise RuntimeError("%s must hold H=%d elements" % (n, H))
+    if input.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("fastgrnn: the affine forward takes float32 or float64 sequences (got %s)" % input.dtype)
+    for t in (initial_h, gate_scale, update_scale):
+        if t.dtype != input.dtype:
+            raise RuntimeError("fastgrnn: all operands must share dtype %s (got %s)" % (input.dtype, t.dtype))
+    plan, params, _, _ = _describe(T, B, F, H, w, u, None, None, None, None, bias_gate, bias_update, zeta, nu,
+                                   input.dtype, z_non_linearity, update_non_linearity, flags)
+    _warn_fallback(plan, 0)
+    dev = input.device
+    hs_shape = (B, H) if flags & _lib.FLAG_HS_LAST else tuple(input.shape[:2]) + (H,)
+    with torch.cuda.device(dev):
+        hs = torch.empty(hs_shape, dtype=input.dtype, device=dev)
+        ws, wsp = _workspace(plan[3], dev)
+        with _Timed("forward_affine", dev):
+            st = lib.fastgrnn_hip_forward_unroll_affine(C.byref(plan[0]), C.byref(params), _ptr(gate_scale),
+                                                        _ptr(update_scale), _ptr(input), _ptr(initial_h), _ptr(hs),
+                                                        wsp, plan[3], _stream(dev))
+        _lib.check(st, "fastgrnn forward_unroll_affine")
+        del ws
+    return hs
+
+
 def backward_unroll(grad_h, input, hidden_states, zeta, nu, w, u, z, h_prime, initial_h, w1, w2, u1, u2,
                     z_non_linearity, *, update_non_linearity=2, flags=0, bias_gate=None, bias_update=None,
                     need_dx=True):

@@ -15,6 +15,11 @@ Same constructor arguments, attribute and parameter names as the reference (``rn
   fused head kernel -- Linear, log_softmax, NLL and all their gradients in two launches;
 * ``sparsify`` / ``sparsifyWithSupport`` work in place on the device (the reference moves every layer to the CPU
   and back, model.py:91-107);
+* ``rnn_name="FastGRNNBatchNorm"`` builds ``kws_amd.FastGRNNBatchNorm`` layers (the reference's trained keyword
+  spotter, model_batchnorm/): eval mode only (``model.eval()``; ``train()`` / ``eval()`` reach the layers as
+  model.py:167-183 does), dense weights only, ``loss()`` stays a ``FastGRNNCUDA`` method.  The head reads the last
+  time step of every utterance in both layouts; the reference's batch_first path indexes ``model_output[-1, :, :]``
+  (model.py:225-227), i.e. the LAST UTTERANCE's state sequence, for a ``[B,T,H]`` output -- that is not reproduced;
 * the shadow ``rnn_list_`` / ``tracking`` ONNX-export path (model.py:72-84,187-195) is not built (export is
   disabled in the reference, trainClassifier.py:42-52), nor are the rolling hidden-state bags
   (model.py:135-148: data-loader bookkeeping, no arithmetic).
@@ -25,18 +30,23 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .batchnorm import FastGRNNBatchNorm
 from .head import keyword_loss
 from .rnn import FastGRNNCUDA
 
+_RNN_CLASSES = {"FastGRNNCUDA": FastGRNNCUDA, "FastGRNNBatchNorm": FastGRNNBatchNorm}     # model.py:12-15
+
 
 class RNNClassifierModel(nn.Module):
-    """1-, 2- or 3-layer FastGRNN classifier (model.py:22-233), ``rnn_name`` fixed to ``"FastGRNNCUDA"``."""
+    """1-, 2- or 3-layer FastGRNN classifier (model.py:22-233), ``rnn_name`` ``"FastGRNNCUDA"`` or
+    ``"FastGRNNBatchNorm"`` (eval mode)."""
 
     def __init__(self, rnn_name, input_dim, num_layers, hidden_units_list, wRank_list, uRank_list,
                  wSparsity_list, uSparsity_list, gate_nonlinearity, update_nonlinearity, num_classes=None,
                  linear=True, batch_first=False, apply_softmax=True, device=None):
-        if rnn_name != "FastGRNNCUDA":
-            raise ValueError("kws_amd builds the FastGRNNCUDA model family only (got %r)" % (rnn_name,))
+        if rnn_name not in _RNN_CLASSES:
+            raise ValueError("kws_amd builds the FastGRNNCUDA and FastGRNNBatchNorm model families only (got %r)"
+                             % (rnn_name,))
         if linear and not num_classes:
             raise Exception("num_classes need to be specified if linear is True")      # model.py:54-56
         super().__init__()
@@ -53,7 +63,7 @@ class RNNClassifierModel(nn.Module):
         self.batch_first = batch_first
         self.apply_softmax = apply_softmax
         self.rnn_list = nn.ModuleList([                                                 # model.py:61-70
-            FastGRNNCUDA(self.input_dim if l == 0 else self.hidden_units_list[l - 1], self.hidden_units_list[l],
+            _RNN_CLASSES[rnn_name](self.input_dim if l == 0 else self.hidden_units_list[l - 1], self.hidden_units_list[l],
                          gate_nonlinearity=gate_nonlinearity, update_nonlinearity=update_nonlinearity,
                          wRank=self.wRank_list[l], uRank=self.uRank_list[l],
                          wSparsity=self.wSparsity_list[l], uSparsity=self.uSparsity_list[l],
@@ -62,6 +72,7 @@ class RNNClassifierModel(nn.Module):
         if self.linear:                                                                 # model.py:85-88
             self.hidden2keyword = nn.Linear(self.hidden_units_list[num_layers - 1], num_classes,
                                             device=self.rnn_list[0].device)
+        self._batchnorm = rnn_name == "FastGRNNBatchNorm"
         self.init_hidden()
 
     # ---- bookkeeping (model.py:91-156) -----------------------------------------------------------------
@@ -92,7 +103,10 @@ class RNNClassifierModel(nn.Module):
         rnn_in = input
         top = self.num_layers - 1
         for l, rnn in enumerate(self.rnn_list):
-            out = rnn(rnn_in, hiddenState=self.hidden_states[l], last_state=(l == top))
+            if self._batchnorm:                          # (model.py:211-215: the layers take the model's mode)
+                out = rnn(rnn_in, hiddenState=self.hidden_states[l], training=self.training, last_state=(l == top))
+            else:
+                out = rnn(rnn_in, hiddenState=self.hidden_states[l], last_state=(l == top))
             # (bf16 sequences: the state a layer carries over is fp32, like the one it starts from)
             if l == top:
                 self.hidden_states[l] = out.detach().float()
@@ -112,6 +126,8 @@ class RNNClassifierModel(nn.Module):
 
     def loss(self, input, labels):
         """``nn.NLLLoss()(self(input), labels)`` (trainClassifier.py:233-236) with the fused head."""
+        if self._batchnorm:
+            raise NotImplementedError("loss() trains FastGRNNCUDA models; FastGRNNBatchNorm runs in eval mode only")
         if not (self.linear and self.apply_softmax):
             raise RuntimeError("loss() is the Linear + log_softmax + NLLLoss tail (linear=True, apply_softmax=True)")
         h_last = self._last_state(input)
