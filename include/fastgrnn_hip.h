@@ -118,6 +118,15 @@ typedef enum fastgrnn_nonlinearity {
  * fastgrnn_hip_forward_workspace_bytes answer for that call, fastgrnn_hip_kernel_path(d, 1) is -1 (there is no
  * backward) and every other entry point answers FASTGRNN_ERR_UNSUPPORTED. */
 #define FASTGRNN_FLAG_PREACT_AFFINE 1024u
+/* Training-mode BatchNorm cell (the reference's FastGRNNBatchNorm, rnn.py:316-452, every BatchNorm1d in training
+ * mode: batch statistics per frame, running statistics updated T times per call in frame order).  Only the
+ * fastgrnn_hip_bn_train_* entry points below run it and they require this flag; every other entry point answers
+ * FASTGRNN_ERR_UNSUPPORTED for a descriptor that carries it, fastgrnn_hip_kernel_path answers -1 and the two older
+ * workspace queries answer 0.  Kernels: one launch per frame, workgroups split the batch and the last one to arrive
+ * combines their per-unit partial sums in a fixed order (no float atomics: bitwise repeatable; no workgroup waits
+ * for another); two reductions per frame in the forward (the statistics of uC, then of the sum that bn_gate and
+ * bn_update normalise), one in the backward; fp32 operands, fp64 accumulation and statistics.  fastgrnn_hip_bn_train_supported lists the shapes. */
+#define FASTGRNN_FLAG_BN_TRAIN 2048u
 
 /* Problem descriptor.  T = 1 for the single-step operators. */
 typedef struct fastgrnn_desc {
@@ -283,6 +292,63 @@ int fastgrnn_hip_head_xent(int32_t B, int32_t H, int32_t C, const void *h_last, 
  * the wide-layer shapes of the table above, else FASTGRNN_ERR_UNSUPPORTED.  No workspace. */
 int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void *x, const void *w, void *p, int32_t dtype,
                             void *stream);
+
+/* ---- training-mode BatchNorm cell (FASTGRNN_FLAG_BN_TRAIN) --------------------------------------------------------
+ * Per layer and frame t, over the B utterances (reference rnn.py:373-414, BatchNorm1d in training mode):
+ *   wC = x_t . w^T,  uC = h_{t-1} . u^T              (w:[H,F], u:[H,H]: this ABI's [out,in] layout)
+ *   s  = bn_w(wC) + bn_u(uC)                         batch mean, biased batch variance, eps, gamma, beta
+ *   z  = gate(bn_gate(s + bias_gate)),  c = tanh(bn_update(s + bias_update))
+ *   h_t = z . h_{t-1} + (sigmoid(zeta) (1 - z) + sigmoid(nu)) . c
+ * Each BatchNorm layer is passed explicitly.  gamma, beta, running_mean, running_var: [H] fp32.  momentum < 0 means
+ * torch's momentum=None (cumulative average: factor 1 / (num_batches_tracked + t + 1) at frame t, num_batches_tracked
+ * read from the device and NOT incremented -- the caller adds T after the call); otherwise num_batches_tracked may be
+ * NULL.  The forward updates every running statistic T times in frame order, r <- (1-m) r + m stat_t, with the
+ * unbiased variance var * B/(B-1) (bn_gate / bn_update: the mean of s + bias_gate / bias_update). */
+typedef struct fastgrnn_bn_layer {
+  const void *gamma, *beta;
+  void *running_mean, *running_var;
+  const int64_t *num_batches_tracked;
+  double eps, momentum;
+} fastgrnn_bn_layer;
+
+typedef struct fastgrnn_bn_params {
+  fastgrnn_bn_layer w, u, gate, update;          /* bn_w, bn_u, bn_gate, bn_update */
+} fastgrnn_bn_params;
+
+/* gradients of the eight BatchNorm affine parameters, [H] each, overwritten */
+typedef struct fastgrnn_bn_grads {
+  void *d_gamma_w, *d_beta_w, *d_gamma_u, *d_beta_u, *d_gamma_gate, *d_beta_gate, *d_gamma_update, *d_beta_update;
+} fastgrnn_bn_grads;
+
+/* 1 if the descriptor (flags FASTGRNN_FLAG_BN_TRAIN, optionally FASTGRNN_FLAG_BATCH_MAJOR, nothing else) runs on the
+ * training kernels, else 0: fp32, dense, gate sigmoid / relu / tanh, update tanh, B >= 2, any T, and
+ *   H = 128 with F = 32 / 64 / 128 / 256,   H = 256 with F = 32 / 64 / 128
+ * (the FASTGRNN_FLAG_PREACT_AFFINE path-2 table).  Time-major [T,B,.] or batch-major [B,T,.] sequences. */
+int fastgrnn_hip_bn_train_supported(const fastgrnn_desc *d);
+/* workspace bytes of the two calls (0 for an unsupported descriptor) */
+size_t fastgrnn_hip_bn_train_forward_workspace_bytes(const fastgrnn_desc *d);
+size_t fastgrnn_hip_bn_train_backward_workspace_bytes(const fastgrnn_desc *d);
+
+/* forward: x, h0 -> hs (sequences in the layout of d->flags, h0 [B,H]); saved: [T,B,H] fp32 (time-major whatever the
+ * layout: uC of every frame), stats: [T, 9H] fp64 (per frame and unit: mean and biased variance of wC and of uC,
+ * their biased covariance; mean and biased variance of d = bn_w(wC) - beta_w + bn_u(uC) - beta_u, its co-moments with
+ * the normalised wC and uC); both are read by the backward.  Updates the running statistics in bn.  p->w, p->u, bias_gate,
+ * bias_update, zeta, nu as in fastgrnn_params.  Errors: FASTGRNN_ERR_NULL_POINTER, FASTGRNN_ERR_BAD_SHAPE (B < 2:
+ * torch's "more than 1 value per channel"), FASTGRNN_ERR_UNSUPPORTED (flag missing, other flags, dtype, factorised
+ * operands, shapes off the table), FASTGRNN_ERR_WORKSPACE. */
+int fastgrnn_hip_bn_train_forward(const fastgrnn_desc *d, const fastgrnn_params *p, const fastgrnn_bn_params *bn,
+                                  const void *x, const void *h0, void *hs, void *saved, void *stats,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* backward: grad_hs (the layout of hs) -> g->d_x (may be NULL), d_h0, d_w, d_u ([out,in]), d_bias_gate,
+ * d_bias_update, d_zeta, d_nu and the eight BatchNorm affine gradients in bg.  beta_w, beta_u, bias_gate and
+ * bias_update only shift the input of a batch-normalised layer: their gradients are written as exact zeros.
+ * saved / stats: the forward's.  Reads the BatchNorm gammas, betas and eps of bn (not its running statistics). */
+int fastgrnn_hip_bn_train_backward(const fastgrnn_desc *d, const fastgrnn_params *p, const fastgrnn_bn_params *bn,
+                                   const void *grad_hs, const void *x, const void *hs, const void *saved,
+                                   const void *stats, const void *h0, const fastgrnn_grads *g,
+                                   const fastgrnn_bn_grads *bg, void *workspace, size_t workspace_bytes,
+                                   void *stream);
 
 /* Test hook, not part of the reference boundary: one launch that leaves `pattern` in every CU's LDS and vector
  * registers (on-chip state is not cleared between kernels).  tests/test_hip_state_independence.py runs it before the

@@ -10,9 +10,10 @@ from .head import KeywordHead, keyword_loss  # noqa: F401
 from .rnn import (FastGRNNCUDA, FastGRNNCUDACell, FastGRNNFunction,  # noqa: F401
                   FastGRNNUnrollFunction)
 from .batchnorm import FastGRNNBatchNorm, FastGRNNBatchNormCell, fold_batchnorm  # noqa: F401
+from .batchnorm_train import FastGRNNBatchNormCUDA  # noqa: F401
 from .model import RNNClassifierModel  # noqa: F401
 from .graph import GraphedStep  # noqa: F401
 
 __all__ = ["fastgrnn_cuda", "utils", "head", "FastGRNNCUDA", "FastGRNNCUDACell", "FastGRNNFunction",
            "FastGRNNUnrollFunction", "KeywordHead", "keyword_loss", "RNNClassifierModel", "GraphedStep",
-           "FastGRNNBatchNorm", "FastGRNNBatchNormCell", "fold_batchnorm"]
+           "FastGRNNBatchNorm", "FastGRNNBatchNormCell", "fold_batchnorm", "FastGRNNBatchNormCUDA"]

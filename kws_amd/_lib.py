@@ -26,6 +26,7 @@ FLAG_GRAD_LAST = 256          # backward_unroll: grad_h is [B,H], the gradient o
 FLAG_HS_LAST = 512            # forward_unroll (inference, no saved tensors): hs is [B,H] = h_T
 FLAG_BATCH_MAJOR = 16         # sequences are [B,T,.] (batch_first) instead of [T,B,.]
 FLAG_PREACT_AFFINE = 1024     # fastgrnn_hip_forward_unroll_affine: per-unit pre-activation scales (eval-mode BatchNorm)
+FLAG_BN_TRAIN = 2048          # fastgrnn_hip_bn_train_*: the training-mode BatchNorm cell
 
 # include/fastgrnn_hip.h: fastgrnn_nonlinearity.  0..2 are the reference's table
 # (rnn.py:478,751); 3..5 the CPU cell's quantised family (rnn.py:53-60).
@@ -38,6 +39,8 @@ EXPORTS = (
     "fastgrnn_hip_forward", "fastgrnn_hip_backward",
     "fastgrnn_hip_head_workspace_bytes", "fastgrnn_hip_head_xent", "fastgrnn_hip_debug_poison_cu_state",
     "fastgrnn_hip_frame_gemm", "fastgrnn_hip_forward_unroll_affine",
+    "fastgrnn_hip_bn_train_supported", "fastgrnn_hip_bn_train_forward_workspace_bytes",
+    "fastgrnn_hip_bn_train_backward_workspace_bytes", "fastgrnn_hip_bn_train_forward", "fastgrnn_hip_bn_train_backward",
 )
 
 
@@ -57,6 +60,22 @@ class Grads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0",
                  "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2")]
+
+
+class BnLayer(C.Structure):
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p),
+                ("running_var", C.c_void_p), ("num_batches_tracked", C.c_void_p),
+                ("eps", C.c_double), ("momentum", C.c_double)]
+
+
+class BnParams(C.Structure):
+    _fields_ = [("w", BnLayer), ("u", BnLayer), ("gate", BnLayer), ("update", BnLayer)]
+
+
+class BnGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in
+                ("d_gamma_w", "d_beta_w", "d_gamma_u", "d_beta_u", "d_gamma_gate", "d_beta_gate",
+                 "d_gamma_update", "d_beta_update")]
 
 
 class FastGRNNLibraryError(RuntimeError):
@@ -108,6 +127,16 @@ def load():
     lib.fastgrnn_hip_head_xent.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.fastgrnn_hip_frame_gemm.restype = i32
     lib.fastgrnn_hip_frame_gemm.argtypes = [sz, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp]
+    BP, BG = C.POINTER(BnParams), C.POINTER(BnGrads)
+    lib.fastgrnn_hip_bn_train_supported.restype = i32
+    lib.fastgrnn_hip_bn_train_supported.argtypes = [DP]
+    for f in (lib.fastgrnn_hip_bn_train_forward_workspace_bytes, lib.fastgrnn_hip_bn_train_backward_workspace_bytes):
+        f.restype = sz
+        f.argtypes = [DP]
+    lib.fastgrnn_hip_bn_train_forward.restype = i32
+    lib.fastgrnn_hip_bn_train_forward.argtypes = [DP, PP, BP, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.fastgrnn_hip_bn_train_backward.restype = i32
+    lib.fastgrnn_hip_bn_train_backward.argtypes = [DP, PP, BP, vp, vp, vp, vp, vp, vp, GP, BG, vp, sz, vp]
     if lib.fastgrnn_hip_abi_version() != ABI_VERSION:
         raise FastGRNNLibraryError("ABI version mismatch: library %d, binding %d"
                                    % (lib.fastgrnn_hip_abi_version(), ABI_VERSION))

@@ -43,6 +43,28 @@ int pick_path(const fastgrnn_desc* d, int direction) {
   return mfma_supported(*d, direction) ? 1 : 0;
 }
 
+// training-mode BatchNorm cell (FASTGRNN_FLAG_BN_TRAIN)
+int check_bn_layer(const fastgrnn_bn_layer& l, bool forward) {
+  if (!l.gamma || !l.beta) return FASTGRNN_ERR_NULL_POINTER;
+  if (forward && (!l.running_mean || !l.running_var || (l.momentum < 0 && !l.num_batches_tracked)))
+    return FASTGRNN_ERR_NULL_POINTER;
+  if (!(l.eps >= 0) || !(l.momentum <= 1)) return FASTGRNN_ERR_BAD_SHAPE;
+  return FASTGRNN_OK;
+}
+
+int check_bn_train(const fastgrnn_desc* d, const fastgrnn_params* p, const fastgrnn_bn_params* bn, bool forward) {
+  int st = check_desc(d);
+  if (st) return st;
+  if (!(d->flags & FASTGRNN_FLAG_BN_TRAIN)) return FASTGRNN_ERR_UNSUPPORTED;
+  if (d->B < 2) return FASTGRNN_ERR_BAD_SHAPE;                 // torch: more than 1 value per channel when training
+  if ((st = check_params(d, p))) return st;
+  if (!bn) return FASTGRNN_ERR_NULL_POINTER;
+  const fastgrnn_bn_layer* layers[4] = {&bn->w, &bn->u, &bn->gate, &bn->update};
+  for (const fastgrnn_bn_layer* l : layers)
+    if ((st = check_bn_layer(*l, forward))) return st;
+  if (!bn_train_supported(*d)) return FASTGRNN_ERR_UNSUPPORTED;
+  return FASTGRNN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -65,12 +87,13 @@ const char* fastgrnn_hip_status_string(int status) {
 
 int fastgrnn_hip_kernel_path(const fastgrnn_desc* d, int direction) {
   if (check_desc(d) != FASTGRNN_OK) return -1;
+  if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return -1;                               // fastgrnn_hip_bn_train_*
   if ((d->flags & FASTGRNN_FLAG_PREACT_AFFINE) && direction != 0) return -1;   // inference only
   return pick_path(d, direction);
 }
 
 size_t fastgrnn_hip_forward_workspace_bytes(const fastgrnn_desc* d) {
-  if (check_desc(d) != FASTGRNN_OK) return 0;
+  if (check_desc(d) != FASTGRNN_OK || (d->flags & FASTGRNN_FLAG_BN_TRAIN)) return 0;
   switch (pick_path(d, 0)) {
     case 2: return split_forward_ws(*d);
     case 1: return mfma_forward_ws(*d);
@@ -79,7 +102,7 @@ size_t fastgrnn_hip_forward_workspace_bytes(const fastgrnn_desc* d) {
 }
 
 size_t fastgrnn_hip_backward_workspace_bytes(const fastgrnn_desc* d) {
-  if (check_desc(d) != FASTGRNN_OK || (d->flags & FASTGRNN_FLAG_PREACT_AFFINE)) return 0;
+  if (check_desc(d) != FASTGRNN_OK || (d->flags & (FASTGRNN_FLAG_PREACT_AFFINE | FASTGRNN_FLAG_BN_TRAIN))) return 0;
   switch (pick_path(d, 1)) {
     case 2: return split_backward_ws(*d);
     case 1: return mfma_backward_ws(*d);
@@ -95,6 +118,7 @@ int fastgrnn_hip_forward_unroll(const fastgrnn_desc* d, const fastgrnn_params* p
   if ((st = check_params(d, p))) return st;
   if (!x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
   if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // fastgrnn_hip_forward_unroll_affine
+  if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return FASTGRNN_ERR_UNSUPPORTED;        // fastgrnn_hip_bn_train_forward
   if (((d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST)) ||
        d->dtype == FASTGRNN_BF16_IO) && pick_path(d, 0) != 2)
     return FASTGRNN_ERR_UNSUPPORTED;
@@ -118,7 +142,7 @@ int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc* d, const fastgrnn_pa
   if ((st = check_params(d, p))) return st;
   if (!gate_scale || !update_scale || !x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
   if (!(d->flags & FASTGRNN_FLAG_PREACT_AFFINE) || d->dtype == FASTGRNN_BF16_IO || d->w_rank || d->u_rank ||
-      (d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)))
+      (d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST | FASTGRNN_FLAG_BN_TRAIN)))
     return FASTGRNN_ERR_UNSUPPORTED;
   const int path = pick_path(d, 0);
   if ((d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_HS_LAST)) && path != 2) return FASTGRNN_ERR_UNSUPPORTED;
@@ -135,6 +159,7 @@ int fastgrnn_hip_backward_unroll(const fastgrnn_desc* d, const fastgrnn_params* 
   if (st) return st;
   if ((st = check_params(d, p))) return st;
   if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // inference only
+  if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return FASTGRNN_ERR_UNSUPPORTED;        // fastgrnn_hip_bn_train_backward
   const bool preact = (d->flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
   if ((preact || (d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)) || d->dtype == FASTGRNN_BF16_IO) && pick_path(d, 1) != 2)
     return FASTGRNN_ERR_UNSUPPORTED;
@@ -197,6 +222,46 @@ int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void* x, co
   if (!rows_gemm_supported(H, F, false)) return FASTGRNN_ERR_UNSUPPORTED;
   return rows_gemm(rows, H, F, false, x, reinterpret_cast<const float*>(w), p, dtype == FASTGRNN_BF16_IO, false,
                    reinterpret_cast<hipStream_t>(stream));
+}
+
+int fastgrnn_hip_bn_train_supported(const fastgrnn_desc* d) {
+  return check_desc(d) == FASTGRNN_OK && (d->flags & FASTGRNN_FLAG_BN_TRAIN) && bn_train_supported(*d) ? 1 : 0;
+}
+
+size_t fastgrnn_hip_bn_train_forward_workspace_bytes(const fastgrnn_desc* d) {
+  return fastgrnn_hip_bn_train_supported(d) ? bn_train_forward_ws(*d) : 0;
+}
+
+size_t fastgrnn_hip_bn_train_backward_workspace_bytes(const fastgrnn_desc* d) {
+  return fastgrnn_hip_bn_train_supported(d) ? bn_train_backward_ws(*d) : 0;
+}
+
+int fastgrnn_hip_bn_train_forward(const fastgrnn_desc* d, const fastgrnn_params* p, const fastgrnn_bn_params* bn,
+                                  const void* x, const void* h0, void* hs, void* saved, void* stats, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  int st = check_bn_train(d, p, bn, true);
+  if (st) return st;
+  if (!x || !h0 || !hs || !saved || !stats) return FASTGRNN_ERR_NULL_POINTER;
+  if ((st = check_ws(workspace, workspace_bytes, bn_train_forward_ws(*d)))) return st;
+  return bn_train_forward(*d, *p, *bn, x, h0, hs, saved, stats, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int fastgrnn_hip_bn_train_backward(const fastgrnn_desc* d, const fastgrnn_params* p, const fastgrnn_bn_params* bn,
+                                   const void* grad_hs, const void* x, const void* hs, const void* saved,
+                                   const void* stats, const void* h0, const fastgrnn_grads* g,
+                                   const fastgrnn_bn_grads* bg, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+  int st = check_bn_train(d, p, bn, false);
+  if (st) return st;
+  if (!grad_hs || !x || !hs || !saved || !stats || !h0 || !g || !bg) return FASTGRNN_ERR_NULL_POINTER;
+  if (!g->d_h0 || !g->d_w || !g->d_u || !g->d_bias_gate || !g->d_bias_update || !g->d_zeta || !g->d_nu)
+    return FASTGRNN_ERR_NULL_POINTER;
+  if (!bg->d_gamma_w || !bg->d_beta_w || !bg->d_gamma_u || !bg->d_beta_u || !bg->d_gamma_gate || !bg->d_beta_gate ||
+      !bg->d_gamma_update || !bg->d_beta_update)
+    return FASTGRNN_ERR_NULL_POINTER;
+  if ((st = check_ws(workspace, workspace_bytes, bn_train_backward_ws(*d)))) return st;
+  return bn_train_backward(*d, *p, *bn, grad_hs, x, hs, saved, stats, h0, *g, *bg, workspace,
+                           reinterpret_cast<hipStream_t>(stream));
 }
 
 int fastgrnn_hip_debug_poison_cu_state(uint32_t pattern, void* stream) {

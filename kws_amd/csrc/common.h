@@ -138,6 +138,16 @@ size_t head_ws_bytes(int B, int H, int C);
 int head_xent(int B, int H, int C, const void* h_last, const void* fc_w, const void* fc_b, const void* labels,
               void* loss, void* logp, void* d_h, void* d_w, void* d_b, void* ws, hipStream_t s);
 
+// training-mode BatchNorm cell (kernels_bn_train.hip): FASTGRNN_FLAG_BN_TRAIN
+bool bn_train_supported(const fastgrnn_desc& d);
+size_t bn_train_forward_ws(const fastgrnn_desc& d);
+size_t bn_train_backward_ws(const fastgrnn_desc& d);
+int bn_train_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const fastgrnn_bn_params& bn, const void* x,
+                     const void* h0, void* hs, void* saved, void* stats, void* ws, hipStream_t s);
+int bn_train_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const fastgrnn_bn_params& bn,
+                      const void* ghs, const void* x, const void* hs, const void* saved, const void* stats,
+                      const void* h0, const fastgrnn_grads& g, const fastgrnn_bn_grads& bg, void* ws, hipStream_t s);
+
 // test hook (kernels_debug.hip): fill every CU's LDS and vector registers with a bit pattern
 int debug_poison(unsigned pattern, hipStream_t s);
 

@@ -20,6 +20,9 @@ Same constructor arguments, attribute and parameter names as the reference (``rn
   model.py:167-183 does), dense weights only, ``loss()`` stays a ``FastGRNNCUDA`` method.  The head reads the last
   time step of every utterance in both layouts; the reference's batch_first path indexes ``model_output[-1, :, :]``
   (model.py:225-227), i.e. the LAST UTTERANCE's state sequence, for a ``[B,T,H]`` output -- that is not reproduced;
+* ``rnn_name="FastGRNNBatchNormCUDA"`` builds ``kws_amd.FastGRNNBatchNormCUDA`` layers: the same model trained on the
+  GPU (training-mode BatchNorm; ``model.train()`` / ``model.eval()`` pick the mode as for ``"FastGRNNBatchNorm"``),
+  and ``loss()`` trains it through the fused head;
 * the shadow ``rnn_list_`` / ``tracking`` ONNX-export path (model.py:72-84,187-195) is not built (export is
   disabled in the reference, trainClassifier.py:42-52), nor are the rolling hidden-state bags
   (model.py:135-148: data-loader bookkeeping, no arithmetic).
@@ -31,10 +34,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .batchnorm import FastGRNNBatchNorm
+from .batchnorm_train import FastGRNNBatchNormCUDA
 from .head import keyword_loss
 from .rnn import FastGRNNCUDA
 
-_RNN_CLASSES = {"FastGRNNCUDA": FastGRNNCUDA, "FastGRNNBatchNorm": FastGRNNBatchNorm}     # model.py:12-15
+_RNN_CLASSES = {"FastGRNNCUDA": FastGRNNCUDA, "FastGRNNBatchNorm": FastGRNNBatchNorm,     # model.py:12-15
+                "FastGRNNBatchNormCUDA": FastGRNNBatchNormCUDA}
 
 
 class RNNClassifierModel(nn.Module):
@@ -45,8 +50,8 @@ class RNNClassifierModel(nn.Module):
                  wSparsity_list, uSparsity_list, gate_nonlinearity, update_nonlinearity, num_classes=None,
                  linear=True, batch_first=False, apply_softmax=True, device=None):
         if rnn_name not in _RNN_CLASSES:
-            raise ValueError("kws_amd builds the FastGRNNCUDA and FastGRNNBatchNorm model families only (got %r)"
-                             % (rnn_name,))
+            raise ValueError("kws_amd builds the FastGRNNCUDA, FastGRNNBatchNorm and FastGRNNBatchNormCUDA model "
+                             "families only (got %r)" % (rnn_name,))
         if linear and not num_classes:
             raise Exception("num_classes need to be specified if linear is True")      # model.py:54-56
         super().__init__()
@@ -72,7 +77,7 @@ class RNNClassifierModel(nn.Module):
         if self.linear:                                                                 # model.py:85-88
             self.hidden2keyword = nn.Linear(self.hidden_units_list[num_layers - 1], num_classes,
                                             device=self.rnn_list[0].device)
-        self._batchnorm = rnn_name == "FastGRNNBatchNorm"
+        self._batchnorm = rnn_name in ("FastGRNNBatchNorm", "FastGRNNBatchNormCUDA")
         self.init_hidden()
 
     # ---- bookkeeping (model.py:91-156) -----------------------------------------------------------------
@@ -126,7 +131,7 @@ class RNNClassifierModel(nn.Module):
 
     def loss(self, input, labels):
         """``nn.NLLLoss()(self(input), labels)`` (trainClassifier.py:233-236) with the fused head."""
-        if self._batchnorm:
+        if self.rnn_name == "FastGRNNBatchNorm":
             raise NotImplementedError("loss() trains FastGRNNCUDA models; FastGRNNBatchNorm runs in eval mode only")
         if not (self.linear and self.apply_softmax):
             raise RuntimeError("loss() is the Linear + log_softmax + NLLLoss tail (linear=True, apply_softmax=True)")

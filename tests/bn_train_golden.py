@@ -1,0 +1,94 @@
+"""Helpers of the FastGRNNBatchNormCUDA tests: the training fixtures of tests/golden/batchnorm/
+(make_bn_train_golden.py), layers built from them, one training step, and the error bound of the GPU tests."""
+import os
+
+import numpy as np
+import torch
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "batchnorm")
+CASES = ("h128_in32", "h256_in64")
+BNS = ("bn_w", "bn_u", "bn_gate", "bn_update")
+PARAMS = ("W", "U", "bias_gate", "bias_update", "zeta", "nu")
+# gradients that are zero in exact arithmetic (the parameter shifts the input of a batch-normalised layer)
+ZERO_GRADS = ("bias_gate", "bias_update", "bn_w.bias", "bn_u.bias")
+
+
+def load_case(name):
+    d = dict(np.load(os.path.join(GOLDEN, "train_%s.npz" % name)))
+    deq = lambda k: d["q" + k].astype(np.float64) * 2.0 ** -int(d["e" + k])  # noqa: E731
+    d["W"], d["U"], d["x"], d["G"] = deq("W"), deq("U"), deq("x"), deq("G")
+    return d
+
+
+def build_layer(d, device, dtype=torch.float64, batch_first=False):
+    """A FastGRNNBatchNormCUDA layer holding the fixture's parameters and pre-forward BatchNorm state."""
+    from kws_amd import FastGRNNBatchNormCUDA
+    F, H = d["W"].shape
+    m = FastGRNNBatchNormCUDA(F, H, gate_nonlinearity=str(d["meta_gate"]), batch_first=batch_first,
+                              device=device).to(dtype)
+    c = m.cell
+    with torch.no_grad():
+        for k in PARAMS:
+            getattr(c, k).copy_(torch.from_numpy(np.asarray(d[k])))
+        for n in BNS:
+            bn = getattr(c, n)
+            for k in ("weight", "bias", "running_mean", "running_var"):
+                getattr(bn, k).copy_(torch.from_numpy(d["%s_%s" % (n, k)]))
+            bn.num_batches_tracked.fill_(int(d["%s_num_batches_tracked" % n]))
+            bn.eps = float(d["%s_eps" % n])
+            mom = float(d["%s_momentum" % n])
+            bn.momentum = None if np.isnan(mom) else mom
+    return m.train()
+
+
+def named_grads(m):
+    c = m.cell
+    out = {k: getattr(c, k).grad for k in PARAMS}
+    for n in BNS:
+        out[n + ".weight"] = getattr(c, n).weight.grad
+        out[n + ".bias"] = getattr(c, n).bias.grad
+    return out
+
+
+def running(m):
+    c = m.cell
+    out = {}
+    for n in BNS:
+        bn = getattr(c, n)
+        out[n + ".running_mean"] = bn.running_mean.detach().clone()
+        out[n + ".running_var"] = bn.running_var.detach().clone()
+        out[n + ".num_batches_tracked"] = bn.num_batches_tracked.detach().clone()
+    return out
+
+
+def step(m, x, h0, G, torch_ops=False):
+    """One training step of a layer: hs, loss sum(hs * G) backward.  Returns (hs, d_x, d_h0, grads, running)."""
+    x = x.clone().requires_grad_(True)
+    h0 = h0.clone().requires_grad_(True)
+    for p in m.parameters():
+        p.grad = None
+    if torch_ops:
+        hs = m._torch_ops(x, h0, m.batch_first is True)
+    else:
+        hs = m(x, hiddenState=h0, training=True)
+    (hs * G).sum().backward()
+    return hs.detach(), x.grad, h0.grad, named_grads(m), running(m)
+
+
+def fixture_expect(d):
+    """The fixture's results under the names step() returns."""
+    g = {k: d["d" + k] for k in PARAMS}
+    for n in BNS:
+        g[n + ".weight"] = d["d%s_weight" % n]
+        g[n + ".bias"] = d["d%s_bias" % n]
+    r = {}
+    for n in BNS:
+        for k in ("running_mean", "running_var", "num_batches_tracked"):
+            r["%s.%s" % (n, k)] = d["post_%s_%s" % (n, k)]
+    return d["hs"], d["d_x"], d["d_h0"], g, r
+
+
+def bound(ref64, f32_err):
+    """The GPU tests' bound: 4x what the formula loses in fp32, at least 2e-6 of the tensor's scale."""
+    scale = float(np.abs(ref64).max()) if np.size(ref64) else 0.0
+    return max(4.0 * f32_err, 2e-6 * max(scale, 1e-30))
