@@ -61,9 +61,11 @@ typedef enum fastgrnn_dtype {
   /* BASELINE config "bf16 with fp32 master grads" (new; the reference has no such type): the SEQUENCES
    * x, hs, grad_hs and d_x are bf16 (2 bytes per element); parameters, h0 / d_h0, the saved
    * pre-activation and every parameter gradient stay fp32, and so does all arithmetic (the state is
-   * carried in fp32 and only its stored copy is rounded, to nearest even).  Kernel path 2, dense
-   * H=128/F=32; forward without gates or with FASTGRNN_FLAG_SAVE_PREACT, backward with
-   * FASTGRNN_FLAG_SAVE_PREACT; anything else answers FASTGRNN_ERR_UNSUPPORTED. */
+   * carried in fp32 and only its stored copy is rounded, to nearest even).  Kernel path 2 only, on the
+   * shapes its table under fastgrnn_hip_kernel_path lists for bf16 sequences (dense H=128 with F=32/64/128/256,
+   * dense H=256 with F=32/64/128, the low-rank H=256 scans); forward without gates or with
+   * FASTGRNN_FLAG_SAVE_PREACT, backward with FASTGRNN_FLAG_SAVE_PREACT; anything else answers
+   * FASTGRNN_ERR_UNSUPPORTED. */
   FASTGRNN_BF16_IO = 2
 } fastgrnn_dtype;
 
@@ -86,9 +88,9 @@ typedef enum fastgrnn_nonlinearity {
  * shapes of kernel path 2. */
 #define FASTGRNN_FLAG_FWD_4WAVE 8u
 /* Batch-major sequences (the trainer's batch_first layout, rnn.py:812-813,823-825): x, hs, z_s, c_s,
- * grad_hs and d_x are [B,T,.] instead of [T,B,.]; h0/d_h0 stay [B,H].  Kernel path 2 (dense H=128 and the
- * low-rank H=256 scans; not the dense H=256 ones) -- anything else answers FASTGRNN_ERR_UNSUPPORTED and the
- * caller transposes as the reference does.  Removes the transpose(0,1).contiguous() copies around the operator. */
+ * grad_hs and d_x are [B,T,.] instead of [T,B,.]; h0/d_h0 stay [B,H].  Kernel path 2 (dense H=128, dense H=256
+ * with the limits of its table entry -- no bf16 backward -- and the low-rank H=256 scans) -- anything else answers
+ * FASTGRNN_ERR_UNSUPPORTED and the caller transposes as the reference does.  Removes the transpose(0,1).contiguous() copies around the operator. */
 #define FASTGRNN_FLAG_BATCH_MAJOR 16u
 /* x and d_x are [B,F,T]: what the trainer's data loader delivers and permute(2,0,1)s into a [T,B,F] VIEW
  * (trainClassifier.py:204,299) that the reference then copies with .contiguous() (rnn.py:910).  Independent
@@ -127,6 +129,29 @@ typedef enum fastgrnn_nonlinearity {
  * for another); two reductions per frame in the forward (the statistics of uC, then of the sum that bn_gate and
  * bn_update normalise), one in the backward; fp32 operands, fp64 accumulation and statistics.  fastgrnn_hip_bn_train_supported lists the shapes. */
 #define FASTGRNN_FLAG_BN_TRAIN 2048u
+/* Zero-extension onto kernel path 2 (kernels_zext.hip).  A permission, not a demand: it takes effect only for a
+ * descriptor that answers path 0 without it and whose padded form (below) answers path 2 -- for the backward, and for
+ * a forward under FASTGRNN_FLAG_SAVE_PREACT, in both directions (the backward always runs under SAVE_PREACT on this
+ * route).  In every other case the call behaves bit for bit as without the flag, and no call is refused because of it:
+ * shapes already on path 2, fp32 H=64/F=32 (path 1), fp64, H or F beyond what the padding reaches,
+ * FASTGRNN_FLAG_FORCE_GENERIC / FORCE_F32_MFMA / X_BFT / PREACT_AFFINE / BN_TRAIN, and a forward that passes the
+ * reference's (z_s, h_prime_s) pair without FASTGRNN_FLAG_SAVE_PREACT.
+ *   Padded shape: Hp = 128 for H <= 128, 256 for 129 <= H <= 256; Fp = the smallest of 32/64/128/256 that is >= F
+ *   and puts the padded descriptor on path 2.  Ranks, gates, dtype (fp32 or bf16 sequences), BATCH_MAJOR, GRAD_LAST
+ *   and HS_LAST carry over; factorised cells are padded factor by factor (W1 [r,Fp], W2 [Hp,r], U1 [r,Hp], U2 [Hp,r]).
+ *   W, U, the biases, h0, x and grad_hs are copied into zero-filled padded buffers in the workspace, the path-2
+ *   kernels run on them, and hs, d_x, d_h0 and the parameter gradients are compacted back.  A padded unit has
+ *   pre-activation 0 at every step and contributes exact zeros to every gradient, so the real units get exactly what
+ *   the library computes for the explicitly padded problem.
+ *   Every caller-visible tensor keeps its unpadded shape and layout, with one exception: under
+ *   FASTGRNN_FLAG_SAVE_PREACT the forward's z_s is an OPAQUE 256-B aligned buffer of
+ *   fastgrnn_hip_zero_extend_plan()'s saved_bytes (the padded pre-activation, the padded hidden-state sequence when
+ *   H != Hp, and the low-rank scans' rank-space vector where the padded cell runs on them); c_s is ignored, the
+ *   backward reads the buffer back through z_s (c_s ignored, may be NULL) and on this route z_s must not be NULL.
+ *   fastgrnn_hip_kernel_path and both workspace queries answer for the padded route where it applies.  d_x may be
+ *   NULL when the padded shape allows it (the plan's dx_optional).
+ *   Not covered: PREACT_AFFINE and BN_TRAIN cells, fp64, X_BFT frames, H > 256, F > 256 and H > 128 with F > 128. */
+#define FASTGRNN_FLAG_ZERO_EXTEND 4096u
 
 /* Problem descriptor.  T = 1 for the single-step operators. */
 typedef struct fastgrnn_desc {
@@ -209,6 +234,8 @@ const char *fastgrnn_hip_status_string(int status);
  *                                 H=128 with F=32/64/128/256 and dense H=256 with F=32/64/128; time- or batch-major,
  *                                 FASTGRNN_FLAG_HS_LAST.  Every other fp32 / fp64 cell (other shapes, quantised
  *                                 nonlinearity codes) runs on path 0, time-major without FASTGRNN_FLAG_HS_LAST.
+ *   FASTGRNN_FLAG_ZERO_EXTEND     every other fp32 / bf16-sequence cell with H <= 256 whose zero-padded shape (Hp, Fp)
+ *                                 is one of the above: run as that shape (copies around the scans, see the flag).
  * Under FASTGRNN_FLAG_SAVE_PREACT a factorised forward with both ranks in 1..16 also writes, through c_s, the rank-space vector
  * [U1.h_{t-1} | W1.x_t] as a time-major fp32 [T*B, 32] tensor (each half zero-extended to 16 columns) that the
  * backward takes back through c_s (with z_s, the pre-activation): its factor gradients are contracted inside the
@@ -216,6 +243,19 @@ const char *fastgrnn_hip_status_string(int status);
  * recompute the pre-activation from c_s is gone: the scan that also contracts the factor gradients has neither the
  * registers nor the LDS for a second copy of [U2|W2]; z_s = NULL is FASTGRNN_ERR_NULL_POINTER again.) */
 int fastgrnn_hip_kernel_path(const fastgrnn_desc *d, int direction);
+
+/* FASTGRNN_FLAG_ZERO_EXTEND: what the flag does for a descriptor.  forward / backward: 1 where forward_unroll /
+ * backward_unroll take the padded route (backward only under FASTGRNN_FLAG_SAVE_PREACT); Hp, Fp: the padded shape
+ * (0 where the route does not apply); dx_optional: 1 where the backward accepts d_x == NULL; saved_bytes: the size
+ * of the opaque z_s buffer under FASTGRNN_FLAG_SAVE_PREACT (0 otherwise).  Returns FASTGRNN_OK, or
+ * FASTGRNN_ERR_NULL_POINTER / a descriptor error (out zeroed). */
+typedef struct fastgrnn_zext_plan {
+  int32_t forward, backward;
+  int32_t Hp, Fp;
+  int32_t dx_optional, reserved;
+  size_t saved_bytes;
+} fastgrnn_zext_plan;
+int fastgrnn_hip_zero_extend_plan(const fastgrnn_desc *d, fastgrnn_zext_plan *out);
 
 /* Workspace sizes in bytes (0 is a valid answer).  Workspace must be 256-B aligned.  The forward answer covers a
  * call without auxiliary outputs; dense H=128 layers with F > 32 park the frame product X.W^T in z_s / c_s when

@@ -27,6 +27,7 @@ FLAG_HS_LAST = 512            # forward_unroll (inference, no saved tensors): hs
 FLAG_BATCH_MAJOR = 16         # sequences are [B,T,.] (batch_first) instead of [T,B,.]
 FLAG_PREACT_AFFINE = 1024     # fastgrnn_hip_forward_unroll_affine: per-unit pre-activation scales (eval-mode BatchNorm)
 FLAG_BN_TRAIN = 2048          # fastgrnn_hip_bn_train_*: the training-mode BatchNorm cell
+FLAG_ZERO_EXTEND = 4096       # odd H <= 256 / F on kernel path 2 by zero-padding to a path-2 shape (a permission)
 
 # include/fastgrnn_hip.h: fastgrnn_nonlinearity.  0..2 are the reference's table
 # (rnn.py:478,751); 3..5 the CPU cell's quantised family (rnn.py:53-60).
@@ -41,6 +42,7 @@ EXPORTS = (
     "fastgrnn_hip_frame_gemm", "fastgrnn_hip_forward_unroll_affine",
     "fastgrnn_hip_bn_train_supported", "fastgrnn_hip_bn_train_forward_workspace_bytes",
     "fastgrnn_hip_bn_train_backward_workspace_bytes", "fastgrnn_hip_bn_train_forward", "fastgrnn_hip_bn_train_backward",
+    "fastgrnn_hip_zero_extend_plan",
 )
 
 
@@ -76,6 +78,12 @@ class BnGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("d_gamma_w", "d_beta_w", "d_gamma_u", "d_beta_u", "d_gamma_gate", "d_beta_gate",
                  "d_gamma_update", "d_beta_update")]
+
+
+class ZextPlan(C.Structure):
+    """fastgrnn_zext_plan: what FLAG_ZERO_EXTEND does for a descriptor."""
+    _fields_ = [("forward", C.c_int32), ("backward", C.c_int32), ("Hp", C.c_int32), ("Fp", C.c_int32),
+                ("dx_optional", C.c_int32), ("reserved", C.c_int32), ("saved_bytes", C.c_size_t)]
 
 
 class FastGRNNLibraryError(RuntimeError):
@@ -137,6 +145,8 @@ def load():
     lib.fastgrnn_hip_bn_train_forward.argtypes = [DP, PP, BP, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.fastgrnn_hip_bn_train_backward.restype = i32
     lib.fastgrnn_hip_bn_train_backward.argtypes = [DP, PP, BP, vp, vp, vp, vp, vp, vp, GP, BG, vp, sz, vp]
+    lib.fastgrnn_hip_zero_extend_plan.restype = i32
+    lib.fastgrnn_hip_zero_extend_plan.argtypes = [DP, C.POINTER(ZextPlan)]
     if lib.fastgrnn_hip_abi_version() != ABI_VERSION:
         raise FastGRNNLibraryError("ABI version mismatch: library %d, binding %d"
                                    % (lib.fastgrnn_hip_abi_version(), ABI_VERSION))

@@ -43,6 +43,42 @@ int pick_path(const fastgrnn_desc* d, int direction) {
   return mfma_supported(*d, direction) ? 1 : 0;
 }
 
+// the descriptor without FASTGRNN_FLAG_ZERO_EXTEND: what every call runs on where the flag does not take effect
+fastgrnn_desc plain(const fastgrnn_desc* d) {
+  fastgrnn_desc u = *d;
+  u.flags &= ~FASTGRNN_FLAG_ZERO_EXTEND;
+  return u;
+}
+
+// FASTGRNN_FLAG_ZERO_EXTEND (include/fastgrnn_hip.h): true when the forward takes the padded route, with *e the padded
+// descriptor; *bwd: the backward takes it too (FASTGRNN_FLAG_SAVE_PREACT).  d has passed check_desc.
+bool zext_route(const fastgrnn_desc* d, fastgrnn_desc* e, bool* bwd) {
+  if (!(d->flags & FASTGRNN_FLAG_ZERO_EXTEND)) return false;
+  if (d->dtype != FASTGRNN_F32 && d->dtype != FASTGRNN_BF16_IO) return false;
+  if (d->flags & (FASTGRNN_FLAG_FORCE_GENERIC | FASTGRNN_FLAG_FORCE_F32_MFMA | FASTGRNN_FLAG_X_BFT |
+                  FASTGRNN_FLAG_PREACT_AFFINE | FASTGRNN_FLAG_BN_TRAIN))
+    return false;
+  if (d->H > 256 || d->F > 256) return false;
+  const fastgrnn_desc u = plain(d);
+  const bool preact = (d->flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
+  if (pick_path(&u, 0) != 0 || (preact && pick_path(&u, 1) != 0)) return false;
+  const int Hp = d->H <= 128 ? 128 : 256;
+  for (int Fp = 32; Fp <= 256; Fp *= 2) {
+    if (Fp < d->F) continue;
+    // element offsets of the padded copies are 32-bit (kernels_zext.hip)
+    if ((double)d->T * d->B * (Hp > Fp ? Hp : Fp) >= 1073741824.0) return false;
+    fastgrnn_desc c = u;
+    c.H = Hp;
+    c.F = Fp;
+    if (pick_path(&c, 0) == 2 && (!preact || pick_path(&c, 1) == 2)) {
+      *e = c;
+      *bwd = preact;
+      return true;
+    }
+  }
+  return false;
+}
+
 // training-mode BatchNorm cell (FASTGRNN_FLAG_BN_TRAIN)
 int check_bn_layer(const fastgrnn_bn_layer& l, bool forward) {
   if (!l.gamma || !l.beta) return FASTGRNN_ERR_NULL_POINTER;
@@ -85,24 +121,49 @@ const char* fastgrnn_hip_status_string(int status) {
   }
 }
 
-int fastgrnn_hip_kernel_path(const fastgrnn_desc* d, int direction) {
-  if (check_desc(d) != FASTGRNN_OK) return -1;
+int fastgrnn_hip_kernel_path(const fastgrnn_desc* dz, int direction) {
+  if (check_desc(dz) != FASTGRNN_OK) return -1;
+  fastgrnn_desc e;
+  bool bwd = false;
+  if (zext_route(dz, &e, &bwd) && (direction == 0 || bwd)) return 2;
+  const fastgrnn_desc u = plain(dz);
+  const fastgrnn_desc* d = &u;
   if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return -1;                               // fastgrnn_hip_bn_train_*
   if ((d->flags & FASTGRNN_FLAG_PREACT_AFFINE) && direction != 0) return -1;   // inference only
   return pick_path(d, direction);
 }
 
-size_t fastgrnn_hip_forward_workspace_bytes(const fastgrnn_desc* d) {
-  if (check_desc(d) != FASTGRNN_OK || (d->flags & FASTGRNN_FLAG_BN_TRAIN)) return 0;
-  switch (pick_path(d, 0)) {
-    case 2: return split_forward_ws(*d);
-    case 1: return mfma_forward_ws(*d);
-    default: return generic_forward_ws(*d);
+size_t fastgrnn_hip_forward_workspace_bytes(const fastgrnn_desc* dz) {
+  if (check_desc(dz) != FASTGRNN_OK) return 0;
+  const fastgrnn_desc u = plain(dz);
+  const fastgrnn_desc* d = &u;
+  size_t zext = 0;
+  fastgrnn_desc e;
+  bool bwd = false;
+  if (zext_route(dz, &e, &bwd)) {
+    zext = zext_forward_ws(*dz, e);
+    // under SAVE_PREACT every forward takes the padded route; without it a forward given the (z_s, h_prime_s) pair
+    // runs as without the flag, so the answer covers that call as well
+    if (dz->flags & FASTGRNN_FLAG_SAVE_PREACT) return zext;
   }
+  if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return 0;
+  size_t n;
+  switch (pick_path(d, 0)) {
+    case 2: n = split_forward_ws(*d); break;
+    case 1: n = mfma_forward_ws(*d); break;
+    default: n = generic_forward_ws(*d); break;
+  }
+  return n > zext ? n : zext;
 }
 
-size_t fastgrnn_hip_backward_workspace_bytes(const fastgrnn_desc* d) {
-  if (check_desc(d) != FASTGRNN_OK || (d->flags & (FASTGRNN_FLAG_PREACT_AFFINE | FASTGRNN_FLAG_BN_TRAIN))) return 0;
+size_t fastgrnn_hip_backward_workspace_bytes(const fastgrnn_desc* dz) {
+  if (check_desc(dz) != FASTGRNN_OK) return 0;
+  fastgrnn_desc e;
+  bool bwd = false;
+  if (zext_route(dz, &e, &bwd) && bwd) return zext_backward_ws(*dz, e);
+  const fastgrnn_desc u = plain(dz);
+  const fastgrnn_desc* d = &u;
+  if (d->flags & (FASTGRNN_FLAG_PREACT_AFFINE | FASTGRNN_FLAG_BN_TRAIN)) return 0;
   switch (pick_path(d, 1)) {
     case 2: return split_backward_ws(*d);
     case 1: return mfma_backward_ws(*d);
@@ -110,11 +171,39 @@ size_t fastgrnn_hip_backward_workspace_bytes(const fastgrnn_desc* d) {
   }
 }
 
-int fastgrnn_hip_forward_unroll(const fastgrnn_desc* d, const fastgrnn_params* p, const void* x, const void* h0,
+int fastgrnn_hip_zero_extend_plan(const fastgrnn_desc* d, fastgrnn_zext_plan* out) {
+  if (!out) return FASTGRNN_ERR_NULL_POINTER;
+  *out = fastgrnn_zext_plan{};
+  const int st = check_desc(d);
+  if (st) return st;
+  fastgrnn_desc e;
+  bool bwd = false;
+  if (!zext_route(d, &e, &bwd)) return FASTGRNN_OK;
+  out->forward = 1;
+  out->backward = bwd ? 1 : 0;
+  out->Hp = e.H;
+  out->Fp = e.F;
+  out->dx_optional = split_dx_optional(e) ? 1 : 0;
+  out->saved_bytes = zext_saved_bytes(*d, e);
+  return FASTGRNN_OK;
+}
+
+int fastgrnn_hip_forward_unroll(const fastgrnn_desc* dz, const fastgrnn_params* p, const void* x, const void* h0,
                                 void* hs, void* z_s, void* c_s, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-  int st = check_desc(d);
+  int st = check_desc(dz);
   if (st) return st;
+  fastgrnn_desc e;
+  bool bwd = false;
+  const bool zpreact = (dz->flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
+  if (zext_route(dz, &e, &bwd) && (zpreact || !z_s)) {      // (the reference's pair: as without the flag)
+    if ((st = check_params(dz, p))) return st;
+    if (!x || !h0 || !hs || (zpreact && !z_s)) return FASTGRNN_ERR_NULL_POINTER;
+    if ((st = check_ws(workspace, workspace_bytes, zext_forward_ws(*dz, e)))) return st;
+    return zext_forward(*dz, e, *p, x, h0, hs, z_s, workspace, reinterpret_cast<hipStream_t>(stream));
+  }
+  const fastgrnn_desc u = plain(dz);
+  const fastgrnn_desc* d = &u;
   if ((st = check_params(d, p))) return st;
   if (!x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
   if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // fastgrnn_hip_forward_unroll_affine
@@ -134,11 +223,13 @@ int fastgrnn_hip_forward_unroll(const fastgrnn_desc* d, const fastgrnn_params* p
   }
 }
 
-int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc* d, const fastgrnn_params* p, const void* gate_scale,
+int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc* dz, const fastgrnn_params* p, const void* gate_scale,
                                        const void* update_scale, const void* x, const void* h0, void* hs,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-  int st = check_desc(d);
+  int st = check_desc(dz);
   if (st) return st;
+  const fastgrnn_desc u = plain(dz);
+  const fastgrnn_desc* d = &u;
   if ((st = check_params(d, p))) return st;
   if (!gate_scale || !update_scale || !x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
   if (!(d->flags & FASTGRNN_FLAG_PREACT_AFFINE) || d->dtype == FASTGRNN_BF16_IO || d->w_rank || d->u_rank ||
@@ -152,11 +243,26 @@ int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc* d, const fastgrnn_pa
   return generic_forward(*d, *p, x, h0, hs, nullptr, nullptr, workspace, s, gate_scale, update_scale);
 }
 
-int fastgrnn_hip_backward_unroll(const fastgrnn_desc* d, const fastgrnn_params* p, const void* grad_hs,
+int fastgrnn_hip_backward_unroll(const fastgrnn_desc* dz, const fastgrnn_params* p, const void* grad_hs,
                                  const void* x, const void* hs, const void* z_s, const void* c_s, const void* h0,
                                  const fastgrnn_grads* g, void* workspace, size_t workspace_bytes, void* stream) {
-  int st = check_desc(d);
+  int st = check_desc(dz);
   if (st) return st;
+  fastgrnn_desc e;
+  bool bwd = false;
+  if (zext_route(dz, &e, &bwd) && bwd) {
+    if ((st = check_params(dz, p))) return st;
+    if (!grad_hs || !x || !hs || !z_s || !h0 || !g) return FASTGRNN_ERR_NULL_POINTER;
+    if ((!g->d_x && !split_dx_optional(e)) || !g->d_bias_gate || !g->d_bias_update || !g->d_zeta || !g->d_nu ||
+        !g->d_h0)
+      return FASTGRNN_ERR_NULL_POINTER;
+    if (dz->w_rank ? (!g->d_w1 || !g->d_w2) : !g->d_w) return FASTGRNN_ERR_NULL_POINTER;
+    if (dz->u_rank ? (!g->d_u1 || !g->d_u2) : !g->d_u) return FASTGRNN_ERR_NULL_POINTER;
+    if ((st = check_ws(workspace, workspace_bytes, zext_backward_ws(*dz, e)))) return st;
+    return zext_backward(*dz, e, *p, grad_hs, x, hs, z_s, h0, *g, workspace, reinterpret_cast<hipStream_t>(stream));
+  }
+  const fastgrnn_desc u = plain(dz);
+  const fastgrnn_desc* d = &u;
   if ((st = check_params(d, p))) return st;
   if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // inference only
   if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return FASTGRNN_ERR_UNSUPPORTED;        // fastgrnn_hip_bn_train_backward
@@ -224,21 +330,26 @@ int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void* x, co
                    reinterpret_cast<hipStream_t>(stream));
 }
 
-int fastgrnn_hip_bn_train_supported(const fastgrnn_desc* d) {
-  return check_desc(d) == FASTGRNN_OK && (d->flags & FASTGRNN_FLAG_BN_TRAIN) && bn_train_supported(*d) ? 1 : 0;
+int fastgrnn_hip_bn_train_supported(const fastgrnn_desc* dz) {
+  if (check_desc(dz) != FASTGRNN_OK) return 0;
+  const fastgrnn_desc d = plain(dz);
+  return (d.flags & FASTGRNN_FLAG_BN_TRAIN) && bn_train_supported(d) ? 1 : 0;
 }
 
 size_t fastgrnn_hip_bn_train_forward_workspace_bytes(const fastgrnn_desc* d) {
-  return fastgrnn_hip_bn_train_supported(d) ? bn_train_forward_ws(*d) : 0;
+  return fastgrnn_hip_bn_train_supported(d) ? bn_train_forward_ws(plain(d)) : 0;
 }
 
 size_t fastgrnn_hip_bn_train_backward_workspace_bytes(const fastgrnn_desc* d) {
-  return fastgrnn_hip_bn_train_supported(d) ? bn_train_backward_ws(*d) : 0;
+  return fastgrnn_hip_bn_train_supported(d) ? bn_train_backward_ws(plain(d)) : 0;
 }
 
-int fastgrnn_hip_bn_train_forward(const fastgrnn_desc* d, const fastgrnn_params* p, const fastgrnn_bn_params* bn,
+int fastgrnn_hip_bn_train_forward(const fastgrnn_desc* dz, const fastgrnn_params* p, const fastgrnn_bn_params* bn,
                                   const void* x, const void* h0, void* hs, void* saved, void* stats, void* workspace,
                                   size_t workspace_bytes, void* stream) {
+  if (!dz) return FASTGRNN_ERR_NULL_POINTER;
+  const fastgrnn_desc u = plain(dz);
+  const fastgrnn_desc* d = &u;
   int st = check_bn_train(d, p, bn, true);
   if (st) return st;
   if (!x || !h0 || !hs || !saved || !stats) return FASTGRNN_ERR_NULL_POINTER;
@@ -246,11 +357,14 @@ int fastgrnn_hip_bn_train_forward(const fastgrnn_desc* d, const fastgrnn_params*
   return bn_train_forward(*d, *p, *bn, x, h0, hs, saved, stats, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
-int fastgrnn_hip_bn_train_backward(const fastgrnn_desc* d, const fastgrnn_params* p, const fastgrnn_bn_params* bn,
+int fastgrnn_hip_bn_train_backward(const fastgrnn_desc* dz, const fastgrnn_params* p, const fastgrnn_bn_params* bn,
                                    const void* grad_hs, const void* x, const void* hs, const void* saved,
                                    const void* stats, const void* h0, const fastgrnn_grads* g,
                                    const fastgrnn_bn_grads* bg, void* workspace, size_t workspace_bytes,
                                    void* stream) {
+  if (!dz) return FASTGRNN_ERR_NULL_POINTER;
+  const fastgrnn_desc u = plain(dz);
+  const fastgrnn_desc* d = &u;
   int st = check_bn_train(d, p, bn, false);
   if (st) return st;
   if (!grad_hs || !x || !hs || !saved || !stats || !h0 || !g || !bg) return FASTGRNN_ERR_NULL_POINTER;

@@ -132,6 +132,17 @@ int densified_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const vo
 int densified_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
                        const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s);
 
+// FASTGRNN_FLAG_ZERO_EXTEND (kernels_zext.hip): the cell d run as the padded cell e (e.H, e.F = Hp, Fp; a path-2
+// descriptor) -- padded copies of the operands, the split-precision code on them, the results compacted back
+size_t zext_forward_ws(const fastgrnn_desc& d, const fastgrnn_desc& e);
+size_t zext_backward_ws(const fastgrnn_desc& d, const fastgrnn_desc& e);
+size_t zext_saved_bytes(const fastgrnn_desc& d, const fastgrnn_desc& e);
+int zext_forward(const fastgrnn_desc& d, const fastgrnn_desc& e, const fastgrnn_params& p, const void* x,
+                 const void* h0, void* hs, void* zs, void* ws, hipStream_t s);
+int zext_backward(const fastgrnn_desc& d, const fastgrnn_desc& e, const fastgrnn_params& p, const void* ghs,
+                  const void* x, const void* hs, const void* zs, const void* h0, const fastgrnn_grads& g, void* ws,
+                  hipStream_t s);
+
 // classifier head on the last state: Linear + log_softmax + NLL, forward and backward (kernels_head.hip)
 bool head_supported(int B, int H, int C);
 size_t head_ws_bytes(int B, int H, int C);

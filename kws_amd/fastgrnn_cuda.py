@@ -120,7 +120,7 @@ def _describe(T, B, F, H, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu
                          _ptr(w1 if w_lr else None), _ptr(w2 if w_lr else None),
                          _ptr(u1 if u_lr else None), _ptr(u2 if u_lr else None),
                          _ptr(bias_gate), _ptr(bias_update), _ptr(zeta), _ptr(nu))
-    return desc, params, w_lr, u_lr          # desc: the cached plan tuple (struct, paths, workspace sizes)
+    return desc, params, w_lr, u_lr          # desc: the cached plan tuple (struct, paths, workspace sizes, zext plan)
 
 
 # Scratch workspace, kept per (device, stream) and grown on demand: its contents never outlive a call and every use
@@ -144,12 +144,19 @@ def _workspace(nbytes, device):
 def _plan(T, B, F, H, rw, ru, gate_nl, update_nl, dtype_code, flags):
     """Everything about a descriptor that does not depend on the tensors: the C struct itself, the kernel family
     each direction dispatches to and the workspace sizes (pure functions of the descriptor in the C ABI).  One
-    dictionary lookup per call instead of four ctypes round trips."""
+    dictionary lookup per call instead of four ctypes round trips.  The last entry is the FLAG_ZERO_EXTEND plan
+    (``_lib.ZextPlan``) where that flag takes the padded route for the forward, else None."""
     lib = _lib.load()
     desc = _lib.Desc(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), dtype_code, int(flags))
+    zx = None
+    if flags & _lib.FLAG_ZERO_EXTEND:
+        zx = _lib.ZextPlan()
+        _lib.check(lib.fastgrnn_hip_zero_extend_plan(C.byref(desc), C.byref(zx)), "fastgrnn zero_extend_plan")
+        if not zx.forward:
+            zx = None
     return (desc, lib.fastgrnn_hip_kernel_path(C.byref(desc), 0), lib.fastgrnn_hip_kernel_path(C.byref(desc), 1),
             int(lib.fastgrnn_hip_forward_workspace_bytes(C.byref(desc))),
-            int(lib.fastgrnn_hip_backward_workspace_bytes(C.byref(desc))))
+            int(lib.fastgrnn_hip_backward_workspace_bytes(C.byref(desc))), zx)
 
 
 _cliff_warned = set()
@@ -194,6 +201,16 @@ def kernel_path(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=to
     return _plan(T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype], int(flags))[1 + int(direction)]
 
 
+def zero_extend_plan(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=torch.float32, flags=0):
+    """What FLAG_ZERO_EXTEND does for a descriptor (include/fastgrnn_hip.h, fastgrnn_hip_zero_extend_plan): a dict with
+    ``forward`` / ``backward`` (the padded route is taken), ``Hp``, ``Fp``, ``dx_optional`` and ``saved_bytes`` (the
+    opaque z_s buffer under FLAG_SAVE_PREACT).  All zero where the route does not apply."""
+    zx = _plan(T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype],
+               int(flags) | _lib.FLAG_ZERO_EXTEND)[5]
+    names = ("forward", "backward", "Hp", "Fp", "dx_optional", "saved_bytes")
+    return {n: (int(getattr(zx, n)) if zx is not None else 0) for n in names}
+
+
 # Signatures (shapes, dtypes, flags of one call) that have passed the full argument checks once.  A training loop makes
 # the same call thousands of times: after the first one only what can change from call to call without changing the
 # signature is re-checked (device, contiguity), and the checks that are pure functions of the signature are skipped --
@@ -218,7 +235,7 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
            zeta.dtype, nu.dtype, gate_nl, update_nl, flags, want_gates, input.device.index)
     ent = _seen.get(sig) if _use_seen else None
     if ent is not None and _all_dense_cuda(input, h0, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu):
-        plan, w_lr, u_lr, oshape, hshape, rank_space, nbytes, T, B, H = ent
+        plan, w_lr, u_lr, oshape, hshape, rank_space, nbytes, T, B, H, zsaved = ent
         desc = plan[0]
         params = _lib.Params(_ptr(None if w_lr else w), _ptr(None if u_lr else u),
                              _ptr(w1 if w_lr else None), _ptr(w2 if w_lr else None),
@@ -229,7 +246,10 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
         pdt = h0.dtype
         with torch.cuda.device(dev):
             hs = torch.empty(hshape, dtype=input.dtype, device=dev)
-            zs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates or preact) else None
+            if zsaved:
+                zs = torch.empty(zsaved, dtype=torch.uint8, device=dev)
+            else:
+                zs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates or preact) else None
             cs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates and not preact) else None
             if rank_space:
                 cs = torch.empty((T * B, 32), dtype=pdt, device=dev)
@@ -282,20 +302,29 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
                            "(want_gates=False and no FLAG_SAVE_PREACT)")
     with torch.cuda.device(dev):
         hs = torch.empty((B, H) if hs_last else oshape, dtype=input.dtype, device=dev)
-        zs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates or preact) else None
+        # FLAG_ZERO_EXTEND on the padded route: under FLAG_SAVE_PREACT the saved tensor is one opaque buffer
+        # (fastgrnn_hip.h: the padded pre-activation, the padded hidden states and, for the low-rank scans, the
+        # rank-space vector) that the backward takes back as z
+        zx = plan[5]
+        zroute = zx is not None and (preact or not want_gates)
+        zsaved = int(zx.saved_bytes) if (zroute and preact) else 0
+        if zsaved:
+            zs = torch.empty(zsaved, dtype=torch.uint8, device=dev)
+        else:
+            zs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates or preact) else None
         cs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates and not preact) else None
-        if preact and desc.H == 256 and desc.F == 32 and 0 < desc.w_rank <= 16 and 0 < desc.u_rank <= 16:
+        if preact and not zsaved and desc.H == 256 and desc.F == 32 and 0 < desc.w_rank <= 16 and 0 < desc.u_rank <= 16:
             # factorised operands: the forward also saves the rank-space vector [U1.h | W1.x] per step, always
             # time-major and zero-extended to 16 + 16 columns (an opaque tensor for the backward)
             cs = torch.empty((T * B, 32), dtype=pdt, device=dev)
         # (dense H=128 layers with a wide input keep the frame product in the workspace only when no auxiliary
         # output is requested: include/fastgrnn_hip.h, forward workspace)
         wide = desc.H == 128 and desc.F > 32 and not desc.w_rank and not desc.u_rank
-        nbytes = 0 if (plan[1] == 2 and zs is not None and wide) else plan[3]
+        nbytes = 0 if (plan[1] == 2 and zs is not None and wide and not zroute) else plan[3]
         ws, wsp = _workspace(nbytes, dev)
         fn = lib.fastgrnn_hip_forward_unroll if unrolled else lib.fastgrnn_hip_forward
         _seen[sig] = (plan, _present(w1), _present(u1), oshape, (B, H) if hs_last else oshape,
-                      bool(preact and cs is not None), nbytes, T, B, H)
+                      bool(preact and cs is not None), nbytes, T, B, H, zsaved)
         with _Timed("forward", dev):
             st = fn(C.byref(desc), C.byref(params), _ptr(input), _ptr(h0), _ptr(hs), _ptr(zs), _ptr(cs),
                     wsp, nbytes, _stream(dev))
@@ -379,13 +408,15 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
         return _launch_backward(lib, plan, tail, unrolled, preact, grad_h, input, hs_or_old_h, z,
                                 z if preact else h_prime, h_prime if rs else None, h0, w, u, w1, w2, u1, u2,
                                 bias_gate if preact else zeta, bias_update if preact else zeta, zeta, nu, need_dx)
+    # FLAG_ZERO_EXTEND's padded route: z is the forward's opaque saved buffer (uint8), h_prime is not used
+    zsaved = preact and bool(flags & _lib.FLAG_ZERO_EXTEND) and z.dtype == torch.uint8
     if preact:
         if bias_gate is None or bias_update is None:
             raise RuntimeError("FLAG_SAVE_PREACT backward needs bias_gate and bias_update")
         # (the register-resident low-rank scans, both ranks 1..16, save a rank-space vector; other factorised cells
         # run on the dense kernels and save the pre-activation alone)
         rank_space = h_prime if (_present(w1) and _present(u1) and w1.shape[0] <= 16 and u1.shape[0] <= 16
-                                 and tuple(w1.shape[1:]) == (32,) and u1.shape[1] == 256) else None
+                                 and tuple(w1.shape[1:]) == (32,) and u1.shape[1] == 256 and not zsaved) else None
         if rank_space is not None:
             _check_input(rank_space, "rank_space")
             _expect(rank_space, (hs_or_old_h.numel() // hs_or_old_h.shape[-1], 32), "rank_space")
@@ -406,7 +437,9 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
         # FLAG_GRAD_LAST: the gradient of the last state only (the classifier head's view, model.py:227)
         _expect(grad_h, (B, H) if flags & _lib.FLAG_GRAD_LAST else lead + (H,), "grad_h")
         _expect(hs_or_old_h, lead + (H,), "hidden_states")
-        _expect(z, lead + (H,), "z"); _expect(h_prime, lead + (H,), "h_prime"); _expect(h0, (B, H), "initial_h")
+        if not zsaved:
+            _expect(z, lead + (H,), "z"); _expect(h_prime, lead + (H,), "h_prime")
+        _expect(h0, (B, H), "initial_h")
     else:
         T = 1
         B, F = input.shape
@@ -415,7 +448,8 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
         _expect(z, (B, H), "z"); _expect(h_prime, (B, H), "h_prime")
     dt = input.dtype
     pdt = _param_dtype(dt)
-    for t, want in ((grad_h, dt), (hs_or_old_h, dt if unrolled else pdt), (z, pdt), (h_prime, pdt), (h0, pdt)):
+    for t, want in ((grad_h, dt), (hs_or_old_h, dt if unrolled else pdt), (z, torch.uint8 if zsaved else pdt),
+                    (h_prime, torch.uint8 if zsaved else pdt), (h0, pdt)):
         if t.dtype != want:
             raise RuntimeError("fastgrnn backward: operand dtypes differ")
     # biases are not needed by the backward when z, h_prime are given: pass zeta as a dummy
@@ -423,11 +457,19 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
                                          bias_gate if preact else zeta, bias_update if preact else zeta,
                                          zeta, nu, dt, gate_nl, update_nl, flags)
     desc = plan[0]
+    zx = plan[5]
+    if zsaved and not (zx is not None and zx.backward and z.numel() == zx.saved_bytes):
+        raise RuntimeError("fastgrnn backward: z is not the saved buffer of a FLAG_ZERO_EXTEND forward of this shape")
+    if preact and not zsaved and zx is not None and zx.backward:
+        raise RuntimeError("fastgrnn backward: FLAG_ZERO_EXTEND takes the saved buffer of its forward as z (uint8)")
     _warn_fallback(plan, 1)
     shapes = ([tuple(w1.shape), tuple(w2.shape)] if w_lr else [(H, F)]) + \
              ([tuple(u1.shape), tuple(u2.shape)] if u_lr else [(H, H)]) + [(1, H), (1, H), (1, 1), (1, 1)]
     sizes = [a * b for a, b in shapes]
-    dx_is_gemm = (plan[2] == 2 and not w_lr and not u_lr and (desc.H == 256 or (desc.H == 128 and desc.F > 32)))
+    if zsaved:
+        dx_is_gemm = bool(zx.dx_optional)
+    else:
+        dx_is_gemm = (plan[2] == 2 and not w_lr and not u_lr and (desc.H == 256 or (desc.H == 128 and desc.F > 32)))
     ent = (w_lr, u_lr, shapes, sizes, dx_is_gemm, B, H)
     _seen[sig] = (plan, preact and rank_space is not None, ent)
     return _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_h, z, h_prime,

@@ -101,10 +101,11 @@ class FastGRNNUnrollFunction(Function):
                      and input.dtype in (torch.float32, torch.bfloat16)
                      and fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, gate_non_linearity, 2, input.dtype, 1,
                                                    _lib.FLAG_SAVE_PREACT | _lib.FLAG_X_BFT) == 2)
+            # (FLAG_ZERO_EXTEND: hidden sizes up to 256 that no kernel-path-2 shape covers run zero-padded to one)
             preact = (input.dtype in (torch.float32, torch.bfloat16) and input.is_cuda and
                       fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, gate_non_linearity, 2, input.dtype, 1,
-                                                _lib.FLAG_SAVE_PREACT) == 2)
-            flags = _lib.FLAG_SAVE_PREACT if preact else 0
+                                                _lib.FLAG_SAVE_PREACT | _lib.FLAG_ZERO_EXTEND) == 2)
+            flags = (_lib.FLAG_SAVE_PREACT | _lib.FLAG_ZERO_EXTEND) if preact else 0
             if batch_major:
                 flags |= _lib.FLAG_BATCH_MAJOR
             if x_bft:
@@ -381,7 +382,7 @@ class FastGRNNCUDA(nn.Module):
             ru = self.U1.shape[0] if self.U1.numel() else 0
             in_place = (input.dtype in (torch.float32, torch.bfloat16) and fastgrnn_cuda.kernel_path(
                 Tn, Bn, Fn, self._hidden_size, rw, ru, self._gate_non_linearity, 2, input.dtype, 1,
-                _lib.FLAG_SAVE_PREACT | _lib.FLAG_BATCH_MAJOR) == 2)
+                _lib.FLAG_SAVE_PREACT | _lib.FLAG_BATCH_MAJOR | _lib.FLAG_ZERO_EXTEND) == 2)
             if not in_place:
                 input = input.transpose(0, 1).contiguous()
         nbatch = input.shape[0] if in_place else input.shape[1]
@@ -421,9 +422,10 @@ class FastGRNNCUDA(nn.Module):
         goes through the autograd function as before)."""
         if not (input.is_cuda and input.is_contiguous() and input.dtype in (torch.float32, torch.bfloat16)):
             return None
-        key = (input.shape, input.dtype, batch_major, self.W1.shape, self.U1.shape, self._gate_non_linearity)
+        key = (input.shape, input.dtype, batch_major, self._hidden_size, self.W1.shape, self.U1.shape,
+               self._gate_non_linearity, input.device.index)
         ok = _inference_ok.get(key)
-        flags = _lib.FLAG_BATCH_MAJOR if batch_major else 0
+        flags = _lib.FLAG_ZERO_EXTEND | (_lib.FLAG_BATCH_MAJOR if batch_major else 0)
         if ok is None:
             if batch_major:
                 Bn, Tn, Fn = input.shape
@@ -447,7 +449,7 @@ class FastGRNNCUDA(nn.Module):
             Tn, Bn, Fn = input.shape
         rw = self.W1.shape[0] if self.W1.numel() else 0
         ru = self.U1.shape[0] if self.U1.numel() else 0
-        flags = _lib.FLAG_HS_LAST | (_lib.FLAG_BATCH_MAJOR if batch_major else 0)
+        flags = _lib.FLAG_HS_LAST | _lib.FLAG_ZERO_EXTEND | (_lib.FLAG_BATCH_MAJOR if batch_major else 0)
         if input.dtype not in (torch.float32, torch.bfloat16) or fastgrnn_cuda.kernel_path(
                 Tn, Bn, Fn, self._hidden_size, rw, ru, self._gate_non_linearity, 2, input.dtype, 0, flags) != 2:
             return None

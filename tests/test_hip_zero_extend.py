@@ -1,0 +1,495 @@
+"""FASTGRNN_FLAG_ZERO_EXTEND on the GPU: odd hidden sizes (H <= 256) run zero-padded on kernel path 2.
+
+1. Bitwise transparency: the padded-route call equals the same library call on explicitly zero-padded tensors of the
+   native (Hp, Fp) shape, sliced back, bit for bit.
+2. The reference's own fixtures with odd shapes, at the suite's fp32 tolerances.
+3. The fp64 oracle over a grid of odd sizes, gates, layouts, bf16 frames and weight scales.
+4. One full-size training step (F=32, H=100, B=4096, T=99).
+5. The modules: FastGRNNCUDA and RNNClassifierModel at H=100, the inference cache key, graph replay, repeatability.
+"""
+import numpy as np
+import pytest
+import torch
+
+from oracle import fastgrnn_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+if torch.cuda.is_available():
+    from kws_amd import FastGRNNCUDA, GraphedStep, RNNClassifierModel, _lib, fastgrnn_cuda
+    from kws_amd import rnn as _rnn
+DEV = "cuda:0"
+SP, BM, GL, HL, ZE = 4, 16, 256, 512, 4096
+GATE = {"sigmoid": 0, "relu": 1, "tanh": 2, "quantTanh": 3, "quantSigm": 4, "quantSigm4": 5}
+NAMES = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
+SCALAR_TERM_TOL = 2e-7          # tests/test_hip_parity.py: d_zeta / d_nu against the sum of their terms' magnitudes
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _P(p):
+    e = torch.empty(0, device=DEV)
+    g = lambda k: _t(p[k]) if k in p else e
+    return dict(w=g("w"), u=g("u"), w1=g("w1"), w2=g("w2"), u1=g("u1"), u2=g("u2"),
+                bias_gate=_t(p["bias_gate"]), bias_update=_t(p["bias_update"]), zeta=_t(p["zeta"]), nu=_t(p["nu"]))
+
+
+def _pad(t, shape):
+    """t zero-extended (trailing rows / columns) to shape"""
+    if t.numel() == 0:
+        return t
+    out = torch.zeros(shape, dtype=t.dtype, device=t.device)
+    out[tuple(slice(0, n) for n in t.shape)] = t
+    return out
+
+
+def _pad_params(P, H, F, Hp, Fp):
+    Q = dict(P)
+    if P["w"].numel():
+        Q["w"] = _pad(P["w"], (Hp, Fp))
+    else:
+        Q["w1"] = _pad(P["w1"], (P["w1"].shape[0], Fp)); Q["w2"] = _pad(P["w2"], (Hp, P["w2"].shape[1]))
+    if P["u"].numel():
+        Q["u"] = _pad(P["u"], (Hp, Hp))
+    else:
+        Q["u1"] = _pad(P["u1"], (P["u1"].shape[0], Hp)); Q["u2"] = _pad(P["u2"], (Hp, P["u2"].shape[1]))
+    Q["bias_gate"] = _pad(P["bias_gate"], (1, Hp)); Q["bias_update"] = _pad(P["bias_update"], (1, Hp))
+    return Q
+
+
+def fwd_bwd(x, h0, G, P, gate, flags, update="tanh", need_dx=True):
+    """forward_unroll under SAVE_PREACT + backward_unroll; returns hs, the saved tensor(s), the 12 gradients"""
+    outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0,
+                                        GATE[gate], P["w1"], P["w2"], P["u1"], P["u2"], flags=flags,
+                                        update_non_linearity=GATE[update])
+    hs, pre = outs[0], outs[1]
+    aux = outs[2] if len(outs) > 2 else pre
+    g = fastgrnn_cuda.backward_unroll(G, x, hs, P["zeta"], P["nu"], P["w"], P["u"], pre, aux, h0, P["w1"], P["w2"],
+                                      P["u1"], P["u2"], GATE[gate], flags=flags, update_non_linearity=GATE[update],
+                                      bias_gate=P["bias_gate"], bias_update=P["bias_update"], need_dx=need_dx)
+    return hs, pre, dict(zip(NAMES, g))
+
+
+def _bits(t):
+    t = t.contiguous()
+    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
+
+
+def _same_bits(a, b, what):
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    assert torch.equal(_bits(a), _bits(b)), (what, float((a.float() - b.float()).abs().max()))
+
+
+# F, H, w_rank, u_rank, B, T, bf16, extra flags, gate
+BITWISE = [
+    (32, 100, 0, 0, 37, 7, False, 0, "sigmoid"),
+    (7, 20, 0, 0, 19, 5, False, BM, "tanh"),
+    (100, 100, 0, 0, 37, 6, False, 0, "relu"),           # wide-input H = 128 scans (Fp = 128)
+    (40, 129, 0, 0, 19, 5, False, 0, "sigmoid"),         # H = 256 / F = 64
+    (32, 200, 0, 0, 37, 4, False, BM, "sigmoid"),        # H = 256 / F = 32, batch-major
+    (32, 1, 0, 0, 16, 3, False, 0, "sigmoid"),
+    (32, 100, 0, 0, 37, 7, True, 0, "sigmoid"),          # bf16 sequences
+    (13, 200, 0, 0, 19, 4, True, 0, "tanh"),
+    (40, 60, 0, 0, 19, 4, True, BM, "sigmoid"),
+    (32, 100, 0, 0, 37, 7, False, GL, "sigmoid"),        # the gradient of the last state alone
+    (100, 60, 0, 0, 37, 5, False, GL | BM, "sigmoid"),
+    (20, 200, 8, 16, 37, 5, False, 0, "sigmoid"),        # low-rank H = 256 scans (ranks <= 16, Fp = 32)
+    (32, 255, 3, 5, 19, 4, False, BM, "tanh"),
+    (32, 100, 5, 7, 37, 5, False, 0, "sigmoid"),         # densified onto H = 128
+    (40, 129, 20, 3, 19, 4, False, 0, "sigmoid"),        # densified onto H = 256 / F = 64
+    (7, 20, 0, 0, 19, 5, False, 0, "quantSigm4"),
+]
+
+
+@pytest.mark.parametrize("case", BITWISE, ids=lambda c: "F%dH%dr%d-%dB%dT%d%s-f%d-%s" % (c[:6] + ("bf" if c[6] else "",) + c[7:]))
+def test_padded_route_equals_the_explicitly_padded_call_bitwise(case):
+    F, H, rw, ru, B, T, bf, extra, gate = case
+    dt = torch.bfloat16 if bf else torch.float32
+    plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, rw, ru, GATE[gate], dtype=dt, flags=SP | extra)
+    assert plan["forward"] == 1 and plan["backward"] == 1, plan
+    Hp, Fp = plan["Hp"], plan["Fp"]
+    rng = np.random.default_rng(F * 1000 + H)
+    p = O.make_params(F, H, rw or None, ru or None, np.float32, seed=H, randomize_scalars=True)
+    if gate == "relu":
+        for k in ("w", "u"):
+            p[k] = (0.3 * p[k]).astype(np.float32)
+    P = _P(p)
+    lead = (B, T) if extra & BM else (T, B)
+    x = _t(rng.standard_normal(lead + (F,)).astype(np.float32)).to(dt)
+    h0 = _t((0.5 * rng.standard_normal((B, H))).astype(np.float32))
+    G = _t(rng.standard_normal(((B,) if extra & GL else lead) + (H,)).astype(np.float32)).to(dt)
+    assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, GATE[gate], dtype=dt, direction=1, flags=SP | extra) == 0
+    hs, saved, g = fwd_bwd(x, h0, G, P, gate, SP | extra | ZE)
+    assert saved.dtype == torch.uint8 and saved.numel() == plan["saved_bytes"]
+    assert hs.shape == lead + (H,) and hs.dtype == dt
+    # the same library on explicitly padded tensors of the native shape
+    Q = _pad_params(P, H, F, Hp, Fp)
+    hs_n, _, g_n = fwd_bwd(_pad(x, lead + (Fp,)), _pad(h0, (B, Hp)), _pad(G, G.shape[:-1] + (Hp,)), Q, gate,
+                           SP | extra)
+    torch.cuda.synchronize()
+    _same_bits(hs, hs_n[..., :H], "hs")
+    _same_bits(g["d_x"], g_n["d_x"][..., :F], "d_x")
+    _same_bits(g["d_h0"], g_n["d_h0"][:, :H], "d_h0")
+    for k in ("d_bias_gate", "d_bias_update"):
+        _same_bits(g[k], g_n[k][:, :H], k)
+    for k in ("d_zeta", "d_nu"):
+        _same_bits(g[k], g_n[k], k)
+    if rw:
+        _same_bits(g["d_w1"], g_n["d_w1"][:, :F], "d_w1"); _same_bits(g["d_w2"], g_n["d_w2"][:H], "d_w2")
+    else:
+        _same_bits(g["d_w"], g_n["d_w"][:H, :F], "d_w")
+    if ru:
+        _same_bits(g["d_u1"], g_n["d_u1"][:, :H], "d_u1"); _same_bits(g["d_u2"], g_n["d_u2"][:H], "d_u2")
+    else:
+        _same_bits(g["d_u"], g_n["d_u"][:H, :H], "d_u")
+    # the padded units' gradients are exact zeros (nothing leaks into the slices above)
+    assert not g_n["d_h0"][:, H:].any() and not g_n["d_bias_gate"][:, H:].any()
+
+
+@pytest.mark.parametrize("F,H,bf,bm", [(32, 100, False, False), (64, 200, False, True), (32, 100, True, False),
+                                       (100, 33, False, False), (20, 200, False, False)])
+def test_inference_forwards_bitwise(F, H, bf, bm):
+    """hs-only and last-state (FLAG_HS_LAST) forwards: the padded route against the explicitly padded call"""
+    T, B = 9, 37
+    dt = torch.bfloat16 if bf else torch.float32
+    p = O.make_params(F, H, dtype=np.float32, seed=5, randomize_scalars=True)
+    P = _P(p)
+    rng = np.random.default_rng(H)
+    lead = (B, T) if bm else (T, B)
+    x = _t(rng.standard_normal(lead + (F,)).astype(np.float32)).to(dt)
+    h0 = _t((0.5 * rng.standard_normal((B, H))).astype(np.float32))
+    plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, dtype=dt, flags=BM if bm else 0)
+    Hp, Fp = plan["Hp"], plan["Fp"]
+    Q = _pad_params(P, H, F, Hp, Fp)
+    for last in (False, True):
+        if last and (bf and (H > 128 or F > 32)):
+            continue
+        fl = (BM if bm else 0) | (HL if last else 0)
+        assert fastgrnn_cuda.kernel_path(T, B, F, H, dtype=dt, flags=fl | ZE) == 2
+        run = lambda xx, hh, PP, f: fastgrnn_cuda.forward_unroll(
+            xx, PP["w"], PP["u"], PP["bias_gate"], PP["bias_update"], PP["zeta"], PP["nu"], hh, 0, PP["w1"], PP["w2"],
+            PP["u1"], PP["u2"], want_gates=False, flags=f)[0]
+        hs = run(x, h0, P, fl | ZE)
+        hs_n = run(_pad(x, lead + (Fp,)), _pad(h0, (B, Hp)), Q, fl)
+        _same_bits(hs, hs_n[..., :H], "hs last=%s" % last)
+
+
+def test_need_dx_false_skips_the_input_gradient():
+    """d_x may be NULL where the padded shape computes it as a GEMM of its own (the plan's dx_optional)"""
+    T, B, F, H = 6, 37, 100, 100
+    assert fastgrnn_cuda.zero_extend_plan(T, B, F, H, flags=SP)["dx_optional"] == 1
+    p = O.make_params(F, H, dtype=np.float32, seed=2, randomize_scalars=True)
+    P = _P(p)
+    rng = np.random.default_rng(0)
+    x = _t(rng.standard_normal((T, B, F)).astype(np.float32)); h0 = _t(np.zeros((B, H), np.float32))
+    G = _t(rng.standard_normal((T, B, H)).astype(np.float32))
+    _, _, g0 = fwd_bwd(x, h0, G, P, "sigmoid", SP | ZE)
+    _, _, g1 = fwd_bwd(x, h0, G, P, "sigmoid", SP | ZE, need_dx=False)
+    assert g1["d_x"].numel() == 0
+    for k in ("d_w", "d_u", "d_h0", "d_zeta"):
+        _same_bits(g0[k], g1[k], k)
+
+
+# ---- against the reference's fixtures and the fp64 oracle ------------------------------------------------------------
+
+def _oracle(x, h0, G, p, gate="sigmoid", update="tanh"):
+    p64 = {k: np.asarray(v, np.float64) for k, v in p.items()}
+    x64, h64 = np.asarray(x, np.float64), np.asarray(h0, np.float64)
+    hs, zs, cs = O.unroll_forward(x64, p64, h64, gate=gate, update=update)
+    g = O.unroll_backward(np.asarray(G, np.float64), x64, hs, zs, cs, p64, h64, gate=gate, update=update,
+                          diagnostics=True)
+    return hs, g
+
+
+def _check(hs, g, hs_o, g_o, tol, tag, hs_tol=1e-5, ill=None):
+    """ill = (hs_32, g_32, fac): an expansive recurrence (weights 8x the reference scale), judged beside the oracle
+    itself run in fp32, as tests/test_hip_stress_inputs.py does -- fac times its error"""
+    hs = hs.float().cpu().numpy()
+    e = (np.abs(hs - hs_o) / np.maximum(1.0, np.abs(hs_o))).max()
+    if ill is not None:
+        hs_tol = max(hs_tol, 3.0 * float((np.abs(ill[0] - hs_o) / np.maximum(1.0, np.abs(hs_o))).max()))
+    assert e <= hs_tol, (tag, "hs", e)
+    for k, v in g_o.items():
+        if k.startswith("_") or k not in g or g[k].numel() == 0:
+            continue
+        a = g[k].float().cpu().numpy().reshape(v.shape)
+        err = float(np.abs(a - v).max())
+        lim = tol * max(1.0, float(np.abs(v).max()))
+        if k in ("d_zeta", "d_nu"):
+            lim = max(lim, SCALAR_TERM_TOL * g_o["_abs_" + k[2:]])
+        if ill is not None:
+            lim = max(lim, ill[2] * float(np.abs(ill[1][k].reshape(v.shape) - v).max()))
+        assert err <= lim, (tag, k, err, lim)
+
+
+@pytest.mark.parametrize("name", ["g6_odd_f32", "g1_tiny_f64", "g4_tanhgate_f64", "g5_mixed_urank_f64",
+                                  "g5_mixed_wrank_f64"])
+def test_reference_fixtures_on_the_padded_route(name):
+    from tests.conftest import load_golden
+    gd = load_golden(name)
+    f32 = lambda a: np.asarray(a, np.float32)
+    p = {k: f32(v) for k, v in gd["params"].items()}
+    x, h0, G = f32(gd["x"]), f32(gd["h0"]), f32(gd["G"])
+    T, B, F = x.shape
+    H = h0.shape[1]
+    rw = p["w1"].shape[0] if "w1" in p else 0
+    ru = p["u1"].shape[0] if "u1" in p else 0
+    assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, GATE[gd["gate"]], direction=1, flags=SP | ZE) == 2
+    hs, _, g = fwd_bwd(_t(x), _t(h0), _t(G), _P(p), gd["gate"], SP | ZE)
+    if name.endswith("_f32"):        # the reference's own fp32 outputs
+        ref = dict(gd["dparams"]); ref["d_x"] = gd["dx"]; ref["d_h0"] = gd["dh0"]
+        _, g_o = _oracle(x, h0, G, p, gd["gate"])
+        ref["_abs_zeta"], ref["_abs_nu"] = g_o["_abs_zeta"], g_o["_abs_nu"]
+        _check(hs, g, gd["hs"], ref, 2e-5, name)
+    else:                            # fp64 fixtures: the oracle on the fp32-rounded inputs (and the fixture itself)
+        hs_o, g_o = _oracle(x, h0, G, p, gd["gate"])
+        assert np.abs(hs_o - gd["hs"]).max() < 1e-6
+        _check(hs, g, hs_o, g_o, 2e-5, name)
+
+
+def test_quantised_fixture_with_the_kernels_own_gates():
+    """g7_quant (quantSigm gate, quantTanh update): piecewise-linear nonlinearities, so the backward is compared with
+    the oracle on the kernel's own gate values (same mask), as the existing quantised-gate tests do.  The padded
+    pre-activation is the first [T*B, Hp] fp32 block of the saved buffer (include/fastgrnn_hip.h)."""
+    from tests.conftest import load_golden
+    gd = load_golden("g7_quant_f64")
+    f32 = lambda a: np.asarray(a, np.float32)
+    p = {k: f32(v) for k, v in gd["params"].items()}
+    x, h0, G = f32(gd["x"]), f32(gd["h0"]), f32(gd["G"])
+    T, B, F = x.shape
+    H = h0.shape[1]
+    plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, gate_nl=GATE["quantSigm"], update_nl=GATE["quantTanh"],
+                                          flags=SP)
+    assert plan["backward"] == 1
+    hs, saved, g = fwd_bwd(_t(x), _t(h0), _t(G), _P(p), "quantSigm", SP | ZE, update="quantTanh")
+    p64 = {k: v.astype(np.float64) for k, v in p.items()}
+    hs_o, _, _ = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate="quantSigm",
+                                  update="quantTanh")
+    assert (np.abs(hs.cpu().numpy() - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
+    pre = saved[:T * B * plan["Hp"] * 4].view(torch.float32).view(T, B, plan["Hp"])[..., :H].cpu().numpy()
+    zk = np.clip((pre + p["bias_gate"] + 1) / 2, 0, 1).astype(np.float32)
+    ck = np.clip(pre + p["bias_update"], -1, 1).astype(np.float32)
+    g_o = O.unroll_backward(G, x, hs.cpu().numpy(), zk, ck, p, h0, gate="quantSigm", update="quantTanh",
+                            diagnostics=True)
+    _check(hs, g, hs_o, g_o, 5e-5, "g7_quant")
+
+
+def _relu_off_kink(p, x, h0, margin=1e-4):
+    p = {k: v.copy() for k, v in p.items()}
+    for _ in range(50):
+        p64 = {k: v.astype(np.float64) for k, v in p.items()}
+        _, _, cs = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate="relu")
+        a = np.arctanh(np.clip(cs, -1 + 1e-15, 1 - 1e-15)) - p64["bias_update"] + p64["bias_gate"]
+        close = np.abs(a).reshape(-1, a.shape[-1]).min(axis=0) < 2 * margin
+        if not close.any():
+            return p
+        p["bias_gate"][0, close] += np.float32(7 * margin)
+    raise AssertionError("could not move the relu gates off the kink")
+
+
+@pytest.mark.parametrize("H", [1, 16, 33, 100, 127, 129, 200, 255])
+@pytest.mark.parametrize("F", [13, 32, 40, 100])
+def test_odd_sizes_vs_the_fp64_oracle(F, H):
+    """Every gate, both layouts, weights at the reference scale, 8x it and 1/1000 of it.  H = 16 padded to 128 leaves
+    seven of the eight waves of the H = 128 scans with all-zero rows of U (the per-wave power-of-two U scale on a zero
+    maximum)."""
+    T, B = 5, 19
+    for i, gate in enumerate(("sigmoid", "tanh", "relu")):
+        for scale in (1.0, 8.0, 1e-3):
+            if gate == "relu" and scale == 8.0:
+                continue                      # (a relu gate at 8x grows the state by orders of magnitude per frame)
+            bm = (i + int(scale > 1)) % 2 == 1
+            rng = np.random.default_rng(F * 7919 + H * 31 + i)
+            p = O.make_params(F, H, dtype=np.float32, seed=F + H + i, randomize_scalars=True)
+            for k in ("w", "u"):
+                p[k] = (scale * (0.3 if gate == "relu" else 1.0) * p[k]).astype(np.float32)
+            x = rng.standard_normal((T, B, F)).astype(np.float32)
+            h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
+            G = rng.standard_normal((T, B, H)).astype(np.float32)
+            if gate == "relu":
+                p = _relu_off_kink(p, x, h0)
+            lay = (lambda a: np.ascontiguousarray(a.transpose(1, 0, 2))) if bm else (lambda a: a)
+            hs, _, g = fwd_bwd(_t(lay(x)), _t(h0), _t(lay(G)), _P(p), gate, SP | ZE | (BM if bm else 0))
+            if bm:
+                hs = hs.transpose(0, 1)
+                g["d_x"] = g["d_x"].transpose(0, 1)
+            hs_o, g_o = _oracle(x, h0, G, p, gate)
+            ill = None
+            if scale > 1 or gate == "relu":      # (a relu gate is not contractive either: |z| is not < 1)
+                hs_32, zs_32, cs_32 = O.unroll_forward(x, p, h0, gate=gate)
+                g_32 = O.unroll_backward(G, x, hs_32, zs_32, cs_32, p, h0, gate=gate)
+                ill = (hs_32, g_32, 6.0 if H > 128 else 3.0)
+            _check(hs, g, hs_o, g_o, 2e-5, (gate, scale, bm), ill=ill)
+
+
+@pytest.mark.parametrize("F,H", [(13, 100), (32, 33), (40, 16), (100, 127), (32, 200), (13, 255)])
+def test_bf16_frames_vs_the_fp64_oracle(F, H):
+    """bf16 sequences on the padded route, against the oracle on the same rounded tensors (as
+    test_bf16_sequences_fp32_master_grads does for the native shapes)"""
+    T, B = 6, 37
+    rng = np.random.default_rng(F + H)
+    p = O.make_params(F, H, dtype=np.float32, seed=3, randomize_scalars=True)
+    bf = lambda a: torch.from_numpy(a).to(torch.bfloat16)
+    x_bf = bf(rng.standard_normal((T, B, F)).astype(np.float32))
+    G_bf = bf(rng.standard_normal((T, B, H)).astype(np.float32))
+    h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
+    plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, dtype=torch.bfloat16, flags=SP)
+    assert plan["backward"] == 1
+    hs, saved, g = fwd_bwd(x_bf.to(DEV), _t(h0), G_bf.to(DEV), _P(p), "sigmoid", SP | ZE)
+    assert hs.dtype == torch.bfloat16 and g["d_x"].dtype == torch.bfloat16 and g["d_u"].dtype == torch.float32
+    p64 = {k: v.astype(np.float64) for k, v in p.items()}
+    x64, G64, h64 = x_bf.double().numpy(), G_bf.double().numpy(), h0.astype(np.float64)
+    hs_o, _, _ = O.unroll_forward(x64, p64, h64)
+    hs_k = hs.double().cpu().numpy()
+    assert (np.abs(hs_k - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 2.0 ** -8 + 1e-5
+    # backward: the kernel sees the rounded hs as h_prev; gates from its own exact pre-activation
+    pre = saved[:T * B * plan["Hp"] * 4].view(torch.float32).view(T, B, plan["Hp"])[..., :H].double().cpu().numpy()
+    z = 1.0 / (1.0 + np.exp(-(pre + p64["bias_gate"]))); c = np.tanh(pre + p64["bias_update"])
+    g_o = O.unroll_backward(G64, x64, hs_k, z, c, p64, h64, diagnostics=True)
+    dx, ref = g.pop("d_x").double().cpu().numpy(), g_o.pop("d_x")
+    assert (np.abs(dx - ref) / np.maximum(1.0, np.abs(ref))).max() <= 2.0 ** -8 + 2e-5
+    _check(hs, g, hs_o, g_o, 2e-5, "bf16", hs_tol=2.0 ** -8 + 1e-5)
+
+
+def test_full_size_training_step_vs_the_oracle():
+    """F=32, H=100, B=4096, T=99 in fp32: the bounds of tests/test_hip_fullsize.py"""
+    T, B, F, H = 99, 4096, 32, 100
+    rng = np.random.default_rng(0)
+    p = O.make_params(F, H, dtype=np.float32, seed=1, randomize_scalars=True)
+    x = rng.standard_normal((T, B, F)).astype(np.float32)
+    G = rng.standard_normal((T, B, H)).astype(np.float32)
+    h0 = np.zeros((B, H), np.float32)
+    assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=1, flags=SP | ZE) == 2
+    hs, _, g = fwd_bwd(_t(x), _t(h0), _t(G), _P(p), "sigmoid", SP | ZE)
+    hs_o, g_o = _oracle(x, h0, G, p)
+    _check(hs, g, hs_o, g_o, 2e-5, "fullsize")
+
+
+# ---- modules --------------------------------------------------------------------------------------------------------
+
+def _copy(m, p):
+    with torch.no_grad():
+        for k, attr in (("w", "W"), ("u", "U"), ("bias_gate", "bias_gate"), ("bias_update", "bias_update"),
+                        ("zeta", "zeta"), ("nu", "nu")):
+            getattr(m, attr).copy_(torch.from_numpy(p[k]))
+
+
+@pytest.mark.parametrize("batch_first", [False, True])
+def test_module_h100_autograd_and_inference_vs_the_oracle(batch_first):
+    T, B, F, H = 23, 37, 32, 100
+    rng = np.random.default_rng(1)
+    p = O.make_params(F, H, dtype=np.float32, seed=8, randomize_scalars=True)
+    x = rng.standard_normal((T, B, F)).astype(np.float32)
+    G = rng.standard_normal((T, B, H)).astype(np.float32)
+    m = FastGRNNCUDA(F, H, batch_first=batch_first, device=DEV)
+    _copy(m, p)
+    lay = (lambda a: np.ascontiguousarray(a.transpose(1, 0, 2))) if batch_first else (lambda a: a)
+    xt = _t(lay(x)).requires_grad_(True)
+    out = m(xt)
+    (out * _t(lay(G))).sum().backward()
+    hs = out.detach().transpose(0, 1) if batch_first else out.detach()
+    g = {"d_x": xt.grad.transpose(0, 1) if batch_first else xt.grad, "d_w": m.W.grad, "d_u": m.U.grad,
+         "d_bias_gate": m.bias_gate.grad, "d_bias_update": m.bias_update.grad, "d_zeta": m.zeta.grad, "d_nu": m.nu.grad}
+    hs_o, g_o = _oracle(x, np.zeros((B, H), np.float32), G, p)
+    _check(hs, g, hs_o, g_o, 2e-5, "module")
+    with torch.no_grad():
+        hs_ng = m(_t(lay(x)))
+        last = m(_t(lay(x)), last_state=True)
+    assert (hs_ng - out.detach()).abs().max() <= 1e-6         # (the hs-only scan variant)
+    assert np.abs(last.cpu().numpy() - hs_o[-1]).max() <= 1e-5
+    # bf16 frames through the module
+    mb = FastGRNNCUDA(F, H, batch_first=batch_first, device=DEV)
+    _copy(mb, p)
+    xb = _t(lay(x)).to(torch.bfloat16).requires_grad_(True)
+    ob = mb(xb)
+    assert ob.dtype == torch.bfloat16
+    ob.float().square().mean().backward()
+    assert torch.isfinite(mb.U.grad).all() and xb.grad is not None and xb.grad.dtype == torch.bfloat16
+    x64 = xb.detach().double().cpu().numpy()
+    x64 = x64.transpose(1, 0, 2) if batch_first else x64
+    hs_ob, _, _ = O.unroll_forward(x64, {k: v.astype(np.float64) for k, v in p.items()}, np.zeros((B, H)))
+    obn = ob.detach().double().cpu().numpy()
+    obn = obn.transpose(1, 0, 2) if batch_first else obn
+    assert (np.abs(obn - hs_ob) / np.maximum(1.0, np.abs(hs_ob))).max() <= 2.0 ** -8 + 1e-5
+
+
+def test_classifier_100_100_all_gradients_vs_the_oracle_chain():
+    T, B, F, C = 17, 40, 32, 12
+    rng = np.random.default_rng(4)
+    layers = [O.make_params(32, 100, dtype=np.float32, seed=3, randomize_scalars=True),
+              O.make_params(100, 100, dtype=np.float32, seed=4, randomize_scalars=True)]
+    fc_w = (0.2 * rng.standard_normal((C, 100))).astype(np.float32)
+    fc_b = (0.1 * rng.standard_normal((C,))).astype(np.float32)
+    x = rng.standard_normal((T, B, F)).astype(np.float32)
+    y = rng.integers(0, C, (B,))
+    model = RNNClassifierModel("FastGRNNCUDA", F, 2, [100, 100], [None, None], [None, None], [1.0, 1.0], [1.0, 1.0],
+                               "sigmoid", "tanh", num_classes=C, device=DEV)
+    for rnn, q in zip(model.rnn_list, layers):
+        _copy(rnn, q)
+    with torch.no_grad():
+        model.hidden2keyword.weight.copy_(torch.from_numpy(fc_w)); model.hidden2keyword.bias.copy_(torch.from_numpy(fc_b))
+    assert [fastgrnn_cuda.kernel_path(T, B, f, 100, direction=1, flags=SP | ZE) for f in (32, 100)] == [2, 2]
+    assert [fastgrnn_cuda.zero_extend_plan(T, B, f, 100, flags=SP)["Fp"] for f in (32, 100)] == [32, 128]
+    loss = model.loss(_t(x), torch.from_numpy(y).to(DEV))
+    loss.backward()
+    l64 = [{k: v.astype(np.float64) for k, v in q.items()} for q in layers]
+    loss_o, _, _, _, grads_o, dw_o, _ = O.stack_forward_backward(x.astype(np.float64), l64, fc_w.astype(np.float64),
+                                                                 fc_b.astype(np.float64), y)
+    assert abs(float(loss) - float(loss_o)) < 1e-5
+    for rnn, go in zip(model.rnn_list, grads_o):
+        for k, attr in (("d_w", "W"), ("d_u", "U"), ("d_bias_gate", "bias_gate"), ("d_bias_update", "bias_update"),
+                        ("d_zeta", "zeta"), ("d_nu", "nu")):
+            a = getattr(rnn, attr).grad.cpu().numpy()
+            ref = go[k].reshape(a.shape)
+            tol = 2e-4 if k in ("d_zeta", "d_nu") else 5e-5     # (one scalar: a sum of cancelling terms)
+            assert np.abs(a - ref).max() / max(1e-3, float(np.abs(ref).max())) < tol, (k, attr)
+
+
+def test_inference_cache_key_tells_h128_from_h100():
+    """two dense modules that share an input shape (H = 128 and H = 100) get their own hs-only decision"""
+    T, B, F = 9, 37, 32
+    x = torch.randn(T, B, F, device=DEV)
+    outs = {}
+    for H in (128, 100):
+        m = FastGRNNCUDA(F, H, device=DEV)
+        with torch.no_grad():
+            outs[H] = (m, m(x))
+        assert outs[H][1].shape == (T, B, H)
+    keys = [k for k in _rnn._inference_ok if k[0] == x.shape]
+    assert len({k[3] for k in keys} & {100, 128}) == 2 and all(_rnn._inference_ok[k] for k in keys)
+    for H, (m, hs) in outs.items():        # each equals its own autograd forward
+        assert (hs - m(x).detach()).abs().max() <= 1e-6, H
+
+
+def test_graph_replay_and_repeatability_bitwise():
+    T, B, F, H = 21, 37, 40, 100
+    torch.manual_seed(3)
+    m = FastGRNNCUDA(F, H, device=DEV)
+    params = list(m.parameters())
+    x = torch.randn(T, B, F, device=DEV)
+    G = torch.randn(T, B, H, device=DEV)
+
+    def step():
+        for q in params:
+            q.grad = None
+        hs = m(x)
+        hs.backward(G)
+        return hs
+
+    def eager():
+        hs = step()
+        torch.cuda.synchronize()
+        return hs.detach().clone(), [q.grad.clone() for q in params]
+
+    a, b = eager(), eager()
+    _same_bits(a[0], b[0], "hs twice")
+    for u, v in zip(a[1], b[1]):
+        _same_bits(u, v, "grad twice")
+    gs = GraphedStep(step)
+    hs_g = gs()
+    torch.cuda.synchronize()
+    _same_bits(hs_g, a[0], "graph hs")
+    for q, v in zip(params, a[1]):
+        _same_bits(q.grad, v, "graph grad")
