@@ -152,6 +152,17 @@ typedef enum fastgrnn_nonlinearity {
  *   NULL when the padded shape allows it (the plan's dx_optional).
  *   Not covered: PREACT_AFFINE and BN_TRAIN cells, fp64, X_BFT frames, H > 256, F > 256 and H > 128 with F > 128. */
 #define FASTGRNN_FLAG_ZERO_EXTEND 4096u
+/* The caller does not want the input's gradient: fastgrnn_hip_backward_unroll then also accepts d_x == NULL on kernel
+ * path 2 for dense H=128/F=32 -- every gate, both saved-tensor contracts, quantTanh, fp32 and bf16 sequences, every
+ * layout flag that shape runs with -- and runs a scan variant without the d_x product (every other output bit for
+ * bit as with d_x given).  With FASTGRNN_FLAG_ZERO_EXTEND the same holds where the padded shape is dense H=128/F=32
+ * (the plan's dx_optional is 1 then).  Where d_x == NULL is already accepted (dense H=256, dense H=128 with F > 32)
+ * the flag changes nothing.  A permission only: with d_x given the call runs as without the flag, and no descriptor
+ * is refused because of it.  Per entry point: backward_unroll as above; fastgrnn_hip_kernel_path, both workspace
+ * queries, fastgrnn_hip_zero_extend_plan (apart from dx_optional), forward_unroll, forward_unroll_affine, the
+ * single-step forward and backward, and every fastgrnn_hip_bn_train_* entry point ignore it (answer and behave as
+ * without it; the single-step backward always requires d_x). */
+#define FASTGRNN_FLAG_NO_INPUT_GRAD 8192u
 
 /* Problem descriptor.  T = 1 for the single-step operators. */
 typedef struct fastgrnn_desc {
@@ -177,7 +188,8 @@ typedef struct fastgrnn_params {
  * ignored and may be NULL (reference returns torch::empty(0), .cu:221-224). */
 typedef struct fastgrnn_grads {
   void *d_x;            /* [T,B,F]; may be NULL on kernel path 2 for dense H=256 and dense H=128 with F > 32 (the
-                           input's gradient is then not computed: one GEMM less -- a model's first layer) */
+                           input's gradient is then not computed: one GEMM less -- a model's first layer), and
+                           for dense H=128/F=32 under FASTGRNN_FLAG_NO_INPUT_GRAD */
   void *d_bias_gate;    /* [1,H] */
   void *d_bias_update;  /* [1,H] */
   void *d_zeta;         /* [1,1] */

@@ -43,11 +43,18 @@ int pick_path(const fastgrnn_desc* d, int direction) {
   return mfma_supported(*d, direction) ? 1 : 0;
 }
 
-// the descriptor without FASTGRNN_FLAG_ZERO_EXTEND: what every call runs on where the flag does not take effect
+// the descriptor without FASTGRNN_FLAG_ZERO_EXTEND: what every call runs on where the flag does not take effect.
+// FASTGRNN_FLAG_NO_INPUT_GRAD goes too: it only admits d_x == NULL in the backward (nograd_dx_ok), so every path
+// choice and support predicate answers for it exactly as without it.
 fastgrnn_desc plain(const fastgrnn_desc* d) {
   fastgrnn_desc u = *d;
-  u.flags &= ~FASTGRNN_FLAG_ZERO_EXTEND;
+  u.flags &= ~(FASTGRNN_FLAG_ZERO_EXTEND | FASTGRNN_FLAG_NO_INPUT_GRAD);
   return u;
+}
+
+// FASTGRNN_FLAG_NO_INPUT_GRAD: the backward of the path-2 descriptor d (flags as the caller passed them) may leave d_x out
+bool nograd_dx_ok(const fastgrnn_desc& d, uint32_t flags) {
+  return (flags & FASTGRNN_FLAG_NO_INPUT_GRAD) && split_dx_skippable(d);
 }
 
 // FASTGRNN_FLAG_ZERO_EXTEND (include/fastgrnn_hip.h): true when the forward takes the padded route, with *e the padded
@@ -183,7 +190,7 @@ int fastgrnn_hip_zero_extend_plan(const fastgrnn_desc* d, fastgrnn_zext_plan* ou
   out->backward = bwd ? 1 : 0;
   out->Hp = e.H;
   out->Fp = e.F;
-  out->dx_optional = split_dx_optional(e) ? 1 : 0;
+  out->dx_optional = (split_dx_optional(e) || nograd_dx_ok(e, d->flags)) ? 1 : 0;
   out->saved_bytes = zext_saved_bytes(*d, e);
   return FASTGRNN_OK;
 }
@@ -253,7 +260,8 @@ int fastgrnn_hip_backward_unroll(const fastgrnn_desc* dz, const fastgrnn_params*
   if (zext_route(dz, &e, &bwd) && bwd) {
     if ((st = check_params(dz, p))) return st;
     if (!grad_hs || !x || !hs || !z_s || !h0 || !g) return FASTGRNN_ERR_NULL_POINTER;
-    if ((!g->d_x && !split_dx_optional(e)) || !g->d_bias_gate || !g->d_bias_update || !g->d_zeta || !g->d_nu ||
+    if ((!g->d_x && !split_dx_optional(e) && !nograd_dx_ok(e, dz->flags)) || !g->d_bias_gate || !g->d_bias_update ||
+        !g->d_zeta || !g->d_nu ||
         !g->d_h0)
       return FASTGRNN_ERR_NULL_POINTER;
     if (dz->w_rank ? (!g->d_w1 || !g->d_w2) : !g->d_w) return FASTGRNN_ERR_NULL_POINTER;
@@ -270,8 +278,9 @@ int fastgrnn_hip_backward_unroll(const fastgrnn_desc* dz, const fastgrnn_params*
   if ((preact || (d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)) || d->dtype == FASTGRNN_BF16_IO) && pick_path(d, 1) != 2)
     return FASTGRNN_ERR_UNSUPPORTED;
   if (!grad_hs || !x || !hs || !z_s || (!c_s && !preact) || !h0 || !g) return FASTGRNN_ERR_NULL_POINTER;
-  // d_x may be NULL (the input's gradient is not wanted) where it is a GEMM of its own behind the scan
-  const bool dx_optional = pick_path(d, 1) == 2 && split_dx_optional(*d);
+  // d_x may be NULL (the input's gradient is not wanted) where it is a GEMM of its own behind the scan, and under
+  // FASTGRNN_FLAG_NO_INPUT_GRAD where the scan can leave its d_x product out
+  const bool dx_optional = pick_path(d, 1) == 2 && (split_dx_optional(*d) || nograd_dx_ok(*d, dz->flags));
   if ((!g->d_x && !dx_optional) || !g->d_bias_gate || !g->d_bias_update || !g->d_zeta || !g->d_nu || !g->d_h0)
     return FASTGRNN_ERR_NULL_POINTER;
   if (d->w_rank ? (!g->d_w1 || !g->d_w2) : !g->d_w) return FASTGRNN_ERR_NULL_POINTER;
@@ -299,8 +308,10 @@ int fastgrnn_hip_backward(const fastgrnn_desc* d, const fastgrnn_params* p, cons
                           void* workspace, size_t workspace_bytes, void* stream) {
   if (!d) return FASTGRNN_ERR_NULL_POINTER;
   if (d->T != 1) return FASTGRNN_ERR_BAD_SHAPE;
+  fastgrnn_desc u = *d;
+  u.flags &= ~FASTGRNN_FLAG_NO_INPUT_GRAD;           // ignored here: the single-step backward always writes d_x
   // hs is required non-NULL by the unrolled entry but never dereferenced at T == 1
-  return fastgrnn_hip_backward_unroll(d, p, grad_h, x, /*hs=*/old_h, z, c, old_h, g, workspace, workspace_bytes,
+  return fastgrnn_hip_backward_unroll(&u, p, grad_h, x, /*hs=*/old_h, z, c, old_h, g, workspace, workspace_bytes,
                                       stream);
 }
 

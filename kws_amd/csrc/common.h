@@ -76,6 +76,7 @@ size_t split_forward_ws(const fastgrnn_desc& d);
 size_t split_backward_ws(const fastgrnn_desc& d);
 bool split_forward_ws_optional(const fastgrnn_desc& d);   // the forward workspace is only used when z_s is NULL
 bool split_dx_optional(const fastgrnn_desc& d);           // the backward accepts d_x == NULL (no input gradient)
+bool split_dx_skippable(const fastgrnn_desc& d);          // ... under FASTGRNN_FLAG_NO_INPUT_GRAD as well
 // the per-unit scaled forward (sg, sc non-NULL, zs = cs = NULL) on the shapes affine_supported() admits
 bool affine_supported(const fastgrnn_desc& d);
 int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0,

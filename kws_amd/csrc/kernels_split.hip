@@ -514,6 +514,7 @@ constexpr int OFF_DP = 0, OFF_HP = 3 * PLANE_H, OFF_XP = 6 * PLANE_H;
 //                2(w&3), 2(w&3)+1 and column tiles 5(w>>2)..+4.  Waves 0-3 contract pair (t+1, t) on even
 //                t, waves 4-7 pair (t+2, t+1) on odd t: every iteration each SIMD has one wave with 60
 //                independent MFMAs in flight and one with only the recurrence.
+template <bool WITH_DX>
 struct BwdW8Lds {
   // Per step s, buffer s&3: natural [utterance][unit] images of the exact bf16 planes of d_pre_s,
   // h_{s-1} and x_s.  Each is read two ways: as MFMA B fragments (ds_read_b128: 8 consecutive units
@@ -526,13 +527,22 @@ struct BwdW8Lds {
   float bias[2][128];                  // bias_gate | bias_update (PREACT: the gates are recomputed)
   float red[16];
 };
+template <>
+struct BwdW8Lds<false> {               // NODX: no d_x partials
+  unsigned char img[4][IMG];
+  float bias[2][128];
+  float red[16];
+};
 
 // NOX: the layer's input is not 32 wide (the reference's second layer: F = 256, model.py:196-203).  Everything that
 // involves W or x leaves the scan: it writes d_pre[T,B,H] (fp32, through the d_x pointer) and the batched GEMMs of
 // kernels_gemm.hip produce  dW = d_pre^T X  and  d_x = d_pre W  afterwards (.cu:538-539 does both per step).  The
 // recurrence, dU (eight column tiles, four per column half) and the bias / zeta / nu sums stay as they are.
 // UQ: update nonlinearity quantTanh (see fwd_scan_split_w8); PREACT contract only.
-template <int GATE, bool PREACT, bool RAGGED, bool BF = false, bool NOX = false, bool UQ = false>
+// NODX (F = 32 only; FASTGRNN_FLAG_NO_INPUT_GRAD with d_x == NULL): the input's gradient is not wanted.  W^T, the d_x
+// MFMAs at the chain's tail, their LDS partials and the d_x stores leave the scan; x stays (dW is contracted here),
+// and d_pre, dW, dU, d_h0 and the bias / zeta / nu sums are the same arithmetic in the same order as without it.
+template <int GATE, bool PREACT, bool RAGGED, bool BF = false, bool NOX = false, bool UQ = false, bool NODX = false>
 __global__ __launch_bounds__(512) void bwd_scan_split_w8(
     int Tn, int B, int rsT, int rsB, int mode, const float* __restrict__ ghs, const float* __restrict__ x,
     const float* __restrict__ hs, const float* __restrict__ aux0, const float* __restrict__ aux1,
@@ -541,7 +551,8 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
     const float* __restrict__ zeta, const float* __restrict__ nu,
     float* __restrict__ d_x, float* __restrict__ d_h0, float* __restrict__ part) {
   constexpr int H = 128, F = 32, KS = 4, NFT = NOX ? 0 : 2, NC = NOX ? 4 : 5;   // NC column tiles per column half
-  __shared__ BwdW8Lds S;
+  static_assert(!(NOX && NODX), "NOX scans leave d_x to a GEMM of its own");
+  __shared__ BwdW8Lds<!NODX> S;
 #ifdef FASTGRNN_DIAG_STAMPS
   unsigned long long dsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dlast = 0;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(dlast)::"memory");
@@ -580,7 +591,7 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
   // d_x[f][b] = sum_n W[n][f] d_pre[b][n]: feature tile xf2, K-step xks
   const int xf2 = wv & 1, xks = wv >> 1;
   Frag3 WTf;
-  if (!NOX) {
+  if (!NOX && !NODX) {
     f32x4 lo, hi;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -749,21 +760,23 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
     }
   };
   auto finish_dx = [&](int t) __attribute__((always_inline)) {
-    if (!NOX && wv < NFT) {                         // wave-uniform: feature tile wv = sum over the four K-steps
-      const f32x4 sacc = (S.DX[t & 1][wv][l] + S.DX[t & 1][wv + 2][l]) + (S.DX[t & 1][wv + 4][l] + S.DX[t & 1][wv + 6][l]);
-      if (xbft) {                                    // d_x in the trainer's [B,F,T]: features are T apart
-        if (valid) {
+    if constexpr (!NOX && !NODX) {
+      if (wv < NFT) {                               // wave-uniform: feature tile wv = sum over the four K-steps
+        const f32x4 sacc = (S.DX[t & 1][wv][l] + S.DX[t & 1][wv + 2][l]) + (S.DX[t & 1][wv + 4][l] + S.DX[t & 1][wv + 6][l]);
+        if (xbft) {                                    // d_x in the trainer's [B,F,T]: features are T apart
+          if (valid) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const size_t o = ((size_t)b * F + wv * 16 + 4 * g + r) * Tn + t;
-            if (BF) reinterpret_cast<unsigned short*>(d_x)[o] = (unsigned short)f32_to_bf16_rne(sacc[r]);
-            else d_x[o] = sacc[r];
+            for (int r = 0; r < 4; ++r) {
+              const size_t o = ((size_t)b * F + wv * 16 + 4 * g + r) * Tn + t;
+              if (BF) reinterpret_cast<unsigned short*>(d_x)[o] = (unsigned short)f32_to_bf16_rne(sacc[r]);
+              else d_x[o] = sacc[r];
+            }
           }
+        } else {
+          char* xo = reinterpret_cast<char*>(d_x) + (size_t)t * rsT * F * ESZ;                 // uniform step base
+          const unsigned lo = ((unsigned)b * (unsigned)rsB * F + wv * 16 + 4 * g) * ESZ;
+          if (valid) { if (BF) st4_bf16(xo + lo, sacc); else *reinterpret_cast<f32x4*>(xo + lo) = sacc; }
         }
-      } else {
-        char* xo = reinterpret_cast<char*>(d_x) + (size_t)t * rsT * F * ESZ;                 // uniform step base
-        const unsigned lo = ((unsigned)b * (unsigned)rsB * F + wv * 16 + 4 * g) * ESZ;
-        if (valid) { if (BF) st4_bf16(xo + lo, sacc); else *reinterpret_cast<f32x4*>(xo + lo) = sacc; }
       }
     }
   };
@@ -873,7 +886,8 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
       // (a runtime index would put the fragments in scratch.)  Every arm issues the product -- the last one
       // unconditionally: xks < KS -- and the partial is stored OUTSIDE the selection: that store is the read which
       // proves these MFMAs, the youngest of the step, have retired (tools/war_scan.py follows every feasible path).
-      if constexpr (!NOX) {
+      // (NODX: no d_x product; the read of dh above is the chain's completion read.)
+      if constexpr (!NOX && !NODX) {
         f32x4 dxp;
         static_assert(KS == 4, "four K-steps");
         if (xks == 0) dxp = mfma6(WTf, dB[0], z4);
@@ -1052,21 +1066,31 @@ void launch_bwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
                        (const float*)p.bias_gate, (const float*)p.bias_update, (const float*)p.zeta,
                        (const float*)p.nu, wide ? dpre : (float*)g.d_x, (float*)g.d_h0, part);
   };
-  if (d.update_nl == FASTGRNN_NL_QUANT_TANH) {       // fp32, SAVE_PREACT, F = 32 (split_supported)
-    if (ragged) go8(bwd_scan_split_w8<GATE, true, true, false, false, true>); else go8(bwd_scan_split_w8<GATE, true, false, false, false, true>);
-  } else if (wide && d.dtype == FASTGRNN_BF16_IO) {  // SAVE_PREACT, gates sigmoid / relu / tanh (split_supported)
+  // F = 32: W and x stay in the scan.  ND: no input gradient (d_x == NULL: FASTGRNN_FLAG_NO_INPUT_GRAD, which the
+  // entry points admit on this shape only); the variant is chosen here, once per launch, never inside a step.
+  auto narrow = [&](auto nodx_tag) __attribute__((always_inline)) {
+    constexpr bool ND = decltype(nodx_tag)::value;
+    if (d.update_nl == FASTGRNN_NL_QUANT_TANH) {     // fp32, SAVE_PREACT, F = 32 (split_supported)
+      if (ragged) go8(bwd_scan_split_w8<GATE, true, true, false, false, true, ND>); else go8(bwd_scan_split_w8<GATE, true, false, false, false, true, ND>);
+    } else if (d.dtype == FASTGRNN_BF16_IO) {
+      if (ragged) go8(bwd_scan_split_w8<GATE, true, true, true, false, false, ND>); else go8(bwd_scan_split_w8<GATE, true, false, true, false, false, ND>);
+    } else if (preact) {
+      if (ragged) go8(bwd_scan_split_w8<GATE, true, true, false, false, false, ND>); else go8(bwd_scan_split_w8<GATE, true, false, false, false, false, ND>);
+    } else {
+      if (ragged) go8(bwd_scan_split_w8<GATE, false, true, false, false, false, ND>); else go8(bwd_scan_split_w8<GATE, false, false, false, false, false, ND>);
+    }
+  };
+  if (wide && d.dtype == FASTGRNN_BF16_IO) {         // SAVE_PREACT, gates sigmoid / relu / tanh (split_supported)
     if constexpr (GATE <= FASTGRNN_NL_TANH) {
       if (ragged) go8(bwd_scan_split_w8<GATE, true, true, true, true>); else go8(bwd_scan_split_w8<GATE, true, false, true, true>);
     }
   } else if (wide) {                                 // fp32 sequences; both saved-tensor contracts
     if (preact) { if (ragged) go8(bwd_scan_split_w8<GATE, true, true, false, true>); else go8(bwd_scan_split_w8<GATE, true, false, false, true>); }
     else        { if (ragged) go8(bwd_scan_split_w8<GATE, false, true, false, true>); else go8(bwd_scan_split_w8<GATE, false, false, false, true>); }
-  } else if (d.dtype == FASTGRNN_BF16_IO) {
-    if (ragged) go8(bwd_scan_split_w8<GATE, true, true, true>); else go8(bwd_scan_split_w8<GATE, true, false, true>);
-  } else if (preact) {
-    if (ragged) go8(bwd_scan_split_w8<GATE, true, true>); else go8(bwd_scan_split_w8<GATE, true, false>);
+  } else if (g.d_x == nullptr) {
+    narrow(std::true_type{});
   } else {
-    if (ragged) go8(bwd_scan_split_w8<GATE, false, true>); else go8(bwd_scan_split_w8<GATE, false, false>);
+    narrow(std::false_type{});
   }
   const int ntot = 128 * 128 + 128 * 32 + 2 * 128 + 2;
   hipLaunchKernelGGL(reduce_slabs_split, dim3((ntot + 63) / 64), dim3(1024), 0, s, nwg, part, (const float*)p.zeta,
@@ -1272,6 +1296,8 @@ size_t split_forward_ws(const fastgrnn_desc& d) {
 bool split_forward_ws_optional(const fastgrnn_desc& d) { return dense_wide_shape(d); }
 // shapes whose d_x is a GEMM of its own behind the scan: the caller may pass d_x = NULL to skip it
 bool split_dx_optional(const fastgrnn_desc& d) { return dense_wide_shape(d) || h256_shape(d); }
+// ... and where the scan can leave its d_x product out (bwd_scan_split_w8<..., NODX>): under FASTGRNN_FLAG_NO_INPUT_GRAD
+bool split_dx_skippable(const fastgrnn_desc& d) { return d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32; }
 
 size_t split_backward_ws(const fastgrnn_desc& d) {
   if (h256_shape(d)) return h256_backward_ws(d);

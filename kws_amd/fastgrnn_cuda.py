@@ -340,7 +340,7 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
 def _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_h, z, h_prime, rank_space, h0,
                      w, u, w1, w2, u1, u2, b0, b1, zeta, nu, need_dx):
     """Allocate the 12 outputs (the parameter gradients as views of ONE flat buffer) and launch."""
-    w_lr, u_lr, shapes, sizes, dx_is_gemm, B, H = ent
+    w_lr, u_lr, shapes, sizes, dx_optional, B, H = ent
     desc = plan[0]
     dev = input.device
     dt = input.dtype
@@ -351,9 +351,9 @@ def _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_
                          _ptr(b0), _ptr(b1), _ptr(zeta), _ptr(nu))
     with torch.cuda.device(dev):
         none = _NONE
-        # the input's gradient is a GEMM of its own on these shapes (fastgrnn_hip.h, fastgrnn_grads.d_x): skipped
-        # when autograd does not ask for it (a model's first layer)
-        d_input = none if (dx_is_gemm and not need_dx) else torch.empty(input.shape, dtype=dt, device=dev)
+        # the input's gradient is optional on these shapes (fastgrnn_hip.h, fastgrnn_grads.d_x): skipped when autograd
+        # does not ask for it (a model's first layer)
+        d_input = none if (dx_optional and not need_dx) else torch.empty(input.shape, dtype=dt, device=dev)
         d_old_h = torch.empty((B, H), dtype=pdt, device=dev)
         # The parameter gradients are views of ONE flat buffer, laid out in the order the modules register
         # their parameters (W | W1,W2 ; U | U1,U2 ; bias_gate ; bias_update ; zeta ; nu).  autograd adopts
@@ -395,6 +395,11 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
                    unrolled, update_nl, flags, bias_gate=None, bias_update=None, need_dx=True):
     lib = _lib.load()
     preact = bool(flags & _lib.FLAG_SAVE_PREACT)
+    if unrolled and not need_dx:
+        # FLAG_NO_INPUT_GRAD lets dense H=128/F=32 skip d_x as well (a scan without the d_x product; elsewhere the flag
+        # changes nothing).  Part of the descriptor, hence of the cached plan and of the signature below: calls with and
+        # without the input's gradient never share an entry.
+        flags |= _lib.FLAG_NO_INPUT_GRAD
     sig = ("b", unrolled, grad_h.shape, grad_h.dtype, input.shape, input.dtype, hs_or_old_h.shape, hs_or_old_h.dtype,
            z.shape, z.dtype, h_prime.shape, h_prime.dtype, h0.shape, h0.dtype, w.shape, u.shape, w1.shape, w2.shape,
            u1.shape, u2.shape, (w if w.numel() else w1).dtype, (u if u.numel() else u1).dtype, zeta.shape, nu.shape,
@@ -467,10 +472,11 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
              ([tuple(u1.shape), tuple(u2.shape)] if u_lr else [(H, H)]) + [(1, H), (1, H), (1, 1), (1, 1)]
     sizes = [a * b for a, b in shapes]
     if zsaved:
-        dx_is_gemm = bool(zx.dx_optional)
+        dx_optional = bool(zx.dx_optional)
     else:
-        dx_is_gemm = (plan[2] == 2 and not w_lr and not u_lr and (desc.H == 256 or (desc.H == 128 and desc.F > 32)))
-    ent = (w_lr, u_lr, shapes, sizes, dx_is_gemm, B, H)
+        dx_optional = (plan[2] == 2 and not w_lr and not u_lr and
+                       (desc.H == 256 or (desc.H == 128 and (desc.F > 32 or bool(flags & _lib.FLAG_NO_INPUT_GRAD)))))
+    ent = (w_lr, u_lr, shapes, sizes, dx_optional, B, H)
     _seen[sig] = (plan, preact and rank_space is not None, ent)
     return _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_h, z, h_prime,
                             rank_space if preact else None, h0, w, u, w1, w2, u1, u2,
