@@ -97,7 +97,13 @@ typedef enum fastgrnn_nonlinearity {
  * of FASTGRNN_FLAG_BATCH_MAJOR (which then only governs hs, the saved tensor and grad_hs).  Kernel path 2:
  * dense H=128/F=32 (read and written in place; backward under FASTGRNN_FLAG_SAVE_PREACT); dense H=256/F=32 and the
  * low-rank H=256/F=32 scans through a time-major copy in the workspace (what the reference's .contiguous() makes,
- * without the tensor it keeps alive for the backward; low-rank backward under FASTGRNN_FLAG_SAVE_PREACT). */
+ * without the tensor it keeps alive for the backward; low-rank backward under FASTGRNN_FLAG_SAVE_PREACT); the layers
+ * whose frame product X.W^T is a GEMM of its own -- dense H=256 with F=64/128, dense H=128 with F=64/128/256, fp32
+ * sequences, and the factorised cells multiplied out onto them: the forward's frame GEMM reads [B,F,T] in place (no
+ * copy of x, no workspace for one; the same bits as on time-major frames), the backward takes a time-major copy of x
+ * in its workspace (align256(T*B*F*4) bytes more) for the dW GEMM and transposes d_x, where wanted, back into the
+ * caller's [B,F,T] tensor.  The backward with BOTH this flag and FASTGRNN_FLAG_BATCH_MAJOR is not on path 2 on the
+ * H=256 and the wide H=128 shapes. */
 #define FASTGRNN_FLAG_X_BFT 128u
 /* A/B only: keep the forward's state product U.h on three bf16 planes (6 MFMAs per K-step) instead of the
  * default fp16 two-plane operands with a per-wave power-of-two scale of U (3 MFMAs per K-step). */
@@ -214,9 +220,12 @@ const char *fastgrnn_hip_status_string(int status);
  *   dense  H=128, F=32            every gate; update tanh or quantTanh (quantTanh: fp32, SAVE_PREACT backward);
  *                                 all layout flags.  Backward with the reference's (z_s, h_prime_s) tensors for the
  *                                 sigmoid / relu / tanh gates, otherwise under FASTGRNN_FLAG_SAVE_PREACT.
- *   dense  H=128, F=64/128/256    (the reference's second layer) time- or batch-major; last-state flags (fp32).
- *                                 bf16 sequences: gates sigmoid / relu / tanh, no last-state flags, backward under
- *                                 FASTGRNN_FLAG_SAVE_PREACT.
+ *   dense  H=128, F=64/128/256    (the reference's second layer) time- or batch-major; last-state flags (fp32);
+ *                                 x in the sequences' layout or, fp32, the loader's [B,F,T] (FASTGRNN_FLAG_X_BFT:
+ *                                 read in place by the forward's frame GEMM, every forward contract and layout;
+ *                                 the backward on a time-major workspace copy, time-major sequences only).
+ *                                 bf16 sequences: gates sigmoid / relu / tanh, no last-state flags, no [B,F,T]
+ *                                 frames, backward under FASTGRNN_FLAG_SAVE_PREACT.
  *   dense  H=256, F=32            (the reference's first layer) time- or batch-major (two-stride rows in
  *                                 both scans, the dU GEMM pairs row b*T+t with hs row b*T+t-1 and every T-th row
  *                                 with h0); x in the sequences' layout or the
@@ -229,9 +238,11 @@ const char *fastgrnn_hip_status_string(int status);
  *                                 (time- or batch-major), backward under it (time-major); no [B,F,T] frames, no
  *                                 FASTGRNN_FLAG_HS_LAST.
  *   dense  H=256, F=64/128        (F = 64: the reference's DEFAULT first layer, feature_type='delta' = 32 MFCCs + 32
- *                                 deltas, trainingConfig.py:36, mfccProcessor.py:27-28) time- or batch-major; as F=32
- *                                 but without FASTGRNN_FLAG_X_BFT: the frame product X.W^T is one batched GEMM into
- *                                 the workspace (T*B*256*4 bytes more of it) in front of the scan.
+ *                                 deltas, trainingConfig.py:36, mfccProcessor.py:27-28) time- or batch-major; as F=32:
+ *                                 the frame product X.W^T is one batched GEMM into the workspace (T*B*256*4 bytes
+ *                                 more of it) in front of the scan.  FASTGRNN_FLAG_X_BFT (fp32): that GEMM reads
+ *                                 the [B,F,T] frames in place -- the forward's workspace is the same with and
+ *                                 without the flag -- and the backward transposes x into its workspace as F=32 does.
  *   low-rank H=256, F=32, both W and U factorised with 1 <= rank <= 16 (the two ranks may differ; ranks are
  *                                 zero-extended to 16 inside the kernels): gates sigmoid / relu / tanh; all layout
  *                                 flags; backward under FASTGRNN_FLAG_SAVE_PREACT only.
@@ -244,7 +255,8 @@ const char *fastgrnn_hip_status_string(int status);
  *                                 No rank-space vector is saved (c_s is ignored under FASTGRNN_FLAG_SAVE_PREACT).
  *   FASTGRNN_FLAG_PREACT_AFFINE (forward only): fp32 sequences, gates sigmoid / relu / tanh, update tanh, dense
  *                                 H=128 with F=32/64/128/256 and dense H=256 with F=32/64/128; time- or batch-major,
- *                                 FASTGRNN_FLAG_HS_LAST.  Every other fp32 / fp64 cell (other shapes, quantised
+ *                                 FASTGRNN_FLAG_HS_LAST; FASTGRNN_FLAG_X_BFT where F > 32 (the frame GEMM reads the
+ *                                 [B,F,T] frames in place; F=32 cells take time-major frames only).  Every other fp32 / fp64 cell (other shapes, quantised
  *                                 nonlinearity codes) runs on path 0, time-major without FASTGRNN_FLAG_HS_LAST.
  *   FASTGRNN_FLAG_ZERO_EXTEND     every other fp32 / bf16-sequence cell with H <= 256 whose zero-padded shape (Hp, Fp)
  *                                 is one of the above: run as that shape (copies around the scans, see the flag).
@@ -288,7 +300,8 @@ int fastgrnn_hip_forward_unroll(const fastgrnn_desc *d, const fastgrnn_params *p
  * which d->flags must carry).  gate_scale, update_scale: [H] in the parameter dtype; p->bias_gate / p->bias_update
  * hold the folded biases, p->w / p->u the folded (dense) matrices.  x:[T,B,F], h0:[B,H] -> hs:[T,B,H] (or the
  * layouts of FASTGRNN_FLAG_BATCH_MAJOR / FASTGRNN_FLAG_HS_LAST on kernel path 2).  No z_s / h_prime_s: nothing is
- * saved for a backward.  fp32 or fp64; bf16 sequences, FASTGRNN_FLAG_X_BFT, FASTGRNN_FLAG_SAVE_PREACT, factorised
+ * saved for a backward.  With FASTGRNN_FLAG_X_BFT (kernel path 2, F = 64 / 128 / 256) x is the loader's [B,F,T].
+ * fp32 or fp64; bf16 sequences, FASTGRNN_FLAG_X_BFT on 32-feature cells, FASTGRNN_FLAG_SAVE_PREACT, factorised
  * operands and the layout flags off path 2 answer FASTGRNN_ERR_UNSUPPORTED. */
 int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc *d, const fastgrnn_params *p,
                                        const void *gate_scale, const void *update_scale,

@@ -254,6 +254,12 @@ class FastGRNNBatchNorm(nn.Module):
             flags |= _lib.FLAG_BATCH_MAJOR
         elif bf:
             x = input.transpose(0, 1)
+        # the trainer's permuted view of the loader's [B,F,T] batch (trainClassifier.py:299): its base as it is where the
+        # scaled forward takes FLAG_X_BFT (the layers whose frame product is a GEMM of its own), else a copy
+        if (not bf and x.dim() == 3 and not x.is_contiguous() and x.permute(1, 2, 0).is_contiguous()
+                and fastgrnn_cuda.kernel_path(Tn, Bn, x.shape[-1], H, 0, 0, cell._gate_code, cell._update_code, x.dtype, 0,
+                                              flags | _lib.FLAG_X_BFT | _lib.FLAG_PREACT_AFFINE) == 2):
+            return _BatchNormInference.apply(cell, x.permute(1, 2, 0), h0, flags | _lib.FLAG_X_BFT, *cell._fold_tensors())
         x = x.contiguous()
         if last_state and fastgrnn_cuda.kernel_path(Tn, Bn, x.shape[-1], H, 0, 0, cell._gate_code, cell._update_code,
                                                     x.dtype, 0, flags | _lib.FLAG_PREACT_AFFINE) != 2:

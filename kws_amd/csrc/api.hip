@@ -240,10 +240,11 @@ int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc* dz, const fastgrnn_p
   if ((st = check_params(d, p))) return st;
   if (!gate_scale || !update_scale || !x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
   if (!(d->flags & FASTGRNN_FLAG_PREACT_AFFINE) || d->dtype == FASTGRNN_BF16_IO || d->w_rank || d->u_rank ||
-      (d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST | FASTGRNN_FLAG_BN_TRAIN)))
+      (d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_GRAD_LAST | FASTGRNN_FLAG_BN_TRAIN)))
     return FASTGRNN_ERR_UNSUPPORTED;
   const int path = pick_path(d, 0);
-  if ((d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_HS_LAST)) && path != 2) return FASTGRNN_ERR_UNSUPPORTED;
+  // (FASTGRNN_FLAG_X_BFT: path 2 takes it on the wide shapes -- affine_supported -- and nothing else does)
+  if ((d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_X_BFT)) && path != 2) return FASTGRNN_ERR_UNSUPPORTED;
   if ((st = check_ws(workspace, workspace_bytes, fastgrnn_hip_forward_workspace_bytes(d)))) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (path == 2) return split_forward(*d, *p, x, h0, hs, nullptr, nullptr, workspace, s, gate_scale, update_scale);

@@ -93,6 +93,9 @@ int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
 bool rows_gemm_supported(int N, int K, bool trans_w);
 int rows_gemm(size_t R, int N, int K, bool trans_w, const void* A, const float* W, void* C, bool bf_in, bool bf_out,
               hipStream_t s);
+// ... with A the data loader's [B,K,T] frames read in place (fp32; N = 128 / 256 of the wide layers) and row (b, t) of C
+// stored at row t * cT + b * cB: the same bits as rows_gemm on the time-major copy
+int rows_gemm_bft(int B, int T, int N, int K, const float* A, const float* W, float* C, size_t cT, size_t cB, hipStream_t s);
 bool tn_gemm_big_supported(int M, int N);
 size_t tn_gemm_big_ws(size_t R, int M, int N);
 int tn_gemm_big_run(size_t R, int M, int N, const float* A, int lda, const float* B0, const void* B1, size_t shiftB,
@@ -112,7 +115,7 @@ int h256_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
                   const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s);
 
 // low-rank H = 256 / F = 32 scans, ranks <= 16 (kernels_lowrank.hip), dispatched like the H = 256 dense ones
-void bft_transpose_f32(int B, int T, const float* src, float* dst, bool to_time_major, hipStream_t s);
+void bft_transpose_f32(int B, int T, const float* src, float* dst, bool to_time_major, hipStream_t s, int F = 32);   // F: 32 / 64 / 128 / 256
 bool lowrank_shape(const fastgrnn_desc& d);
 bool lowrank_supported(const fastgrnn_desc& d, int direction);
 size_t lowrank_forward_ws(const fastgrnn_desc& d);

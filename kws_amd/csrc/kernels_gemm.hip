@@ -30,17 +30,30 @@ namespace {
 // fragments (columns = rows of A) from there with conflict-free ds_read_b128.
 //   TRANS_W: Wt[n][k] = W[k * N + n] (the caller's matrix is [K,N]: d_x = d_pre . W with W:[H,F]).
 //   BF_IN / BF_OUT: A / C are bf16 (FASTGRNN_BF16_IO sequences); arithmetic and W stay fp32.
+//   BFT_IN (fp32 A, !TRANS_W): A is the data loader's [B,K,T] batch (FASTGRNN_FLAG_X_BFT), read in place.  Rows are
+//     enumerated utterance-major, r = b * Tn + t, and element (r, k) is A[(b * K + k) * Tn + t]: for one k the 32 rows
+//     of a stage are 128 contiguous bytes (but for the jump where a stage straddles two utterances), so a stage is
+//     loaded with consecutive lanes on consecutive ROWS, 4 bytes each ([B,K,T] rows are only 4-byte aligned for odd
+//     Tn).  A lane still collects four consecutive k of its row, so the split and the [row][k] plane images -- hence
+//     everything from the fragment reads on -- are those of the time-major kernel, and every row's sum is formed as
+//     there: the same bits.  The 8-byte plane writes of 16 consecutive rows would meet two-way in the 32 banks a
+//     ds_write_b64 lane group sees (row pitch 2K + 16 bytes = 4 banks mod 32, 2 banks per write): rows 8-15 of a group
+//     take the neighbouring k-quad instead (c4 ^ 1, which the other half of the wave covers for rows 0-7), and the 16
+//     writes of a group fall on 32 different banks; the wave's loads still cover the same two 128-byte runs.
+//     Row (b, t) of C is stored at row t * cT + b * cB: where the scan that consumes the product reads it.
 constexpr int RG_ROWS = 32;                       // rows per stage (two MFMA column tiles)
 
-template <int NT, int KS, bool TRANS_W, bool BF_IN = false, bool BF_OUT = false>
+template <int NT, int KS, bool TRANS_W, bool BF_IN = false, bool BF_OUT = false, bool BFT_IN = false>
 __global__ __launch_bounds__(512) void rows_gemm_split(size_t R, int stages_per_wg, const void* __restrict__ Av,
-                                                       const float* __restrict__ W, void* __restrict__ Cv) {
+                                                       const float* __restrict__ W, void* __restrict__ Cv,
+                                                       int Tn = 0, unsigned cT = 0, unsigned cB = 0) {
   constexpr int K = 32 * KS, N = 16 * NT;
   constexpr int WN = NT >= 8 ? 8 : NT, WR = 8 / WN, NPW = NT / WN, RT = RG_ROWS / 16;
   constexpr int ROWB = K * 2 + 16;                // bytes per row of a plane image (+16: conflict-free b128 reads)
   constexpr int VPT = RG_ROWS * K / 4 / 512;      // float4 per thread per stage
   constexpr int KB = KS < 4 ? KS : 4;             // K-steps per fragment batch
   static_assert(NT % WN == 0 && VPT >= 1 && KS % KB == 0, "shape");
+  static_assert(!BFT_IN || (!BF_IN && !BF_OUT && !TRANS_W && VPT * 64 == K), "[B,K,T] frames: fp32, 16 k-quads per pass of the workgroup");
   constexpr int PA = BF_IN ? 1 : 3;               // planes of A in LDS: a bf16 value is its own first plane, the others zero
   __shared__ __attribute__((aligned(16))) unsigned char pl[2][PA][RG_ROWS * ROWB];
 
@@ -84,6 +97,24 @@ __global__ __launch_bounds__(512) void rows_gemm_split(size_t R, int stages_per_
   auto load_stage = [&](size_t st, Stage& S) __attribute__((always_inline)) {
     f32x4 (&va)[VPT] = S.va; uint2 (&vraw)[VPT] = S.vraw;
     const size_t r0 = st * RG_ROWS;
+    if constexpr (BFT_IN) {
+      // lane -> row tid & 31; every load is issued (rows beyond R re-read the last row), then replaced by zeros: no
+      // branch around a memory instruction
+      const size_t rr = r0 + (tid & 31);
+      const bool ok = rr < R;
+      const unsigned rc = (unsigned)(ok ? rr : R - 1);
+      const unsigned b = rc / (unsigned)Tn, t = rc - b * (unsigned)Tn;
+      const float* ap = reinterpret_cast<const float*>(Av) + (size_t)b * K * Tn + t;
+#pragma unroll
+      for (int j = 0; j < VPT; ++j) {
+        const int c4 = ((tid >> 5) + 16 * j) ^ ((tid >> 3) & 1);
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = ap[(size_t)(4 * c4 + e) * Tn];
+        va[j] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < VPT; ++j) {
       const int idx = tid + 512 * j, row = idx / (K / 4);
@@ -97,7 +128,9 @@ __global__ __launch_bounds__(512) void rows_gemm_split(size_t R, int stages_per_
     const f32x4 (&va)[VPT] = S.va; const uint2 (&vraw)[VPT] = S.vraw;
 #pragma unroll
     for (int j = 0; j < VPT; ++j) {
-      const int idx = tid + 512 * j, row = idx / (K / 4), c4 = idx % (K / 4);
+      const int idx = tid + 512 * j;
+      const int row = BFT_IN ? (tid & 31) : idx / (K / 4);
+      const int c4 = BFT_IN ? (((tid >> 5) + 16 * j) ^ ((tid >> 3) & 1)) : idx % (K / 4);   // (as load_stage)
       const unsigned off = (unsigned)(row * ROWB + c4 * 8);
       if (BF_IN) {                                  // the raw 8 bytes ARE plane 0 (no vector arithmetic at all)
         *reinterpret_cast<uint2*>(&pl[buf][0][off]) = vraw[j];
@@ -159,10 +192,15 @@ __global__ __launch_bounds__(512) void rows_gemm_split(size_t R, int stages_per_
       }
       const size_t r = r0 + rt * 16 + i;
       if (r < R) {
+        size_t crow = r;
+        if constexpr (BFT_IN) {                      // row (b, t) of the product goes where its consumer reads it
+          const unsigned b = (unsigned)r / (unsigned)Tn, t = (unsigned)r - b * (unsigned)Tn;
+          crow = (size_t)t * cT + (size_t)b * cB;
+        }
 #pragma unroll
         for (int a = 0; a < NPW; ++a) {
           const f32x4 o = hi[a] + lo[a];
-          const size_t e = r * N + 16 * (wn * NPW + a) + 4 * g;
+          const size_t e = crow * N + 16 * (wn * NPW + a) + 4 * g;
           if (BF_OUT) st4_bf16(reinterpret_cast<unsigned short*>(Cv) + e, o);
           else st4(reinterpret_cast<float*>(Cv) + e, o);
         }
@@ -201,6 +239,15 @@ void launch_rows_gemm(size_t R, const void* A, const float* W, void* C, bool bf_
   else if (bf_in) hipLaunchKernelGGL((rows_gemm_split<NT, KS, TRANS_W, true, false>), dim3(nwg), dim3(512), 0, s, R, spw, A, W, C);
   else if (bf_out) hipLaunchKernelGGL((rows_gemm_split<NT, KS, TRANS_W, false, true>), dim3(nwg), dim3(512), 0, s, R, spw, A, W, C);
   else hipLaunchKernelGGL((rows_gemm_split<NT, KS, TRANS_W, false, false>), dim3(nwg), dim3(512), 0, s, R, spw, A, W, C);
+}
+
+template <int NT, int KS>
+void launch_rows_gemm_bft(int B, int T, const float* A, const float* W, float* C, unsigned cT, unsigned cB, hipStream_t s) {
+  const size_t R = (size_t)B * T, nstages = (R + RG_ROWS - 1) / RG_ROWS;
+  const int nwg = (int)(nstages < 256 ? nstages : 256);
+  const int spw = (int)((nstages + nwg - 1) / nwg);
+  hipLaunchKernelGGL((rows_gemm_split<NT, KS, false, false, false, true>), dim3(nwg), dim3(512), 0, s, R, spw, (const void*)A, W,
+                     (void*)C, T, cT, cB);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -690,6 +737,20 @@ int rows_gemm(size_t R, int N, int K, bool trans_w, const void* A, const float* 
   RG_CASE(256, 64) RG_CASE(256, 128)
   RG_CASE(32, 64) RG_CASE(32, 128) RG_CASE(32, 256) RG_CASE(64, 64) RG_CASE(64, 128) RG_CASE(64, 256)
 #undef RG_CASE
+  return FASTGRNN_ERR_UNSUPPORTED;
+}
+
+// the frame GEMM on [B,K,T] frames in place (rows_gemm_split<..., BFT_IN>): N = 128 with K = 64 / 128 / 256, N = 256
+// with K = 64 / 128; B * T < 2^32
+int rows_gemm_bft(int B, int T, int N, int K, const float* A, const float* W, float* C, size_t cT, size_t cB, hipStream_t s) {
+  if ((double)B * T >= 4294967296.0 || cT >= ((size_t)1 << 32) || cB >= ((size_t)1 << 32)) return FASTGRNN_ERR_UNSUPPORTED;
+#define RGB_CASE(n, k)                                                                              \
+  if (N == n && K == k) {                                                                           \
+    launch_rows_gemm_bft<n / 16, k / 32>(B, T, A, W, C, (unsigned)cT, (unsigned)cB, s);             \
+    return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;                     \
+  }
+  RGB_CASE(128, 64) RGB_CASE(128, 128) RGB_CASE(128, 256) RGB_CASE(256, 64) RGB_CASE(256, 128)
+#undef RGB_CASE
   return FASTGRNN_ERR_UNSUPPORTED;
 }
 

@@ -786,7 +786,7 @@ H256BwdWs h256_bwd_layout(const fastgrnn_desc& d) {
   L.tn = o; o += tn_u > tn_w ? tn_u : tn_w;
   // FASTGRNN_FLAG_X_BFT: the time-major copy of x for the dW GEMM; the d_x GEMM then writes over it and the result is
   // transposed into the caller's [B,F,T] tensor
-  L.xtm = o; if (d.flags & FASTGRNN_FLAG_X_BFT) o += align256(TB * F2 * 4);
+  L.xtm = o; if (d.flags & FASTGRNN_FLAG_X_BFT) o += align256(TB * (size_t)d.F * 4);
   L.total = o;
   return L;
 }
@@ -800,16 +800,21 @@ void launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
   unsigned* flags = reinterpret_cast<unsigned*>(ws);
   // FASTGRNN_FLAG_X_BFT: the loader's [B,F,T] frames are transposed into the workspace first (25 us at B = 4096; a
   // lane's frame-by-frame read of [B,F,T] in place touches 64 cache lines per wave load and cost the scan 120 us)
-  if (d.flags & FASTGRNN_FLAG_X_BFT) {
+  // (F = 32 only: a wider layer's frames are consumed by the frame GEMM, which reads [B,F,T] in place)
+  const bool prein = d.F != F2, bf = d.dtype == FASTGRNN_BF16_IO;
+  const bool bm_hs = (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0;
+  if ((d.flags & FASTGRNN_FLAG_X_BFT) && !prein) {
     float* xtm = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + h256_flag_bytes(d));
     bft_transpose_f32(d.B, d.T, (const float*)x, xtm, true, s);
     x = xtm;
   }
   // a wider input (F = 64 / 128): the batched frame GEMM  P = X . W^T  into the workspace, then the PREIN scan on P
-  const bool prein = d.F != F2, bf = d.dtype == FASTGRNN_BF16_IO;
   if (prein) {
     float* P = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + h256_flag_bytes(d));
-    rows_gemm((size_t)d.T * d.B, H2, d.F, false, x, (const float*)p.w, P, bf, false, s);   // (bf16 frames, fp32 P)
+    if (d.flags & FASTGRNN_FLAG_X_BFT)               // (fp32: h256_supported) rows of P land in the order of hs
+      rows_gemm_bft(d.B, d.T, H2, d.F, (const float*)x, (const float*)p.w, P, bm_hs ? 1 : (size_t)d.B, bm_hs ? (size_t)d.T : 1, s);
+    else
+      rows_gemm((size_t)d.T * d.B, H2, d.F, false, x, (const float*)p.w, P, bf, false, s);   // (bf16 frames, fp32 P)
     x = P;
   }
   // strides of the sequences (elements): FASTGRNN_FLAG_BATCH_MAJOR lays hs / zs / cs and x out as [B,T,*]; the
@@ -911,14 +916,14 @@ void launch_bwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* gh
   else tn_gemm_big_run(TB, H2, H2, dpre, H2, (const float*)h0, hs, (size_t)d.B, H2, tn, (float*)g.d_u, H2, s, bf);
   const bool bft = (d.flags & FASTGRNN_FLAG_X_BFT) != 0;
   float* xtm = (float*)(base + L.xtm);
-  if (bft) bft_transpose_f32(d.B, d.T, (const float*)x, xtm, true, s);
+  if (bft) bft_transpose_f32(d.B, d.T, (const float*)x, xtm, true, s, d.F);
   const float* xr = bft ? xtm : (const float*)x;
   tn_gemm_big_run(TB, H2, d.F, dpre, H2, xr, xr, (size_t)0, d.F, tn, (float*)g.d_w, d.F, s, bf);
   // d_x = d_pre . W   (.cu:538; W is [H,F] = [K,N]); skipped when the caller does not want the input's gradient
   // (g.d_x == NULL: the first layer of a model, whose input is data)
   if (g.d_x) {
     rows_gemm(TB, d.F, H2, true, dpre, (const float*)p.w, bft ? (void*)xtm : g.d_x, false, bf, s);   // (bf16 d_x)
-    if (bft) bft_transpose_f32(d.B, d.T, xtm, (float*)g.d_x, false, s);
+    if (bft) bft_transpose_f32(d.B, d.T, xtm, (float*)g.d_x, false, s, d.F);
   }
 }
 
@@ -940,7 +945,8 @@ bool h256_supported(const fastgrnn_desc& d, int direction) {
     if (direction == 1 && !(d.flags & FASTGRNN_FLAG_SAVE_PREACT)) return false;
     if (direction == 1 && (d.flags & FASTGRNN_FLAG_BATCH_MAJOR)) return false;   // (no bf16 variant of the periodic dU GEMM)
   }
-  if (d.F != F2 && (d.flags & FASTGRNN_FLAG_X_BFT)) return false;      // (the loader's [B,F,T] batches: 32 features)
+  // (the loader's [B,F,T] batches, fp32: F = 32 through a workspace transpose; F = 64 / 128 read in place by the frame
+  // GEMM, the backward on a time-major workspace copy)
   // batch-major sequences: two-stride rows in both scans; the backward's d_pre rows then follow [B,T], which a
   // time-major workspace copy of [B,F,T] frames would not match
   if (direction == 1 && (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) && (d.flags & FASTGRNN_FLAG_X_BFT)) return false;
@@ -953,10 +959,10 @@ bool h256_supported(const fastgrnn_desc& d, int direction) {
 
 size_t h256_backward_ws(const fastgrnn_desc& d) { return h256_bwd_layout(d).total; }
 // one word per workgroup: "my rows of h0 are outside the fp16 path's range" (fwd_scan_h256 MODE 1 -> MODE 2)
-// + under FASTGRNN_FLAG_X_BFT the time-major copy of x
-// + for F = 64 / 128 the frame product P[T*B, 256]
+// + under FASTGRNN_FLAG_X_BFT with F = 32 the time-major copy of x
+// + for F = 64 / 128 the frame product P[T*B, 256] (the frame GEMM reads [B,F,T] frames in place: no copy of x)
 size_t h256_forward_ws(const fastgrnn_desc& d) {
-  return h256_flag_bytes(d) + ((d.flags & FASTGRNN_FLAG_X_BFT) ? align256((size_t)d.T * d.B * F2 * 4) : 0) +
+  return h256_flag_bytes(d) + (((d.flags & FASTGRNN_FLAG_X_BFT) && d.F == F2) ? align256((size_t)d.T * d.B * F2 * 4) : 0) +
          (d.F != F2 ? align256((size_t)d.T * d.B * H2 * 4) : 0);
 }
 

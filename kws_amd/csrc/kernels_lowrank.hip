@@ -722,11 +722,17 @@ __global__ __launch_bounds__(1024) void reduce_lowrank_slabs(int nwg, const floa
 // x[B][F][T] (FASTGRNN_FLAG_X_BFT, the data loader's layout, trainClassifier.py:204) <-> time-major [T][B][F].  The
 // low-rank scans take the time-major copy from the workspace (the reference makes the same copy with .contiguous(),
 // rnn.py:910); the dense H = 128 scans read [B,F,T] in place.  One workgroup per utterance, 64 frames at a time.
-template <typename E, bool TO_TBF>
+// FW: the width of a frame (32; 64 / 128 / 256 for the backward of the wide layers, whose weight-gradient GEMM wants
+// time-major rows): workgroup (b, y) moves features 32y .. 32y + 31.
+template <typename E, bool TO_TBF, int FW = 32>
 __global__ __launch_bounds__(256) void bft_transpose(int B, int T, const E* __restrict__ src, E* __restrict__ dst) {
   constexpr int F = 32;
   __shared__ E tile[F][65];
   const int b = blockIdx.x, tid = threadIdx.x;
+  if (FW != 32) {                                    // (uniform per workgroup, ahead of every barrier and LDS access)
+    src += TO_TBF ? (size_t)blockIdx.y * 32 * T : (size_t)blockIdx.y * 32;
+    dst += TO_TBF ? (size_t)blockIdx.y * 32 : (size_t)blockIdx.y * 32 * T;
+  }
   for (int tc = 0; tc < T; tc += 64) {
     __syncthreads();
     // all (predicated) loads first, then unconditional LDS writes: no LDS write sits in front of a branch with memory
@@ -736,7 +742,7 @@ __global__ __launch_bounds__(256) void bft_transpose(int B, int T, const E* __re
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int f = (tid >> 6) + 4 * k, tt = tid & 63;
-        v[k] = (tc + tt < T) ? src[((size_t)b * F + f) * T + tc + tt] : E(0);
+        v[k] = (tc + tt < T) ? src[((size_t)b * FW + f) * T + tc + tt] : E(0);
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) tile[(tid >> 6) + 4 * k][tid & 63] = v[k];
@@ -744,7 +750,7 @@ __global__ __launch_bounds__(256) void bft_transpose(int B, int T, const E* __re
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int tt = (tid >> 5) + 8 * k, f = tid & 31;
-        v[k] = (tc + tt < T) ? src[((size_t)(tc + tt) * B + b) * F + f] : E(0);
+        v[k] = (tc + tt < T) ? src[((size_t)(tc + tt) * B + b) * FW + f] : E(0);
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) tile[tid & 31][(tid >> 5) + 8 * k] = v[k];
@@ -754,13 +760,13 @@ __global__ __launch_bounds__(256) void bft_transpose(int B, int T, const E* __re
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int tt = (tid >> 5) + 8 * k, f = tid & 31;
-        if (tc + tt < T) dst[((size_t)(tc + tt) * B + b) * F + f] = tile[f][tt];
+        if (tc + tt < T) dst[((size_t)(tc + tt) * B + b) * FW + f] = tile[f][tt];
       }
     } else {
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int f = (tid >> 6) + 4 * k, tt = tid & 63;
-        if (tc + tt < T) dst[((size_t)b * F + f) * T + tc + tt] = tile[f][tt];
+        if (tc + tt < T) dst[((size_t)b * FW + f) * T + tc + tt] = tile[f][tt];
       }
     }
   }
@@ -920,7 +926,15 @@ int lowrank_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
 
 // fp32 [B,32,T] <-> [T,B,32] for the dense H = 256 layer's backward (kernels_h256.hip): its dW GEMM and d_x GEMM work on
 // time-major rows
-void bft_transpose_f32(int B, int T, const float* src, float* dst, bool to_time_major, hipStream_t s) {
+void bft_transpose_f32(int B, int T, const float* src, float* dst, bool to_time_major, hipStream_t s, int F) {
+#define BFT_WIDE(fw)                                                                                                  \
+  if (F == fw) {                                                                                                      \
+    if (to_time_major) hipLaunchKernelGGL((bft_transpose<float, true, fw>), dim3(B, fw / 32), dim3(256), 0, s, B, T, src, dst); \
+    else hipLaunchKernelGGL((bft_transpose<float, false, fw>), dim3(B, fw / 32), dim3(256), 0, s, B, T, src, dst);    \
+    return;                                                                                                           \
+  }
+  BFT_WIDE(64) BFT_WIDE(128) BFT_WIDE(256)
+#undef BFT_WIDE
   if (to_time_major) hipLaunchKernelGGL((bft_transpose<float, true>), dim3(B), dim3(256), 0, s, B, T, src, dst);
   else hipLaunchKernelGGL((bft_transpose<float, false>), dim3(B), dim3(256), 0, s, B, T, src, dst);
 }

@@ -1037,13 +1037,16 @@ bool dense_wide_shape(const fastgrnn_desc& d) {
          // 32-bit byte offsets inside a tensor (see split_supported), the d_pre workspace's 16 sink rows included
          ((double)d.T * d.B + 16.0) * (d.F > 128 ? d.F : 128) * 4.0 < 4294967296.0;
 }
-struct WideBwdWs { size_t slabs, dpre, tn, total; };
+struct WideBwdWs { size_t slabs, dpre, tn, xtm, total; };
 WideBwdWs wide_bwd_layout(const fastgrnn_desc& d) {
   const size_t TB = (size_t)d.T * d.B, nwg = (d.B + 15) / 16;
   WideBwdWs L; size_t o = 0;
   L.slabs = o; o += align256(nwg * SLAB * 4);
   L.dpre = o; o += align256((TB + 16) * 128 * 4);    // + 16 sink rows for the lanes beyond a ragged batch
   L.tn = o; o += tn_gemm_big_ws(TB, 128, d.F);
+  // FASTGRNN_FLAG_X_BFT: the time-major copy of x for the dW GEMM (its rows follow d_pre's); the d_x GEMM then writes
+  // over it and the result is transposed into the caller's [B,F,T] tensor (as kernels_h256.hip)
+  L.xtm = o; if (d.flags & FASTGRNN_FLAG_X_BFT) o += align256(TB * (size_t)d.F * 4);
   L.total = o;
   return L;
 }
@@ -1055,7 +1058,7 @@ void launch_bwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
   dim3 grid(nwg);
   const bool ragged = (d.B % 16) != 0, preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
   const bool wide = dense_wide_shape(d);
-  const WideBwdWs L = wide ? wide_bwd_layout(d) : WideBwdWs{0, 0, 0, 0};
+  const WideBwdWs L = wide ? wide_bwd_layout(d) : WideBwdWs{0, 0, 0, 0, 0};
   float* part = reinterpret_cast<float*>(ws);
   float* dpre = wide ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.dpre) : nullptr;
   auto go8 = [&](auto kern) __attribute__((always_inline)) {     // 8-wave kernels also take the x layout
@@ -1100,10 +1103,16 @@ void launch_bwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
     const size_t TB = (size_t)d.T * d.B;
     // dW[H,F] = d_pre^T . X   (.cu:539 summed over the steps)
     const bool bfw = d.dtype == FASTGRNN_BF16_IO;    // (x and d_x are bf16 then; d_pre is fp32 always)
+    const bool bft = (d.flags & FASTGRNN_FLAG_X_BFT) != 0;   // (fp32, time-major sequences: split_supported)
+    float* xtm = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.xtm);
+    if (bft) { bft_transpose_f32(d.B, d.T, (const float*)x, xtm, true, s, d.F); x = xtm; }
     tn_gemm_big_run(TB, 128, d.F, dpre, 128, (const float*)x, x, (size_t)0, d.F,
                     reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.tn), (float*)g.d_w, d.F, s, bfw);
     // d_x[T*B,F] = d_pre . W   (.cu:538 for every step at once; W is [H,F] = [K,N])
-    if (g.d_x) rows_gemm(TB, d.F, 128, true, dpre, (const float*)p.w, g.d_x, false, bfw, s);   // (NULL: not wanted)
+    if (g.d_x) {                                     // (NULL: not wanted)
+      rows_gemm(TB, d.F, 128, true, dpre, (const float*)p.w, bft ? (void*)xtm : g.d_x, false, bfw, s);
+      if (bft) bft_transpose_f32(d.B, d.T, xtm, (float*)g.d_x, false, s, d.F);
+    }
   }
 }
 
@@ -1252,7 +1261,10 @@ bool split_supported(const fastgrnn_desc& d, int direction) {
   // dense H = 128 with a wider input (F = 64 / 128 / 256; the reference's second layer): recurrence-only scans +
   // batched GEMMs.  fp32 sequences, time- or batch-major, every gate, full or last-state outputs / gradients.
   if (dense_wide_shape(d)) {
-    if (d.flags & FASTGRNN_FLAG_X_BFT) return false;
+    // the loader's [B,F,T] batches: fp32; the frame GEMM reads them in place, the backward takes a time-major workspace
+    // copy, which rows of batch-major d_pre would not match
+    if ((d.flags & FASTGRNN_FLAG_X_BFT) &&
+        (d.dtype != FASTGRNN_F32 || (direction == 1 && (d.flags & FASTGRNN_FLAG_BATCH_MAJOR)))) return false;
     if (d.dtype == FASTGRNN_BF16_IO)                 // bf16 sequences (round 3): the reference's three gates, no last-state
       return d.gate_nl <= FASTGRNN_NL_TANH &&        // flags, the backward under the one-saved-tensor contract
              !(d.flags & (FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_GRAD_LAST)) && (direction == 0 || preact);
@@ -1276,7 +1288,9 @@ bool split_supported(const fastgrnn_desc& d, int direction) {
 // H = 128 (F = 32 / 64 / 128 / 256) and H = 256 (F = 32 / 64 / 128); time- or batch-major, hs or h_T alone
 bool affine_supported(const fastgrnn_desc& d) {
   if (d.dtype != FASTGRNN_F32 || d.gate_nl > FASTGRNN_NL_TANH || d.update_nl != FASTGRNN_NL_TANH) return false;
-  if (d.flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)) return false;
+  if (d.flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_GRAD_LAST)) return false;
+  // [B,F,T] frames: only where the frame product is a GEMM of its own (the scaled F = 32 scans read time-major frames)
+  if ((d.flags & FASTGRNN_FLAG_X_BFT) && !((h256_shape(d) && d.F != 32) || dense_wide_shape(d))) return false;
   if (h256_shape(d)) return h256_supported(d, 0);
   const bool fits32 = (double)d.T * d.B * (d.H > d.F ? d.H : d.F) * 4.0 < 4294967296.0;
   return (d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && fits32) || dense_wide_shape(d);
@@ -1341,7 +1355,10 @@ int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
     // the workspace when the caller wants neither
     pws = zs == nullptr ? ws : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? zs : cs);
     if (!pws) return FASTGRNN_ERR_WORKSPACE;
-    const int st = rows_gemm((size_t)d.T * d.B, 128, d.F, false, x, (const float*)p.w, pws, d.dtype == FASTGRNN_BF16_IO, false, s);
+    // (FASTGRNN_FLAG_X_BFT: the [B,F,T] frames are read in place; the rows of P land in the order of hs)
+    const int st = (d.flags & FASTGRNN_FLAG_X_BFT)
+        ? rows_gemm_bft(d.B, d.T, 128, d.F, (const float*)x, (const float*)p.w, (float*)pws, (size_t)row_stride_t(d), (size_t)row_stride_b(d), s)
+        : rows_gemm((size_t)d.T * d.B, 128, d.F, false, x, (const float*)p.w, pws, d.dtype == FASTGRNN_BF16_IO, false, s);
     if (st != FASTGRNN_OK) return st;
   }
   switch (d.gate_nl) {

@@ -529,7 +529,8 @@ def forward_unroll_affine(input, w, u, bias_gate, bias_update, zeta, nu, gate_sc
     ``fastgrnn_hip_forward_unroll_affine``): ``z = gate(gate_scale*pre + bias_gate)``, ``h' = update(update_scale*pre
     + bias_update)``, ``pre = w.x + u.h`` -- an eval-mode BatchNorm cell after folding.  Dense operands in the
     ``[out,in]`` layout, fp32 or fp64.  Returns hs (``[T,B,H]``, ``[B,T,H]`` under FLAG_BATCH_MAJOR, ``[B,H]`` under
-    FLAG_HS_LAST).  Nothing is saved for a backward."""
+    FLAG_HS_LAST).  With FLAG_X_BFT ``input`` is the data loader's ``[B,F,T]`` batch (layers whose frame product is a
+    GEMM of its own: F = 64 / 128 / 256 on kernel path 2).  Nothing is saved for a backward."""
     lib = _lib.load()
     flags = int(flags) | _lib.FLAG_PREACT_AFFINE
     for t, n in ((input, "input"), (initial_h, "initial_h"), (bias_gate, "bias_gate"), (bias_update, "bias_update"),
@@ -537,7 +538,9 @@ def forward_unroll_affine(input, w, u, bias_gate, bias_update, zeta, nu, gate_sc
         _check_input(t, n)
     if input.dim() != 3:
         raise RuntimeError("input must be [timesteps, batch, features]")
-    if flags & _lib.FLAG_BATCH_MAJOR:
+    if flags & _lib.FLAG_X_BFT:
+        B, F, T = input.shape
+    elif flags & _lib.FLAG_BATCH_MAJOR:
         B, T, F = input.shape
     else:
         T, B, F = input.shape
@@ -556,7 +559,7 @@ def forward_unroll_affine(input, w, u, bias_gate, bias_update, zeta, nu, gate_sc
                                    input.dtype, z_non_linearity, update_non_linearity, flags)
     _warn_fallback(plan, 0)
     dev = input.device
-    hs_shape = (B, H) if flags & _lib.FLAG_HS_LAST else tuple(input.shape[:2]) + (H,)
+    hs_shape = (B, H) if flags & _lib.FLAG_HS_LAST else ((B, T, H) if flags & _lib.FLAG_BATCH_MAJOR else (T, B, H))
     with torch.cuda.device(dev):
         hs = torch.empty(hs_shape, dtype=input.dtype, device=dev)
         ws, wsp = _workspace(plan[3], dev)

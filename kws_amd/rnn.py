@@ -60,6 +60,13 @@ class FastGRNNFunction(Function):
         return _as_autograd_grads(outputs, ctx.needs_input_grad)
 
 
+def _is_bft_view(input):
+    """``input`` is what the trainer hands over: permute(2,0,1) of the loader's [B,F,T] batch (trainClassifier.py:204,
+    299), a [T,B,F] view whose base the kernels can take under FLAG_X_BFT."""
+    return (input.is_cuda and input.dim() == 3 and not input.is_contiguous()
+            and input.permute(1, 2, 0).is_contiguous())
+
+
 _unroll_decisions = {}
 _zero_states = {}        # (B, H, dtype, device) -> the default h0
 _inference_ok = {}       # call signature -> "the hs-only forward is on kernel path 2"
@@ -96,8 +103,7 @@ class FastGRNNUnrollFunction(Function):
             # The trainer hands over permute(2,0,1) of the loader's [B,F,T] batch (trainClassifier.py:204,299), a
             # [T,B,F] VIEW; the reference copies it here with .contiguous().  Where the kernels can read [B,F,T]
             # in place (FLAG_X_BFT) the view's base is passed instead and d_input comes back as the same view.
-            x_bft = (not batch_major and input.is_cuda and not input.is_contiguous()
-                     and input.permute(1, 2, 0).is_contiguous()
+            x_bft = (not batch_major and _is_bft_view(input)
                      and input.dtype in (torch.float32, torch.bfloat16)
                      and fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, gate_non_linearity, 2, input.dtype, 1,
                                                    _lib.FLAG_SAVE_PREACT | _lib.FLAG_X_BFT) == 2)
@@ -420,12 +426,15 @@ class FastGRNNCUDA(nn.Module):
         """hs alone when nothing will be differentiated (torch.no_grad()): no tensor is saved for a backward, so the
         scan writes one [T,B,H] tensor instead of two.  None where the kernels have no such variant (the caller then
         goes through the autograd function as before)."""
-        if not (input.is_cuda and input.is_contiguous() and input.dtype in (torch.float32, torch.bfloat16)):
+        # the trainer's permuted view of a [B,F,T] batch (evaluate(), trainClassifier.py:299): its base is passed under
+        # FLAG_X_BFT where the kernels take it (not beside FLAG_ZERO_EXTEND: such a view goes the autograd function's way)
+        bft = not batch_major and _is_bft_view(input)
+        if not (input.is_cuda and (input.is_contiguous() or bft) and input.dtype in (torch.float32, torch.bfloat16)):
             return None
         key = (input.shape, input.dtype, batch_major, self._hidden_size, self.W1.shape, self.U1.shape,
-               self._gate_non_linearity, input.device.index)
+               self._gate_non_linearity, input.device.index, bft)
         ok = _inference_ok.get(key)
-        flags = _lib.FLAG_ZERO_EXTEND | (_lib.FLAG_BATCH_MAJOR if batch_major else 0)
+        flags = _lib.FLAG_X_BFT if bft else (_lib.FLAG_ZERO_EXTEND | (_lib.FLAG_BATCH_MAJOR if batch_major else 0))
         if ok is None:
             if batch_major:
                 Bn, Tn, Fn = input.shape
@@ -437,6 +446,8 @@ class FastGRNNCUDA(nn.Module):
                 Tn, Bn, Fn, self._hidden_size, rw, ru, self._gate_non_linearity, 2, input.dtype, 0, flags) == 2
         if not ok:
             return None
+        if bft:
+            input = input.permute(1, 2, 0)
         return fastgrnn_cuda.forward_unroll(input, self.W, self.U, self.bias_gate, self.bias_update, self.zeta, self.nu,
                                             hiddenState.contiguous(), self._gate_non_linearity, self.W1, self.W2,
                                             self.U1, self.U2, want_gates=False, flags=flags)[0]
@@ -450,6 +461,14 @@ class FastGRNNCUDA(nn.Module):
         rw = self.W1.shape[0] if self.W1.numel() else 0
         ru = self.U1.shape[0] if self.U1.numel() else 0
         flags = _lib.FLAG_HS_LAST | _lib.FLAG_ZERO_EXTEND | (_lib.FLAG_BATCH_MAJOR if batch_major else 0)
+        if (not batch_major and input.dtype in (torch.float32, torch.bfloat16) and _is_bft_view(input)
+                and fastgrnn_cuda.kernel_path(Tn, Bn, Fn, self._hidden_size, rw, ru, self._gate_non_linearity, 2,
+                                              input.dtype, 0, _lib.FLAG_HS_LAST | _lib.FLAG_X_BFT) == 2):
+            # the trainer's permuted view: the [B,F,T] base as it is (a view on a zero-extended shape is copied below)
+            return fastgrnn_cuda.forward_unroll(input.permute(1, 2, 0), self.W, self.U, self.bias_gate,
+                                                self.bias_update, self.zeta, self.nu, hiddenState.contiguous(),
+                                                self._gate_non_linearity, self.W1, self.W2, self.U1, self.U2,
+                                                want_gates=False, flags=_lib.FLAG_HS_LAST | _lib.FLAG_X_BFT)[0]
         if input.dtype not in (torch.float32, torch.bfloat16) or fastgrnn_cuda.kernel_path(
                 Tn, Bn, Fn, self._hidden_size, rw, ru, self._gate_non_linearity, 2, input.dtype, 0, flags) != 2:
             return None
