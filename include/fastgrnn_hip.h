@@ -281,6 +281,29 @@ typedef struct fastgrnn_zext_plan {
 } fastgrnn_zext_plan;
 int fastgrnn_hip_zero_extend_plan(const fastgrnn_desc *d, fastgrnn_zext_plan *out);
 
+/* Everything the library decides from a descriptor alone, in one query: what the calls of d run on and what that route
+ * needs from the caller.  fastgrnn_hip_kernel_path, the two workspace queries and fastgrnn_hip_zero_extend_plan each
+ * answer one field of it.
+ *   path[direction]         fastgrnn_hip_kernel_path(d, direction)
+ *   workspace_bytes[0 / 1]  fastgrnn_hip_forward_workspace_bytes(d) / fastgrnn_hip_backward_workspace_bytes(d)
+ *   forward_ws_optional     1 where forward_unroll accepts workspace == NULL when z_s is passed (path 2, dense H=128
+ *                           with F > 32: the frame product is parked in z_s / c_s; never on the padded route)
+ *   dx_optional             1 where backward_unroll accepts g->d_x == NULL, on the padded route (zext.dx_optional then)
+ *                           or off it (fastgrnn_grads.d_x; the only field FASTGRNN_FLAG_NO_INPUT_GRAD changes)
+ *   rank_space_cols         32 where a forward under FASTGRNN_FLAG_SAVE_PREACT writes the rank-space vector through
+ *                           c_s as [T*B, 32] and the backward reads it back (path 2, low-rank H=256/F=32 with both
+ *                           ranks in 1..16; never on the padded route, whose z_s buffer holds it); 0 otherwise
+ *   zext                    fastgrnn_hip_zero_extend_plan(d)
+ * Returns FASTGRNN_OK, or FASTGRNN_ERR_NULL_POINTER / a descriptor error (out zeroed). */
+typedef struct fastgrnn_plan {
+  int32_t path[2];
+  int32_t forward_ws_optional, dx_optional;
+  int32_t rank_space_cols, reserved;
+  size_t workspace_bytes[2];
+  fastgrnn_zext_plan zext;
+} fastgrnn_plan;
+int fastgrnn_hip_plan(const fastgrnn_desc *d, fastgrnn_plan *out);
+
 /* Workspace sizes in bytes (0 is a valid answer).  Workspace must be 256-B aligned.  The forward answer covers a
  * call without auxiliary outputs; dense H=128 layers with F > 32 park the frame product X.W^T in z_s / c_s when
  * the caller passes them and then accept workspace == NULL. */

@@ -43,7 +43,7 @@ EXPORTS = (
     "fastgrnn_hip_frame_gemm", "fastgrnn_hip_forward_unroll_affine",
     "fastgrnn_hip_bn_train_supported", "fastgrnn_hip_bn_train_forward_workspace_bytes",
     "fastgrnn_hip_bn_train_backward_workspace_bytes", "fastgrnn_hip_bn_train_forward", "fastgrnn_hip_bn_train_backward",
-    "fastgrnn_hip_zero_extend_plan",
+    "fastgrnn_hip_zero_extend_plan", "fastgrnn_hip_plan",
 )
 
 
@@ -85,6 +85,13 @@ class ZextPlan(C.Structure):
     """fastgrnn_zext_plan: what FLAG_ZERO_EXTEND does for a descriptor."""
     _fields_ = [("forward", C.c_int32), ("backward", C.c_int32), ("Hp", C.c_int32), ("Fp", C.c_int32),
                 ("dx_optional", C.c_int32), ("reserved", C.c_int32), ("saved_bytes", C.c_size_t)]
+
+
+class Plan(C.Structure):
+    """fastgrnn_plan: what the calls of a descriptor run on and what that route needs from the caller."""
+    _fields_ = [("path", C.c_int32 * 2), ("forward_ws_optional", C.c_int32), ("dx_optional", C.c_int32),
+                ("rank_space_cols", C.c_int32), ("reserved", C.c_int32), ("workspace_bytes", C.c_size_t * 2),
+                ("zext", ZextPlan)]
 
 
 class FastGRNNLibraryError(RuntimeError):
@@ -148,6 +155,8 @@ def load():
     lib.fastgrnn_hip_bn_train_backward.argtypes = [DP, PP, BP, vp, vp, vp, vp, vp, vp, GP, BG, vp, sz, vp]
     lib.fastgrnn_hip_zero_extend_plan.restype = i32
     lib.fastgrnn_hip_zero_extend_plan.argtypes = [DP, C.POINTER(ZextPlan)]
+    lib.fastgrnn_hip_plan.restype = i32
+    lib.fastgrnn_hip_plan.argtypes = [DP, C.POINTER(Plan)]
     if lib.fastgrnn_hip_abi_version() != ABI_VERSION:
         raise FastGRNNLibraryError("ABI version mismatch: library %d, binding %d"
                                    % (lib.fastgrnn_hip_abi_version(), ABI_VERSION))

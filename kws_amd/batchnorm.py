@@ -43,6 +43,14 @@ _TRAINING_MSG = ("FastGRNNBatchNorm runs in eval mode only (training=False / mod
                  "grid-wide reduction inside every step of the fused scan")
 
 
+def _affine_on_path2(cell, x, T, B, flags):
+    """The scaled forward of this call (FLAG_PREACT_AFFINE added to ``flags``) is on kernel path 2: the sibling of
+    ``rnn._on_path2`` for the dense BatchNorm cell, whose update nonlinearity is its own."""
+    return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)
+            and fastgrnn_cuda.kernel_path(T, B, x.shape[-1], cell._hidden_size, 0, 0, cell._gate_code,
+                                          cell._update_code, x.dtype, 0, flags | _lib.FLAG_PREACT_AFFINE) == 2)
+
+
 def _bn_affine(bn):
     """(a, b) with bn(v) == a * v + b in eval mode (torch.nn.functional.batch_norm, running statistics)."""
     rv = bn.running_var if bn.running_var is not None else torch.ones_like(bn.weight)
@@ -246,9 +254,7 @@ class FastGRNNBatchNorm(nn.Module):
             h0 = hiddenState.to(dev).reshape(Bn, H).contiguous()
         flags = _lib.FLAG_HS_LAST if last_state else 0
         # batch_first in place where the kernels index [B,T,.] (kernel path 2), else transposed as BaseRNN does
-        in_place = bf and fastgrnn_cuda.kernel_path(
-            Tn, Bn, input.shape[-1], H, 0, 0, cell._gate_code, cell._update_code, input.dtype, 0,
-            flags | _lib.FLAG_BATCH_MAJOR | _lib.FLAG_PREACT_AFFINE) == 2
+        in_place = bf and _affine_on_path2(cell, input, Tn, Bn, flags | _lib.FLAG_BATCH_MAJOR)
         x = input
         if in_place:
             flags |= _lib.FLAG_BATCH_MAJOR
@@ -257,12 +263,10 @@ class FastGRNNBatchNorm(nn.Module):
         # the trainer's permuted view of the loader's [B,F,T] batch (trainClassifier.py:299): its base as it is where the
         # scaled forward takes FLAG_X_BFT (the layers whose frame product is a GEMM of its own), else a copy
         if (not bf and x.dim() == 3 and not x.is_contiguous() and x.permute(1, 2, 0).is_contiguous()
-                and fastgrnn_cuda.kernel_path(Tn, Bn, x.shape[-1], H, 0, 0, cell._gate_code, cell._update_code, x.dtype, 0,
-                                              flags | _lib.FLAG_X_BFT | _lib.FLAG_PREACT_AFFINE) == 2):
+                and _affine_on_path2(cell, x, Tn, Bn, flags | _lib.FLAG_X_BFT)):
             return _BatchNormInference.apply(cell, x.permute(1, 2, 0), h0, flags | _lib.FLAG_X_BFT, *cell._fold_tensors())
         x = x.contiguous()
-        if last_state and fastgrnn_cuda.kernel_path(Tn, Bn, x.shape[-1], H, 0, 0, cell._gate_code, cell._update_code,
-                                                    x.dtype, 0, flags | _lib.FLAG_PREACT_AFFINE) != 2:
+        if last_state and not _affine_on_path2(cell, x, Tn, Bn, flags):
             flags &= ~_lib.FLAG_HS_LAST               # (kernel path 0 writes every state; the last one is taken)
             hs = _BatchNormInference.apply(cell, x, h0, flags, *cell._fold_tensors())
             return hs[:, -1] if (flags & _lib.FLAG_BATCH_MAJOR) else hs[-1]

@@ -43,47 +43,101 @@ int pick_path(const fastgrnn_desc* d, int direction) {
   return mfma_supported(*d, direction) ? 1 : 0;
 }
 
-// the descriptor without FASTGRNN_FLAG_ZERO_EXTEND: what every call runs on where the flag does not take effect.
-// FASTGRNN_FLAG_NO_INPUT_GRAD goes too: it only admits d_x == NULL in the backward (nograd_dx_ok), so every path
-// choice and support predicate answers for it exactly as without it.
-fastgrnn_desc plain(const fastgrnn_desc* d) {
-  fastgrnn_desc u = *d;
-  u.flags &= ~(FASTGRNN_FLAG_ZERO_EXTEND | FASTGRNN_FLAG_NO_INPUT_GRAD);
-  return u;
+size_t path_ws(const fastgrnn_desc& d, int path, int direction) {
+  switch (path) {
+    case 2: return direction ? split_backward_ws(d) : split_forward_ws(d);
+    case 1: return direction ? mfma_backward_ws(d) : mfma_forward_ws(d);
+    case 0: return direction ? generic_backward_ws(d) : generic_forward_ws(d);
+    default: return 0;
+  }
 }
 
-// FASTGRNN_FLAG_NO_INPUT_GRAD: the backward of the path-2 descriptor d (flags as the caller passed them) may leave d_x out
-bool nograd_dx_ok(const fastgrnn_desc& d, uint32_t flags) {
-  return (flags & FASTGRNN_FLAG_NO_INPUT_GRAD) && split_dx_skippable(d);
-}
+// What a caller's descriptor runs on and what that route needs from the caller.  resolve() validates and decides
+// once; every entry point and every query starts from its answer and asks no predicate of its own.
+struct route {
+  fastgrnn_desc u;       // the descriptor without FASTGRNN_FLAG_ZERO_EXTEND / NO_INPUT_GRAD (which only sets
+                         // plan.dx_optional): what a call runs on where the padded route does not apply
+  fastgrnn_desc e;       // the padded descriptor, where plan.zext.forward
+  int path[2];           // u's kernel family per direction; -1 where no unrolled call runs u in that direction
+  size_t need[2];        // u's workspace per direction
+  size_t zneed[2];       // the padded route's
+  fastgrnn_plan plan;    // the public answers (fastgrnn_hip_plan); plan.zext.forward / backward: the padded route applies
+};
 
-// FASTGRNN_FLAG_ZERO_EXTEND (include/fastgrnn_hip.h): true when the forward takes the padded route, with *e the padded
-// descriptor; *bwd: the backward takes it too (FASTGRNN_FLAG_SAVE_PREACT).  d has passed check_desc.
-bool zext_route(const fastgrnn_desc* d, fastgrnn_desc* e, bool* bwd) {
+// FASTGRNN_FLAG_ZERO_EXTEND (include/fastgrnn_hip.h): true when the forward takes the padded route, with r->e the padded
+// descriptor; under FASTGRNN_FLAG_SAVE_PREACT the backward takes it too.  r->u and r->path are filled.
+bool zext_route(const fastgrnn_desc* d, route* r) {
   if (!(d->flags & FASTGRNN_FLAG_ZERO_EXTEND)) return false;
   if (d->dtype != FASTGRNN_F32 && d->dtype != FASTGRNN_BF16_IO) return false;
   if (d->flags & (FASTGRNN_FLAG_FORCE_GENERIC | FASTGRNN_FLAG_FORCE_F32_MFMA | FASTGRNN_FLAG_X_BFT |
                   FASTGRNN_FLAG_PREACT_AFFINE | FASTGRNN_FLAG_BN_TRAIN))
     return false;
   if (d->H > 256 || d->F > 256) return false;
-  const fastgrnn_desc u = plain(d);
   const bool preact = (d->flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
-  if (pick_path(&u, 0) != 0 || (preact && pick_path(&u, 1) != 0)) return false;
+  if (r->path[0] != 0 || (preact && r->path[1] != 0)) return false;
   const int Hp = d->H <= 128 ? 128 : 256;
   for (int Fp = 32; Fp <= 256; Fp *= 2) {
     if (Fp < d->F) continue;
     // element offsets of the padded copies are 32-bit (kernels_zext.hip)
     if ((double)d->T * d->B * (Hp > Fp ? Hp : Fp) >= 1073741824.0) return false;
-    fastgrnn_desc c = u;
-    c.H = Hp;
-    c.F = Fp;
-    if (pick_path(&c, 0) == 2 && (!preact || pick_path(&c, 1) == 2)) {
-      *e = c;
-      *bwd = preact;
-      return true;
-    }
+    r->e = r->u;
+    r->e.H = Hp;
+    r->e.F = Fp;
+    if (pick_path(&r->e, 0) == 2 && (!preact || pick_path(&r->e, 1) == 2)) return true;
   }
   return false;
+}
+
+int resolve(const fastgrnn_desc* d, route* r) {
+  *r = route{};
+  const int st = check_desc(d);
+  if (st) return st;
+  r->u = *d;
+  r->u.flags &= ~(FASTGRNN_FLAG_ZERO_EXTEND | FASTGRNN_FLAG_NO_INPUT_GRAD);
+  const fastgrnn_desc& u = r->u;
+  const bool preact = (u.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
+  const bool affine = (u.flags & FASTGRNN_FLAG_PREACT_AFFINE) != 0;      // fastgrnn_hip_forward_unroll_affine: inference only
+  const bool bn_train = (u.flags & FASTGRNN_FLAG_BN_TRAIN) != 0;         // fastgrnn_hip_bn_train_*
+  for (int dir = 0; dir < 2; ++dir) {
+    r->path[dir] = (bn_train || (affine && dir)) ? -1 : pick_path(&u, dir);
+    r->need[dir] = path_ws(u, r->path[dir], dir);
+  }
+  // d_x may be NULL (the input's gradient is not wanted) where it is a GEMM of its own behind the scan, and under
+  // FASTGRNN_FLAG_NO_INPUT_GRAD where the scan can leave its d_x product out
+  const bool nograd = (d->flags & FASTGRNN_FLAG_NO_INPUT_GRAD) != 0;
+  const auto dx_optional = [nograd](const fastgrnn_desc& c) { return split_dx_optional(c) || (nograd && split_dx_skippable(c)); };
+  fastgrnn_plan& o = r->plan;
+  fastgrnn_zext_plan& z = o.zext;
+  if (zext_route(d, r)) {
+    z.forward = 1;
+    z.backward = preact;
+    z.Hp = r->e.H;
+    z.Fp = r->e.F;
+    z.dx_optional = dx_optional(r->e);
+    z.saved_bytes = zext_saved_bytes(*d, r->e);
+    r->zneed[0] = zext_forward_ws(*d, r->e);
+    if (preact) r->zneed[1] = zext_backward_ws(*d, r->e);
+  }
+  o.path[0] = z.forward ? 2 : r->path[0];
+  o.path[1] = z.backward ? 2 : r->path[1];
+  // forward workspace: under SAVE_PREACT every forward takes the padded route; without it a forward given the
+  // (z_s, h_prime_s) pair runs as without the flag, so the answer covers that call as well
+  o.workspace_bytes[0] = (z.forward && (preact || r->zneed[0] > r->need[0])) ? r->zneed[0] : r->need[0];
+  o.workspace_bytes[1] = z.backward ? r->zneed[1] : r->need[1];
+  // (path 2 only needs its workspace when no auxiliary output is requested: see split_forward_ws)
+  o.forward_ws_optional = !affine && r->path[0] == 2 && split_forward_ws_optional(u);
+  o.dx_optional = z.backward ? z.dx_optional : (r->path[1] == 2 && dx_optional(u));
+  o.rank_space_cols = (preact && lowrank_shape(u) && (r->path[0] == 2 || r->path[1] == 2)) ? 32 : 0;
+  return FASTGRNN_OK;
+}
+
+// the gradient pointers a backward of d needs (fastgrnn_grads: the others are ignored)
+int check_grads(const fastgrnn_desc& d, const fastgrnn_grads* g, bool dx_optional) {
+  if ((!g->d_x && !dx_optional) || !g->d_bias_gate || !g->d_bias_update || !g->d_zeta || !g->d_nu || !g->d_h0)
+    return FASTGRNN_ERR_NULL_POINTER;
+  if (d.w_rank ? (!g->d_w1 || !g->d_w2) : !g->d_w) return FASTGRNN_ERR_NULL_POINTER;
+  if (d.u_rank ? (!g->d_u1 || !g->d_u2) : !g->d_u) return FASTGRNN_ERR_NULL_POINTER;
+  return FASTGRNN_OK;
 }
 
 // training-mode BatchNorm cell (FASTGRNN_FLAG_BN_TRAIN)
@@ -96,8 +150,7 @@ int check_bn_layer(const fastgrnn_bn_layer& l, bool forward) {
 }
 
 int check_bn_train(const fastgrnn_desc* d, const fastgrnn_params* p, const fastgrnn_bn_params* bn, bool forward) {
-  int st = check_desc(d);
-  if (st) return st;
+  int st;
   if (!(d->flags & FASTGRNN_FLAG_BN_TRAIN)) return FASTGRNN_ERR_UNSUPPORTED;
   if (d->B < 2) return FASTGRNN_ERR_BAD_SHAPE;                 // torch: more than 1 value per channel when training
   if ((st = check_params(d, p))) return st;
@@ -107,6 +160,11 @@ int check_bn_train(const fastgrnn_desc* d, const fastgrnn_params* p, const fastg
     if ((st = check_bn_layer(*l, forward))) return st;
   if (!bn_train_supported(*d)) return FASTGRNN_ERR_UNSUPPORTED;
   return FASTGRNN_OK;
+}
+
+// r->u runs on the training kernels
+bool bn_train_route(const fastgrnn_desc* d, route* r) {
+  return resolve(d, r) == FASTGRNN_OK && (r->u.flags & FASTGRNN_FLAG_BN_TRAIN) && bn_train_supported(r->u);
 }
 }  // namespace
 
@@ -128,102 +186,61 @@ const char* fastgrnn_hip_status_string(int status) {
   }
 }
 
-int fastgrnn_hip_kernel_path(const fastgrnn_desc* dz, int direction) {
-  if (check_desc(dz) != FASTGRNN_OK) return -1;
-  fastgrnn_desc e;
-  bool bwd = false;
-  if (zext_route(dz, &e, &bwd) && (direction == 0 || bwd)) return 2;
-  const fastgrnn_desc u = plain(dz);
-  const fastgrnn_desc* d = &u;
-  if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return -1;                               // fastgrnn_hip_bn_train_*
-  if ((d->flags & FASTGRNN_FLAG_PREACT_AFFINE) && direction != 0) return -1;   // inference only
-  return pick_path(d, direction);
+int fastgrnn_hip_plan(const fastgrnn_desc* d, fastgrnn_plan* out) {
+  if (!out) return FASTGRNN_ERR_NULL_POINTER;
+  route r;
+  const int st = resolve(d, &r);
+  *out = r.plan;
+  return st;
 }
 
-size_t fastgrnn_hip_forward_workspace_bytes(const fastgrnn_desc* dz) {
-  if (check_desc(dz) != FASTGRNN_OK) return 0;
-  const fastgrnn_desc u = plain(dz);
-  const fastgrnn_desc* d = &u;
-  size_t zext = 0;
-  fastgrnn_desc e;
-  bool bwd = false;
-  if (zext_route(dz, &e, &bwd)) {
-    zext = zext_forward_ws(*dz, e);
-    // under SAVE_PREACT every forward takes the padded route; without it a forward given the (z_s, h_prime_s) pair
-    // runs as without the flag, so the answer covers that call as well
-    if (dz->flags & FASTGRNN_FLAG_SAVE_PREACT) return zext;
-  }
-  if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return 0;
-  size_t n;
-  switch (pick_path(d, 0)) {
-    case 2: n = split_forward_ws(*d); break;
-    case 1: n = mfma_forward_ws(*d); break;
-    default: n = generic_forward_ws(*d); break;
-  }
-  return n > zext ? n : zext;
+int fastgrnn_hip_kernel_path(const fastgrnn_desc* d, int direction) {
+  route r;
+  return resolve(d, &r) ? -1 : r.plan.path[direction ? 1 : 0];
 }
 
-size_t fastgrnn_hip_backward_workspace_bytes(const fastgrnn_desc* dz) {
-  if (check_desc(dz) != FASTGRNN_OK) return 0;
-  fastgrnn_desc e;
-  bool bwd = false;
-  if (zext_route(dz, &e, &bwd) && bwd) return zext_backward_ws(*dz, e);
-  const fastgrnn_desc u = plain(dz);
-  const fastgrnn_desc* d = &u;
-  if (d->flags & (FASTGRNN_FLAG_PREACT_AFFINE | FASTGRNN_FLAG_BN_TRAIN)) return 0;
-  switch (pick_path(d, 1)) {
-    case 2: return split_backward_ws(*d);
-    case 1: return mfma_backward_ws(*d);
-    default: return generic_backward_ws(*d);
-  }
+size_t fastgrnn_hip_forward_workspace_bytes(const fastgrnn_desc* d) {
+  route r;
+  return resolve(d, &r) ? 0 : r.plan.workspace_bytes[0];
+}
+
+size_t fastgrnn_hip_backward_workspace_bytes(const fastgrnn_desc* d) {
+  route r;
+  return resolve(d, &r) ? 0 : r.plan.workspace_bytes[1];
 }
 
 int fastgrnn_hip_zero_extend_plan(const fastgrnn_desc* d, fastgrnn_zext_plan* out) {
   if (!out) return FASTGRNN_ERR_NULL_POINTER;
-  *out = fastgrnn_zext_plan{};
-  const int st = check_desc(d);
-  if (st) return st;
-  fastgrnn_desc e;
-  bool bwd = false;
-  if (!zext_route(d, &e, &bwd)) return FASTGRNN_OK;
-  out->forward = 1;
-  out->backward = bwd ? 1 : 0;
-  out->Hp = e.H;
-  out->Fp = e.F;
-  out->dx_optional = (split_dx_optional(e) || nograd_dx_ok(e, d->flags)) ? 1 : 0;
-  out->saved_bytes = zext_saved_bytes(*d, e);
-  return FASTGRNN_OK;
+  route r;
+  const int st = resolve(d, &r);
+  *out = r.plan.zext;
+  return st;
 }
 
 int fastgrnn_hip_forward_unroll(const fastgrnn_desc* dz, const fastgrnn_params* p, const void* x, const void* h0,
                                 void* hs, void* z_s, void* c_s, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-  int st = check_desc(dz);
+  route r;
+  int st = resolve(dz, &r);
   if (st) return st;
-  fastgrnn_desc e;
-  bool bwd = false;
-  const bool zpreact = (dz->flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
-  if (zext_route(dz, &e, &bwd) && (zpreact || !z_s)) {      // (the reference's pair: as without the flag)
-    if ((st = check_params(dz, p))) return st;
-    if (!x || !h0 || !hs || (zpreact && !z_s)) return FASTGRNN_ERR_NULL_POINTER;
-    if ((st = check_ws(workspace, workspace_bytes, zext_forward_ws(*dz, e)))) return st;
-    return zext_forward(*dz, e, *p, x, h0, hs, z_s, workspace, reinterpret_cast<hipStream_t>(stream));
-  }
-  const fastgrnn_desc u = plain(dz);
-  const fastgrnn_desc* d = &u;
+  const fastgrnn_desc* d = &r.u;
   if ((st = check_params(d, p))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool preact = (d->flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
+  if (r.plan.zext.forward && (preact || !z_s)) {      // (the reference's pair: as without the flag)
+    if (!x || !h0 || !hs || (preact && !z_s)) return FASTGRNN_ERR_NULL_POINTER;
+    if ((st = check_ws(workspace, workspace_bytes, r.zneed[0]))) return st;
+    return zext_forward(*dz, r.e, *p, x, h0, hs, z_s, workspace, s);
+  }
   if (!x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
   if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // fastgrnn_hip_forward_unroll_affine
   if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return FASTGRNN_ERR_UNSUPPORTED;        // fastgrnn_hip_bn_train_forward
   if (((d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST)) ||
-       d->dtype == FASTGRNN_BF16_IO) && pick_path(d, 0) != 2)
+       d->dtype == FASTGRNN_BF16_IO) && r.path[0] != 2)
     return FASTGRNN_ERR_UNSUPPORTED;
   if ((d->flags & FASTGRNN_FLAG_HS_LAST) && z_s) return FASTGRNN_ERR_UNSUPPORTED;   // nothing is saved for a backward
-  // (path 2 only needs its workspace when no auxiliary output is requested: see split_forward_ws)
-  const size_t need = (pick_path(d, 0) == 2 && z_s && split_forward_ws_optional(*d)) ? 0 : fastgrnn_hip_forward_workspace_bytes(d);
-  if ((st = check_ws(workspace, workspace_bytes, need))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (pick_path(d, 0)) {
+  if ((st = check_ws(workspace, workspace_bytes, (z_s && r.plan.forward_ws_optional) ? 0 : r.need[0]))) return st;
+  switch (r.path[0]) {
     case 2: return split_forward(*d, *p, x, h0, hs, z_s, c_s, workspace, s);
     case 1: return mfma_forward(*d, *p, x, h0, hs, z_s, c_s, workspace, s);
     default: return generic_forward(*d, *p, x, h0, hs, z_s, c_s, workspace, s);
@@ -233,62 +250,47 @@ int fastgrnn_hip_forward_unroll(const fastgrnn_desc* dz, const fastgrnn_params* 
 int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc* dz, const fastgrnn_params* p, const void* gate_scale,
                                        const void* update_scale, const void* x, const void* h0, void* hs,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-  int st = check_desc(dz);
+  route r;
+  int st = resolve(dz, &r);
   if (st) return st;
-  const fastgrnn_desc u = plain(dz);
-  const fastgrnn_desc* d = &u;
+  const fastgrnn_desc* d = &r.u;
   if ((st = check_params(d, p))) return st;
   if (!gate_scale || !update_scale || !x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
   if (!(d->flags & FASTGRNN_FLAG_PREACT_AFFINE) || d->dtype == FASTGRNN_BF16_IO || d->w_rank || d->u_rank ||
       (d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_GRAD_LAST | FASTGRNN_FLAG_BN_TRAIN)))
     return FASTGRNN_ERR_UNSUPPORTED;
-  const int path = pick_path(d, 0);
   // (FASTGRNN_FLAG_X_BFT: path 2 takes it on the wide shapes -- affine_supported -- and nothing else does)
-  if ((d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_X_BFT)) && path != 2) return FASTGRNN_ERR_UNSUPPORTED;
-  if ((st = check_ws(workspace, workspace_bytes, fastgrnn_hip_forward_workspace_bytes(d)))) return st;
+  if ((d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_X_BFT)) && r.path[0] != 2) return FASTGRNN_ERR_UNSUPPORTED;
+  if ((st = check_ws(workspace, workspace_bytes, r.need[0]))) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (path == 2) return split_forward(*d, *p, x, h0, hs, nullptr, nullptr, workspace, s, gate_scale, update_scale);
+  if (r.path[0] == 2) return split_forward(*d, *p, x, h0, hs, nullptr, nullptr, workspace, s, gate_scale, update_scale);
   return generic_forward(*d, *p, x, h0, hs, nullptr, nullptr, workspace, s, gate_scale, update_scale);
 }
 
 int fastgrnn_hip_backward_unroll(const fastgrnn_desc* dz, const fastgrnn_params* p, const void* grad_hs,
                                  const void* x, const void* hs, const void* z_s, const void* c_s, const void* h0,
                                  const fastgrnn_grads* g, void* workspace, size_t workspace_bytes, void* stream) {
-  int st = check_desc(dz);
+  route r;
+  int st = resolve(dz, &r);
   if (st) return st;
-  fastgrnn_desc e;
-  bool bwd = false;
-  if (zext_route(dz, &e, &bwd) && bwd) {
-    if ((st = check_params(dz, p))) return st;
-    if (!grad_hs || !x || !hs || !z_s || !h0 || !g) return FASTGRNN_ERR_NULL_POINTER;
-    if ((!g->d_x && !split_dx_optional(e) && !nograd_dx_ok(e, dz->flags)) || !g->d_bias_gate || !g->d_bias_update ||
-        !g->d_zeta || !g->d_nu ||
-        !g->d_h0)
-      return FASTGRNN_ERR_NULL_POINTER;
-    if (dz->w_rank ? (!g->d_w1 || !g->d_w2) : !g->d_w) return FASTGRNN_ERR_NULL_POINTER;
-    if (dz->u_rank ? (!g->d_u1 || !g->d_u2) : !g->d_u) return FASTGRNN_ERR_NULL_POINTER;
-    if ((st = check_ws(workspace, workspace_bytes, zext_backward_ws(*dz, e)))) return st;
-    return zext_backward(*dz, e, *p, grad_hs, x, hs, z_s, h0, *g, workspace, reinterpret_cast<hipStream_t>(stream));
-  }
-  const fastgrnn_desc u = plain(dz);
-  const fastgrnn_desc* d = &u;
+  const fastgrnn_desc* d = &r.u;
   if ((st = check_params(d, p))) return st;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (r.plan.zext.backward) {
+    if (!grad_hs || !x || !hs || !z_s || !h0 || !g) return FASTGRNN_ERR_NULL_POINTER;
+    if ((st = check_grads(*d, g, r.plan.dx_optional))) return st;
+    if ((st = check_ws(workspace, workspace_bytes, r.zneed[1]))) return st;
+    return zext_backward(*dz, r.e, *p, grad_hs, x, hs, z_s, h0, *g, workspace, s);
+  }
   if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // inference only
   if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return FASTGRNN_ERR_UNSUPPORTED;        // fastgrnn_hip_bn_train_backward
   const bool preact = (d->flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
-  if ((preact || (d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)) || d->dtype == FASTGRNN_BF16_IO) && pick_path(d, 1) != 2)
+  if ((preact || (d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)) || d->dtype == FASTGRNN_BF16_IO) && r.path[1] != 2)
     return FASTGRNN_ERR_UNSUPPORTED;
   if (!grad_hs || !x || !hs || !z_s || (!c_s && !preact) || !h0 || !g) return FASTGRNN_ERR_NULL_POINTER;
-  // d_x may be NULL (the input's gradient is not wanted) where it is a GEMM of its own behind the scan, and under
-  // FASTGRNN_FLAG_NO_INPUT_GRAD where the scan can leave its d_x product out
-  const bool dx_optional = pick_path(d, 1) == 2 && (split_dx_optional(*d) || nograd_dx_ok(*d, dz->flags));
-  if ((!g->d_x && !dx_optional) || !g->d_bias_gate || !g->d_bias_update || !g->d_zeta || !g->d_nu || !g->d_h0)
-    return FASTGRNN_ERR_NULL_POINTER;
-  if (d->w_rank ? (!g->d_w1 || !g->d_w2) : !g->d_w) return FASTGRNN_ERR_NULL_POINTER;
-  if (d->u_rank ? (!g->d_u1 || !g->d_u2) : !g->d_u) return FASTGRNN_ERR_NULL_POINTER;
-  if ((st = check_ws(workspace, workspace_bytes, fastgrnn_hip_backward_workspace_bytes(d)))) return st;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (pick_path(d, 1)) {
+  if ((st = check_grads(*d, g, r.plan.dx_optional))) return st;
+  if ((st = check_ws(workspace, workspace_bytes, r.need[1]))) return st;
+  switch (r.path[1]) {
     case 2: return split_backward(*d, *p, grad_hs, x, hs, z_s, c_s, h0, *g, workspace, s);
     case 1: return mfma_backward(*d, *p, grad_hs, x, hs, z_s, c_s, h0, *g, workspace, s);
     default: return generic_backward(*d, *p, grad_hs, x, hs, z_s, c_s, h0, *g, workspace, s);
@@ -342,28 +344,29 @@ int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void* x, co
                    reinterpret_cast<hipStream_t>(stream));
 }
 
-int fastgrnn_hip_bn_train_supported(const fastgrnn_desc* dz) {
-  if (check_desc(dz) != FASTGRNN_OK) return 0;
-  const fastgrnn_desc d = plain(dz);
-  return (d.flags & FASTGRNN_FLAG_BN_TRAIN) && bn_train_supported(d) ? 1 : 0;
+int fastgrnn_hip_bn_train_supported(const fastgrnn_desc* d) {
+  route r;
+  return bn_train_route(d, &r) ? 1 : 0;
 }
 
 size_t fastgrnn_hip_bn_train_forward_workspace_bytes(const fastgrnn_desc* d) {
-  return fastgrnn_hip_bn_train_supported(d) ? bn_train_forward_ws(plain(d)) : 0;
+  route r;
+  return bn_train_route(d, &r) ? bn_train_forward_ws(r.u) : 0;
 }
 
 size_t fastgrnn_hip_bn_train_backward_workspace_bytes(const fastgrnn_desc* d) {
-  return fastgrnn_hip_bn_train_supported(d) ? bn_train_backward_ws(plain(d)) : 0;
+  route r;
+  return bn_train_route(d, &r) ? bn_train_backward_ws(r.u) : 0;
 }
 
 int fastgrnn_hip_bn_train_forward(const fastgrnn_desc* dz, const fastgrnn_params* p, const fastgrnn_bn_params* bn,
                                   const void* x, const void* h0, void* hs, void* saved, void* stats, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  if (!dz) return FASTGRNN_ERR_NULL_POINTER;
-  const fastgrnn_desc u = plain(dz);
-  const fastgrnn_desc* d = &u;
-  int st = check_bn_train(d, p, bn, true);
+  route r;
+  int st = resolve(dz, &r);
   if (st) return st;
+  const fastgrnn_desc* d = &r.u;
+  if ((st = check_bn_train(d, p, bn, true))) return st;
   if (!x || !h0 || !hs || !saved || !stats) return FASTGRNN_ERR_NULL_POINTER;
   if ((st = check_ws(workspace, workspace_bytes, bn_train_forward_ws(*d)))) return st;
   return bn_train_forward(*d, *p, *bn, x, h0, hs, saved, stats, workspace, reinterpret_cast<hipStream_t>(stream));
@@ -374,11 +377,11 @@ int fastgrnn_hip_bn_train_backward(const fastgrnn_desc* dz, const fastgrnn_param
                                    const void* stats, const void* h0, const fastgrnn_grads* g,
                                    const fastgrnn_bn_grads* bg, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-  if (!dz) return FASTGRNN_ERR_NULL_POINTER;
-  const fastgrnn_desc u = plain(dz);
-  const fastgrnn_desc* d = &u;
-  int st = check_bn_train(d, p, bn, false);
+  route r;
+  int st = resolve(dz, &r);
   if (st) return st;
+  const fastgrnn_desc* d = &r.u;
+  if ((st = check_bn_train(d, p, bn, false))) return st;
   if (!grad_hs || !x || !hs || !saved || !stats || !h0 || !g || !bg) return FASTGRNN_ERR_NULL_POINTER;
   if (!g->d_h0 || !g->d_w || !g->d_u || !g->d_bias_gate || !g->d_bias_update || !g->d_zeta || !g->d_nu)
     return FASTGRNN_ERR_NULL_POINTER;

@@ -24,6 +24,7 @@ the HIP kernels; there is no eager fallback.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import functools
 
@@ -115,12 +116,27 @@ def _describe(T, B, F, H, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu
     for t in tensors:
         if t.dtype != dtype:
             raise RuntimeError("fastgrnn: all operands must share dtype %s (got %s)" % (dtype, t.dtype))
-    desc = _plan(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), _DTYPES[io_dtype], int(flags))
-    params = _lib.Params(_ptr(None if w_lr else w), _ptr(None if u_lr else u),
-                         _ptr(w1 if w_lr else None), _ptr(w2 if w_lr else None),
-                         _ptr(u1 if u_lr else None), _ptr(u2 if u_lr else None),
-                         _ptr(bias_gate), _ptr(bias_update), _ptr(zeta), _ptr(nu))
-    return desc, params, w_lr, u_lr          # desc: the cached plan tuple (struct, paths, workspace sizes, zext plan)
+    plan = _plan(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), _DTYPES[io_dtype], int(flags))
+    return plan, _params(w_lr, u_lr, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu), w_lr, u_lr
+
+
+def _params(w_lr, u_lr, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu):
+    """The C params struct: dense matrices or their factors, whichever the cell has."""
+    return _lib.Params(_ptr(None if w_lr else w), _ptr(None if u_lr else u),
+                       _ptr(w1 if w_lr else None), _ptr(w2 if w_lr else None),
+                       _ptr(u1 if u_lr else None), _ptr(u2 if u_lr else None),
+                       _ptr(bias_gate), _ptr(bias_update), _ptr(zeta), _ptr(nu))
+
+
+def _seq_dims(input, flags):
+    """(T, B, F) of an unrolled call's input under the layout flags."""
+    if flags & _lib.FLAG_X_BFT:              # the trainer's [B,F,T] (trainClassifier.py:204)
+        B, F, T = input.shape
+    elif flags & _lib.FLAG_BATCH_MAJOR:
+        B, T, F = input.shape
+    else:
+        T, B, F = input.shape
+    return T, B, F
 
 
 # Scratch workspace, kept per (device, stream) and grown on demand: its contents never outlive a call and every use
@@ -140,23 +156,25 @@ def _workspace(nbytes, device):
     return ws, C.c_void_p(ws.data_ptr())
 
 
+# What the library decides from a descriptor alone (include/fastgrnn_hip.h, fastgrnn_plan): the kernel family and the
+# workspace size per direction, what the route lets the caller leave out, and the FLAG_ZERO_EXTEND plan
+_Plan = collections.namedtuple("_Plan", "desc path ws forward_ws_optional dx_optional rank_space_cols zext")
+
+
 @functools.lru_cache(maxsize=1024)
 def _plan(T, B, F, H, rw, ru, gate_nl, update_nl, dtype_code, flags):
-    """Everything about a descriptor that does not depend on the tensors: the C struct itself, the kernel family
-    each direction dispatches to and the workspace sizes (pure functions of the descriptor in the C ABI).  One
-    dictionary lookup per call instead of four ctypes round trips.  The last entry is the FLAG_ZERO_EXTEND plan
-    (``_lib.ZextPlan``) where that flag takes the padded route for the forward, else None."""
-    lib = _lib.load()
+    """Everything about a descriptor that does not depend on the tensors: the C struct itself and the library's plan
+    for it (a pure function of the descriptor in the C ABI, one call).  One dictionary lookup per operator call
+    instead of a ctypes round trip.  ``zext`` is the ``_lib.ZextPlan``: all zero where FLAG_ZERO_EXTEND does not take
+    the padded route."""
     desc = _lib.Desc(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), dtype_code, int(flags))
-    zx = None
+    out = _lib.Plan()
+    st = _lib.load().fastgrnn_hip_plan(C.byref(desc), C.byref(out))
     if flags & _lib.FLAG_ZERO_EXTEND:
-        zx = _lib.ZextPlan()
-        _lib.check(lib.fastgrnn_hip_zero_extend_plan(C.byref(desc), C.byref(zx)), "fastgrnn zero_extend_plan")
-        if not zx.forward:
-            zx = None
-    return (desc, lib.fastgrnn_hip_kernel_path(C.byref(desc), 0), lib.fastgrnn_hip_kernel_path(C.byref(desc), 1),
-            int(lib.fastgrnn_hip_forward_workspace_bytes(C.byref(desc))),
-            int(lib.fastgrnn_hip_backward_workspace_bytes(C.byref(desc))), zx)
+        _lib.check(st, "fastgrnn zero_extend_plan")
+    # (any other descriptor error is the operator call's to report; the path query answers -1 for it)
+    return _Plan(desc, (-1, -1) if st else tuple(out.path), tuple(int(n) for n in out.workspace_bytes),
+                 bool(out.forward_ws_optional), bool(out.dx_optional), int(out.rank_space_cols), out.zext)
 
 
 _cliff_warned = set()
@@ -165,8 +183,8 @@ _cliff_warned = set()
 def _warn_fallback(plan, direction):
     """Perf cliffs are not silent: the first call of a shape that lands on the generic scan (kernel path 0) at a size
     where that matters says so once (include/fastgrnn_hip.h lists what runs on the matrix pipe)."""
-    d = plan[0]
-    if plan[1 + direction] != 0 or d.T * d.B < 4096 or (d.flags & _lib.FLAG_FORCE_GENERIC):
+    d = plan.desc
+    if plan.path[direction] != 0 or d.T * d.B < 4096 or (d.flags & _lib.FLAG_FORCE_GENERIC):
         return
     key = (d.T, d.B, d.F, d.H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, d.flags, direction)
     if key in _cliff_warned:
@@ -198,7 +216,7 @@ def _stream(device):
 def kernel_path(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=torch.float32,
                 direction=0, flags=0):
     """0 = generic scan, 1 = fp32-MFMA scan, 2 = split-precision scan (pure function of the descriptor; cached)."""
-    return _plan(T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype], int(flags))[1 + int(direction)]
+    return _plan(T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype], int(flags)).path[int(direction)]
 
 
 def zero_extend_plan(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=torch.float32, flags=0):
@@ -206,9 +224,9 @@ def zero_extend_plan(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dty
     ``forward`` / ``backward`` (the padded route is taken), ``Hp``, ``Fp``, ``dx_optional`` and ``saved_bytes`` (the
     opaque z_s buffer under FLAG_SAVE_PREACT).  All zero where the route does not apply."""
     zx = _plan(T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype],
-               int(flags) | _lib.FLAG_ZERO_EXTEND)[5]
+               int(flags) | _lib.FLAG_ZERO_EXTEND).zext
     names = ("forward", "backward", "Hp", "Fp", "dx_optional", "saved_bytes")
-    return {n: (int(getattr(zx, n)) if zx is not None else 0) for n in names}
+    return {n: int(getattr(zx, n)) for n in names}
 
 
 # Signatures (shapes, dtypes, flags of one call) that have passed the full argument checks once.  A training loop makes
@@ -226,43 +244,45 @@ def _all_dense_cuda(*ts):
     return True
 
 
+def _launch_forward(lib, plan, ent, unrolled, preact, want_gates, input, h0, params):
+    """Allocate the outputs and launch (the counterpart of _launch_backward)."""
+    oshape, hshape, rank_space_shape, nbytes, zsaved = ent
+    dev = input.device
+    pdt = h0.dtype
+    with torch.cuda.device(dev):
+        hs = torch.empty(hshape, dtype=input.dtype, device=dev)
+        if zsaved:
+            zs = torch.empty(zsaved, dtype=torch.uint8, device=dev)
+        else:
+            zs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates or preact) else None
+        cs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates and not preact) else None
+        if rank_space_shape:
+            cs = torch.empty(rank_space_shape, dtype=pdt, device=dev)
+        ws, wsp = _workspace(nbytes, dev)
+        fn = lib.fastgrnn_hip_forward_unroll if unrolled else lib.fastgrnn_hip_forward
+        with _Timed("forward", dev):
+            st = fn(C.byref(plan.desc), C.byref(params), _ptr(input), _ptr(h0), _ptr(hs), _ptr(zs), _ptr(cs),
+                    wsp, nbytes, _stream(dev))
+        _lib.check(st, "fastgrnn forward_unroll" if unrolled else "fastgrnn forward")
+        del ws                   # (cached per stream: reuse by the next call is stream-ordered behind these launches)
+    if preact:                   # zs holds the pre-activation W.x + U.h
+        return [hs, zs] if cs is None else [hs, zs, cs]
+    return [hs, zs, cs] if want_gates else [hs]
+
+
 def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1, w2, u1, u2,
                   unrolled, update_nl, want_gates, flags):
     lib = _lib.load()
+    preact = bool(flags & _lib.FLAG_SAVE_PREACT)
     sig = ("f", unrolled, input.shape, input.dtype, h0.shape, h0.dtype, w.shape, u.shape, w1.shape, w2.shape,
            u1.shape, u2.shape, bias_gate.shape, bias_update.shape, zeta.shape, nu.shape,
            (w if w.numel() else w1).dtype, (u if u.numel() else u1).dtype, bias_gate.dtype, bias_update.dtype,
            zeta.dtype, nu.dtype, gate_nl, update_nl, flags, want_gates, input.device.index)
     ent = _seen.get(sig) if _use_seen else None
     if ent is not None and _all_dense_cuda(input, h0, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu):
-        plan, w_lr, u_lr, oshape, hshape, rank_space, nbytes, T, B, H, zsaved = ent
-        desc = plan[0]
-        params = _lib.Params(_ptr(None if w_lr else w), _ptr(None if u_lr else u),
-                             _ptr(w1 if w_lr else None), _ptr(w2 if w_lr else None),
-                             _ptr(u1 if u_lr else None), _ptr(u2 if u_lr else None),
-                             _ptr(bias_gate), _ptr(bias_update), _ptr(zeta), _ptr(nu))
-        dev = input.device
-        preact = bool(flags & _lib.FLAG_SAVE_PREACT)
-        pdt = h0.dtype
-        with torch.cuda.device(dev):
-            hs = torch.empty(hshape, dtype=input.dtype, device=dev)
-            if zsaved:
-                zs = torch.empty(zsaved, dtype=torch.uint8, device=dev)
-            else:
-                zs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates or preact) else None
-            cs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates and not preact) else None
-            if rank_space:
-                cs = torch.empty((T * B, 32), dtype=pdt, device=dev)
-            ws, wsp = _workspace(nbytes, dev)
-            fn = lib.fastgrnn_hip_forward_unroll if unrolled else lib.fastgrnn_hip_forward
-            with _Timed("forward", dev):
-                st = fn(C.byref(desc), C.byref(params), _ptr(input), _ptr(h0), _ptr(hs), _ptr(zs), _ptr(cs),
-                        wsp, nbytes, _stream(dev))
-            _lib.check(st, "fastgrnn forward_unroll" if unrolled else "fastgrnn forward")
-            del ws
-        if preact:
-            return [hs, zs] if cs is None else [hs, zs, cs]
-        return [hs, zs, cs] if want_gates else [hs]
+        plan, w_lr, u_lr, tail = ent
+        return _launch_forward(lib, plan, tail, unrolled, preact, want_gates, input, h0,
+                               _params(w_lr, u_lr, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu))
     _check_input(input, "input")
     _check_input(bias_gate, "bias_gate"); _check_input(bias_update, "bias_update")
     _check_input(h0, "initial_h" if unrolled else "old_h")
@@ -270,12 +290,7 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
     if unrolled:
         if input.dim() != 3:
             raise RuntimeError("input must be [timesteps, batch, features]")
-        if flags & _lib.FLAG_X_BFT:          # the trainer's [B,F,T] (trainClassifier.py:204)
-            B, F, T = input.shape
-        elif batch_major:
-            B, T, F = input.shape
-        else:
-            T, B, F = input.shape
+        T, B, F = _seq_dims(input, flags)
     else:
         if input.dim() != 2:
             raise RuntimeError("input must be [batch, features]")
@@ -289,66 +304,39 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
     if h0.dtype != pdt:
         raise RuntimeError("input and hidden state dtypes differ" if pdt == input.dtype
                            else "bfloat16 sequences take a float32 hidden state")
-    plan, params, _, _ = _describe(T, B, F, H, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu,
-                                   input.dtype, gate_nl, update_nl, flags)
-    desc = plan[0]
+    plan, params, w_lr, u_lr = _describe(T, B, F, H, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu,
+                                         input.dtype, gate_nl, update_nl, flags)
     _warn_fallback(plan, 0)
-    dev = input.device
     oshape = ((B, T, H) if batch_major else (T, B, H)) if unrolled else (B, H)
-    preact = bool(flags & _lib.FLAG_SAVE_PREACT)
     hs_last = bool(unrolled and (flags & _lib.FLAG_HS_LAST))
     if hs_last and (want_gates or preact):
         raise RuntimeError("FLAG_HS_LAST is an inference mode: nothing can be saved for a backward "
                            "(want_gates=False and no FLAG_SAVE_PREACT)")
-    with torch.cuda.device(dev):
-        hs = torch.empty((B, H) if hs_last else oshape, dtype=input.dtype, device=dev)
-        # FLAG_ZERO_EXTEND on the padded route: under FLAG_SAVE_PREACT the saved tensor is one opaque buffer
-        # (fastgrnn_hip.h: the padded pre-activation, the padded hidden states and, for the low-rank scans, the
-        # rank-space vector) that the backward takes back as z
-        zx = plan[5]
-        zroute = zx is not None and (preact or not want_gates)
-        zsaved = int(zx.saved_bytes) if (zroute and preact) else 0
-        if zsaved:
-            zs = torch.empty(zsaved, dtype=torch.uint8, device=dev)
-        else:
-            zs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates or preact) else None
-        cs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates and not preact) else None
-        if preact and not zsaved and desc.H == 256 and desc.F == 32 and 0 < desc.w_rank <= 16 and 0 < desc.u_rank <= 16:
-            # factorised operands: the forward also saves the rank-space vector [U1.h | W1.x] per step, always
-            # time-major and zero-extended to 16 + 16 columns (an opaque tensor for the backward)
-            cs = torch.empty((T * B, 32), dtype=pdt, device=dev)
-        # (dense H=128 layers with a wide input keep the frame product in the workspace only when no auxiliary
-        # output is requested: include/fastgrnn_hip.h, forward workspace)
-        wide = desc.H == 128 and desc.F > 32 and not desc.w_rank and not desc.u_rank
-        nbytes = 0 if (plan[1] == 2 and zs is not None and wide and not zroute) else plan[3]
-        ws, wsp = _workspace(nbytes, dev)
-        fn = lib.fastgrnn_hip_forward_unroll if unrolled else lib.fastgrnn_hip_forward
-        _seen[sig] = (plan, _present(w1), _present(u1), oshape, (B, H) if hs_last else oshape,
-                      bool(preact and cs is not None), nbytes, T, B, H, zsaved)
-        with _Timed("forward", dev):
-            st = fn(C.byref(desc), C.byref(params), _ptr(input), _ptr(h0), _ptr(hs), _ptr(zs), _ptr(cs),
-                    wsp, nbytes, _stream(dev))
-        _lib.check(st, "fastgrnn forward_unroll" if unrolled else "fastgrnn forward")
-        del ws                   # (cached per stream: reuse by the next call is stream-ordered behind these launches)
-    if preact:                   # zs holds the pre-activation W.x + U.h
-        if zs is None:
-            zs = torch.empty(0, dtype=pdt, device=dev)
-        return [hs, zs] if cs is None else [hs, zs, cs]
-    return [hs, zs, cs] if want_gates else [hs]
+    # FLAG_ZERO_EXTEND on the padded route: under FLAG_SAVE_PREACT the saved tensor is one opaque buffer
+    # (fastgrnn_hip.h: the padded pre-activation, the padded hidden states and, for the low-rank scans, the
+    # rank-space vector) that the backward takes back as z
+    zroute = bool(plan.zext.forward) and (preact or not want_gates)
+    zsaved = int(plan.zext.saved_bytes) if (zroute and preact) else 0
+    # factorised operands on the low-rank scans: the forward also saves the rank-space vector [U1.h | W1.x] per step,
+    # always time-major and zero-extended to 16 + 16 columns (an opaque tensor for the backward)
+    rank_space_shape = (T * B, plan.rank_space_cols) if plan.rank_space_cols else None
+    # (layers that park the frame product in the auxiliary outputs need no workspace when those are requested:
+    # include/fastgrnn_hip.h, forward workspace)
+    nbytes = 0 if (plan.forward_ws_optional and (want_gates or preact)) else plan.ws[0]
+    tail = (oshape, (B, H) if hs_last else oshape, rank_space_shape, nbytes, zsaved)
+    _seen[sig] = (plan, w_lr, u_lr, tail)
+    return _launch_forward(lib, plan, tail, unrolled, preact, want_gates, input, h0, params)
 
 
 def _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_h, z, h_prime, rank_space, h0,
                      w, u, w1, w2, u1, u2, b0, b1, zeta, nu, need_dx):
     """Allocate the 12 outputs (the parameter gradients as views of ONE flat buffer) and launch."""
     w_lr, u_lr, shapes, sizes, dx_optional, B, H = ent
-    desc = plan[0]
+    desc = plan.desc
     dev = input.device
     dt = input.dtype
     pdt = h0.dtype
-    params = _lib.Params(_ptr(None if w_lr else w), _ptr(None if u_lr else u),
-                         _ptr(w1 if w_lr else None), _ptr(w2 if w_lr else None),
-                         _ptr(u1 if u_lr else None), _ptr(u2 if u_lr else None),
-                         _ptr(b0), _ptr(b1), _ptr(zeta), _ptr(nu))
+    params = _params(w_lr, u_lr, w, u, w1, w2, u1, u2, b0, b1, zeta, nu)
     with torch.cuda.device(dev):
         none = _NONE
         # the input's gradient is optional on these shapes (fastgrnn_hip.h, fastgrnn_grads.d_x): skipped when autograd
@@ -371,7 +359,7 @@ def _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_
         del flat, views
         grads = _lib.Grads(_ptr(d_input), _ptr(d_bz), _ptr(d_bh), _ptr(d_zeta), _ptr(d_nu), _ptr(d_old_h),
                            _ptr(d_w), _ptr(d_u), _ptr(d_w1), _ptr(d_w2), _ptr(d_u1), _ptr(d_u2))
-        nbytes = plan[4]
+        nbytes = plan.ws[1]
         ws, wsp = _workspace(nbytes, dev)
         with _Timed("backward", dev):
             if unrolled:
@@ -415,28 +403,17 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
                                 bias_gate if preact else zeta, bias_update if preact else zeta, zeta, nu, need_dx)
     # FLAG_ZERO_EXTEND's padded route: z is the forward's opaque saved buffer (uint8), h_prime is not used
     zsaved = preact and bool(flags & _lib.FLAG_ZERO_EXTEND) and z.dtype == torch.uint8
+    rank_space = None
     if preact:
         if bias_gate is None or bias_update is None:
             raise RuntimeError("FLAG_SAVE_PREACT backward needs bias_gate and bias_update")
-        # (the register-resident low-rank scans, both ranks 1..16, save a rank-space vector; other factorised cells
-        # run on the dense kernels and save the pre-activation alone)
-        rank_space = h_prime if (_present(w1) and _present(u1) and w1.shape[0] <= 16 and u1.shape[0] <= 16
-                                 and tuple(w1.shape[1:]) == (32,) and u1.shape[1] == 256 and not zsaved) else None
-        if rank_space is not None:
-            _check_input(rank_space, "rank_space")
-            _expect(rank_space, (hs_or_old_h.numel() // hs_or_old_h.shape[-1], 32), "rank_space")
-        h_prime = z              # keeps the shape checks below uniform
+        rank_space, h_prime = h_prime, z         # (h_prime = z keeps the shape checks below uniform)
     for t, n in ((grad_h, "grad_h"), (input, "input"), (hs_or_old_h, "hidden_states" if unrolled else "old_h"),
                  (z, "z"), (h_prime, "h_prime"), (h0, "initial_h")):
         if not (preact and t.device.type == "meta"):
             _check_input(t, n)
     if unrolled:
-        if flags & _lib.FLAG_X_BFT:
-            B, F, T = input.shape
-        elif flags & _lib.FLAG_BATCH_MAJOR:
-            B, T, F = input.shape
-        else:
-            T, B, F = input.shape
+        T, B, F = _seq_dims(input, flags)
         H = grad_h.shape[-1]
         lead = (B, T) if flags & _lib.FLAG_BATCH_MAJOR else (T, B)
         # FLAG_GRAD_LAST: the gradient of the last state only (the classifier head's view, model.py:227)
@@ -461,25 +438,26 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
     plan, params, w_lr, u_lr = _describe(T, B, F, H, w, u, w1, w2, u1, u2,
                                          bias_gate if preact else zeta, bias_update if preact else zeta,
                                          zeta, nu, dt, gate_nl, update_nl, flags)
-    desc = plan[0]
-    zx = plan[5]
-    if zsaved and not (zx is not None and zx.backward and z.numel() == zx.saved_bytes):
+    zx = plan.zext
+    if zsaved and not (zx.backward and z.numel() == zx.saved_bytes):
         raise RuntimeError("fastgrnn backward: z is not the saved buffer of a FLAG_ZERO_EXTEND forward of this shape")
-    if preact and not zsaved and zx is not None and zx.backward:
+    if preact and not zsaved and zx.backward:
         raise RuntimeError("fastgrnn backward: FLAG_ZERO_EXTEND takes the saved buffer of its forward as z (uint8)")
+    # (the low-rank scans save a rank-space vector that comes back as h_prime; every other FLAG_SAVE_PREACT cell saves
+    # the pre-activation alone and h_prime is not used)
+    if plan.rank_space_cols:
+        _check_input(rank_space, "rank_space")
+        _expect(rank_space, (T * B, plan.rank_space_cols), "rank_space")
+    else:
+        rank_space = None
     _warn_fallback(plan, 1)
     shapes = ([tuple(w1.shape), tuple(w2.shape)] if w_lr else [(H, F)]) + \
              ([tuple(u1.shape), tuple(u2.shape)] if u_lr else [(H, H)]) + [(1, H), (1, H), (1, 1), (1, 1)]
     sizes = [a * b for a, b in shapes]
-    if zsaved:
-        dx_optional = bool(zx.dx_optional)
-    else:
-        dx_optional = (plan[2] == 2 and not w_lr and not u_lr and
-                       (desc.H == 256 or (desc.H == 128 and (desc.F > 32 or bool(flags & _lib.FLAG_NO_INPUT_GRAD)))))
-    ent = (w_lr, u_lr, shapes, sizes, dx_optional, B, H)
-    _seen[sig] = (plan, preact and rank_space is not None, ent)
+    ent = (w_lr, u_lr, shapes, sizes, plan.dx_optional, B, H)
+    _seen[sig] = (plan, rank_space is not None, ent)
     return _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_h, z, h_prime,
-                            rank_space if preact else None, h0, w, u, w1, w2, u1, u2,
+                            rank_space, h0, w, u, w1, w2, u1, u2,
                             bias_gate if preact else zeta, bias_update if preact else zeta, zeta, nu, need_dx)
 
 
@@ -538,12 +516,7 @@ def forward_unroll_affine(input, w, u, bias_gate, bias_update, zeta, nu, gate_sc
         _check_input(t, n)
     if input.dim() != 3:
         raise RuntimeError("input must be [timesteps, batch, features]")
-    if flags & _lib.FLAG_X_BFT:
-        B, F, T = input.shape
-    elif flags & _lib.FLAG_BATCH_MAJOR:
-        B, T, F = input.shape
-    else:
-        T, B, F = input.shape
+    T, B, F = _seq_dims(input, flags)
     H = initial_h.shape[-1]
     _expect(initial_h, (B, H), "initial_h")
     for t, n in ((bias_gate, "bias_gate"), (bias_update, "bias_update"), (gate_scale, "gate_scale"),
@@ -562,11 +535,11 @@ def forward_unroll_affine(input, w, u, bias_gate, bias_update, zeta, nu, gate_sc
     hs_shape = (B, H) if flags & _lib.FLAG_HS_LAST else ((B, T, H) if flags & _lib.FLAG_BATCH_MAJOR else (T, B, H))
     with torch.cuda.device(dev):
         hs = torch.empty(hs_shape, dtype=input.dtype, device=dev)
-        ws, wsp = _workspace(plan[3], dev)
+        ws, wsp = _workspace(plan.ws[0], dev)
         with _Timed("forward_affine", dev):
-            st = lib.fastgrnn_hip_forward_unroll_affine(C.byref(plan[0]), C.byref(params), _ptr(gate_scale),
+            st = lib.fastgrnn_hip_forward_unroll_affine(C.byref(plan.desc), C.byref(params), _ptr(gate_scale),
                                                         _ptr(update_scale), _ptr(input), _ptr(initial_h), _ptr(hs),
-                                                        wsp, plan[3], _stream(dev))
+                                                        wsp, plan.ws[0], _stream(dev))
         _lib.check(st, "fastgrnn forward_unroll_affine")
         del ws
     return hs

@@ -67,6 +67,15 @@ def _is_bft_view(input):
             and input.permute(1, 2, 0).is_contiguous())
 
 
+def _on_path2(input, T, B, F, H, w1, u1, gate_non_linearity, direction, flags):
+    """This call is on kernel path 2 (the split-precision scans): a GPU tensor of a dtype they take and the library's
+    answer for the descriptor.  ``w1`` / ``u1``: the cell's W1 / U1, whose leading sizes are the ranks (empty = dense)."""
+    return (input.is_cuda and input.dtype in (torch.float32, torch.bfloat16)
+            and fastgrnn_cuda.kernel_path(T, B, F, H, w1.shape[0] if w1.numel() else 0,
+                                          u1.shape[0] if u1.numel() else 0, gate_non_linearity, 2, input.dtype,
+                                          direction, flags) == 2)
+
+
 _unroll_decisions = {}
 _zero_states = {}        # (B, H, dtype, device) -> the default h0
 _inference_ok = {}       # call signature -> "the hs-only forward is on kernel path 2"
@@ -98,26 +107,20 @@ class FastGRNNUnrollFunction(Function):
             else:
                 T, B, F = input.shape
             H = old_h.shape[1]
-            rw = w1.shape[0] if w1.numel() else 0
-            ru = u1.shape[0] if u1.numel() else 0
             # The trainer hands over permute(2,0,1) of the loader's [B,F,T] batch (trainClassifier.py:204,299), a
             # [T,B,F] VIEW; the reference copies it here with .contiguous().  Where the kernels can read [B,F,T]
             # in place (FLAG_X_BFT) the view's base is passed instead and d_input comes back as the same view.
+            call = (input, T, B, F, H, w1, u1, gate_non_linearity)
             x_bft = (not batch_major and _is_bft_view(input)
-                     and input.dtype in (torch.float32, torch.bfloat16)
-                     and fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, gate_non_linearity, 2, input.dtype, 1,
-                                                   _lib.FLAG_SAVE_PREACT | _lib.FLAG_X_BFT) == 2)
+                     and _on_path2(*call, 1, _lib.FLAG_SAVE_PREACT | _lib.FLAG_X_BFT))
             # (FLAG_ZERO_EXTEND: hidden sizes up to 256 that no kernel-path-2 shape covers run zero-padded to one)
-            preact = (input.dtype in (torch.float32, torch.bfloat16) and input.is_cuda and
-                      fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, gate_non_linearity, 2, input.dtype, 1,
-                                                _lib.FLAG_SAVE_PREACT | _lib.FLAG_ZERO_EXTEND) == 2)
+            preact = _on_path2(*call, 1, _lib.FLAG_SAVE_PREACT | _lib.FLAG_ZERO_EXTEND)
             flags = (_lib.FLAG_SAVE_PREACT | _lib.FLAG_ZERO_EXTEND) if preact else 0
             if batch_major:
                 flags |= _lib.FLAG_BATCH_MAJOR
             if x_bft:
                 flags |= _lib.FLAG_X_BFT
-            grad_last = bool(last_state and input.is_cuda and fastgrnn_cuda.kernel_path(
-                T, B, F, H, rw, ru, gate_non_linearity, 2, input.dtype, 1, flags | _lib.FLAG_GRAD_LAST) == 2)
+            grad_last = bool(last_state and _on_path2(*call, 1, flags | _lib.FLAG_GRAD_LAST))
             dec = _unroll_decisions[key] = (x_bft, preact, flags, grad_last)
         x_bft, preact, flags, grad_last = dec
         input = input.permute(1, 2, 0) if x_bft else input.contiguous()
@@ -384,11 +387,8 @@ class FastGRNNCUDA(nn.Module):
         in_place = False
         if self.batch_first is True:
             Bn, Tn, Fn = input.shape
-            rw = self.W1.shape[0] if self.W1.numel() else 0
-            ru = self.U1.shape[0] if self.U1.numel() else 0
-            in_place = (input.dtype in (torch.float32, torch.bfloat16) and fastgrnn_cuda.kernel_path(
-                Tn, Bn, Fn, self._hidden_size, rw, ru, self._gate_non_linearity, 2, input.dtype, 1,
-                _lib.FLAG_SAVE_PREACT | _lib.FLAG_BATCH_MAJOR | _lib.FLAG_ZERO_EXTEND) == 2)
+            in_place = self._on_path2(input, Tn, Bn, Fn, 1,
+                                      _lib.FLAG_SAVE_PREACT | _lib.FLAG_BATCH_MAJOR | _lib.FLAG_ZERO_EXTEND)
             if not in_place:
                 input = input.transpose(0, 1).contiguous()
         nbatch = input.shape[0] if in_place else input.shape[1]
@@ -422,6 +422,9 @@ class FastGRNNCUDA(nn.Module):
             return result.transpose(0, 1)
         return result
 
+    def _on_path2(self, input, T, B, F, direction, flags):
+        return _on_path2(input, T, B, F, self._hidden_size, self.W1, self.U1, self._gate_non_linearity, direction, flags)
+
     def _inference_forward(self, input, hiddenState, batch_major):
         """hs alone when nothing will be differentiated (torch.no_grad()): no tensor is saved for a backward, so the
         scan writes one [T,B,H] tensor instead of two.  None where the kernels have no such variant (the caller then
@@ -440,10 +443,7 @@ class FastGRNNCUDA(nn.Module):
                 Bn, Tn, Fn = input.shape
             else:
                 Tn, Bn, Fn = input.shape
-            rw = self.W1.shape[0] if self.W1.numel() else 0
-            ru = self.U1.shape[0] if self.U1.numel() else 0
-            ok = _inference_ok[key] = fastgrnn_cuda.kernel_path(
-                Tn, Bn, Fn, self._hidden_size, rw, ru, self._gate_non_linearity, 2, input.dtype, 0, flags) == 2
+            ok = _inference_ok[key] = self._on_path2(input, Tn, Bn, Fn, 0, flags)
         if not ok:
             return None
         if bft:
@@ -458,19 +458,15 @@ class FastGRNNCUDA(nn.Module):
             Bn, Tn, Fn = input.shape
         else:
             Tn, Bn, Fn = input.shape
-        rw = self.W1.shape[0] if self.W1.numel() else 0
-        ru = self.U1.shape[0] if self.U1.numel() else 0
         flags = _lib.FLAG_HS_LAST | _lib.FLAG_ZERO_EXTEND | (_lib.FLAG_BATCH_MAJOR if batch_major else 0)
-        if (not batch_major and input.dtype in (torch.float32, torch.bfloat16) and _is_bft_view(input)
-                and fastgrnn_cuda.kernel_path(Tn, Bn, Fn, self._hidden_size, rw, ru, self._gate_non_linearity, 2,
-                                              input.dtype, 0, _lib.FLAG_HS_LAST | _lib.FLAG_X_BFT) == 2):
+        if (not batch_major and _is_bft_view(input)
+                and self._on_path2(input, Tn, Bn, Fn, 0, _lib.FLAG_HS_LAST | _lib.FLAG_X_BFT)):
             # the trainer's permuted view: the [B,F,T] base as it is (a view on a zero-extended shape is copied below)
             return fastgrnn_cuda.forward_unroll(input.permute(1, 2, 0), self.W, self.U, self.bias_gate,
                                                 self.bias_update, self.zeta, self.nu, hiddenState.contiguous(),
                                                 self._gate_non_linearity, self.W1, self.W2, self.U1, self.U2,
                                                 want_gates=False, flags=_lib.FLAG_HS_LAST | _lib.FLAG_X_BFT)[0]
-        if input.dtype not in (torch.float32, torch.bfloat16) or fastgrnn_cuda.kernel_path(
-                Tn, Bn, Fn, self._hidden_size, rw, ru, self._gate_non_linearity, 2, input.dtype, 0, flags) != 2:
+        if not self._on_path2(input, Tn, Bn, Fn, 0, flags):
             return None
         return fastgrnn_cuda.forward_unroll(input.contiguous(), self.W, self.U, self.bias_gate, self.bias_update,
                                             self.zeta, self.nu, hiddenState.contiguous(), self._gate_non_linearity,

@@ -127,9 +127,14 @@ def _answers(lib, d):
     st = lib.fastgrnn_hip_zero_extend_plan(C.byref(d), C.byref(plan))
     bn = (lib.fastgrnn_hip_bn_train_supported(C.byref(d)), lib.fastgrnn_hip_bn_train_forward_workspace_bytes(C.byref(d)),
           lib.fastgrnn_hip_bn_train_backward_workspace_bytes(C.byref(d)))
+    full = _lib.Plan()
+    st_full = lib.fastgrnn_hip_plan(C.byref(d), C.byref(full))
+    zx = full.zext
+    new = (st_full, tuple(full.path), tuple(full.workspace_bytes), full.forward_ws_optional, full.rank_space_cols,
+           zx.forward, zx.backward, zx.Hp, zx.Fp, zx.saved_bytes)
     return (lib.fastgrnn_hip_kernel_path(C.byref(d), 0), lib.fastgrnn_hip_kernel_path(C.byref(d), 1),
             lib.fastgrnn_hip_forward_workspace_bytes(C.byref(d)), lib.fastgrnn_hip_backward_workspace_bytes(C.byref(d)),
-            st, plan.forward, plan.backward, plan.Hp, plan.Fp, plan.saved_bytes) + bn
+            st, plan.forward, plan.backward, plan.Hp, plan.Fp, plan.saved_bytes) + bn + new
 
 
 def test_every_query_and_predicate_answers_the_same_with_the_flag(lib):
@@ -182,7 +187,7 @@ def test_the_flag_is_part_of_the_cached_plan_key():
     from kws_amd import fastgrnn_cuda
     a = fastgrnn_cuda._plan(99, 4096, 32, 128, 0, 0, 0, 2, _lib.F32, SP)
     b = fastgrnn_cuda._plan(99, 4096, 32, 128, 0, 0, 0, 2, _lib.F32, SP | NIG)
-    assert a[0].flags == SP and b[0].flags == SP | NIG and a[1:5] == b[1:5]
+    assert a.desc.flags == SP and b.desc.flags == SP | NIG and a.path == b.path and a.ws == b.ws
     assert fastgrnn_cuda.kernel_path(99, 4096, 32, 128, flags=SP | NIG, direction=1) == 2
 
 
