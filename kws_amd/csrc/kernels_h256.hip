@@ -50,6 +50,14 @@ constexpr int SLAB2 = 576;                      // floats per workgroup: d_bz[25
 // registers hold no 16 more per lane without scratch (tools/resource_usage.py), so an AFF kernel sizes `smem` for
 // the path its MODE runs: MODE 1 (the fp16 path's 90 624 B) stages both scales in sbias; MODE 0 / 2 stage the update
 // scales there (1 KB) and keep the lane's eight gate scales in registers (loaded once).
+// The instantiations the library holds (each with RAGGED false and true); launch_fwd builds exactly these.
+constexpr bool fwd_h256_built(int gate, int aux, int mode, bool prein, bool bf, bool aff) {
+  const bool ref_gate = gate <= FASTGRNN_NL_TANH;
+  if (mode != 0 && !gate_bounds_state(gate)) return false;
+  if (aff) return ref_gate && !bf && (aux == 0 || aux == 3);
+  if (bf) return ref_gate && (aux == 0 || aux == 2);
+  return true;
+}
 template <int GATE, int AUX, bool RAGGED, int MODE, bool PREIN = false, bool BF = false, bool AFF = false>
 __global__ __launch_bounds__(512) void fwd_scan_h256(
     int Tn, int B, unsigned hsT, unsigned hsB, unsigned xsT, unsigned xsB,
@@ -421,6 +429,8 @@ __global__ __launch_bounds__(512) void fwd_scan_h256(
 // d_bz, d_bh, d_zeta, d_nu partial sums per workgroup.  mode bit 1 (FASTGRNN_FLAG_GRAD_LAST): ghs is [B,H], the
 // gradient of the last state alone.
 // BF: FASTGRNN_BF16_IO -- grad_hs and hs are bf16 in HBM (the saved pre-activation, h0, d_pre and d_h0 stay fp32).
+// The instantiations the library holds (each with RAGGED false and true); launch_bwd builds exactly these.
+constexpr bool bwd_h256_built(int gate, bool preact, bool bf) { return !bf || (gate <= FASTGRNN_NL_TANH && preact); }
 template <int GATE, bool PREACT, bool RAGGED, bool BF = false>
 __global__ __launch_bounds__(512) void bwd_scan_h256(
     int Tn, int B, int mode, unsigned hsT, unsigned hsB, const float* __restrict__ ghs, const float* __restrict__ hs,
@@ -791,12 +801,13 @@ H256BwdWs h256_bwd_layout(const fastgrnn_desc& d) {
   return L;
 }
 
-template <int GATE>
-void launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
+// run-time values of fwd_scan_h256's template parameters (MODE: 1 then 2 under f16h, else 0)
+struct FwdH256 { int gate, aux; bool ragged, f16h, prein, bf, aff; };
+
+// false: the library holds no kernel for this call (fwd_h256_built), no scan was launched
+bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
                 void* cs, void* ws, hipStream_t s, const float* sg, const float* sc) {
   dim3 grid((d.B + 15) / 16), block(512);
-  const bool ragged = (d.B % 16) != 0;
-  const int aux = (d.flags & FASTGRNN_FLAG_HS_LAST) ? 3 : (zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1));
   unsigned* flags = reinterpret_cast<unsigned*>(ws);
   // FASTGRNN_FLAG_X_BFT: the loader's [B,F,T] frames are transposed into the workspace first (25 us at B = 4096; a
   // lane's frame-by-frame read of [B,F,T] in place touches 64 cache lines per wave load and cost the scan 120 us)
@@ -827,66 +838,39 @@ void launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
                        (const float*)p.u, (const float*)p.bias_gate, (const float*)p.bias_update, (const float*)p.zeta,
                        (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, flags, sg, sc);
   };
-  // fp16 two-plane state product only for gates that keep z in [0,1] (see fwd_scan_split_w8); FWD_BF16X3: A/B
-  constexpr bool BOUNDED = GATE == FASTGRNN_NL_SIGMOID || GATE == FASTGRNN_NL_QUANT_SIGM || GATE == FASTGRNN_NL_QUANT_SIGM4;
-  const bool h16 = BOUNDED && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3);
-  if constexpr (GATE <= FASTGRNN_NL_TANH) {
-    if (sg) {                                        // FASTGRNN_FLAG_PREACT_AFFINE (affine_supported: fp32, AUX 0 / 3)
-      auto aff = [&](auto aux_tag, auto prein_tag) __attribute__((always_inline)) {
-        constexpr int A = decltype(aux_tag)::value;
-        constexpr bool PI = decltype(prein_tag)::value;
-        if constexpr (BOUNDED) {
-          if (h16) {
-            if (ragged) { go(fwd_scan_h256<GATE, A, true, 1, PI, false, true>); go(fwd_scan_h256<GATE, A, true, 2, PI, false, true>); }
-            else        { go(fwd_scan_h256<GATE, A, false, 1, PI, false, true>); go(fwd_scan_h256<GATE, A, false, 2, PI, false, true>); }
-            return;
-          }
-        }
-        if (ragged) go(fwd_scan_h256<GATE, A, true, 0, PI, false, true>); else go(fwd_scan_h256<GATE, A, false, 0, PI, false, true>);
-      };
-      auto aff_in = [&](auto aux_tag) __attribute__((always_inline)) {
-        if (prein) aff(aux_tag, std::true_type{}); else aff(aux_tag, std::false_type{});
-      };
-      if (aux == 3) aff_in(std::integral_constant<int, 3>{}); else aff_in(std::integral_constant<int, 0>{});
-      return;
-    }
-  }
-  auto pick = [&](auto aux_tag) __attribute__((always_inline)) {
-    constexpr int A = decltype(aux_tag)::value;
-    auto with = [&](auto prein_tag, auto bf_tag) __attribute__((always_inline)) {
-      constexpr bool PI = decltype(prein_tag)::value, BFV = decltype(bf_tag)::value;
-      if constexpr (BOUNDED) {
-        if (h16) {                                   // fp16 launch, then the bf16 one for workgroups it turned down
-          if (ragged) { go(fwd_scan_h256<GATE, A, true, 1, PI, BFV>); go(fwd_scan_h256<GATE, A, true, 2, PI, BFV>); }
-          else        { go(fwd_scan_h256<GATE, A, false, 1, PI, BFV>); go(fwd_scan_h256<GATE, A, false, 2, PI, BFV>); }
-          return;
-        }
-      }
-      if (ragged) go(fwd_scan_h256<GATE, A, true, 0, PI, BFV>); else go(fwd_scan_h256<GATE, A, false, 0, PI, BFV>);
-    };
-    // bf16 sequences (h256_supported: gates sigmoid / relu / tanh, hs alone or the one-saved-tensor contract)
-    if constexpr (GATE <= FASTGRNN_NL_TANH && (A == 0 || A == 2)) {
-      if (bf) {
-        if (prein) with(std::true_type{}, std::true_type{}); else with(std::false_type{}, std::true_type{});
-        return;
-      }
-    }
-    if (prein) with(std::true_type{}, std::false_type{}); else with(std::false_type{}, std::false_type{});
-  };
-  if (aux == 3) pick(std::integral_constant<int, 3>{});
-  else if (aux == 2) pick(std::integral_constant<int, 2>{});
-  else if (aux == 1) pick(std::integral_constant<int, 1>{});
-  else pick(std::integral_constant<int, 0>{});
+  // fp16 two-plane state product only for gates that keep z in [0,1] (see fwd_scan_split_w8): the fp16 launch, then
+  // the bf16 one for the workgroups it turned down; FWD_BF16X3: A/B
+  const int aux = (d.flags & FASTGRNN_FLAG_HS_LAST) ? 3 : (zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1));
+  const FwdH256 v{d.gate_nl, aux, (d.B % 16) != 0, gate_bounds_state(d.gate_nl) && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3),
+                  prein, bf, sg != nullptr};
+  return pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
+         return pick_int<0, 1, 2, 3>(v.aux, [&](auto A_) {
+         return pick_bool(v.f16h, [&](auto FH_) {
+         return pick_bool(v.prein, [&](auto PI_) {
+         return pick_bool(v.bf, [&](auto BF_) {
+         return pick_bool(v.aff, [&](auto AF_) {
+         return pick_bool(v.ragged, [&](auto RG_) {
+           constexpr int G = decltype(G_)::value, A = decltype(A_)::value;
+           constexpr bool FH = decltype(FH_)::value, PI = decltype(PI_)::value, BF = decltype(BF_)::value,
+                          AF = decltype(AF_)::value, RG = decltype(RG_)::value;
+           if constexpr (fwd_h256_built(G, A, FH ? 1 : 0, PI, BF, AF)) {
+             if constexpr (FH) { go(fwd_scan_h256<G, A, RG, 1, PI, BF, AF>); go(fwd_scan_h256<G, A, RG, 2, PI, BF, AF>); }
+             else go(fwd_scan_h256<G, A, RG, 0, PI, BF, AF>);
+             return true;
+           } else return false;
+         }); }); }); }); }); }); });
 }
 
-template <int GATE>
-void launch_bwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
+// run-time values of bwd_scan_h256's template parameters
+struct BwdH256 { int gate; bool preact, ragged, bf; };
+
+// false: the library holds no kernel for this call (bwd_h256_built), nothing was launched
+bool launch_bwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
                 const void* a0, const void* a1, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
   const H256BwdWs L = h256_bwd_layout(d);
   char* base = reinterpret_cast<char*>(ws);
   float* part = (float*)(base + L.part); float* dpre = (float*)(base + L.dpre); float* tn = (float*)(base + L.tn);
   const int nwg = (d.B + 15) / 16;
-  const bool ragged = (d.B % 16) != 0, preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
   const bool bm = (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0;
   const unsigned hsT = bm ? H2 : (unsigned)d.B * H2, hsB = bm ? (unsigned)d.T * H2 : H2;
   auto go = [&](auto kern) __attribute__((always_inline)) {
@@ -896,17 +880,18 @@ void launch_bwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* gh
                        (const float*)p.nu, (float*)g.d_h0, dpre, part);
   };
   const bool bf = d.dtype == FASTGRNN_BF16_IO;       // (h256_supported: under SAVE_PREACT, gates sigmoid / relu / tanh)
-  bool launched = false;
-  if constexpr (GATE <= FASTGRNN_NL_TANH) {
-    if (bf) {
-      if (ragged) go(bwd_scan_h256<GATE, true, true, true>); else go(bwd_scan_h256<GATE, true, false, true>);
-      launched = true;
-    }
-  }
-  if (!launched) {
-    if (preact) { if (ragged) go(bwd_scan_h256<GATE, true, true>); else go(bwd_scan_h256<GATE, true, false>); }
-    else        { if (ragged) go(bwd_scan_h256<GATE, false, true>); else go(bwd_scan_h256<GATE, false, false>); }
-  }
+  const BwdH256 v{d.gate_nl, (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0, (d.B % 16) != 0, bf};
+  const bool launched =
+      pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
+      return pick_bool(v.preact, [&](auto PA_) {
+      return pick_bool(v.bf, [&](auto BF_) {
+      return pick_bool(v.ragged, [&](auto RG_) {
+        constexpr int G = decltype(G_)::value;
+        constexpr bool PA = decltype(PA_)::value, BF = decltype(BF_)::value, RG = decltype(RG_)::value;
+        if constexpr (bwd_h256_built(G, PA, BF)) { go(bwd_scan_h256<G, PA, RG, BF>); return true; }
+        else return false;
+      }); }); }); });
+  if (!launched) return false;
   hipLaunchKernelGGL(reduce_h256_small, dim3((2 * H2 + 2 + 63) / 64), dim3(1024), 0, s, nwg, part, (const float*)p.zeta,
                      (const float*)p.nu, (float*)g.d_bias_gate, (float*)g.d_bias_update, (float*)g.d_zeta, (float*)g.d_nu);
   const size_t TB = (size_t)d.T * d.B;
@@ -925,6 +910,7 @@ void launch_bwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* gh
     rows_gemm(TB, d.F, H2, true, dpre, (const float*)p.w, bft ? (void*)xtm : g.d_x, false, bf, s);   // (bf16 d_x)
     if (bft) bft_transpose_f32(d.B, d.T, xtm, (float*)g.d_x, false, s, d.F);
   }
+  return true;
 }
 
 }  // namespace
@@ -969,27 +955,13 @@ size_t h256_forward_ws(const fastgrnn_desc& d) {
 int h256_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
                  void* cs, void* ws, hipStream_t s, const float* sg, const float* sc) {
   if (!ws) return FASTGRNN_ERR_WORKSPACE;
-  switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: launch_fwd<FASTGRNN_NL_SIGMOID>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
-    case FASTGRNN_NL_RELU: launch_fwd<FASTGRNN_NL_RELU>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
-    case FASTGRNN_NL_TANH: launch_fwd<FASTGRNN_NL_TANH>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
-    case FASTGRNN_NL_QUANT_TANH: launch_fwd<FASTGRNN_NL_QUANT_TANH>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
-    case FASTGRNN_NL_QUANT_SIGM: launch_fwd<FASTGRNN_NL_QUANT_SIGM>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
-    default: launch_fwd<FASTGRNN_NL_QUANT_SIGM4>(d, p, x, h0, hs, zs, cs, ws, s, sg, sc); break;
-  }
+  if (!launch_fwd(d, p, x, h0, hs, zs, cs, ws, s, sg, sc)) return FASTGRNN_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 
 int h256_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
                   const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
-  switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: launch_bwd<FASTGRNN_NL_SIGMOID>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    case FASTGRNN_NL_RELU: launch_bwd<FASTGRNN_NL_RELU>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    case FASTGRNN_NL_TANH: launch_bwd<FASTGRNN_NL_TANH>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    case FASTGRNN_NL_QUANT_TANH: launch_bwd<FASTGRNN_NL_QUANT_TANH>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    case FASTGRNN_NL_QUANT_SIGM: launch_bwd<FASTGRNN_NL_QUANT_SIGM>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    default: launch_bwd<FASTGRNN_NL_QUANT_SIGM4>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-  }
+  if (!launch_bwd(d, p, ghs, x, hs, zs, cs, h0, g, ws, s)) return FASTGRNN_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 

@@ -22,6 +22,12 @@ namespace {
 // Row (t, b) of hs / zs is t*rsT + b*rsB (time- or batch-major), of x t*xsT + b*xsB; the saved rank-space vector cs
 // is always [T*B, 32] time-major (it only travels from this kernel to the backward).  BF: x and hs are bf16 (the
 // state itself stays fp32 in registers, as in the dense scans).  LAST (AUX == 0): hs is [B,H] and receives h_T only.
+// The instantiations the library holds (each with RAGGED false and true, NW = 8); launch_fwd_lowrank builds exactly these.
+constexpr bool fwd_lowrank_built(int gate, int aux, bool bf, bool last) {
+  if (gate > FASTGRNN_NL_TANH) return false;
+  if (last) return aux == 0;
+  return !(bf && aux == 1);          // the reference's (z_s, h_prime_s) outputs: fp32 sequences
+}
 template <int GATE, int AUX, bool RAGGED, bool BF = false, bool LAST = false, int NW = 8>
 __global__ __launch_bounds__(NW * 64) void fwd_scan_lowrank_split(
     int Tn, int B, int rsT, int rsB, int xsT, int xsB, int rw, int ru, const float* __restrict__ x,
@@ -250,6 +256,8 @@ __global__ __launch_bounds__(NW * 64) void fwd_scan_lowrank_split(
 constexpr int SL_UW2 = 0, SL_U1T = 256 * 32, SL_W1T = SL_U1T + 256 * 16, SL_BZ = SL_W1T + 32 * 16, SL_ZN = SL_BZ + 512;
 constexpr int SLAB_LR = ((SL_ZN + 2 + 63) / 64) * 64;
 
+// The instantiations the library holds: every RAGGED and BF of the reference's three gates.
+constexpr bool bwd_lowrank_built(int gate) { return gate <= FASTGRNN_NL_TANH; }
 template <int GATE, bool RAGGED, bool BF = false>
 __global__ __launch_bounds__(512) void bwd_scan_lowrank_split(
     int Tn, int B, int rsT, int rsB, int xsT, int xsB, int rw, int ru, int glast,
@@ -772,8 +780,6 @@ __global__ __launch_bounds__(256) void bft_transpose(int B, int T, const E* __re
   }
 }
 
-static inline int row_stride_t(const fastgrnn_desc& d) { return (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) ? 1 : d.B; }
-static inline int row_stride_b(const fastgrnn_desc& d) { return (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) ? d.T : 1; }
 static inline size_t esz(const fastgrnn_desc& d) { return d.dtype == FASTGRNN_BF16_IO ? 2 : 4; }
 
 struct LowrankBwdWs { size_t part, sink, xt, dxt, total; };
@@ -791,10 +797,10 @@ LowrankBwdWs lowrank_bwd_layout(const fastgrnn_desc& d) {
   return L;
 }
 
-template <int GATE>
-void launch_bwd_lowrank_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x,
-                             const void* hs, const void* pre_s, const void* m_s, const void* h0,
-                             const fastgrnn_grads& g, void* ws, hipStream_t s) {
+// false: the library holds no kernel for this call (bwd_lowrank_built), no scan was launched
+bool launch_bwd_lowrank(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x,
+                        const void* hs, const void* pre_s, const void* m_s, const void* h0,
+                        const fastgrnn_grads& g, void* ws, hipStream_t s) {
   const LowrankBwdWs L = lowrank_bwd_layout(d);
   char* base = reinterpret_cast<char*>(ws);
   float* part = (float*)(base + L.part);
@@ -821,8 +827,15 @@ void launch_bwd_lowrank_gate(const fastgrnn_desc& d, const fastgrnn_params& p, c
   };
   // 8 waves (two per SIMD) for full and ragged batches alike (lanes beyond a ragged batch only get a zero gradient,
   // which needs no extra registers; the first ragged variant masked five values per element and spilled)
-  if (bf) { if (d.B % 16) go(bwd_scan_lowrank_split<GATE, true, true>); else go(bwd_scan_lowrank_split<GATE, false, true>); }
-  else    { if (d.B % 16) go(bwd_scan_lowrank_split<GATE, true, false>); else go(bwd_scan_lowrank_split<GATE, false, false>); }
+  const bool launched =
+      pick_int<0, 1, 2>(d.gate_nl, [&](auto G_) {
+      return pick_bool((d.B % 16) != 0, [&](auto RG_) {
+      return pick_bool(bf, [&](auto BF_) {
+        constexpr int G = decltype(G_)::value;
+        if constexpr (bwd_lowrank_built(G)) { go(bwd_scan_lowrank_split<G, decltype(RG_)::value, decltype(BF_)::value>); return true; }
+        else return false;
+      }); }); });
+  if (!launched) return false;
   if (bft) {
     if (bf) hipLaunchKernelGGL((bft_transpose<unsigned short, false>), dim3(d.B), dim3(256), 0, s, d.B, d.T,
                                (const unsigned short*)(base + L.dxt), (unsigned short*)g.d_x);
@@ -833,11 +846,15 @@ void launch_bwd_lowrank_gate(const fastgrnn_desc& d, const fastgrnn_params& p, c
   hipLaunchKernelGGL(reduce_lowrank_slabs, dim3((SL_ZN + 2 + 63) / 64), dim3(1024), 0, s, nwg, part, (const float*)p.zeta,
                      (const float*)p.nu, d.u_rank, d.w_rank, (float*)g.d_u1, (float*)g.d_u2, (float*)g.d_w1,
                      (float*)g.d_w2, (float*)g.d_bias_gate, (float*)g.d_bias_update, (float*)g.d_zeta, (float*)g.d_nu);
+  return true;
 }
 
-template <int GATE>
-void launch_fwd_lowrank_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                             void* zs, void* cs, void* ws, hipStream_t s) {
+// run-time values of fwd_scan_lowrank_split's template parameters
+struct FwdLowrank { int gate, aux; bool ragged, bf, last; };
+
+// false: the library holds no kernel for this call (fwd_lowrank_built), no scan was launched
+bool launch_fwd_lowrank(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
+                        void* zs, void* cs, void* ws, hipStream_t s) {
   dim3 grid((d.B + 15) / 16), block(512);
   const bool ragged = (d.B % 16) != 0, bf = d.dtype == FASTGRNN_BF16_IO, bft = (d.flags & FASTGRNN_FLAG_X_BFT) != 0;
   const int rsT = row_stride_t(d), rsB = row_stride_b(d);
@@ -854,21 +871,18 @@ void launch_fwd_lowrank_gate(const fastgrnn_desc& d, const fastgrnn_params& p, c
                        (const float*)p.bias_gate, (const float*)p.bias_update, (const float*)p.zeta, (const float*)p.nu,
                        (float*)hs, (float*)zs, (float*)cs);
   };
-  const bool preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
-  const int aux = zs == nullptr ? 0 : (preact ? 2 : 1);
-  auto pick = [&](auto bf_tag) __attribute__((always_inline)) {
-    constexpr bool BFv = decltype(bf_tag)::value;
-    if (d.flags & FASTGRNN_FLAG_HS_LAST) {           // inference: aux == 0 (lowrank_forward)
-      if (ragged) go(fwd_scan_lowrank_split<GATE, 0, true, BFv, true>); else go(fwd_scan_lowrank_split<GATE, 0, false, BFv, true>);
-    } else if (aux == 2) {
-      if (ragged) go(fwd_scan_lowrank_split<GATE, 2, true, BFv>); else go(fwd_scan_lowrank_split<GATE, 2, false, BFv>);
-    } else if (aux == 0) {
-      if (ragged) go(fwd_scan_lowrank_split<GATE, 0, true, BFv>); else go(fwd_scan_lowrank_split<GATE, 0, false, BFv>);
-    } else if constexpr (!BFv) {                     // the reference's (z_s, h_prime_s) outputs: fp32 sequences
-      if (ragged) go(fwd_scan_lowrank_split<GATE, 1, true, false>); else go(fwd_scan_lowrank_split<GATE, 1, false, false>);
-    }
-  };
-  if (bf) pick(std::true_type{}); else pick(std::false_type{});
+  const FwdLowrank v{d.gate_nl, zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1), ragged, bf,
+                     (d.flags & FASTGRNN_FLAG_HS_LAST) != 0};   // (last: inference, no auxiliary output -- lowrank_forward)
+  return pick_int<0, 1, 2>(v.gate, [&](auto G_) {
+         return pick_int<0, 1, 2>(v.aux, [&](auto A_) {
+         return pick_bool(v.bf, [&](auto BF_) {
+         return pick_bool(v.last, [&](auto LS_) {
+         return pick_bool(v.ragged, [&](auto RG_) {
+           constexpr int G = decltype(G_)::value, A = decltype(A_)::value;
+           constexpr bool BF = decltype(BF_)::value, LS = decltype(LS_)::value, RG = decltype(RG_)::value;
+           if constexpr (fwd_lowrank_built(G, A, BF, LS)) { go(fwd_scan_lowrank_split<G, A, RG, BF, LS>); return true; }
+           else return false;
+         }); }); }); }); });
 }
 
 }  // namespace
@@ -905,22 +919,14 @@ int lowrank_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void
   if ((d.flags & FASTGRNN_FLAG_HS_LAST) && (zs || (preact && cs))) return FASTGRNN_ERR_UNSUPPORTED;
   if (d.dtype == FASTGRNN_BF16_IO && zs && !preact) return FASTGRNN_ERR_UNSUPPORTED;
   if ((d.flags & FASTGRNN_FLAG_X_BFT) && !ws) return FASTGRNN_ERR_WORKSPACE;
-  switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: launch_fwd_lowrank_gate<FASTGRNN_NL_SIGMOID>(d, p, x, h0, hs, zs, cs, ws, s); break;
-    case FASTGRNN_NL_RELU: launch_fwd_lowrank_gate<FASTGRNN_NL_RELU>(d, p, x, h0, hs, zs, cs, ws, s); break;
-    default: launch_fwd_lowrank_gate<FASTGRNN_NL_TANH>(d, p, x, h0, hs, zs, cs, ws, s); break;
-  }
+  if (!launch_fwd_lowrank(d, p, x, h0, hs, zs, cs, ws, s)) return FASTGRNN_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 
 int lowrank_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
                      const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
   if (!cs || !zs) return FASTGRNN_ERR_NULL_POINTER;  // the rank-space vector and the pre-activation saved by the forward
-  switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: launch_bwd_lowrank_gate<FASTGRNN_NL_SIGMOID>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    case FASTGRNN_NL_RELU: launch_bwd_lowrank_gate<FASTGRNN_NL_RELU>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    default: launch_bwd_lowrank_gate<FASTGRNN_NL_TANH>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-  }
+  if (!launch_bwd_lowrank(d, p, ghs, x, hs, zs, cs, h0, g, ws, s)) return FASTGRNN_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 

@@ -22,7 +22,7 @@
 //
 // Reference semantics: forward .cu:42-60 + .cu:367-413; backward .cu:91-119 + .cu:473-545.
 #include "common.h"
-#include <type_traits>
+#include "variant_pick.h"
 
 namespace fastgrnn {
 namespace {
@@ -101,6 +101,8 @@ __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4
 // DIAG (tools/diag_scan.hip only; production instantiates 0): 1 = no global stores,
 // 2 = no per-step barrier, 4 = cheap epilogue, 8 = no recurrent-chain MFMAs, 16 = cycle
 // stamps.  Ablations for timing; their results are wrong by construction.
+// The instantiations the library holds (shapes: shape_ok): every GATES_OUT and RAGGED of the reference's three gates.
+constexpr bool fwd_mfma_built(int gate) { return gate <= FASTGRNN_NL_TANH; }
 template <int H, int F, int GATE, bool GATES_OUT, bool RAGGED, int DIAG = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void fwd_scan_mfma(
     int Tn, int B, const float* __restrict__ x, const float* __restrict__ h0,
@@ -300,6 +302,11 @@ struct BwdLds {
 // matrix pipe works on the 96 independent MFMAs while the VALU prepares the next step's
 // d_pre; one raw s_barrier per step.  Global operands are requested one iteration before
 // their use into alternating register sets (no copies, no early waits).
+// The instantiations the library holds (shapes: shape_ok).  No ragged-batch one for H = 128: it needs more registers
+// than a wave has (F = 64) or spills inside the loop (F = 32), and spill reloads are loads nobody placed (operand rule,
+// DESIGN.md 4.0; tools/war_scan.py rejects both); mfma_supported() sends that case on -- in practice only under
+// FASTGRNN_FLAG_FORCE_F32_MFMA, the split-precision kernels take these shapes first.
+constexpr bool bwd_mfma_built(int h, int gate, bool ragged) { return gate <= FASTGRNN_NL_TANH && !(h == 128 && ragged); }
 template <int H, int F, int GATE, bool RAGGED, int DIAG = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void bwd_scan_mfma(
     int Tn, int B, const float* __restrict__ ghs, const float* __restrict__ x,
@@ -703,17 +710,15 @@ int launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, 
                        (const float*)p.u, (const float*)p.bias_gate, (const float*)p.bias_update,
                        (const float*)p.zeta, (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs);
   };
-  const bool ragged = (d.B % 16) != 0, gates = zs != nullptr;
-  auto pick = [&](auto gate_c) __attribute__((always_inline)) {
-    constexpr int G = decltype(gate_c)::value;
-    if (gates) { if (ragged) args(fwd_scan_mfma<H, F, G, true, true>); else args(fwd_scan_mfma<H, F, G, true, false>); }
-    else       { if (ragged) args(fwd_scan_mfma<H, F, G, false, true>); else args(fwd_scan_mfma<H, F, G, false, false>); }
-  };
-  switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: pick(std::integral_constant<int, FASTGRNN_NL_SIGMOID>{}); break;
-    case FASTGRNN_NL_RELU: pick(std::integral_constant<int, FASTGRNN_NL_RELU>{}); break;
-    default: pick(std::integral_constant<int, FASTGRNN_NL_TANH>{}); break;
-  }
+  const bool launched =
+      pick_int<0, 1, 2>(d.gate_nl, [&](auto G_) {
+      return pick_bool(zs != nullptr, [&](auto GO_) {
+      return pick_bool((d.B % 16) != 0, [&](auto RG_) {
+        constexpr int G = decltype(G_)::value;
+        if constexpr (fwd_mfma_built(G)) { args(fwd_scan_mfma<H, F, G, decltype(GO_)::value, decltype(RG_)::value>); return true; }
+        else return false;
+      }); }); });
+  if (!launched) return FASTGRNN_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 
@@ -728,24 +733,15 @@ int launch_bwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs
                        (const float*)zs, (const float*)cs, (const float*)h0, (const float*)p.w, (const float*)p.u,
                        (const float*)p.zeta, (const float*)p.nu, (float*)g.d_x, (float*)g.d_h0, part);
   };
-  const bool ragged = (d.B % 16) != 0;
-  auto pick = [&](auto gate_c) __attribute__((always_inline)) {
-    constexpr int G = decltype(gate_c)::value;
-    if constexpr (H == 128) {
-      // no ragged-batch instantiation for H = 128: it needs more registers than a wave has (F = 64) or spills inside
-      // the loop (F = 32), and spill reloads are loads nobody placed (operand rule; tools/war_scan.py
-      // rejects both); mfma_supported() sends that case on -- in practice only under FASTGRNN_FLAG_FORCE_F32_MFMA,
-      // the split-precision kernels take these shapes first
-      args(bwd_scan_mfma<H, F, G, false>);
-    } else {
-      if (ragged) args(bwd_scan_mfma<H, F, G, true>); else args(bwd_scan_mfma<H, F, G, false>);
-    }
-  };
-  switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: pick(std::integral_constant<int, FASTGRNN_NL_SIGMOID>{}); break;
-    case FASTGRNN_NL_RELU: pick(std::integral_constant<int, FASTGRNN_NL_RELU>{}); break;
-    default: pick(std::integral_constant<int, FASTGRNN_NL_TANH>{}); break;
-  }
+  const bool launched =
+      pick_int<0, 1, 2>(d.gate_nl, [&](auto G_) {
+      return pick_bool((d.B % 16) != 0, [&](auto RG_) {
+        constexpr int G = decltype(G_)::value;
+        constexpr bool RG = decltype(RG_)::value;
+        if constexpr (bwd_mfma_built(H, G, RG)) { args(bwd_scan_mfma<H, F, G, RG>); return true; }
+        else return false;
+      }); });
+  if (!launched) return FASTGRNN_ERR_UNSUPPORTED;
   const int ntot = H * H + H * F + 2 * H + 2;
   hipLaunchKernelGGL(reduce_slabs, dim3((ntot + 63) / 64), dim3(1024), 0, s, nwg, H, F, slab_stride(H, F), part,
                      (const float*)p.zeta, (const float*)p.nu, (float*)g.d_u, (float*)g.d_w,

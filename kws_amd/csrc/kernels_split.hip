@@ -235,6 +235,15 @@ constexpr int W8_ROWX = 80;             // bytes per utterance row of a 32-wide 
 // sc are read only here (two more f32x4 beside bzv / bhv).  The fp16 state product stays eligible: the gate is still
 // z in [0,1] for the gates F16H is instantiated for, so the bound on h above holds, and the rows of u carry the BN
 // scales, which the per-wave power-of-two pre-scale of U absorbs like any other row magnitude.
+// The instantiations the library holds (each with RAGGED false and true); launch_fwd_w8 builds exactly these.
+constexpr bool fwd_w8_built(int gate, int aux, bool bf, bool f16h, bool prein, bool uq, bool aff) {
+  const bool ref_gate = gate <= FASTGRNN_NL_TANH;
+  if (f16h && !gate_bounds_state(gate)) return false;
+  if (aff) return ref_gate && !bf && !uq && (aux == 0 || aux == 3);
+  if (uq) return !bf && !prein && (aux == 0 || aux == 2);
+  if (bf && prein) return ref_gate && (aux == 0 || aux == 2);
+  return true;
+}
 template <int GATE, int AUX, bool RAGGED, bool BF = false, bool F16H = true, bool PREIN = false, bool UQ = false,
           bool AFF = false>
 __global__ __launch_bounds__(512) void fwd_scan_split_w8(
@@ -484,10 +493,6 @@ __global__ __launch_bounds__(512) void fwd_scan_split_w8(
 // floats per workgroup slab of backward partial sums, padded to 64: dU | dW | d_bz | d_bh | (zeta, nu)
 constexpr int SLAB = (128 * 128 + 128 * 32 + 2 * 128 + 2 + 63) & ~63;
 
-// row (t, b) of a [T,B,*] / [B,T,*] tensor = t * row_stride_t + b * row_stride_b
-static inline int row_stride_t(const fastgrnn_desc& d) { return (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) ? 1 : d.B; }
-static inline int row_stride_b(const fastgrnn_desc& d) { return (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) ? d.T : 1; }
-
 constexpr int ROW_H = 288;             // bytes per utterance row of a 128-wide bf16 plane (256 + 32 pad)
 constexpr int ROW_X = 96;              // bytes per utterance row of a 32-wide bf16 plane (64 + 32 pad)
 constexpr int PLANE_H = 16 * ROW_H;    // 4608
@@ -542,6 +547,14 @@ struct BwdW8Lds<false> {               // NODX: no d_x partials
 // NODX (F = 32 only; FASTGRNN_FLAG_NO_INPUT_GRAD with d_x == NULL): the input's gradient is not wanted.  W^T, the d_x
 // MFMAs at the chain's tail, their LDS partials and the d_x stores leave the scan; x stays (dW is contracted here),
 // and d_pre, dW, dU, d_h0 and the bias / zeta / nu sums are the same arithmetic in the same order as without it.
+// The instantiations the library holds (each with RAGGED false and true); launch_bwd_w8 builds exactly these.
+constexpr bool bwd_w8_built(int gate, bool preact, bool bf, bool nox, bool uq, bool nodx) {
+  const bool ref_gate = gate <= FASTGRNN_NL_TANH;
+  if (nox) return !uq && !nodx && (!bf || (ref_gate && preact));
+  if (uq) return preact && !bf;
+  if (bf) return preact;
+  return true;
+}
 template <int GATE, bool PREACT, bool RAGGED, bool BF = false, bool NOX = false, bool UQ = false, bool NODX = false>
 __global__ __launch_bounds__(512) void bwd_scan_split_w8(
     int Tn, int B, int rsT, int rsB, int mode, const float* __restrict__ ghs, const float* __restrict__ x,
@@ -1051,12 +1064,14 @@ WideBwdWs wide_bwd_layout(const fastgrnn_desc& d) {
   return L;
 }
 
-template <int GATE>
-void launch_bwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
-                     const void* a0, const void* a1, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
+// run-time values of bwd_scan_split_w8's template parameters
+struct BwdW8 { int gate; bool preact, ragged, bf, nox, uq, nodx; };
+
+// false: the library holds no kernel for this call (bwd_w8_built), nothing was launched
+bool launch_bwd_w8(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
+                   const void* a0, const void* a1, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
   const int nwg = (d.B + 15) / 16;
   dim3 grid(nwg);
-  const bool ragged = (d.B % 16) != 0, preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
   const bool wide = dense_wide_shape(d);
   const WideBwdWs L = wide ? wide_bwd_layout(d) : WideBwdWs{0, 0, 0, 0, 0};
   float* part = reinterpret_cast<float*>(ws);
@@ -1069,32 +1084,26 @@ void launch_bwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
                        (const float*)p.bias_gate, (const float*)p.bias_update, (const float*)p.zeta,
                        (const float*)p.nu, wide ? dpre : (float*)g.d_x, (float*)g.d_h0, part);
   };
-  // F = 32: W and x stay in the scan.  ND: no input gradient (d_x == NULL: FASTGRNN_FLAG_NO_INPUT_GRAD, which the
-  // entry points admit on this shape only); the variant is chosen here, once per launch, never inside a step.
-  auto narrow = [&](auto nodx_tag) __attribute__((always_inline)) {
-    constexpr bool ND = decltype(nodx_tag)::value;
-    if (d.update_nl == FASTGRNN_NL_QUANT_TANH) {     // fp32, SAVE_PREACT, F = 32 (split_supported)
-      if (ragged) go8(bwd_scan_split_w8<GATE, true, true, false, false, true, ND>); else go8(bwd_scan_split_w8<GATE, true, false, false, false, true, ND>);
-    } else if (d.dtype == FASTGRNN_BF16_IO) {
-      if (ragged) go8(bwd_scan_split_w8<GATE, true, true, true, false, false, ND>); else go8(bwd_scan_split_w8<GATE, true, false, true, false, false, ND>);
-    } else if (preact) {
-      if (ragged) go8(bwd_scan_split_w8<GATE, true, true, false, false, false, ND>); else go8(bwd_scan_split_w8<GATE, true, false, false, false, false, ND>);
-    } else {
-      if (ragged) go8(bwd_scan_split_w8<GATE, false, true, false, false, false, ND>); else go8(bwd_scan_split_w8<GATE, false, false, false, false, false, ND>);
-    }
-  };
-  if (wide && d.dtype == FASTGRNN_BF16_IO) {         // SAVE_PREACT, gates sigmoid / relu / tanh (split_supported)
-    if constexpr (GATE <= FASTGRNN_NL_TANH) {
-      if (ragged) go8(bwd_scan_split_w8<GATE, true, true, true, true>); else go8(bwd_scan_split_w8<GATE, true, false, true, true>);
-    }
-  } else if (wide) {                                 // fp32 sequences; both saved-tensor contracts
-    if (preact) { if (ragged) go8(bwd_scan_split_w8<GATE, true, true, false, true>); else go8(bwd_scan_split_w8<GATE, true, false, false, true>); }
-    else        { if (ragged) go8(bwd_scan_split_w8<GATE, false, true, false, true>); else go8(bwd_scan_split_w8<GATE, false, false, false, true>); }
-  } else if (g.d_x == nullptr) {
-    narrow(std::true_type{});
-  } else {
-    narrow(std::false_type{});
-  }
+  // NOX: a wide layer, W and x leave the scan.  NODX: F = 32 and no input gradient (d_x == NULL:
+  // FASTGRNN_FLAG_NO_INPUT_GRAD, which the entry points admit on this shape only).  The variant is chosen here, once
+  // per launch, never inside a step.
+  const BwdW8 v{d.gate_nl, (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0, (d.B % 16) != 0, d.dtype == FASTGRNN_BF16_IO,
+                wide, d.update_nl == FASTGRNN_NL_QUANT_TANH, !wide && g.d_x == nullptr};
+  const bool launched =
+      pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
+      return pick_bool(v.preact, [&](auto PA_) {
+      return pick_bool(v.bf, [&](auto BF_) {
+      return pick_bool(v.nox, [&](auto NX_) {
+      return pick_bool(v.uq, [&](auto UQ_) {
+      return pick_bool(v.nodx, [&](auto ND_) {
+      return pick_bool(v.ragged, [&](auto RG_) {
+        constexpr int G = decltype(G_)::value;
+        constexpr bool PA = decltype(PA_)::value, BF = decltype(BF_)::value, NX = decltype(NX_)::value,
+                       UQ = decltype(UQ_)::value, ND = decltype(ND_)::value, RG = decltype(RG_)::value;
+        if constexpr (bwd_w8_built(G, PA, BF, NX, UQ, ND)) { go8(bwd_scan_split_w8<G, PA, RG, BF, NX, UQ, ND>); return true; }
+        else return false;
+      }); }); }); }); }); }); });
+  if (!launched) return false;
   const int ntot = 128 * 128 + 128 * 32 + 2 * 128 + 2;
   hipLaunchKernelGGL(reduce_slabs_split, dim3((ntot + 63) / 64), dim3(1024), 0, s, nwg, part, (const float*)p.zeta,
                      (const float*)p.nu, (float*)g.d_u, wide ? (float*)nullptr : (float*)g.d_w, (float*)g.d_bias_gate,
@@ -1114,20 +1123,21 @@ void launch_bwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
       if (bft) bft_transpose_f32(d.B, d.T, xtm, (float*)g.d_x, false, s, d.F);
     }
   }
+  return true;
 }
 
+// run-time values of fwd_scan_split_w8's template parameters
+struct FwdW8 { int gate, aux; bool ragged, bf, f16h, prein, uq, aff; };
 
 // pws != nullptr: PREIN -- the frame product P = X.W^T has been written by rows_gemm to zs (SAVE_PREACT), cs (the
 // reference's outputs) or, when the caller wants no auxiliary tensor, to the workspace pws
 // sg, sc: FASTGRNN_FLAG_PREACT_AFFINE -- the AFF variants (gates sigmoid / relu / tanh, fp32, hs only or h_T alone)
-template <int GATE>
-void launch_fwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                     void* zs, void* cs, hipStream_t s, void* pws = nullptr, const float* sg = nullptr,
-                     const float* sc = nullptr) {
+// false: the library holds no kernel for this call (fwd_w8_built), nothing was launched
+bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
+                void* zs, void* cs, hipStream_t s, void* pws, const float* sg, const float* sc) {
   dim3 grid((d.B + 15) / 16), block(256);
-  const bool ragged = (d.B % 16) != 0;
+  const bool ragged = (d.B % 16) != 0, bf = d.dtype == FASTGRNN_BF16_IO, prein = pws != nullptr;
   const int aux = zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1);
-  const bool prein = pws != nullptr;
   if (prein && aux == 0) zs = pws;
   auto go = [&](auto kern) __attribute__((always_inline)) {
     hipLaunchKernelGGL(kern, grid, block, 0, s, d.T, d.B, row_stride_t(d), row_stride_b(d), (const float*)x,
@@ -1141,100 +1151,38 @@ void launch_fwd_gate(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
                        (const float*)p.u, (const float*)p.bias_gate, (const float*)p.bias_update,
                        (const float*)p.zeta, (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, sg, sc);
   };
-  // fp16 two-plane state product (F16H) only for gates that keep z in [0,1] -- they bound the growth of h to
-  // sigma(nu) per step, and the kernel itself checks h0 (see fwd_scan_split_w8); relu / tanh / quantTanh gates
-  // always run the three-bf16-plane product, as does FASTGRNN_FLAG_FWD_BF16X3 (A/B)
-  constexpr bool BOUNDED = GATE == FASTGRNN_NL_SIGMOID || GATE == FASTGRNN_NL_QUANT_SIGM || GATE == FASTGRNN_NL_QUANT_SIGM4;
-  const bool h16 = BOUNDED && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3);
-  const bool bf = d.dtype == FASTGRNN_BF16_IO;
-  if constexpr (GATE <= FASTGRNN_NL_TANH) {
-    if (sg) {                                        // affine_supported(): fp32, no saved tensors
-      auto aff = [&](auto aux_tag, auto prein_tag) __attribute__((always_inline)) {
-        constexpr int A = decltype(aux_tag)::value;
-        constexpr bool PI = decltype(prein_tag)::value;
-        if constexpr (BOUNDED) {
-          if (h16) {
-            if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, true, PI, false, true>);
-            else        go8(fwd_scan_split_w8<GATE, A, false, false, true, PI, false, true>);
-            return;
-          }
-        }
-        if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, false, PI, false, true>);
-        else        go8(fwd_scan_split_w8<GATE, A, false, false, false, PI, false, true>);
-      };
-      auto aff_in = [&](auto aux_tag) __attribute__((always_inline)) {
-        if (prein) aff(aux_tag, std::true_type{}); else aff(aux_tag, std::false_type{});
-      };
-      if (d.flags & FASTGRNN_FLAG_HS_LAST) aff_in(std::integral_constant<int, 3>{});
-      else aff_in(std::integral_constant<int, 0>{});
-      return;
-    }
-  }
-  auto pick8 = [&](auto aux_tag) __attribute__((always_inline)) {
-    constexpr int A = decltype(aux_tag)::value;
-    if constexpr (A == 0 || A == 2) {
-      if (d.update_nl == FASTGRNN_NL_QUANT_TANH) {   // fp32, no PREIN (split_supported)
-        if constexpr (BOUNDED) {
-          if (h16) { if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, true, false, true>); else go8(fwd_scan_split_w8<GATE, A, false, false, true, false, true>); return; }
-        }
-        if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, false, false, true>); else go8(fwd_scan_split_w8<GATE, A, false, false, false, false, true>);
-        return;
-      }
-    }
-    if constexpr (GATE <= FASTGRNN_NL_TANH && (A == 0 || A == 2)) {
-      if (prein && bf) {                             // wide layer, bf16 hs (P is fp32 whatever the frames are)
-        if constexpr (BOUNDED) {
-          if (h16) {
-            if (ragged) go8(fwd_scan_split_w8<GATE, A, true, true, true, true>); else go8(fwd_scan_split_w8<GATE, A, false, true, true, true>);
-            return;
-          }
-        }
-        if (ragged) go8(fwd_scan_split_w8<GATE, A, true, true, false, true>); else go8(fwd_scan_split_w8<GATE, A, false, true, false, true>);
-        return;
-      }
-    }
-    if (prein) {                                     // fp32 sequences
-      if constexpr (BOUNDED) {
-        if (h16) {
-          if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, true, true>); else go8(fwd_scan_split_w8<GATE, A, false, false, true, true>);
-          return;
-        }
-      }
-      if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, false, true>); else go8(fwd_scan_split_w8<GATE, A, false, false, false, true>);
-      return;
-    }
-    if constexpr (BOUNDED) {
-      if (h16) {
-        if (bf) { if (ragged) go8(fwd_scan_split_w8<GATE, A, true, true, true>); else go8(fwd_scan_split_w8<GATE, A, false, true, true>); }
-        else    { if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, true>); else go8(fwd_scan_split_w8<GATE, A, false, false, true>); }
-        return;
-      }
-    }
-    if (bf) { if (ragged) go8(fwd_scan_split_w8<GATE, A, true, true, false>); else go8(fwd_scan_split_w8<GATE, A, false, true, false>); }
-    else    { if (ragged) go8(fwd_scan_split_w8<GATE, A, true, false, false>); else go8(fwd_scan_split_w8<GATE, A, false, false, false>); }
-  };
-  if (d.flags & FASTGRNN_FLAG_HS_LAST) {             // inference: h_T alone (split_supported() admits aux == 0 only)
-    pick8(std::integral_constant<int, 3>{});
-    return;
-  }
-  if (bf) {                                          // bf16 sequences: hs only or hs + pre-activation
-    if (aux == 2) pick8(std::integral_constant<int, 2>{}); else pick8(std::integral_constant<int, 0>{});
-    return;
-  }
-  if (GATE > FASTGRNN_NL_TANH || (d.flags & (FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_FWD_BF16X3)) ||
-      !(d.flags & FASTGRNN_FLAG_FWD_4WAVE)) {        // default: the 8-wave shape
-    if (aux == 1)      pick8(std::integral_constant<int, 1>{});
-    else if (aux == 2) pick8(std::integral_constant<int, 2>{});
-    else               pick8(std::integral_constant<int, 0>{});
-    return;
-  }
-  if constexpr (GATE <= FASTGRNN_NL_TANH) {          // the 4-wave kernel knows the reference's three gates only
-    if (aux == 1)      { if (ragged) go(fwd_scan_split<GATE, 1, true>); else go(fwd_scan_split<GATE, 1, false>); }
-    else if (aux == 2) { if (ragged) go(fwd_scan_split<GATE, 2, true>); else go(fwd_scan_split<GATE, 2, false>); }
-    else               { if (ragged) go(fwd_scan_split<GATE, 0, true>); else go(fwd_scan_split<GATE, 0, false>); }
-  }
+  // FASTGRNN_FLAG_FWD_4WAVE (A/B): the 4-wave kernel knows the reference's three gates, fp32 time- or batch-major
+  // sequences and the plain cell only; every gate, aux and batch remainder of those is built
+  if ((d.flags & FASTGRNN_FLAG_FWD_4WAVE) && !sg && !bf && d.gate_nl <= FASTGRNN_NL_TANH &&
+      !(d.flags & (FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_FWD_BF16X3)))
+    return pick_int<0, 1, 2>(d.gate_nl, [&](auto G_) {
+           return pick_int<0, 1, 2>(aux, [&](auto A_) {
+           return pick_bool(ragged, [&](auto RG_) {
+             go(fwd_scan_split<decltype(G_)::value, decltype(A_)::value, decltype(RG_)::value>);
+             return true;
+           }); }); });
+  // default: the 8-wave shape.  aux 3 = h_T alone (inference).  fp16 two-plane state product (F16H) only for gates
+  // that keep z in [0,1] -- they bound the growth of h to sigma(nu) per step, and the kernel itself checks h0 (see
+  // fwd_scan_split_w8); relu / tanh / quantTanh gates always run the three-bf16-plane product, as does
+  // FASTGRNN_FLAG_FWD_BF16X3 (A/B).  PREIN: wide layer (P is fp32 whatever the frames are).
+  const FwdW8 v{d.gate_nl, (d.flags & FASTGRNN_FLAG_HS_LAST) ? 3 : aux, ragged, bf,
+                gate_bounds_state(d.gate_nl) && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3), prein,
+                d.update_nl == FASTGRNN_NL_QUANT_TANH, sg != nullptr};
+  return pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
+         return pick_int<0, 1, 2, 3>(v.aux, [&](auto A_) {
+         return pick_bool(v.bf, [&](auto BF_) {
+         return pick_bool(v.f16h, [&](auto FH_) {
+         return pick_bool(v.prein, [&](auto PI_) {
+         return pick_bool(v.uq, [&](auto UQ_) {
+         return pick_bool(v.aff, [&](auto AF_) {
+         return pick_bool(v.ragged, [&](auto RG_) {
+           constexpr int G = decltype(G_)::value, A = decltype(A_)::value;
+           constexpr bool BF = decltype(BF_)::value, FH = decltype(FH_)::value, PI = decltype(PI_)::value,
+                          UQ = decltype(UQ_)::value, AF = decltype(AF_)::value, RG = decltype(RG_)::value;
+           if constexpr (fwd_w8_built(G, A, BF, FH, PI, UQ, AF)) { go8(fwd_scan_split_w8<G, A, RG, BF, FH, PI, UQ, AF>); return true; }
+           else return false;
+         }); }); }); }); }); }); }); });
 }
-
 
 }  // namespace
 
@@ -1245,15 +1193,11 @@ bool split_supported(const fastgrnn_desc& d, int direction) {
     return false;
   if (d.update_nl == FASTGRNN_NL_QUANT_TANH) {
     // quantTanh update (rnn.py:57-58,292-293): dense H = 128 / F = 32, fp32, hs only or the one-saved-tensor contract
-    const bool shape = d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && d.dtype == FASTGRNN_F32 &&
-                       (double)d.T * d.B * 128 * 4.0 < 4294967296.0;
+    const bool shape = d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && d.dtype == FASTGRNN_F32 && seq_fits32(d);
     if (!shape || (d.flags & (FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_FWD_4WAVE))) return false;
     return direction == 0 || (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
   }
-  // the 8-wave scans address a step's rows with 32-bit byte offsets from a scalar base: whole sequence tensors
-  // below 2^32 bytes (B = 4096, T = 99, H = 128 is 2e8; anything larger goes to the other paths)
-  const bool fits32 = (double)d.T * d.B * (d.H > d.F ? d.H : d.F) * 4.0 < 4294967296.0;
-  const bool dense = d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && fits32;
+  const bool dense = d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && seq_fits32(d);
   const bool preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
   if (h256_shape(d)) return h256_supported(d, direction);      // dense H = 256 / F = 32: kernels_h256.hip
   if (lowrank_shape(d)) return lowrank_supported(d, direction); // H = 256 / F = 32, ranks <= 16: kernels_lowrank.hip
@@ -1292,8 +1236,7 @@ bool affine_supported(const fastgrnn_desc& d) {
   // [B,F,T] frames: only where the frame product is a GEMM of its own (the scaled F = 32 scans read time-major frames)
   if ((d.flags & FASTGRNN_FLAG_X_BFT) && !((h256_shape(d) && d.F != 32) || dense_wide_shape(d))) return false;
   if (h256_shape(d)) return h256_supported(d, 0);
-  const bool fits32 = (double)d.T * d.B * (d.H > d.F ? d.H : d.F) * 4.0 < 4294967296.0;
-  return (d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && fits32) || dense_wide_shape(d);
+  return (d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && seq_fits32(d)) || dense_wide_shape(d);
 }
 
 size_t split_forward_ws(const fastgrnn_desc& d) {
@@ -1327,14 +1270,7 @@ int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
   if (h256_shape(d)) return h256_backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s);
   if (lowrank_shape(d)) return lowrank_backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s);
   if (densified_shape(d)) return densified_backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s);
-  switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: launch_bwd_gate<FASTGRNN_NL_SIGMOID>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    case FASTGRNN_NL_RELU: launch_bwd_gate<FASTGRNN_NL_RELU>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    case FASTGRNN_NL_TANH: launch_bwd_gate<FASTGRNN_NL_TANH>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    case FASTGRNN_NL_QUANT_TANH: launch_bwd_gate<FASTGRNN_NL_QUANT_TANH>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    case FASTGRNN_NL_QUANT_SIGM: launch_bwd_gate<FASTGRNN_NL_QUANT_SIGM>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-    default: launch_bwd_gate<FASTGRNN_NL_QUANT_SIGM4>(d, p, ghs, x, hs, zs, cs, h0, g, ws, s); break;
-  }
+  if (!launch_bwd_w8(d, p, ghs, x, hs, zs, cs, h0, g, ws, s)) return FASTGRNN_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 
@@ -1361,14 +1297,7 @@ int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
         : rows_gemm((size_t)d.T * d.B, 128, d.F, false, x, (const float*)p.w, pws, d.dtype == FASTGRNN_BF16_IO, false, s);
     if (st != FASTGRNN_OK) return st;
   }
-  switch (d.gate_nl) {
-    case FASTGRNN_NL_SIGMOID: launch_fwd_gate<FASTGRNN_NL_SIGMOID>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
-    case FASTGRNN_NL_RELU: launch_fwd_gate<FASTGRNN_NL_RELU>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
-    case FASTGRNN_NL_TANH: launch_fwd_gate<FASTGRNN_NL_TANH>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
-    case FASTGRNN_NL_QUANT_TANH: launch_fwd_gate<FASTGRNN_NL_QUANT_TANH>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
-    case FASTGRNN_NL_QUANT_SIGM: launch_fwd_gate<FASTGRNN_NL_QUANT_SIGM>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
-    default: launch_fwd_gate<FASTGRNN_NL_QUANT_SIGM4>(d, p, x, h0, hs, zs, cs, s, pws, sg, sc); break;
-  }
+  if (!launch_fwd(d, p, x, h0, hs, zs, cs, s, pws, sg, sc)) return FASTGRNN_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 

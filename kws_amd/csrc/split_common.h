@@ -5,6 +5,7 @@
 // users are written to.
 #pragma once
 #include "common.h"
+#include "variant_pick.h"
 #include <type_traits>
 #include <utility>
 
@@ -281,6 +282,15 @@ __device__ __forceinline__ u32x4 tr_frag(unsigned lds_byte_addr, int rowb) {
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_s16x4*>((size_t)(lds_byte_addr + 4 * rowb)));
   const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(u32x4, v);
+}
+
+// row (t, b) of a [T,B,*] / [B,T,*] tensor = t * row_stride_t + b * row_stride_b
+static inline int row_stride_t(const fastgrnn_desc& d) { return (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) ? 1 : d.B; }
+static inline int row_stride_b(const fastgrnn_desc& d) { return (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) ? d.T : 1; }
+// the 8-wave scans address a step's rows with 32-bit byte offsets from a scalar base: whole sequence tensors
+// below 2^32 bytes (B = 4096, T = 99, H = 128 is 2e8; anything larger goes to the other paths)
+static inline bool seq_fits32(const fastgrnn_desc& d) {
+  return (double)d.T * d.B * (d.H > d.F ? d.H : d.F) * 4.0 < 4294967296.0;
 }
 
 }  // namespace
