@@ -260,6 +260,10 @@ const char *fastgrnn_hip_status_string(int status);
  *                                 nonlinearity codes) runs on path 0, time-major without FASTGRNN_FLAG_HS_LAST.
  *   FASTGRNN_FLAG_ZERO_EXTEND     every other fp32 / bf16-sequence cell with H <= 256 whose zero-padded shape (Hp, Fp)
  *                                 is one of the above: run as that shape (copies around the scans, see the flag).
+ *   fastgrnn_hip_forward_windows  (inference; utterances are windows of a shared frame pool, see below) fp32, dense,
+ *                                 gates sigmoid / relu / tanh, update tanh, plain or FASTGRNN_FLAG_PREACT_AFFINE:
+ *                                 H=128 with F=32, H=256 with F=32, H=256 with F=64; hs time-major, batch-major or
+ *                                 (FASTGRNN_FLAG_HS_LAST) h_T alone.  Nothing else: ask fastgrnn_hip_windows_supported.
  * Under FASTGRNN_FLAG_SAVE_PREACT a factorised forward with both ranks in 1..16 also writes, through c_s, the rank-space vector
  * [U1.h_{t-1} | W1.x_t] as a time-major fp32 [T*B, 32] tensor (each half zero-extended to 16 columns) that the
  * backward takes back through c_s (with z_s, the pre-activation): its factor gradients are contracted inside the
@@ -330,6 +334,38 @@ int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc *d, const fastgrnn_pa
                                        const void *gate_scale, const void *update_scale,
                                        const void *x, const void *h0, void *hs,
                                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* forward_windows -- inference forward over OVERLAPPING utterances: utterance b is the d->T consecutive rows that
+ * start at row x_start[b] of a shared frame pool x_pool:[pool_rows, F] (fp32, contiguous); at step t it reads pool row
+ * x_start[b] + t.  This is how the reference's detector uses the model (inferencetry.py:165-227: a 99-frame window
+ * slid over continuous audio, every window scored from a zero state): d->B windows at hop h are x_start[w] = w * h,
+ * with no T/h-fold copy of the stream.  Starts may overlap, repeat and come in any order (random crops of longer
+ * clips are the same call).  x_start: [B] int32 on the device; the library cannot look at its contents:
+ *   0 <= x_start[b] <= pool_rows - T  for every b  IS THE CALLER'S OBLIGATION (a start outside reads outside the pool).
+ * h0:[B,H]; hs follows d->flags as in forward_unroll_affine: [T,B,H], [B,T,H] (FASTGRNN_FLAG_BATCH_MAJOR) or [B,H]
+ * (FASTGRNN_FLAG_HS_LAST).  Nothing is saved for a backward (the gradient w.r.t. overlapping windows is a scatter-add
+ * and is not built).  gate_scale / update_scale: both NULL for the plain cell; both non-NULL ([H] fp32) for the
+ * eval-mode BatchNorm arithmetic, and d->flags must then carry FASTGRNN_FLAG_PREACT_AFFINE (and only then).
+ * Cells (fastgrnn_hip_windows_supported answers 1): fp32, dense, gate sigmoid / relu / tanh, update tanh, and
+ *   H=128 with F=32;  H=256 with F=32;  H=256 with F=64
+ * with no flag other than BATCH_MAJOR, HS_LAST and PREACT_AFFINE.  F=32: the scans read the pool in place.  F=64: the
+ * frame product X.W^T is computed ONCE per pool row, P_pool[pool_rows, 256] in the workspace (pool_rows*1024 bytes
+ * instead of T*B*1024), and the scan reads row x_start[b] + t of it.  Everything else -- other shapes, bf16
+ * sequences, fp64, factorised operands, quantised codes, FASTGRNN_FLAG_SAVE_PREACT / X_BFT / ZERO_EXTEND / BN_TRAIN /
+ * FORCE_* and the remaining flags -- answers FASTGRNN_ERR_UNSUPPORTED (gather the windows and call forward_unroll).
+ * Errors otherwise: FASTGRNN_ERR_NULL_POINTER (x_pool, x_start, h0, hs, a parameter; exactly one scale NULL; the flag
+ * without scales), FASTGRNN_ERR_BAD_SHAPE (pool_rows < T, pool_rows >= 2^31, size overflow), FASTGRNN_ERR_WORKSPACE.
+ * Workspace: fastgrnn_hip_forward_windows_workspace_bytes(d, pool_rows) -- 0 for H=128; for H=256 512 KB of flag
+ * words (one per workgroup of the largest batch the shape takes) plus, for F=64, P_pool: a function of pool_rows
+ * alone, not of d->B or d->T, so one allocation serves every set of windows cut from a pool; 0 for an unsupported
+ * descriptor. */
+int fastgrnn_hip_windows_supported(const fastgrnn_desc *d);            /* 1 / 0 */
+size_t fastgrnn_hip_forward_windows_workspace_bytes(const fastgrnn_desc *d, size_t pool_rows);
+int fastgrnn_hip_forward_windows(const fastgrnn_desc *d, const fastgrnn_params *p,
+                                 const void *gate_scale, const void *update_scale,
+                                 const void *x_pool, size_t pool_rows, const int32_t *x_start,
+                                 const void *h0, void *hs,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* backward_unroll -- replaces fastgrnn_unroll_backward (fastgrnn_cuda.cpp:182-232 ->
  * .cu:417-557).  grad_hs:[T,B,H] is dL/d(hs[t]) for every t; z_s,c_s are the

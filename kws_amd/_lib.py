@@ -44,6 +44,7 @@ EXPORTS = (
     "fastgrnn_hip_bn_train_supported", "fastgrnn_hip_bn_train_forward_workspace_bytes",
     "fastgrnn_hip_bn_train_backward_workspace_bytes", "fastgrnn_hip_bn_train_forward", "fastgrnn_hip_bn_train_backward",
     "fastgrnn_hip_zero_extend_plan", "fastgrnn_hip_plan",
+    "fastgrnn_hip_windows_supported", "fastgrnn_hip_forward_windows_workspace_bytes", "fastgrnn_hip_forward_windows",
 )
 
 
@@ -157,6 +158,12 @@ def load():
     lib.fastgrnn_hip_zero_extend_plan.argtypes = [DP, C.POINTER(ZextPlan)]
     lib.fastgrnn_hip_plan.restype = i32
     lib.fastgrnn_hip_plan.argtypes = [DP, C.POINTER(Plan)]
+    lib.fastgrnn_hip_windows_supported.restype = i32
+    lib.fastgrnn_hip_windows_supported.argtypes = [DP]
+    lib.fastgrnn_hip_forward_windows_workspace_bytes.restype = sz
+    lib.fastgrnn_hip_forward_windows_workspace_bytes.argtypes = [DP, sz]
+    lib.fastgrnn_hip_forward_windows.restype = i32
+    lib.fastgrnn_hip_forward_windows.argtypes = [DP, PP, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]
     if lib.fastgrnn_hip_abi_version() != ABI_VERSION:
         raise FastGRNNLibraryError("ABI version mismatch: library %d, binding %d"
                                    % (lib.fastgrnn_hip_abi_version(), ABI_VERSION))

@@ -36,7 +36,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib, fastgrnn_cuda
-from .rnn import NON_LINEARITY, _resolve_device, _sparsify, _sparsify_with_support
+from .rnn import NON_LINEARITY, _resolve_device, _sparsify, _sparsify_with_support, gather_windows
 
 _TRAINING_MSG = ("FastGRNNBatchNorm runs in eval mode only (training=False / model.eval()): training-mode BatchNorm "
                  "normalises every frame with the statistics of the whole batch at that frame, which needs a "
@@ -274,3 +274,33 @@ class FastGRNNBatchNorm(nn.Module):
         if bf and not in_place and not last_state:
             hs = hs.transpose(0, 1)
         return hs
+
+    @torch.no_grad()
+    def forward_windows(self, pool, starts, T, hiddenState=None, last_state=False, check=True, training=False):
+        """Eval-mode inference over windows of a shared frame pool (``FastGRNNCUDA.forward_windows``): utterance ``b``
+        is the ``T`` consecutive rows of ``pool:[R,F]`` from row ``starts[b]`` on.  Returns what ``forward(...,
+        training=False)`` returns for the gathered batch, without a graph; the pool is read in place where the windowed
+        scans hold the cell (``fastgrnn_cuda.windows_supported``), gathered elsewhere."""
+        if training:
+            raise NotImplementedError(_TRAINING_MSG)
+        cell = self.cell
+        dev = cell.W.device
+        if dev.type != "cuda":
+            raise RuntimeError("FastGRNNBatchNorm.forward_windows runs on the GPU only (parameters are on %s)" % dev)
+        pool, starts = pool.to(dev), starts.to(dev)
+        if pool.dtype != cell.W.dtype:
+            raise RuntimeError("pool dtype %s differs from the parameters' %s" % (pool.dtype, cell.W.dtype))
+        B, H, T = starts.numel(), cell._hidden_size, int(T)
+        h0 = torch.zeros(B, H, dtype=pool.dtype, device=dev) if hiddenState is None else \
+            hiddenState.to(dev).reshape(B, H).contiguous()
+        bm = self.batch_first is True
+        flags = (_lib.FLAG_BATCH_MAJOR if bm else 0) | (_lib.FLAG_HS_LAST if last_state else 0) | _lib.FLAG_PREACT_AFFINE
+        if pool.dim() == 2 and fastgrnn_cuda.windows_supported(T, B, pool.shape[1], H, 0, 0, cell._gate_code,
+                                                               cell._update_code, pool.dtype, flags):
+            w, u, bg, bu, sg, sc = cell._folded()
+            return fastgrnn_cuda.forward_windows(pool.contiguous(), starts, T, w, u, bg, bu, cell.zeta, cell.nu, h0,
+                                                 cell._gate_code, sg, sc, batch_major=bm, last_state=last_state,
+                                                 update_non_linearity=cell._update_code, check=check)
+        windows = gather_windows(pool, starts, T, check)                       # [B,T,F]
+        return FastGRNNBatchNorm.forward(self, windows if bm else windows.transpose(0, 1).contiguous(),
+                                         hiddenState=h0, training=False, last_state=last_state)

@@ -172,6 +172,12 @@ class FastGRNNBatchNormCUDA(FastGRNNBatchNorm):
             return hs[:, -1] if bf else hs[-1]
         return hs
 
+    def forward_windows(self, pool, starts, T, hiddenState=None, last_state=False, check=True, training=False):
+        """``FastGRNNBatchNorm.forward_windows`` (eval mode only), folding again on every call as ``forward`` does."""
+        self.cell._fold_key = None
+        return super().forward_windows(pool, starts, T, hiddenState=hiddenState, last_state=last_state, check=check,
+                                       training=training)
+
     def _torch_ops(self, x, h0, bf):
         """The reference formula per frame in torch ops (rnn.py:373-414 under BaseRNN, rnn.py:588-668)."""
         cell = self.cell

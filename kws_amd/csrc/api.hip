@@ -162,6 +162,12 @@ int check_bn_train(const fastgrnn_desc* d, const fastgrnn_params* p, const fastg
   return FASTGRNN_OK;
 }
 
+// fastgrnn_hip_forward_windows runs d on the windowed scans (flags outside the three it knows, FASTGRNN_FLAG_ZERO_EXTEND
+// and NO_INPUT_GRAD among them, are refused: judged on d, not on r->u)
+bool windows_route(const fastgrnn_desc* d, route* r) {
+  return resolve(d, r) == FASTGRNN_OK && r->path[0] == 2 && windows_supported(*d);
+}
+
 // r->u runs on the training kernels
 bool bn_train_route(const fastgrnn_desc* d, route* r) {
   return resolve(d, r) == FASTGRNN_OK && (r->u.flags & FASTGRNN_FLAG_BN_TRAIN) && bn_train_supported(r->u);
@@ -265,6 +271,40 @@ int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc* dz, const fastgrnn_p
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (r.path[0] == 2) return split_forward(*d, *p, x, h0, hs, nullptr, nullptr, workspace, s, gate_scale, update_scale);
   return generic_forward(*d, *p, x, h0, hs, nullptr, nullptr, workspace, s, gate_scale, update_scale);
+}
+
+int fastgrnn_hip_windows_supported(const fastgrnn_desc* d) {
+  route r;
+  return windows_route(d, &r) ? 1 : 0;
+}
+
+size_t fastgrnn_hip_forward_windows_workspace_bytes(const fastgrnn_desc* d, size_t pool_rows) {
+  route r;
+  if (!windows_route(d, &r) || pool_rows > (size_t)INT32_MAX) return 0;
+  return windows_ws(*d, pool_rows);
+}
+
+int fastgrnn_hip_forward_windows(const fastgrnn_desc* d, const fastgrnn_params* p, const void* gate_scale,
+                                 const void* update_scale, const void* x_pool, size_t pool_rows, const int32_t* x_start,
+                                 const void* h0, void* hs, void* workspace, size_t workspace_bytes, void* stream) {
+  route r;
+  int st = resolve(d, &r);
+  if (st) return st;
+  if ((st = check_params(d, p))) return st;
+  if (!x_pool || !x_start || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
+  const bool affine = (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) != 0;
+  if ((gate_scale == nullptr) != (update_scale == nullptr) || (affine && !gate_scale)) return FASTGRNN_ERR_NULL_POINTER;
+  if (gate_scale && !affine) return FASTGRNN_ERR_UNSUPPORTED;           // scales select the flag's arithmetic
+  // rows are addressed through the int32 starts; element offsets into the pool and its frame product are size_t
+  if (pool_rows < (size_t)d->T || pool_rows > (size_t)INT32_MAX ||
+      (double)pool_rows * (d->H > d->F ? d->H : d->F) > 1099511627776.0)
+    return FASTGRNN_ERR_BAD_SHAPE;
+  if (r.path[0] != 2 || !windows_supported(*d)) return FASTGRNN_ERR_UNSUPPORTED;
+  const size_t need = windows_ws(*d, pool_rows);
+  if ((st = check_ws(workspace, workspace_bytes, need))) return st;
+  const window_src win{x_start, pool_rows};
+  return split_forward(*d, *p, x_pool, h0, hs, nullptr, nullptr, workspace, reinterpret_cast<hipStream_t>(stream),
+                       gate_scale, update_scale, &win);
 }
 
 int fastgrnn_hip_backward_unroll(const fastgrnn_desc* dz, const fastgrnn_params* p, const void* grad_hs,

@@ -79,9 +79,14 @@ bool split_dx_optional(const fastgrnn_desc& d);           // the backward accept
 bool split_dx_skippable(const fastgrnn_desc& d);          // ... under FASTGRNN_FLAG_NO_INPUT_GRAD as well
 // the per-unit scaled forward (sg, sc non-NULL, zs = cs = NULL) on the shapes affine_supported() admits
 bool affine_supported(const fastgrnn_desc& d);
+// fastgrnn_hip_forward_windows: utterance b is the T consecutive rows from row start[b] of a frame pool [rows, F]
+// (x then points at the pool); start: [B] int32 on the device, 0 <= start[b] <= rows - T
+struct window_src { const int32_t* start; size_t rows; };
+bool windows_supported(const fastgrnn_desc& d);                  // the windowed scans hold this cell (path 2 only)
+size_t windows_ws(const fastgrnn_desc& d, size_t pool_rows);
 int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0,
                   void* hs, void* zs, void* cs, void* ws, hipStream_t s, const void* sg = nullptr,
-                  const void* sc = nullptr);
+                  const void* sc = nullptr, const window_src* win = nullptr);
 int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x,
                    const void* hs, const void* zs, const void* cs, const void* h0,
                    const fastgrnn_grads& g, void* ws, hipStream_t s);
@@ -110,7 +115,9 @@ bool h256_supported(const fastgrnn_desc& d, int direction);
 size_t h256_forward_ws(const fastgrnn_desc& d);
 size_t h256_backward_ws(const fastgrnn_desc& d);
 int h256_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                 void* cs, void* ws, hipStream_t s, const float* sg = nullptr, const float* sc = nullptr);
+                 void* cs, void* ws, hipStream_t s, const float* sg = nullptr, const float* sc = nullptr,
+                 const window_src* win = nullptr);
+size_t h256_windows_ws(const fastgrnn_desc& d, size_t pool_rows);
 int h256_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
                   const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s);
 

@@ -50,15 +50,22 @@ constexpr int SLAB2 = 576;                      // floats per workgroup: d_bz[25
 // registers hold no 16 more per lane without scratch (tools/resource_usage.py), so an AFF kernel sizes `smem` for
 // the path its MODE runs: MODE 1 (the fp16 path's 90 624 B) stages both scales in sbias; MODE 0 / 2 stage the update
 // scales there (1 KB) and keep the lane's eight gate scales in registers (loaded once).
+// WIN: utterance b is the Tn consecutive rows from row xstart[b] of a shared pool (fastgrnn_hip_forward_windows):
+// `x` is the frame pool [R,32] or, under PREIN, the frame product of the whole pool P_pool[R,256] -- one GEMM row per
+// frame, not per frame and window.  The lane's base comes from xstart (loaded once, in front of the scan; lanes beyond
+// a ragged batch take utterance B-1's) and the step stride is one pool row, so P no longer follows the strides of hs;
+// hs is written through hsT / hsB as ever.  fp32, the reference's gates, AUX 0 / 3, one state product per gate.
 // The instantiations the library holds (each with RAGGED false and true); launch_fwd builds exactly these.
-constexpr bool fwd_h256_built(int gate, int aux, int mode, bool prein, bool bf, bool aff) {
+constexpr bool fwd_h256_built(int gate, int aux, int mode, bool prein, bool bf, bool aff, bool win = false) {
   const bool ref_gate = gate <= FASTGRNN_NL_TANH;
   if (mode != 0 && !gate_bounds_state(gate)) return false;
+  if (win) return ref_gate && !bf && (aux == 0 || aux == 3) && (mode != 0) == gate_bounds_state(gate);
   if (aff) return ref_gate && !bf && (aux == 0 || aux == 3);
   if (bf) return ref_gate && (aux == 0 || aux == 2);
   return true;
 }
-template <int GATE, int AUX, bool RAGGED, int MODE, bool PREIN = false, bool BF = false, bool AFF = false>
+template <int GATE, int AUX, bool RAGGED, int MODE, bool PREIN = false, bool BF = false, bool AFF = false,
+          bool WIN = false>
 __global__ __launch_bounds__(512) void fwd_scan_h256(
     int Tn, int B, unsigned hsT, unsigned hsB, unsigned xsT, unsigned xsB,
     const float* __restrict__ x, const float* __restrict__ h0,
@@ -66,7 +73,9 @@ __global__ __launch_bounds__(512) void fwd_scan_h256(
     const float* __restrict__ bz, const float* __restrict__ bh,
     const float* __restrict__ zeta, const float* __restrict__ nu,
     float* __restrict__ hs, float* __restrict__ zs, float* __restrict__ cs, unsigned* __restrict__ flags,
-    const float* __restrict__ sg = nullptr, const float* __restrict__ sc = nullptr) {
+    const float* __restrict__ sg = nullptr, const float* __restrict__ sc = nullptr,
+    const int* __restrict__ xstart = nullptr) {
+  static_assert(!(WIN && BF), "WIN: fp32 pool");
   // hsT / hsB: element strides of one step / one utterance in hs, zs, cs (and in P under PREIN, whose rows follow the
   // frames' order); xsT / xsB: the same for x.  Time-major: (B*256, 256) and (B*32, 32); FASTGRNN_FLAG_BATCH_MAJOR:
   // (256, T*256) and (32, T*32) -- rnn.py:812-813 transposes instead.
@@ -223,16 +232,19 @@ __global__ __launch_bounds__(512) void fwd_scan_h256(
   };
   // this lane's value of frame t, as raw bits (a bf16 value is widened when it is published, not here: the conversion
   // would wait for the load at once)
-  const char* xlane = reinterpret_cast<const char*>(x) + ((size_t)xbc * xsB + xf) * (BF ? 2 : 4);
+  // WIN: the utterance's frames are the pool's rows xstart[xbc] + t (one row per step)
+  const char* xlane = reinterpret_cast<const char*>(x) +
+                      (((WIN && !PREIN) ? (size_t)xstart[xbc] * F2 : (size_t)xbc * xsB) + xf) * (BF ? 2 : 4);
   auto load_x = [&](int t) __attribute__((always_inline)) -> unsigned {
     if (BF) return (unsigned)*reinterpret_cast<const unsigned short*>(xlane + (size_t)t * xsT * 2);
-    return *reinterpret_cast<const unsigned*>(xlane + (size_t)t * xsT * 4);
+    return *reinterpret_cast<const unsigned*>(xlane + (size_t)t * (WIN ? (unsigned)F2 : xsT) * 4);
   };
   // PREIN: this lane's eight values of P(t) (rows of lanes beyond a ragged batch: the last utterance's)
-  const float* plane = x + (size_t)bc * hsB + n0;
+  // WIN: P_pool's rows xstart[bc] + t
+  const float* plane = x + ((WIN && PREIN) ? (size_t)xstart[bc] * H2 : (size_t)bc * hsB) + n0;
   auto load_p = [&](int t, f32x4 (&q)[2]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) q[mt] = ld4(plane + (size_t)t * hsT + 16 * mt);
+    for (int mt = 0; mt < 2; ++mt) q[mt] = ld4(plane + (size_t)t * (WIN ? (unsigned)H2 : hsT) + 16 * mt);
   };
   const unsigned lane_hs = (unsigned)b * hsB + n0, lane_bh = (unsigned)b * H2 + n0;   // in a sequence / in a [B,H] tensor
   auto store_step = [&](int t, const f32x4* aux) __attribute__((always_inline)) {   // hown holds h_t
@@ -785,6 +797,9 @@ __global__ __launch_bounds__(1024) void reduce_h256_small(int nwg, const float* 
 }
 
 static inline size_t h256_flag_bytes(const fastgrnn_desc& d) { return align256((size_t)((d.B + 15) / 16) * sizeof(unsigned)); }
+// fastgrnn_hip_forward_windows: the flag words of the largest batch the shape takes (h256_shape: B < 2^21), so that the
+// workspace of a pool depends on its rows alone and one allocation serves every set of windows cut from it
+constexpr size_t H256_WIN_FLAG_BYTES = (size_t)(1 << 21) / 16 * sizeof(unsigned);
 
 struct H256BwdWs { size_t part, dpre, tn, xtm, total; };
 H256BwdWs h256_bwd_layout(const fastgrnn_desc& d) {
@@ -802,11 +817,12 @@ H256BwdWs h256_bwd_layout(const fastgrnn_desc& d) {
 }
 
 // run-time values of fwd_scan_h256's template parameters (MODE: 1 then 2 under f16h, else 0)
-struct FwdH256 { int gate, aux; bool ragged, f16h, prein, bf, aff; };
+struct FwdH256 { int gate, aux; bool ragged, f16h, prein, bf, aff, win; };
 
+// win: x is the frame pool and win->start the utterances' first rows (the WIN variants)
 // false: the library holds no kernel for this call (fwd_h256_built), no scan was launched
 bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                void* cs, void* ws, hipStream_t s, const float* sg, const float* sc) {
+                void* cs, void* ws, hipStream_t s, const float* sg, const float* sc, const window_src* win) {
   dim3 grid((d.B + 15) / 16), block(512);
   unsigned* flags = reinterpret_cast<unsigned*>(ws);
   // FASTGRNN_FLAG_X_BFT: the loader's [B,F,T] frames are transposed into the workspace first (25 us at B = 4096; a
@@ -821,8 +837,10 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
   }
   // a wider input (F = 64 / 128): the batched frame GEMM  P = X . W^T  into the workspace, then the PREIN scan on P
   if (prein) {
-    float* P = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + h256_flag_bytes(d));
-    if (d.flags & FASTGRNN_FLAG_X_BFT)               // (fp32: h256_supported) rows of P land in the order of hs
+    float* P = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + (win ? H256_WIN_FLAG_BYTES : h256_flag_bytes(d)));
+    if (win)                                         // one row of P per pool frame, whatever the windows share
+      rows_gemm(win->rows, H2, d.F, false, x, (const float*)p.w, P, false, false, s);
+    else if (d.flags & FASTGRNN_FLAG_X_BFT)               // (fp32: h256_supported) rows of P land in the order of hs
       rows_gemm_bft(d.B, d.T, H2, d.F, (const float*)x, (const float*)p.w, P, bm_hs ? 1 : (size_t)d.B, bm_hs ? (size_t)d.T : 1, s);
     else
       rows_gemm((size_t)d.T * d.B, H2, d.F, false, x, (const float*)p.w, P, bf, false, s);   // (bf16 frames, fp32 P)
@@ -836,29 +854,30 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
   auto go = [&](auto kern) __attribute__((always_inline)) {
     hipLaunchKernelGGL(kern, grid, block, 0, s, d.T, d.B, hsT, hsB, xsT, xsB, (const float*)x, (const float*)h0, (const float*)p.w,
                        (const float*)p.u, (const float*)p.bias_gate, (const float*)p.bias_update, (const float*)p.zeta,
-                       (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, flags, sg, sc);
+                       (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, flags, sg, sc, win ? win->start : nullptr);
   };
   // fp16 two-plane state product only for gates that keep z in [0,1] (see fwd_scan_split_w8): the fp16 launch, then
   // the bf16 one for the workgroups it turned down; FWD_BF16X3: A/B
   const int aux = (d.flags & FASTGRNN_FLAG_HS_LAST) ? 3 : (zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1));
   const FwdH256 v{d.gate_nl, aux, (d.B % 16) != 0, gate_bounds_state(d.gate_nl) && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3),
-                  prein, bf, sg != nullptr};
+                  prein, bf, sg != nullptr, win != nullptr};
   return pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
          return pick_int<0, 1, 2, 3>(v.aux, [&](auto A_) {
          return pick_bool(v.f16h, [&](auto FH_) {
          return pick_bool(v.prein, [&](auto PI_) {
          return pick_bool(v.bf, [&](auto BF_) {
          return pick_bool(v.aff, [&](auto AF_) {
+         return pick_bool(v.win, [&](auto WN_) {
          return pick_bool(v.ragged, [&](auto RG_) {
            constexpr int G = decltype(G_)::value, A = decltype(A_)::value;
            constexpr bool FH = decltype(FH_)::value, PI = decltype(PI_)::value, BF = decltype(BF_)::value,
-                          AF = decltype(AF_)::value, RG = decltype(RG_)::value;
-           if constexpr (fwd_h256_built(G, A, FH ? 1 : 0, PI, BF, AF)) {
-             if constexpr (FH) { go(fwd_scan_h256<G, A, RG, 1, PI, BF, AF>); go(fwd_scan_h256<G, A, RG, 2, PI, BF, AF>); }
-             else go(fwd_scan_h256<G, A, RG, 0, PI, BF, AF>);
+                          AF = decltype(AF_)::value, WN = decltype(WN_)::value, RG = decltype(RG_)::value;
+           if constexpr (fwd_h256_built(G, A, FH ? 1 : 0, PI, BF, AF, WN)) {
+             if constexpr (FH) { go(fwd_scan_h256<G, A, RG, 1, PI, BF, AF, WN>); go(fwd_scan_h256<G, A, RG, 2, PI, BF, AF, WN>); }
+             else go(fwd_scan_h256<G, A, RG, 0, PI, BF, AF, WN>);
              return true;
            } else return false;
-         }); }); }); }); }); }); });
+         }); }); }); }); }); }); }); });
 }
 
 // run-time values of bwd_scan_h256's template parameters
@@ -952,10 +971,15 @@ size_t h256_forward_ws(const fastgrnn_desc& d) {
          (d.F != F2 ? align256((size_t)d.T * d.B * H2 * 4) : 0);
 }
 
+// the flag words + for F = 64 the frame product of the pool, P_pool[R, 256]
+size_t h256_windows_ws(const fastgrnn_desc& d, size_t pool_rows) {
+  return H256_WIN_FLAG_BYTES + (d.F != F2 ? align256(pool_rows * H2 * 4) : 0);
+}
+
 int h256_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                 void* cs, void* ws, hipStream_t s, const float* sg, const float* sc) {
+                 void* cs, void* ws, hipStream_t s, const float* sg, const float* sc, const window_src* win) {
   if (!ws) return FASTGRNN_ERR_WORKSPACE;
-  if (!launch_fwd(d, p, x, h0, hs, zs, cs, ws, s, sg, sc)) return FASTGRNN_ERR_UNSUPPORTED;
+  if (!launch_fwd(d, p, x, h0, hs, zs, cs, ws, s, sg, sc, win)) return FASTGRNN_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 

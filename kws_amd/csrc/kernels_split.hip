@@ -235,25 +235,32 @@ constexpr int W8_ROWX = 80;             // bytes per utterance row of a 32-wide 
 // sc are read only here (two more f32x4 beside bzv / bhv).  The fp16 state product stays eligible: the gate is still
 // z in [0,1] for the gates F16H is instantiated for, so the bound on h above holds, and the rows of u carry the BN
 // scales, which the per-wave power-of-two pre-scale of U absorbs like any other row magnitude.
+// WIN: utterance b is the Tn consecutive rows from row xstart[b] of a shared frame pool x:[R,F]
+// (fastgrnn_hip_forward_windows: overlapping windows of a stream, scored in place).  Only the lane's frame base and the
+// step stride differ: the index is loaded once in front of the scan and lanes beyond a ragged batch take utterance
+// B-1's.  fp32 frames, the reference's gates, hs only or h_T alone, with and without AFF; one state product per gate.
 // The instantiations the library holds (each with RAGGED false and true); launch_fwd_w8 builds exactly these.
-constexpr bool fwd_w8_built(int gate, int aux, bool bf, bool f16h, bool prein, bool uq, bool aff) {
+constexpr bool fwd_w8_built(int gate, int aux, bool bf, bool f16h, bool prein, bool uq, bool aff, bool win = false) {
   const bool ref_gate = gate <= FASTGRNN_NL_TANH;
   if (f16h && !gate_bounds_state(gate)) return false;
+  if (win) return ref_gate && !bf && !prein && !uq && (aux == 0 || aux == 3) && f16h == gate_bounds_state(gate);
   if (aff) return ref_gate && !bf && !uq && (aux == 0 || aux == 3);
   if (uq) return !bf && !prein && (aux == 0 || aux == 2);
   if (bf && prein) return ref_gate && (aux == 0 || aux == 2);
   return true;
 }
 template <int GATE, int AUX, bool RAGGED, bool BF = false, bool F16H = true, bool PREIN = false, bool UQ = false,
-          bool AFF = false>
+          bool AFF = false, bool WIN = false>
 __global__ __launch_bounds__(512) void fwd_scan_split_w8(
     int Tn, int B, int rsT, int rsB, int mode, const float* __restrict__ x, const float* __restrict__ h0,
     const float* __restrict__ w, const float* __restrict__ u,
     const float* __restrict__ bz, const float* __restrict__ bh,
     const float* __restrict__ zeta, const float* __restrict__ nu,
     float* __restrict__ hs, float* __restrict__ zs, float* __restrict__ cs,
-    const float* __restrict__ sg = nullptr, const float* __restrict__ sc = nullptr) {
+    const float* __restrict__ sg = nullptr, const float* __restrict__ sc = nullptr,
+    const int* __restrict__ xstart = nullptr) {
   constexpr int H = 128, F = 32, KS = H / 32;
+  static_assert(!(WIN && (PREIN || BF)), "WIN: fp32 frames of a 32-feature pool");
   __shared__ __attribute__((aligned(16))) unsigned char hpl[2][3][16 * W8_ROWH];
   __shared__ __attribute__((aligned(16))) unsigned char xpl[PREIN ? 1 : 2][3][PREIN ? 16 : 16 * W8_ROWX];
   float* const pbuf = (AUX == 1) ? cs : zs;        // PREIN: where P lives
@@ -364,9 +371,10 @@ __global__ __launch_bounds__(512) void fwd_scan_split_w8(
     *reinterpret_cast<unsigned short*>(&xpl[buf][2][off]) = s2;
   };
   // x is [T,B,F] / [B,T,F] (rsT, rsB) or, with FASTGRNN_FLAG_X_BFT, the trainer's [B,F,T]: this lane's value of
-  // frame t is x[xbase + t * xstep]
-  const size_t xbase = xbft ? ((size_t)xbc * F + xf) * Tn : (size_t)xbc * rsB * F + xf;
-  const size_t xstep = xbft ? 1 : (size_t)rsT * F;
+  // frame t is x[xbase + t * xstep].  WIN: x is the frame pool and the utterance starts at its row xstart[xbc]
+  const size_t xbase = WIN ? (size_t)xstart[xbc] * F + xf
+                           : (xbft ? ((size_t)xbc * F + xf) * Tn : (size_t)xbc * rsB * F + xf);
+  const size_t xstep = WIN ? (size_t)F : (xbft ? 1 : (size_t)rsT * F);
   auto load_x = [&](int t) __attribute__((always_inline)) {
     const size_t e = xbase + (size_t)t * xstep;
     return BF ? bf16_to_f32(reinterpret_cast<const unsigned short*>(x)[e]) : x[e];
@@ -1127,14 +1135,16 @@ bool launch_bwd_w8(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
 }
 
 // run-time values of fwd_scan_split_w8's template parameters
-struct FwdW8 { int gate, aux; bool ragged, bf, f16h, prein, uq, aff; };
+struct FwdW8 { int gate, aux; bool ragged, bf, f16h, prein, uq, aff, win; };
 
 // pws != nullptr: PREIN -- the frame product P = X.W^T has been written by rows_gemm to zs (SAVE_PREACT), cs (the
 // reference's outputs) or, when the caller wants no auxiliary tensor, to the workspace pws
 // sg, sc: FASTGRNN_FLAG_PREACT_AFFINE -- the AFF variants (gates sigmoid / relu / tanh, fp32, hs only or h_T alone)
+// win: x is the frame pool and win->start the utterances' first rows (the WIN variants)
 // false: the library holds no kernel for this call (fwd_w8_built), nothing was launched
 bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                void* zs, void* cs, hipStream_t s, void* pws, const float* sg, const float* sc) {
+                void* zs, void* cs, hipStream_t s, void* pws, const float* sg, const float* sc,
+                const window_src* win = nullptr) {
   dim3 grid((d.B + 15) / 16), block(256);
   const bool ragged = (d.B % 16) != 0, bf = d.dtype == FASTGRNN_BF16_IO, prein = pws != nullptr;
   const int aux = zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1);
@@ -1149,11 +1159,12 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
     hipLaunchKernelGGL(kern, grid, dim3(512), 0, s, d.T, d.B, row_stride_t(d), row_stride_b(d),
                        (d.flags & FASTGRNN_FLAG_X_BFT) ? 1 : 0, (const float*)x, (const float*)h0, (const float*)p.w,
                        (const float*)p.u, (const float*)p.bias_gate, (const float*)p.bias_update,
-                       (const float*)p.zeta, (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, sg, sc);
+                       (const float*)p.zeta, (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, sg, sc,
+                       win ? win->start : nullptr);
   };
   // FASTGRNN_FLAG_FWD_4WAVE (A/B): the 4-wave kernel knows the reference's three gates, fp32 time- or batch-major
   // sequences and the plain cell only; every gate, aux and batch remainder of those is built
-  if ((d.flags & FASTGRNN_FLAG_FWD_4WAVE) && !sg && !bf && d.gate_nl <= FASTGRNN_NL_TANH &&
+  if ((d.flags & FASTGRNN_FLAG_FWD_4WAVE) && !win && !sg && !bf && d.gate_nl <= FASTGRNN_NL_TANH &&
       !(d.flags & (FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_FWD_BF16X3)))
     return pick_int<0, 1, 2>(d.gate_nl, [&](auto G_) {
            return pick_int<0, 1, 2>(aux, [&](auto A_) {
@@ -1167,7 +1178,7 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
   // FASTGRNN_FLAG_FWD_BF16X3 (A/B).  PREIN: wide layer (P is fp32 whatever the frames are).
   const FwdW8 v{d.gate_nl, (d.flags & FASTGRNN_FLAG_HS_LAST) ? 3 : aux, ragged, bf,
                 gate_bounds_state(d.gate_nl) && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3), prein,
-                d.update_nl == FASTGRNN_NL_QUANT_TANH, sg != nullptr};
+                d.update_nl == FASTGRNN_NL_QUANT_TANH, sg != nullptr, win != nullptr};
   return pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
          return pick_int<0, 1, 2, 3>(v.aux, [&](auto A_) {
          return pick_bool(v.bf, [&](auto BF_) {
@@ -1175,13 +1186,15 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
          return pick_bool(v.prein, [&](auto PI_) {
          return pick_bool(v.uq, [&](auto UQ_) {
          return pick_bool(v.aff, [&](auto AF_) {
+         return pick_bool(v.win, [&](auto WN_) {
          return pick_bool(v.ragged, [&](auto RG_) {
            constexpr int G = decltype(G_)::value, A = decltype(A_)::value;
            constexpr bool BF = decltype(BF_)::value, FH = decltype(FH_)::value, PI = decltype(PI_)::value,
-                          UQ = decltype(UQ_)::value, AF = decltype(AF_)::value, RG = decltype(RG_)::value;
-           if constexpr (fwd_w8_built(G, A, BF, FH, PI, UQ, AF)) { go8(fwd_scan_split_w8<G, A, RG, BF, FH, PI, UQ, AF>); return true; }
+                          UQ = decltype(UQ_)::value, AF = decltype(AF_)::value, WN = decltype(WN_)::value,
+                          RG = decltype(RG_)::value;
+           if constexpr (fwd_w8_built(G, A, BF, FH, PI, UQ, AF, WN)) { go8(fwd_scan_split_w8<G, A, RG, BF, FH, PI, UQ, AF, WN>); return true; }
            else return false;
-         }); }); }); }); }); }); }); });
+         }); }); }); }); }); }); }); }); });
 }
 
 }  // namespace
@@ -1239,6 +1252,19 @@ bool affine_supported(const fastgrnn_desc& d) {
   return (d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && seq_fits32(d)) || dense_wide_shape(d);
 }
 
+// fastgrnn_hip_forward_windows on kernel path 2: fp32, dense, gates sigmoid / relu / tanh, update tanh; H = 128 with
+// F = 32 and H = 256 with F = 32 / 64; hs time- or batch-major or h_T alone; plain or FASTGRNN_FLAG_PREACT_AFFINE
+bool windows_supported(const fastgrnn_desc& d) {
+  if (d.flags & ~(FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_PREACT_AFFINE)) return false;
+  const bool shape = (d.H == 128 && d.F == 32) || (d.H == 256 && (d.F == 32 || d.F == 64));
+  if (!shape || d.w_rank || d.u_rank) return false;
+  if (d.dtype != FASTGRNN_F32 || d.gate_nl > FASTGRNN_NL_TANH || d.update_nl != FASTGRNN_NL_TANH) return false;
+  return (d.flags & FASTGRNN_FLAG_PREACT_AFFINE) ? affine_supported(d) : split_supported(d, 0);
+}
+
+// the H = 256 scans' flag words and, for F = 64, the frame product of the whole pool P_pool[R, 256]; 0 for H = 128
+size_t windows_ws(const fastgrnn_desc& d, size_t pool_rows) { return h256_shape(d) ? h256_windows_ws(d, pool_rows) : 0; }
+
 size_t split_forward_ws(const fastgrnn_desc& d) {
   // wide layers: the frame product P = X.W^T goes to the auxiliary output the caller passes (z_s under SAVE_PREACT,
   // c_s otherwise); a forward without auxiliary outputs needs room for it.  The query cannot see the pointers, so
@@ -1275,13 +1301,14 @@ int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
 }
 
 int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                  void* zs, void* cs, void* ws, hipStream_t s, const void* sg_, const void* sc_) {
+                  void* zs, void* cs, void* ws, hipStream_t s, const void* sg_, const void* sc_, const window_src* win) {
+  if (win && (zs || cs || !windows_supported(d))) return FASTGRNN_ERR_UNSUPPORTED;
   if (!(d.flags & FASTGRNN_FLAG_SAVE_PREACT) && (zs == nullptr) != (cs == nullptr)) return FASTGRNN_ERR_NULL_POINTER;
   if (d.dtype == FASTGRNN_BF16_IO && zs && !(d.flags & FASTGRNN_FLAG_SAVE_PREACT)) return FASTGRNN_ERR_UNSUPPORTED;
   const float* sg = reinterpret_cast<const float*>(sg_);
   const float* sc = reinterpret_cast<const float*>(sc_);
   if (sg && (zs || !affine_supported(d))) return FASTGRNN_ERR_UNSUPPORTED;
-  if (h256_shape(d)) return h256_forward(d, p, x, h0, hs, zs, cs, ws, s, sg, sc);
+  if (h256_shape(d)) return h256_forward(d, p, x, h0, hs, zs, cs, ws, s, sg, sc, win);
   if (lowrank_shape(d)) return lowrank_forward(d, p, x, h0, hs, zs, cs, ws, s);
   if (densified_shape(d)) return densified_forward(d, p, x, h0, hs, zs, cs, ws, s);
   void* pws = nullptr;
@@ -1297,7 +1324,7 @@ int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
         : rows_gemm((size_t)d.T * d.B, 128, d.F, false, x, (const float*)p.w, pws, d.dtype == FASTGRNN_BF16_IO, false, s);
     if (st != FASTGRNN_OK) return st;
   }
-  if (!launch_fwd(d, p, x, h0, hs, zs, cs, s, pws, sg, sc)) return FASTGRNN_ERR_UNSUPPORTED;
+  if (!launch_fwd(d, p, x, h0, hs, zs, cs, s, pws, sg, sc, win)) return FASTGRNN_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 

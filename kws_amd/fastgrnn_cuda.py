@@ -545,6 +545,90 @@ def forward_unroll_affine(input, w, u, bias_gate, bias_update, zeta, nu, gate_sc
     return hs
 
 
+@functools.lru_cache(maxsize=1024)
+def _windows_plan(T, B, F, H, rw, ru, gate_nl, update_nl, dtype_code, flags, rows):
+    """(descriptor, windowed scans hold it, workspace bytes for a pool of ``rows`` frames): pure functions of the
+    descriptor in the C ABI, asked once per signature like ``_plan``."""
+    desc = _lib.Desc(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), dtype_code, int(flags))
+    lib = _lib.load()
+    ok = bool(lib.fastgrnn_hip_windows_supported(C.byref(desc)))
+    return desc, ok, int(lib.fastgrnn_hip_forward_windows_workspace_bytes(C.byref(desc), rows)) if ok else 0
+
+
+def windows_supported(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=torch.float32, flags=0):
+    """``forward_windows`` runs this descriptor on the windowed scans (include/fastgrnn_hip.h,
+    ``fastgrnn_hip_windows_supported``); where it does not, the modules gather the windows and call the existing
+    forward.  ``flags``: FLAG_BATCH_MAJOR / FLAG_HS_LAST / FLAG_PREACT_AFFINE."""
+    if dtype not in _DTYPES:
+        return False
+    return _windows_plan(T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype], int(flags), T)[1]
+
+
+def forward_windows(pool, starts, T, w, u, bias_gate, bias_update, zeta, nu, initial_h, z_non_linearity,
+                    gate_scale=None, update_scale=None, batch_major=False, last_state=False, *,
+                    update_non_linearity=2, check=True):
+    """Inference forward over windows of a shared frame pool (include/fastgrnn_hip.h, ``fastgrnn_hip_forward_windows``):
+    utterance ``b`` is the ``T`` consecutive rows of ``pool:[R,F]`` from row ``starts[b]`` on, read in place -- no
+    gathered ``[T,B,F]`` copy.  ``starts``: ``[B]`` int32 or int64 on the pool's device, ``0 <= starts[b] <= R - T``;
+    overlapping, repeated and unordered starts are fine.  ``check=True`` validates that range with one ``aminmax``
+    (one host synchronisation) and raises ``ValueError``; ``check=False`` skips it and makes the range the caller's
+    obligation.  ``gate_scale`` / ``update_scale``: both given for the eval-mode BatchNorm arithmetic of
+    ``forward_unroll_affine``, both None for the plain cell.  Returns hs: ``[T,B,H]``, ``[B,T,H]`` with
+    ``batch_major`` or ``[B,H]`` (h_T) with ``last_state``.  Nothing is saved for a backward.  Cells the windowed scans
+    do not hold (``windows_supported``) raise: there is no eager fallback here."""
+    lib = _lib.load()
+    affine = gate_scale is not None or update_scale is not None
+    if affine and (gate_scale is None or update_scale is None):
+        raise RuntimeError("forward_windows: gate_scale and update_scale go together")
+    named = [(pool, "pool"), (starts, "starts"), (initial_h, "initial_h"), (bias_gate, "bias_gate"),
+             (bias_update, "bias_update")] + ([(gate_scale, "gate_scale"), (update_scale, "update_scale")] if affine else [])
+    for t, n in named:
+        _check_input(t, n)
+    if pool.dim() != 2:
+        raise RuntimeError("pool must be [frames, features]")
+    if starts.dim() != 1 or starts.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("starts must be a 1-D int32 or int64 tensor")
+    if starts.device != pool.device:
+        raise RuntimeError("starts must be on the pool's device")
+    R, F = pool.shape
+    B, T = starts.numel(), int(T)
+    H = initial_h.shape[-1]
+    _expect(initial_h, (B, H), "initial_h")
+    if T < 1 or T > R:
+        raise ValueError("forward_windows: window length T=%d does not fit a pool of %d frames" % (T, R))
+    for t, n in named[3:]:
+        if t.numel() != H:
+            raise RuntimeError("%s must hold H=%d elements" % (n, H))
+    for t in (initial_h,) + ((gate_scale, update_scale) if affine else ()):
+        if t.dtype != _param_dtype(pool.dtype):
+            raise RuntimeError("fastgrnn: all operands must share dtype %s (got %s)" % (_param_dtype(pool.dtype), t.dtype))
+    if check and B:
+        lo, hi = torch.stack(torch.aminmax(starts)).tolist()        # one device-to-host copy
+        if lo < 0 or hi > R - T:
+            raise ValueError("forward_windows: starts must lie in [0, %d] (pool of %d frames, T=%d); got [%d, %d]"
+                             % (R - T, R, T, lo, hi))
+    if starts.dtype != torch.int32:
+        starts = starts.to(torch.int32)
+    flags = (_lib.FLAG_BATCH_MAJOR if batch_major else 0) | (_lib.FLAG_HS_LAST if last_state else 0) | \
+        (_lib.FLAG_PREACT_AFFINE if affine else 0)
+    plan, params, w_lr, u_lr = _describe(T, B, F, H, w, u, None, None, None, None, bias_gate, bias_update, zeta, nu,
+                                         pool.dtype, z_non_linearity, update_non_linearity, flags)
+    d = plan.desc
+    _, _, nbytes = _windows_plan(T, B, F, H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, flags, R)
+    dev = pool.device
+    hs_shape = (B, H) if last_state else ((B, T, H) if batch_major else (T, B, H))
+    with torch.cuda.device(dev):
+        hs = torch.empty(hs_shape, dtype=pool.dtype, device=dev)
+        ws, wsp = _workspace(nbytes, dev)
+        with _Timed("forward_windows", dev):
+            st = lib.fastgrnn_hip_forward_windows(C.byref(d), C.byref(params), _ptr(gate_scale), _ptr(update_scale),
+                                                  _ptr(pool), R, _ptr(starts), _ptr(initial_h), _ptr(hs), wsp, nbytes,
+                                                  _stream(dev))
+        _lib.check(st, "fastgrnn forward_windows")
+        del ws
+    return hs
+
+
 def backward_unroll(grad_h, input, hidden_states, zeta, nu, w, u, z, h_prime, initial_h, w1, w2, u1, u2,
                     z_non_linearity, *, update_non_linearity=2, flags=0, bias_gate=None, bias_update=None,
                     need_dx=True):

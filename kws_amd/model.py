@@ -129,6 +129,42 @@ class RNNClassifierModel(nn.Module):
             model_output = F.log_softmax(model_output, dim=1)
         return model_output
 
+    @torch.no_grad()
+    def score_stream(self, stream, hop=1, window=99):
+        """Score every window of continuous audio, as the reference's detector does one window at a time
+        (inferencetry.py:165-227: a 99-frame window slid over the stream, the model run from a zero state on each).
+        ``stream``: ``[S,L,F]`` (or ``[L,F]``: one stream) -> ``[S,Nw,C]`` scores, ``Nw = (L - window) // hop + 1``,
+        window ``w`` of stream ``s`` being frames ``w*hop .. w*hop + window - 1``.  Layer 0 reads the stream in place
+        (``forward_windows``: the window is the batch dimension, no ``window/hop``-fold copy); the layers above and
+        the head run as ``forward`` does under ``torch.no_grad()``.  Every window starts from a zero state:
+        ``hidden_states`` is neither read nor written.  Majority voting over consecutive windows is bookkeeping on
+        ``argmax`` and stays the caller's.  BatchNorm models: eval mode only."""
+        if stream.dim() == 2:
+            stream = stream[None]
+        if stream.dim() != 3:
+            raise ValueError("stream must be [streams, frames, features] or [frames, features]")
+        S, L, Fn = stream.shape
+        hop, window = int(hop), int(window)
+        if hop < 1 or window < 1:
+            raise ValueError("hop and window must be positive (got hop=%d, window=%d)" % (hop, window))
+        if L < window:
+            raise ValueError("stream of %d frames is shorter than the window of %d" % (L, window))
+        dev = self.rnn_list[0].device
+        pool = stream.to(dev).reshape(S * L, Fn)
+        nw = (L - window) // hop + 1
+        starts = (torch.arange(S, device=dev)[:, None] * L + torch.arange(nw, device=dev)[None, :] * hop).reshape(-1)
+        top = self.num_layers - 1
+        kw = {"training": self.training} if self._batchnorm else {}
+        out = self.rnn_list[0].forward_windows(pool, starts, window, last_state=(top == 0), check=False, **kw)
+        for l in range(1, self.num_layers):
+            out = self.rnn_list[l](out, hiddenState=None, last_state=(l == top), **kw)
+        out = out.float()
+        if self.linear:
+            out = self.hidden2keyword(out)
+        if self.apply_softmax:
+            out = F.log_softmax(out, dim=1)
+        return out.reshape(S, nw, -1)
+
     def loss(self, input, labels):
         """``nn.NLLLoss()(self(input), labels)`` (trainClassifier.py:233-236) with the fused head."""
         if self.rnn_name == "FastGRNNBatchNorm":

@@ -76,6 +76,20 @@ def _on_path2(input, T, B, F, H, w1, u1, gate_non_linearity, direction, flags):
                                           direction, flags) == 2)
 
 
+def gather_windows(pool, starts, T, check=True):
+    """``[B,T,F]``: window ``b`` = rows ``starts[b] .. starts[b]+T-1`` of ``pool:[R,F]``, materialised (what
+    ``forward_windows`` avoids where the windowed scans hold the cell)."""
+    R, T = pool.shape[0], int(T)
+    if T < 1 or T > R:
+        raise ValueError("forward_windows: window length T=%d does not fit a pool of %d frames" % (T, R))
+    if check and starts.numel():
+        lo, hi = torch.stack(torch.aminmax(starts)).tolist()
+        if lo < 0 or hi > R - T:
+            raise ValueError("forward_windows: starts must lie in [0, %d] (pool of %d frames, T=%d); got [%d, %d]"
+                             % (R - T, R, T, lo, hi))
+    return pool[starts.long()[:, None] + torch.arange(T, device=pool.device)]
+
+
 _unroll_decisions = {}
 _zero_states = {}        # (B, H, dtype, device) -> the default h0
 _inference_ok = {}       # call signature -> "the hs-only forward is on kernel path 2"
@@ -471,6 +485,31 @@ class FastGRNNCUDA(nn.Module):
         return fastgrnn_cuda.forward_unroll(input.contiguous(), self.W, self.U, self.bias_gate, self.bias_update,
                                             self.zeta, self.nu, hiddenState.contiguous(), self._gate_non_linearity,
                                             self.W1, self.W2, self.U1, self.U2, want_gates=False, flags=flags)[0]
+
+    @torch.no_grad()
+    def forward_windows(self, pool, starts, T, hiddenState=None, last_state=False, check=True):
+        """Inference over windows of a shared frame pool (not in the reference; its detector gathers every window,
+        inferencetry.py:165-227): utterance ``b`` is the ``T`` consecutive rows of ``pool:[R,F]`` from row
+        ``starts[b]`` on.  Returns what ``forward`` returns for the gathered batch under ``torch.no_grad()`` -- hs
+        ``[T,B,H]`` (``[B,T,H]`` with ``batch_first``), or h_T ``[B,H]`` with ``last_state`` -- without a graph.
+        Where the windowed scans hold the cell (``fastgrnn_cuda.windows_supported``) the pool is read in place;
+        elsewhere (factorised weights, other sizes, bf16) the windows are gathered and ``forward`` runs them."""
+        pool = pool.to(self.device) if not pool.is_cuda else pool
+        starts = starts.to(pool.device)
+        B, H, T = starts.numel(), self._hidden_size, int(T)
+        h0 = torch.zeros([B, H], dtype=fastgrnn_cuda._param_dtype(pool.dtype), device=pool.device) \
+            if hiddenState is None else hiddenState.to(pool.device).contiguous()
+        bm = self.batch_first is True
+        flags = (_lib.FLAG_BATCH_MAJOR if bm else 0) | (_lib.FLAG_HS_LAST if last_state else 0)
+        if pool.dim() == 2 and fastgrnn_cuda.windows_supported(
+                T, B, pool.shape[1], H, self.W1.shape[0] if self.W1.numel() else 0,
+                self.U1.shape[0] if self.U1.numel() else 0, self._gate_non_linearity, 2, pool.dtype, flags):
+            return fastgrnn_cuda.forward_windows(pool.contiguous(), starts, T, self.W, self.U, self.bias_gate,
+                                                 self.bias_update, self.zeta, self.nu, h0, self._gate_non_linearity,
+                                                 batch_major=bm, last_state=last_state, check=check)
+        windows = gather_windows(pool, starts, T, check)                       # [B,T,F]
+        return self.forward(windows if bm else windows.transpose(0, 1).contiguous(), hiddenState=h0,
+                            last_state=last_state)
 
     def getVars(self):
         return _get_vars(self)
