@@ -94,7 +94,8 @@ int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
 // batched split-precision GEMMs around the scans (kernels_gemm.hip)
 //   rows_gemm:   C[R,N] = A[R,K] . Wt^T, Wt[n][k] = trans_w ? W[k*N + n] : W[n*K + k]; A / C may be bf16 sequences
 //   tn_gemm_big: C[M,N] (row stride ldc) = A[R,M]^T . B[R,N]; rows of B below shiftB come from B0, the rest from B1
-//                shifted down by shiftB rows; part: tn_gemm_big_ws(R, M, N) bytes
+//                shifted down by shiftB rows; part: tn_gemm_big_ws(R, M, N) bytes (bf_b with 0 < shiftB < R:
+//                tn_gemm_big_ws(R, M, N, shiftB) -- the head and the body are cut into chunks independently)
 bool rows_gemm_supported(int N, int K, bool trans_w);
 int rows_gemm(size_t R, int N, int K, bool trans_w, const void* A, const float* W, void* C, bool bf_in, bool bf_out,
               hipStream_t s);
@@ -102,7 +103,7 @@ int rows_gemm(size_t R, int N, int K, bool trans_w, const void* A, const float* 
 // stored at row t * cT + b * cB: the same bits as rows_gemm on the time-major copy
 int rows_gemm_bft(int B, int T, int N, int K, const float* A, const float* W, float* C, size_t cT, size_t cB, hipStream_t s);
 bool tn_gemm_big_supported(int M, int N);
-size_t tn_gemm_big_ws(size_t R, int M, int N);
+size_t tn_gemm_big_ws(size_t R, int M, int N, size_t bf_shiftB = 0);
 int tn_gemm_big_run(size_t R, int M, int N, const float* A, int lda, const float* B0, const void* B1, size_t shiftB,
                     int ldb, float* part, float* C, int ldc, hipStream_t s, bool bf_b = false);   // bf_b: B1 holds bf16
 // ... with row r of B = B0[r / period] where r is a multiple of period, else B1[r - 1] (N = 256 only)

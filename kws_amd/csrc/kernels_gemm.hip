@@ -778,12 +778,20 @@ int tn_gemm_big_run_periodic(size_t R, int M, int N, const float* A, int lda, co
 
 bool tn_gemm_big_supported(int M, int N) { return (M == 128 || M == 256) && (N == 32 || N == 64 || N == 128 || N == 256); }
 
-size_t tn_gemm_big_ws(size_t R, int M, int N) {
+size_t tn_gemm_big_ws(size_t R, int M, int N, size_t bf_shiftB) {
   int spw;
   const int nblk = M / 128, nch = tnb_chunks(R, nblk, &spw);
   // (twice the chunks of the product: with bf16 rows of B the rows that pair with fp32 h0 are a product of their own,
   // its partials behind the others')
-  return align256((size_t)2 * nch * nblk * 128 * N * sizeof(float));
+  size_t slots = (size_t)2 * nch;
+  // ... and the two products are cut on their own row counts: the body's R - shiftB rows can fall below a step of
+  // stages-per-chunk that R is above and make MORE chunks than R does (R = 4131, shiftB = 1377, M = 256: 87 + 44
+  // against 2 * 65), so the caller that splits names its shiftB and gets room for exactly what tn_gemm_big_run writes
+  if (bf_shiftB > 0 && bf_shiftB < R) {
+    const size_t split = (size_t)tnb_chunks(R - bf_shiftB, nblk, &spw) + (size_t)tnb_chunks(bf_shiftB, nblk, &spw);
+    if (split > slots) slots = split;
+  }
+  return align256(slots * nblk * 128 * N * sizeof(float));
 }
 
 int tn_gemm_big_run(size_t R, int M, int N, const float* A, int lda, const float* B0, const void* B1v, size_t shiftB,

@@ -807,7 +807,9 @@ H256BwdWs h256_bwd_layout(const fastgrnn_desc& d) {
   H256BwdWs L; size_t o = 0;
   L.part = o; o += align256(nwg * SLAB2 * 4);
   L.dpre = o; o += align256((TB + 16) * H2 * 4);     // + 16 sink rows for the lanes beyond a ragged batch
-  const size_t tn_u = tn_gemm_big_ws(TB, H2, H2), tn_w = tn_gemm_big_ws(TB, H2, d.F);
+  // (bf16 sequences: the dU product runs as an fp32 head over the B rows of h0 and a bf16 body)
+  const size_t tn_u = tn_gemm_big_ws(TB, H2, H2, d.dtype == FASTGRNN_BF16_IO ? (size_t)d.B : 0);
+  const size_t tn_w = tn_gemm_big_ws(TB, H2, d.F);
   L.tn = o; o += tn_u > tn_w ? tn_u : tn_w;
   // FASTGRNN_FLAG_X_BFT: the time-major copy of x for the dW GEMM; the d_x GEMM then writes over it and the result is
   // transposed into the caller's [B,F,T] tensor

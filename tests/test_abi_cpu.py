@@ -101,6 +101,21 @@ def test_argument_validation_without_launch(lib):
         assert lib.fastgrnn_hip_backward_unroll(C.byref(dd), C.byref(pf), one, one, one, one, one, one, C.byref(gx), null, 0, null) == 5
 
 
+def test_frame_gemm_argument_validation_without_launch(lib):
+    """fastgrnn_hip_frame_gemm (P = X . W^T as a call of its own): NULL tensors, an empty product, a type or an (H, F)
+    pair without a kernel are refused in that order, before any launch."""
+    null, one = C.c_void_p(None), C.c_void_p(256)
+    fg = lib.fastgrnn_hip_frame_gemm
+    for x, w, p in ((null, one, one), (one, null, one), (one, one, null)):
+        assert fg(64, 128, 256, x, w, p, _lib.F32, null) == 1
+    assert fg(0, 128, 256, one, one, one, _lib.F32, null) == 2
+    assert fg(64, 128, 256, one, one, one, _lib.F64, null) == 4
+    for H, F in ((256, 256), (128, 32)):
+        for dtype in (_lib.F32, _lib.BF16_IO):
+            assert fg(64, H, F, one, one, one, dtype, null) == 7
+    assert fg(0, 128, 256, null, one, one, _lib.F64, null) == 1          # (the order of the checks)
+
+
 def test_last_state_flags_are_refused_where_no_kernel_implements_them(lib):
     """FLAG_GRAD_LAST / FLAG_HS_LAST exist on the split-precision kernels only: every other path --
     and HS_LAST together with tensors saved for a backward -- answers FASTGRNN_ERR_UNSUPPORTED (7) before any

@@ -588,7 +588,12 @@ def test_bf16_sequences_fp32_master_grads(B, batch_major, F, H):
     saved pre-activation and every parameter gradient are fp32.  Checked against the fp64 oracle run
     on the SAME rounded tensors: hs and d_x to bf16 rounding (2^-8 relative), the fp32 outputs to the
     fp32 tolerances of the other tests."""
-    T = 31                                # (H = 256: the first layer of the default stack, round 3)
+    bf16_master_grads_case(31, B, batch_major, F, H)   # (H = 256: the first layer of the default stack, round 3)
+
+
+def bf16_master_grads_case(T, B, batch_major, F, H):
+    """the reference and the bounds of test_bf16_sequences_fp32_master_grads at any (T, B)
+    (tests/test_hip_partition_seams.py runs them where the weight-gradient GEMMs cut long chunks)"""
     SAVE_PREACT, BATCH_MAJOR = 4, 16
     rng = np.random.default_rng(77 + B)
     p = O.make_params(F, H, dtype=np.float32, seed=23, randomize_scalars=True)
