@@ -264,6 +264,11 @@ const char *fastgrnn_hip_status_string(int status);
  *                                 gates sigmoid / relu / tanh, update tanh, plain or FASTGRNN_FLAG_PREACT_AFFINE:
  *                                 H=128 with F=32, H=256 with F=32, H=256 with F=64; hs time-major, batch-major or
  *                                 (FASTGRNN_FLAG_HS_LAST) h_T alone.  Nothing else: ask fastgrnn_hip_windows_supported.
+ *   fastgrnn_hip_forward_windows_train / fastgrnn_hip_backward_windows  (training on windows of a frame pool, see below)
+ *                                 the plain cells of fastgrnn_hip_forward_windows -- fp32, dense, gates sigmoid / relu /
+ *                                 tanh, update tanh, H=128 with F=32, H=256 with F=32 / 64 -- under the one-saved-tensor
+ *                                 contract; time- or batch-major, the backward with FASTGRNN_FLAG_GRAD_LAST as well; no
+ *                                 input gradient.  Nothing else: ask fastgrnn_hip_train_windows_supported.
  * Under FASTGRNN_FLAG_SAVE_PREACT a factorised forward with both ranks in 1..16 also writes, through c_s, the rank-space vector
  * [U1.h_{t-1} | W1.x_t] as a time-major fp32 [T*B, 32] tensor (each half zero-extended to 16 columns) that the
  * backward takes back through c_s (with z_s, the pre-activation): its factor gradients are contracted inside the
@@ -343,8 +348,8 @@ int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc *d, const fastgrnn_pa
  * clips are the same call).  x_start: [B] int32 on the device; the library cannot look at its contents:
  *   0 <= x_start[b] <= pool_rows - T  for every b  IS THE CALLER'S OBLIGATION (a start outside reads outside the pool).
  * h0:[B,H]; hs follows d->flags as in forward_unroll_affine: [T,B,H], [B,T,H] (FASTGRNN_FLAG_BATCH_MAJOR) or [B,H]
- * (FASTGRNN_FLAG_HS_LAST).  Nothing is saved for a backward (the gradient w.r.t. overlapping windows is a scatter-add
- * and is not built).  gate_scale / update_scale: both NULL for the plain cell; both non-NULL ([H] fp32) for the
+ * (FASTGRNN_FLAG_HS_LAST).  Nothing is saved for a backward: this is the inference call; training on windows is
+ * fastgrnn_hip_forward_windows_train / fastgrnn_hip_backward_windows below (no gradient w.r.t. the pool).  gate_scale / update_scale: both NULL for the plain cell; both non-NULL ([H] fp32) for the
  * eval-mode BatchNorm arithmetic, and d->flags must then carry FASTGRNN_FLAG_PREACT_AFFINE (and only then).
  * Cells (fastgrnn_hip_windows_supported answers 1): fp32, dense, gate sigmoid / relu / tanh, update tanh, and
  *   H=128 with F=32;  H=256 with F=32;  H=256 with F=64
@@ -366,6 +371,56 @@ int fastgrnn_hip_forward_windows(const fastgrnn_desc *d, const fastgrnn_params *
                                  const void *x_pool, size_t pool_rows, const int32_t *x_start,
                                  const void *h0, void *hs,
                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* forward_windows_train / backward_windows -- TRAINING on windows of a frame pool: the layer that reads the pool is a
+ * model's first layer, nobody wants its input gradient, and without d_x the backward over windows needs no scatter-add,
+ * only the gather of x the forward does.  x_pool, pool_rows and x_start are those of fastgrnn_hip_forward_windows
+ * (x_pool 16-byte aligned), and so is the range of the starts:
+ *   0 <= x_start[b] <= pool_rows - T  for every b  IS THE CALLER'S OBLIGATION (a start outside reads outside the pool).
+ * Both calls ALWAYS run under the one-saved-tensor contract of FASTGRNN_FLAG_SAVE_PREACT: `saved` is the fp32
+ * pre-activation W.x_t + U.h_{t-1} (no bias) in the sequences' layout, [T,B,H] or (FASTGRNN_FLAG_BATCH_MAJOR) [B,T,H] --
+ * what forward_unroll writes to z_s under that flag, bit for bit, on the gathered windows.  The caller does NOT pass
+ * FASTGRNN_FLAG_SAVE_PREACT: a descriptor that carries it is refused (FASTGRNN_ERR_UNSUPPORTED, supported query 0)
+ * like every other flag the two calls do not know, so that the flag keeps one meaning per entry point and
+ * fastgrnn_hip_windows_supported / fastgrnn_hip_forward_windows go on refusing it.  hs is always the full sequence
+ * (training saves it): there is no FASTGRNN_FLAG_HS_LAST.
+ * Cells (fastgrnn_hip_train_windows_supported answers 1): fp32, dense, gate sigmoid / relu / tanh, update tanh, and
+ *   H=128 with F=32;  H=256 with F=32;  H=256 with F=64.
+ * Flags: FASTGRNN_FLAG_BATCH_MAJOR in both calls and the queries; FASTGRNN_FLAG_GRAD_LAST in the backward, its workspace
+ * query and the supported query (grad_hs is [B,H]; the forward and its workspace query refuse / answer 0).  Any other
+ * flag, bf16 sequences, fp64, factorised operands, quantised codes and other shapes answer FASTGRNN_ERR_UNSUPPORTED /
+ * 0 (gather the windows and call forward_unroll / backward_unroll).
+ *   forward:  x_pool, x_start, h0:[B,H] -> hs, saved.  H=256 reads the pool in place; workspace as
+ *             fastgrnn_hip_forward_windows: the flag words plus, for F=64, P_pool[pool_rows,256] -- a function of
+ *             pool_rows alone.  H=128 gathers the windows into a copy of x in the workspace (align256(T*B*F*4) bytes,
+ *             the backward's kernel) and runs the scan of forward_unroll on it: a windowed scan that saves the
+ *             pre-activation is not built for H=128.
+ *   backward: grad_hs (the layout of hs, or [B,H]), x_pool, x_start, hs, saved, h0 -> g->d_h0, d_w, d_u, d_bias_gate,
+ *             d_bias_update, d_zeta, d_nu (overwritten): bit for bit what backward_unroll writes for the gathered
+ *             windows with d_x == NULL (FASTGRNN_FLAG_SAVE_PREACT, on H=128 with FASTGRNN_FLAG_NO_INPUT_GRAD).
+ *             g->d_x MUST BE NULL: the gradient with respect to the pool is a scatter-add over overlapping windows
+ *             and is deliberately not built; a non-NULL d_x answers FASTGRNN_ERR_UNSUPPORTED.  The factor gradients
+ *             are ignored.
+ *             The windows are gathered into a copy of x, [T,B,F] or [B,T,F], in the LAST align256(T*B*F*4) bytes of
+ *             the workspace (one small kernel) and the route of backward_unroll runs on it: workspace =
+ *             fastgrnn_hip_backward_workspace_bytes(d) + align256(T*B*F*4) for every shape.  (A scan that reads the
+ *             pool in place on H=128 is not built: DESIGN.md 4.1g.)
+ * Errors, all before any launch: FASTGRNN_ERR_NULL_POINTER (any pointer above, a parameter, a gradient output),
+ * FASTGRNN_ERR_BAD_SHAPE (pool_rows < T, pool_rows >= 2^31, size overflow), FASTGRNN_ERR_UNSUPPORTED,
+ * FASTGRNN_ERR_WORKSPACE (missing, short or not 256-byte aligned).  Both workspace queries answer 0 for an unsupported
+ * descriptor and for pool_rows >= 2^31. */
+int fastgrnn_hip_train_windows_supported(const fastgrnn_desc *d);      /* 1 / 0 */
+size_t fastgrnn_hip_train_windows_forward_workspace_bytes(const fastgrnn_desc *d, size_t pool_rows);
+size_t fastgrnn_hip_train_windows_backward_workspace_bytes(const fastgrnn_desc *d, size_t pool_rows);
+int fastgrnn_hip_forward_windows_train(const fastgrnn_desc *d, const fastgrnn_params *p,
+                                       const void *x_pool, size_t pool_rows, const int32_t *x_start,
+                                       const void *h0, void *hs, void *saved,
+                                       void *workspace, size_t workspace_bytes, void *stream);
+int fastgrnn_hip_backward_windows(const fastgrnn_desc *d, const fastgrnn_params *p,
+                                  const void *grad_hs, const void *x_pool, size_t pool_rows, const int32_t *x_start,
+                                  const void *hs, const void *saved, const void *h0,
+                                  const fastgrnn_grads *g,
+                                  void *workspace, size_t workspace_bytes, void *stream);
 
 /* backward_unroll -- replaces fastgrnn_unroll_backward (fastgrnn_cuda.cpp:182-232 ->
  * .cu:417-557).  grad_hs:[T,B,H] is dL/d(hs[t]) for every t; z_s,c_s are the

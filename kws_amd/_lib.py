@@ -45,6 +45,9 @@ EXPORTS = (
     "fastgrnn_hip_bn_train_backward_workspace_bytes", "fastgrnn_hip_bn_train_forward", "fastgrnn_hip_bn_train_backward",
     "fastgrnn_hip_zero_extend_plan", "fastgrnn_hip_plan",
     "fastgrnn_hip_windows_supported", "fastgrnn_hip_forward_windows_workspace_bytes", "fastgrnn_hip_forward_windows",
+    "fastgrnn_hip_train_windows_supported", "fastgrnn_hip_train_windows_forward_workspace_bytes",
+    "fastgrnn_hip_train_windows_backward_workspace_bytes", "fastgrnn_hip_forward_windows_train",
+    "fastgrnn_hip_backward_windows",
 )
 
 
@@ -164,6 +167,16 @@ def load():
     lib.fastgrnn_hip_forward_windows_workspace_bytes.argtypes = [DP, sz]
     lib.fastgrnn_hip_forward_windows.restype = i32
     lib.fastgrnn_hip_forward_windows.argtypes = [DP, PP, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]
+    lib.fastgrnn_hip_train_windows_supported.restype = i32
+    lib.fastgrnn_hip_train_windows_supported.argtypes = [DP]
+    for f in (lib.fastgrnn_hip_train_windows_forward_workspace_bytes,
+              lib.fastgrnn_hip_train_windows_backward_workspace_bytes):
+        f.restype = sz
+        f.argtypes = [DP, sz]
+    lib.fastgrnn_hip_forward_windows_train.restype = i32
+    lib.fastgrnn_hip_forward_windows_train.argtypes = [DP, PP, vp, sz, vp, vp, vp, vp, vp, sz, vp]
+    lib.fastgrnn_hip_backward_windows.restype = i32
+    lib.fastgrnn_hip_backward_windows.argtypes = [DP, PP, vp, vp, sz, vp, vp, vp, vp, GP, vp, sz, vp]
     if lib.fastgrnn_hip_abi_version() != ABI_VERSION:
         raise FastGRNNLibraryError("ABI version mismatch: library %d, binding %d"
                                    % (lib.fastgrnn_hip_abi_version(), ABI_VERSION))

@@ -168,6 +168,22 @@ bool windows_route(const fastgrnn_desc* d, route* r) {
   return resolve(d, r) == FASTGRNN_OK && r->path[0] == 2 && windows_supported(*d);
 }
 
+// fastgrnn_hip_forward_windows_train / fastgrnn_hip_backward_windows run d (judged on d, as windows_route does: the two
+// calls know FASTGRNN_FLAG_BATCH_MAJOR and, the backward, FASTGRNN_FLAG_GRAD_LAST; FASTGRNN_FLAG_SAVE_PREACT is theirs to
+// add -- r->e is d with it -- and is refused like every other flag when the caller passes it)
+bool train_windows_route(const fastgrnn_desc* d, route* r) {
+  if (resolve(d, r) != FASTGRNN_OK || !train_windows_supported(*d)) return false;
+  r->e = *d;
+  r->e.flags |= FASTGRNN_FLAG_SAVE_PREACT;
+  return true;
+}
+
+// the pool of a windowed training call: it holds a window, and its rows are addressed through the int32 starts (element
+// offsets into the pool and its frame product are size_t: at most 2^31 rows of at most 256 floats cannot overflow them)
+bool pool_rows_ok(const fastgrnn_desc* d, size_t pool_rows) {
+  return pool_rows >= (size_t)d->T && pool_rows <= (size_t)INT32_MAX;
+}
+
 // r->u runs on the training kernels
 bool bn_train_route(const fastgrnn_desc* d, route* r) {
   return resolve(d, r) == FASTGRNN_OK && (r->u.flags & FASTGRNN_FLAG_BN_TRAIN) && bn_train_supported(r->u);
@@ -305,6 +321,58 @@ int fastgrnn_hip_forward_windows(const fastgrnn_desc* d, const fastgrnn_params* 
   const window_src win{x_start, pool_rows};
   return split_forward(*d, *p, x_pool, h0, hs, nullptr, nullptr, workspace, reinterpret_cast<hipStream_t>(stream),
                        gate_scale, update_scale, &win);
+}
+
+int fastgrnn_hip_train_windows_supported(const fastgrnn_desc* d) {
+  route r;
+  return train_windows_route(d, &r) ? 1 : 0;
+}
+
+size_t fastgrnn_hip_train_windows_forward_workspace_bytes(const fastgrnn_desc* d, size_t pool_rows) {
+  route r;
+  if (!train_windows_route(d, &r) || (d->flags & FASTGRNN_FLAG_GRAD_LAST) || pool_rows > (size_t)INT32_MAX) return 0;
+  return train_windows_forward_ws(*d, pool_rows);
+}
+
+size_t fastgrnn_hip_train_windows_backward_workspace_bytes(const fastgrnn_desc* d, size_t pool_rows) {
+  route r;
+  if (!train_windows_route(d, &r) || pool_rows > (size_t)INT32_MAX) return 0;
+  return train_windows_backward_ws(*d);
+}
+
+int fastgrnn_hip_forward_windows_train(const fastgrnn_desc* d, const fastgrnn_params* p, const void* x_pool,
+                                       size_t pool_rows, const int32_t* x_start, const void* h0, void* hs, void* saved,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  route r;
+  int st = resolve(d, &r);
+  if (st) return st;
+  if ((st = check_params(d, p))) return st;
+  if (!x_pool || !x_start || !h0 || !hs || !saved) return FASTGRNN_ERR_NULL_POINTER;
+  if (!pool_rows_ok(d, pool_rows)) return FASTGRNN_ERR_BAD_SHAPE;
+  if ((d->flags & FASTGRNN_FLAG_GRAD_LAST) || !train_windows_route(d, &r)) return FASTGRNN_ERR_UNSUPPORTED;
+  if ((st = check_ws(workspace, workspace_bytes, train_windows_forward_ws(*d, pool_rows)))) return st;
+  const window_src win{x_start, pool_rows};
+  return split_forward(r.e, *p, x_pool, h0, hs, saved, nullptr, workspace, reinterpret_cast<hipStream_t>(stream),
+                       nullptr, nullptr, &win);
+}
+
+int fastgrnn_hip_backward_windows(const fastgrnn_desc* d, const fastgrnn_params* p, const void* grad_hs,
+                                  const void* x_pool, size_t pool_rows, const int32_t* x_start, const void* hs,
+                                  const void* saved, const void* h0, const fastgrnn_grads* g, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  route r;
+  int st = resolve(d, &r);
+  if (st) return st;
+  if ((st = check_params(d, p))) return st;
+  if (!grad_hs || !x_pool || !x_start || !hs || !saved || !h0 || !g) return FASTGRNN_ERR_NULL_POINTER;
+  if ((st = check_grads(*d, g, true))) return st;
+  if (!pool_rows_ok(d, pool_rows)) return FASTGRNN_ERR_BAD_SHAPE;
+  if (!train_windows_route(d, &r)) return FASTGRNN_ERR_UNSUPPORTED;
+  if (g->d_x) return FASTGRNN_ERR_UNSUPPORTED;        // the pool's gradient is a scatter-add over the windows: not built
+  if ((st = check_ws(workspace, workspace_bytes, train_windows_backward_ws(*d)))) return st;
+  const window_src win{x_start, pool_rows};
+  return split_backward(r.e, *p, grad_hs, x_pool, hs, saved, nullptr, h0, *g, workspace,
+                        reinterpret_cast<hipStream_t>(stream), &win);
 }
 
 int fastgrnn_hip_backward_unroll(const fastgrnn_desc* dz, const fastgrnn_params* p, const void* grad_hs,

@@ -84,12 +84,20 @@ bool affine_supported(const fastgrnn_desc& d);
 struct window_src { const int32_t* start; size_t rows; };
 bool windows_supported(const fastgrnn_desc& d);                  // the windowed scans hold this cell (path 2 only)
 size_t windows_ws(const fastgrnn_desc& d, size_t pool_rows);
+// fastgrnn_hip_forward_windows_train / fastgrnn_hip_backward_windows: d carries FASTGRNN_FLAG_BATCH_MAJOR and (backward)
+// FASTGRNN_FLAG_GRAD_LAST at most; the calls run it with FASTGRNN_FLAG_SAVE_PREACT added.  The backward gathers the
+// windows into the LAST align256(T*B*F*4) bytes of its workspace (train_windows_gather_bytes) and runs the existing
+// route on that copy.
+bool train_windows_supported(const fastgrnn_desc& d);
+size_t train_windows_gather_bytes(const fastgrnn_desc& d);
+size_t train_windows_forward_ws(const fastgrnn_desc& d, size_t pool_rows);
+size_t train_windows_backward_ws(const fastgrnn_desc& d);
 int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0,
                   void* hs, void* zs, void* cs, void* ws, hipStream_t s, const void* sg = nullptr,
                   const void* sc = nullptr, const window_src* win = nullptr);
 int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x,
                    const void* hs, const void* zs, const void* cs, const void* h0,
-                   const fastgrnn_grads& g, void* ws, hipStream_t s);
+                   const fastgrnn_grads& g, void* ws, hipStream_t s, const window_src* win = nullptr);
 
 // batched split-precision GEMMs around the scans (kernels_gemm.hip)
 //   rows_gemm:   C[R,N] = A[R,K] . Wt^T, Wt[n][k] = trans_w ? W[k*N + n] : W[n*K + k]; A / C may be bf16 sequences
@@ -102,6 +110,10 @@ int rows_gemm(size_t R, int N, int K, bool trans_w, const void* A, const float* 
 // ... with A the data loader's [B,K,T] frames read in place (fp32; N = 128 / 256 of the wide layers) and row (b, t) of C
 // stored at row t * cT + b * cB: the same bits as rows_gemm on the time-major copy
 int rows_gemm_bft(int B, int T, int N, int K, const float* A, const float* W, float* C, size_t cT, size_t cB, hipStream_t s);
+// the windows of a frame pool as a copy of x (fastgrnn_hip_backward_windows): row (t, b) = pool row start[b] + t, out
+// [T,B,F] or, batch_major, [B,T,F]; F = 32 / 64
+int gather_windows(int T, int B, int F, bool batch_major, const float* pool, const int32_t* start, float* out,
+                   hipStream_t s);
 bool tn_gemm_big_supported(int M, int N);
 size_t tn_gemm_big_ws(size_t R, int M, int N, size_t bf_shiftB = 0);
 int tn_gemm_big_run(size_t R, int M, int N, const float* A, int lda, const float* B0, const void* B1, size_t shiftB,

@@ -712,9 +712,39 @@ __global__ __launch_bounds__(1024) void tn_big_reduce(int nchunk, int nblk, int 
   }
 }
 
+// gather_windows_rows: the copy of x that the training calls over windows run the existing scans on -- every
+// fastgrnn_hip_backward_windows (all shapes, all pool sizes) and the H = 128 fastgrnn_hip_forward_windows_train.  Window b is the Tn consecutive rows from row xstart[b] of the pool [R,F];
+// row (t, b) of the copy is pool row xstart[b] + t, stored at row t * oT + b * oB (time-major: (B, 1); batch-major:
+// (1, Tn)).  One row of F floats per group of F / 4 lanes, one 16-byte load and one 16-byte store per lane: whole rows,
+// coalesced on both sides; no LDS.  A block holds 256 / (F / 4) rows of one step t (blockIdx.y, strided by the grid
+// where Tn exceeds its second dimension), so t costs no division; rows beyond B are not touched.
+template <int F>
+__global__ __launch_bounds__(256) void gather_windows_rows(int Tn, int B, unsigned oT, unsigned oB,
+                                                           const float* __restrict__ pool,
+                                                           const int* __restrict__ xstart, float* __restrict__ out) {
+  constexpr int LPR = F / 4, RPB = 256 / LPR;        // lanes per row, rows per block
+  const int b = blockIdx.x * RPB + (int)threadIdx.x / LPR, q = (int)threadIdx.x % LPR;
+  if (b >= B) return;
+  const float* src = pool + (size_t)xstart[b] * F + 4 * q;
+  for (int t = blockIdx.y; t < Tn; t += gridDim.y) {
+    const float4 v = *reinterpret_cast<const float4*>(src + (size_t)t * F);
+    *reinterpret_cast<float4*>(out + ((size_t)t * oT + (size_t)b * oB) * F + 4 * q) = v;
+  }
+}
+
 }  // namespace
 
 // ---- launchers (declared in common.h) -------------------------------------------------------------------------
+int gather_windows(int T, int B, int F, bool batch_major, const float* pool, const int32_t* start, float* out,
+                   hipStream_t s) {
+  if (F != 32 && F != 64) return FASTGRNN_ERR_UNSUPPORTED;
+  const unsigned oT = batch_major ? 1u : (unsigned)B, oB = batch_major ? (unsigned)T : 1u;
+  const unsigned gy = T < 65535 ? (unsigned)T : 65535u;
+  if (F == 32) hipLaunchKernelGGL(gather_windows_rows<32>, dim3((B + 31) / 32, gy), dim3(256), 0, s, T, B, oT, oB, pool, start, out);
+  else hipLaunchKernelGGL(gather_windows_rows<64>, dim3((B + 15) / 16, gy), dim3(256), 0, s, T, B, oT, oB, pool, start, out);
+  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+}
+
 bool rows_gemm_supported(int N, int K, bool trans_w) {
   // N * K <= 128 * 256: the weight planes of a wave's tiles (N * K * 12 / 512 registers per lane) fit beside the
   // fragments; N = 256 with K = 256 would spill (and spill reloads are loads: operand rule)

@@ -54,12 +54,14 @@ constexpr int SLAB2 = 576;                      // floats per workgroup: d_bz[25
 // `x` is the frame pool [R,32] or, under PREIN, the frame product of the whole pool P_pool[R,256] -- one GEMM row per
 // frame, not per frame and window.  The lane's base comes from xstart (loaded once, in front of the scan; lanes beyond
 // a ragged batch take utterance B-1's) and the step stride is one pool row, so P no longer follows the strides of hs;
-// hs is written through hsT / hsB as ever.  fp32, the reference's gates, AUX 0 / 3, one state product per gate.
+// hs is written through hsT / hsB as ever.  fp32, the reference's gates, AUX 0 / 3 and, for the plain cell, AUX 2
+// (fastgrnn_hip_forward_windows_train; zs follows hsT / hsB like hs), one state product per gate.
 // The instantiations the library holds (each with RAGGED false and true); launch_fwd builds exactly these.
 constexpr bool fwd_h256_built(int gate, int aux, int mode, bool prein, bool bf, bool aff, bool win = false) {
   const bool ref_gate = gate <= FASTGRNN_NL_TANH;
   if (mode != 0 && !gate_bounds_state(gate)) return false;
-  if (win) return ref_gate && !bf && (aux == 0 || aux == 3) && (mode != 0) == gate_bounds_state(gate);
+  // (AUX 2: fastgrnn_hip_forward_windows_train saves the pre-activation; the plain cell only)
+  if (win) return ref_gate && !bf && (aux == 0 || aux == 3 || (aux == 2 && !aff)) && (mode != 0) == gate_bounds_state(gate);
   if (aff) return ref_gate && !bf && (aux == 0 || aux == 3);
   if (bf) return ref_gate && (aux == 0 || aux == 2);
   return true;

@@ -1265,6 +1265,34 @@ bool windows_supported(const fastgrnn_desc& d) {
 // the H = 256 scans' flag words and, for F = 64, the frame product of the whole pool P_pool[R, 256]; 0 for H = 128
 size_t windows_ws(const fastgrnn_desc& d, size_t pool_rows) { return h256_shape(d) ? h256_windows_ws(d, pool_rows) : 0; }
 
+// fastgrnn_hip_forward_windows_train / fastgrnn_hip_backward_windows: the plain cells the windowed scans hold, under the
+// one-saved-tensor contract in both directions; FASTGRNN_FLAG_BATCH_MAJOR, and FASTGRNN_FLAG_GRAD_LAST for the backward
+bool train_windows_supported(const fastgrnn_desc& d) {
+  if (d.flags & ~(FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_GRAD_LAST)) return false;
+  fastgrnn_desc f = d, b = d;
+  f.flags &= ~FASTGRNN_FLAG_GRAD_LAST;
+  if (!windows_supported(f)) return false;
+  f.flags |= FASTGRNN_FLAG_SAVE_PREACT;
+  b.flags |= FASTGRNN_FLAG_SAVE_PREACT;
+  return split_supported(f, 0) && split_supported(b, 1);
+}
+
+// bytes of the gathered copy of x: at the end of the backward's workspace for every shape (the backward scans read no
+// pool in place) and, for H = 128, at the start of the forward's
+size_t train_windows_gather_bytes(const fastgrnn_desc& d) { return align256((size_t)d.T * d.B * d.F * 4); }
+
+// the training forward: the H = 256 scans read the pool in place (windows_ws); H = 128 runs the plain forward on a
+// gathered copy of x at the start of the workspace (this file holds no WIN scan that saves the pre-activation)
+size_t train_windows_forward_ws(const fastgrnn_desc& d, size_t pool_rows) {
+  return h256_shape(d) ? h256_windows_ws(d, pool_rows) : train_windows_gather_bytes(d);
+}
+
+size_t train_windows_backward_ws(const fastgrnn_desc& d) {
+  fastgrnn_desc b = d;
+  b.flags |= FASTGRNN_FLAG_SAVE_PREACT;
+  return split_backward_ws(b) + train_windows_gather_bytes(d);
+}
+
 size_t split_forward_ws(const fastgrnn_desc& d) {
   // wide layers: the frame product P = X.W^T goes to the auxiliary output the caller passes (z_s under SAVE_PREACT,
   // c_s otherwise); a forward without auxiliary outputs needs room for it.  The query cannot see the pointers, so
@@ -1292,7 +1320,17 @@ size_t split_backward_ws(const fastgrnn_desc& d) {
 
 int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
                    const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws,
-                   hipStream_t s) {
+                   hipStream_t s, const window_src* win) {
+  if (win) {                                         // fastgrnn_hip_backward_windows: no d_x, the one saved tensor
+    fastgrnn_desc c = d;
+    c.flags &= ~FASTGRNN_FLAG_SAVE_PREACT;
+    if (g.d_x || !(d.flags & FASTGRNN_FLAG_SAVE_PREACT) || !train_windows_supported(c)) return FASTGRNN_ERR_UNSUPPORTED;
+    // the windows as a copy of x behind the route's own workspace; the existing dispatch runs on it
+    float* xg = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + split_backward_ws(d));
+    const int st = gather_windows(d.T, d.B, d.F, (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0, (const float*)x, win->start, xg, s);
+    if (st != FASTGRNN_OK) return st;
+    x = xg;
+  }
   if (h256_shape(d)) return h256_backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s);
   if (lowrank_shape(d)) return lowrank_backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s);
   if (densified_shape(d)) return densified_backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s);
@@ -1302,7 +1340,20 @@ int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
 
 int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
                   void* zs, void* cs, void* ws, hipStream_t s, const void* sg_, const void* sc_, const window_src* win) {
-  if (win && (zs || cs || !windows_supported(d))) return FASTGRNN_ERR_UNSUPPORTED;
+  if (win) {
+    // fastgrnn_hip_forward_windows: nothing saved; fastgrnn_hip_forward_windows_train: the pre-activation through zs
+    fastgrnn_desc c = d;
+    c.flags &= ~FASTGRNN_FLAG_SAVE_PREACT;
+    const bool train = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
+    if (cs || (zs != nullptr) != train || !(train ? train_windows_supported(c) : windows_supported(d))) return FASTGRNN_ERR_UNSUPPORTED;
+    if (train && !h256_shape(d)) {                   // H = 128: the plain forward on a gathered copy of x in the workspace
+      if (!ws) return FASTGRNN_ERR_WORKSPACE;
+      const int st = gather_windows(d.T, d.B, d.F, (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0, (const float*)x, win->start, (float*)ws, s);
+      if (st != FASTGRNN_OK) return st;
+      x = ws;
+      win = nullptr;
+    }
+  }
   if (!(d.flags & FASTGRNN_FLAG_SAVE_PREACT) && (zs == nullptr) != (cs == nullptr)) return FASTGRNN_ERR_NULL_POINTER;
   if (d.dtype == FASTGRNN_BF16_IO && zs && !(d.flags & FASTGRNN_FLAG_SAVE_PREACT)) return FASTGRNN_ERR_UNSUPPORTED;
   const float* sg = reinterpret_cast<const float*>(sg_);

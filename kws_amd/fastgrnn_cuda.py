@@ -594,19 +594,13 @@ def forward_windows(pool, starts, T, w, u, bias_gate, bias_update, zeta, nu, ini
     B, T = starts.numel(), int(T)
     H = initial_h.shape[-1]
     _expect(initial_h, (B, H), "initial_h")
-    if T < 1 or T > R:
-        raise ValueError("forward_windows: window length T=%d does not fit a pool of %d frames" % (T, R))
+    check_starts_range(starts if check else starts[:0], R, T)
     for t, n in named[3:]:
         if t.numel() != H:
             raise RuntimeError("%s must hold H=%d elements" % (n, H))
     for t in (initial_h,) + ((gate_scale, update_scale) if affine else ()):
         if t.dtype != _param_dtype(pool.dtype):
             raise RuntimeError("fastgrnn: all operands must share dtype %s (got %s)" % (_param_dtype(pool.dtype), t.dtype))
-    if check and B:
-        lo, hi = torch.stack(torch.aminmax(starts)).tolist()        # one device-to-host copy
-        if lo < 0 or hi > R - T:
-            raise ValueError("forward_windows: starts must lie in [0, %d] (pool of %d frames, T=%d); got [%d, %d]"
-                             % (R - T, R, T, lo, hi))
     if starts.dtype != torch.int32:
         starts = starts.to(torch.int32)
     flags = (_lib.FLAG_BATCH_MAJOR if batch_major else 0) | (_lib.FLAG_HS_LAST if last_state else 0) | \
@@ -627,6 +621,145 @@ def forward_windows(pool, starts, T, w, u, bias_gate, bias_update, zeta, nu, ini
         _lib.check(st, "fastgrnn forward_windows")
         del ws
     return hs
+
+
+@functools.lru_cache(maxsize=1024)
+def _train_windows_plan(T, B, F, H, rw, ru, gate_nl, update_nl, dtype_code, flags, rows):
+    """(descriptor, the training calls over windows hold it, forward workspace bytes, backward workspace bytes) for a
+    pool of ``rows`` frames: pure functions of the descriptor in the C ABI, asked once per signature like ``_plan``.
+    ``flags``: FLAG_BATCH_MAJOR, and FLAG_GRAD_LAST for a backward that takes the last state's gradient."""
+    desc = _lib.Desc(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), dtype_code, int(flags))
+    lib = _lib.load()
+    ok = bool(lib.fastgrnn_hip_train_windows_supported(C.byref(desc)))
+    if not ok:
+        return desc, False, 0, 0
+    return (desc, True, int(lib.fastgrnn_hip_train_windows_forward_workspace_bytes(C.byref(desc), rows)),
+            int(lib.fastgrnn_hip_train_windows_backward_workspace_bytes(C.byref(desc), rows)))
+
+
+def train_windows_supported(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=torch.float32, flags=0):
+    """``forward_windows_train`` / ``backward_windows`` run this descriptor (include/fastgrnn_hip.h,
+    ``fastgrnn_hip_train_windows_supported``); where they do not, ``FastGRNNCUDA.unroll_windows`` gathers the windows
+    and calls the existing forward.  ``flags``: FLAG_BATCH_MAJOR / FLAG_GRAD_LAST."""
+    if dtype not in _DTYPES:
+        return False
+    return _train_windows_plan(T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype], int(flags), T)[1]
+
+
+def check_starts_range(starts, R, T):
+    """The one host range check of every windowed call (``forward_windows``, ``forward_windows_train``,
+    ``rnn.gather_windows``): ``T`` fits the pool and ``0 <= starts[b] <= R - T``, with one ``aminmax`` (one
+    device-to-host copy); ``ValueError`` otherwise.  An empty ``starts`` checks ``T`` alone (``check=False``)."""
+    if T < 1 or T > R:
+        raise ValueError("forward_windows: window length T=%d does not fit a pool of %d frames" % (T, R))
+    if starts.numel():
+        lo, hi = torch.stack(torch.aminmax(starts)).tolist()
+        if lo < 0 or hi > R - T:
+            raise ValueError("forward_windows: starts must lie in [0, %d] (pool of %d frames, T=%d); got [%d, %d]"
+                             % (R - T, R, T, lo, hi))
+
+
+def _windows_operands(pool, starts, T, initial_h, bias_gate, bias_update, check):
+    """The argument checks the windowed training calls share (those of ``forward_windows``); (R, F, B, T, H, starts
+    as int32)."""
+    named = [(pool, "pool"), (starts, "starts"), (initial_h, "initial_h"), (bias_gate, "bias_gate"),
+             (bias_update, "bias_update")]
+    for t, n in named:
+        _check_input(t, n)
+    if pool.dim() != 2:
+        raise RuntimeError("pool must be [frames, features]")
+    if starts.dim() != 1 or starts.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("starts must be a 1-D int32 or int64 tensor")
+    if starts.device != pool.device:
+        raise RuntimeError("starts must be on the pool's device")
+    R, F = pool.shape
+    B, T = starts.numel(), int(T)
+    H = initial_h.shape[-1]
+    _expect(initial_h, (B, H), "initial_h")
+    check_starts_range(starts if check else starts[:0], R, T)
+    for t, n in named[3:]:
+        if t.numel() != H:
+            raise RuntimeError("%s must hold H=%d elements" % (n, H))
+    if initial_h.dtype != _param_dtype(pool.dtype):
+        raise RuntimeError("fastgrnn: all operands must share dtype %s (got %s)" % (_param_dtype(pool.dtype), initial_h.dtype))
+    if starts.dtype != torch.int32:
+        starts = starts.to(torch.int32)
+    return R, F, B, T, H, starts
+
+
+def forward_windows_train(pool, starts, T, w, u, bias_gate, bias_update, zeta, nu, initial_h, z_non_linearity,
+                          batch_major=False, check=True, *, update_non_linearity=2):
+    """Training forward over windows of a shared frame pool (include/fastgrnn_hip.h,
+    ``fastgrnn_hip_forward_windows_train``): utterance ``b`` is the ``T`` consecutive rows of ``pool:[R,F]`` from row
+    ``starts[b]`` on (H=256 reads the pool in place, H=128 gathers into the call's workspace).  Returns
+    ``(hs, saved)``: the hidden states ``[T,B,H]`` (``[B,T,H]`` with ``batch_major``) and the fp32 pre-activation in the same layout, the one tensor ``backward_windows`` needs -- both
+    bit for bit what ``forward_unroll(..., flags=FLAG_SAVE_PREACT)`` returns for the gathered windows.  ``starts`` and
+    ``check`` as in ``forward_windows``.  Cells the calls do not hold (``train_windows_supported``) raise: there is no
+    eager fallback here."""
+    lib = _lib.load()
+    R, F, B, T, H, starts = _windows_operands(pool, starts, T, initial_h, bias_gate, bias_update, check)
+    flags = _lib.FLAG_BATCH_MAJOR if batch_major else 0
+    plan, params, _, _ = _describe(T, B, F, H, w, u, None, None, None, None, bias_gate, bias_update, zeta, nu,
+                                   pool.dtype, z_non_linearity, update_non_linearity, flags)
+    d = plan.desc
+    _, _, nbytes, _ = _train_windows_plan(T, B, F, H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, flags, R)
+    dev = pool.device
+    shape = (B, T, H) if batch_major else (T, B, H)
+    with torch.cuda.device(dev):
+        hs = torch.empty(shape, dtype=pool.dtype, device=dev)
+        saved = torch.empty(shape, dtype=torch.float32, device=dev)
+        ws, wsp = _workspace(nbytes, dev)
+        with _Timed("forward_windows_train", dev):
+            st = lib.fastgrnn_hip_forward_windows_train(C.byref(d), C.byref(params), _ptr(pool), R, _ptr(starts),
+                                                        _ptr(initial_h), _ptr(hs), _ptr(saved), wsp, nbytes,
+                                                        _stream(dev))
+        _lib.check(st, "fastgrnn forward_windows_train")
+        del ws
+    return hs, saved
+
+
+def backward_windows(grad_h, pool, starts, T, hidden_states, saved, zeta, nu, w, u, bias_gate, bias_update, initial_h,
+                     z_non_linearity, batch_major=False, grad_last=False, *, update_non_linearity=2):
+    """Backward of ``forward_windows_train`` (include/fastgrnn_hip.h, ``fastgrnn_hip_backward_windows``).  ``grad_h``:
+    the layout of ``hidden_states``, or ``[B,H]`` with ``grad_last`` (the gradient of the last state alone).  Returns
+    the 12-tuple of ``backward_unroll`` with an empty ``d_input``: the gradient with respect to the pool is a
+    scatter-add over overlapping windows and is not built.  The parameter gradients are views of one flat buffer, as
+    in ``backward_unroll``.  ``starts`` must be the (range-checked) starts of the forward."""
+    lib = _lib.load()
+    for t, n in ((grad_h, "grad_h"), (hidden_states, "hidden_states"), (saved, "saved")):
+        _check_input(t, n)
+    R, F, B, T, H, starts = _windows_operands(pool, starts, T, initial_h, bias_gate, bias_update, False)
+    lead = (B, T) if batch_major else (T, B)
+    _expect(grad_h, (B, H) if grad_last else lead + (H,), "grad_h")
+    _expect(hidden_states, lead + (H,), "hidden_states")
+    _expect(saved, lead + (H,), "saved")
+    if grad_h.dtype != pool.dtype or hidden_states.dtype != pool.dtype or saved.dtype != _param_dtype(pool.dtype):
+        raise RuntimeError("fastgrnn backward: operand dtypes differ")
+    flags = (_lib.FLAG_BATCH_MAJOR if batch_major else 0) | (_lib.FLAG_GRAD_LAST if grad_last else 0)
+    plan, params, _, _ = _describe(T, B, F, H, w, u, None, None, None, None, bias_gate, bias_update, zeta, nu,
+                                   pool.dtype, z_non_linearity, update_non_linearity, flags)
+    d = plan.desc
+    _, _, _, nbytes = _train_windows_plan(T, B, F, H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, flags, R)
+    dev = pool.device
+    pdt = initial_h.dtype
+    shapes = [(H, F), (H, H), (1, H), (1, H), (1, 1), (1, 1)]
+    sizes = [a * b for a, b in shapes]
+    with torch.cuda.device(dev):
+        none = _NONE
+        d_old_h = torch.empty((B, H), dtype=pdt, device=dev)
+        flat = torch.empty(sum(sizes), dtype=pdt, device=dev)
+        d_w, d_u, d_bz, d_bh, d_zeta, d_nu = [v.view(sh) for v, sh in zip(flat.split(sizes), shapes)]
+        del flat
+        grads = _lib.Grads(_ptr(none), _ptr(d_bz), _ptr(d_bh), _ptr(d_zeta), _ptr(d_nu), _ptr(d_old_h),
+                           _ptr(d_w), _ptr(d_u), _ptr(none), _ptr(none), _ptr(none), _ptr(none))
+        ws, wsp = _workspace(nbytes, dev)
+        with _Timed("backward_windows", dev):
+            st = lib.fastgrnn_hip_backward_windows(C.byref(d), C.byref(params), _ptr(grad_h), _ptr(pool), R,
+                                                   _ptr(starts), _ptr(hidden_states), _ptr(saved), _ptr(initial_h),
+                                                   C.byref(grads), wsp, nbytes, _stream(dev))
+        _lib.check(st, "fastgrnn backward_windows")
+        del ws
+    return [none, d_bz, d_bh, d_zeta, d_nu, d_old_h, d_w, d_u, none, none, none, none]
 
 
 def backward_unroll(grad_h, input, hidden_states, zeta, nu, w, u, z, h_prime, initial_h, w1, w2, u1, u2,

@@ -36,7 +36,8 @@ import torch.nn.functional as F
 from .batchnorm import FastGRNNBatchNorm
 from .batchnorm_train import FastGRNNBatchNormCUDA
 from .head import keyword_loss
-from .rnn import FastGRNNCUDA
+from .fastgrnn_cuda import check_starts_range
+from .rnn import FastGRNNCUDA, gather_windows
 
 _RNN_CLASSES = {"FastGRNNCUDA": FastGRNNCUDA, "FastGRNNBatchNorm": FastGRNNBatchNorm,     # model.py:12-15
                 "FastGRNNBatchNormCUDA": FastGRNNBatchNormCUDA}
@@ -103,13 +104,17 @@ class RNNClassifierModel(nn.Module):
         self.hidden_states = [None] * self.num_layers
 
     # ---- the hot path ------------------------------------------------------------------------------------
-    def _last_state(self, input):
-        """Layers chained as model.py:196-203 does; returns the top layer's final state [B, H_top]."""
+    def _last_state(self, input, windows=None):
+        """Layers chained as model.py:196-203 does; returns the top layer's final state [B, H_top].  ``windows``:
+        ``(pool, starts, T)`` -- layer 0 reads the batch as windows of a frame pool (``unroll_windows``; ``input`` is
+        not used then)."""
         rnn_in = input
         top = self.num_layers - 1
         for l, rnn in enumerate(self.rnn_list):
             if self._batchnorm:                          # (model.py:211-215: the layers take the model's mode)
                 out = rnn(rnn_in, hiddenState=self.hidden_states[l], training=self.training, last_state=(l == top))
+            elif l == 0 and windows is not None:
+                out = rnn.unroll_windows(*windows, hiddenState=self.hidden_states[0], last_state=(top == 0), check=False)
             else:
                 out = rnn(rnn_in, hiddenState=self.hidden_states[l], last_state=(l == top))
             # (bf16 sequences: the state a layer carries over is fp32, like the one it starts from)
@@ -172,4 +177,29 @@ class RNNClassifierModel(nn.Module):
         if not (self.linear and self.apply_softmax):
             raise RuntimeError("loss() is the Linear + log_softmax + NLLLoss tail (linear=True, apply_softmax=True)")
         h_last = self._last_state(input)
+        return keyword_loss(h_last, self.hidden2keyword.weight, self.hidden2keyword.bias, labels)
+
+    def loss_windows(self, pool, starts, labels, window=99):
+        """``loss()`` on the batch whose utterance ``b`` is the ``window`` consecutive rows of ``pool:[R,F]`` from row
+        ``starts[b]`` on -- a training step from a frame pool that lives on the device: the batch is ``B`` start rows
+        (random time-shift crops are other start rows), with no host batch assembly and no ``[B,T,F]`` tensor kept for
+        the backward.  Layer 0 goes through ``FastGRNNCUDA.unroll_windows``; the layers above and the fused head run
+        as in ``loss()``, and ``hidden_states`` is carried exactly as there.  The starts' range is checked once here
+        (``ValueError``).  BatchNorm model families gather the windows in front of layer 0: training-mode BatchNorm
+        over windows is not built."""
+        if self.rnn_name == "FastGRNNBatchNorm":
+            raise NotImplementedError("loss() trains FastGRNNCUDA models; FastGRNNBatchNorm runs in eval mode only")
+        if not (self.linear and self.apply_softmax):
+            raise RuntimeError("loss() is the Linear + log_softmax + NLLLoss tail (linear=True, apply_softmax=True)")
+        window = int(window)
+        if self._batchnorm:
+            x = gather_windows(pool.to(self.rnn_list[0].device), starts.to(self.rnn_list[0].device), window)
+            h_last = self._last_state(x if self.batch_first else x.transpose(0, 1).contiguous())
+        else:
+            if pool.requires_grad:
+                raise ValueError("loss_windows: the pool must not require grad (unroll_windows)")
+            dev = self.rnn_list[0].device
+            pool, starts = pool.to(dev), starts.to(dev)
+            check_starts_range(starts, pool.shape[0], window)
+            h_last = self._last_state(None, windows=(pool, starts, window))
         return keyword_loss(h_last, self.hidden2keyword.weight, self.hidden2keyword.bias, labels)

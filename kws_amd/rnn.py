@@ -79,14 +79,8 @@ def _on_path2(input, T, B, F, H, w1, u1, gate_non_linearity, direction, flags):
 def gather_windows(pool, starts, T, check=True):
     """``[B,T,F]``: window ``b`` = rows ``starts[b] .. starts[b]+T-1`` of ``pool:[R,F]``, materialised (what
     ``forward_windows`` avoids where the windowed scans hold the cell)."""
-    R, T = pool.shape[0], int(T)
-    if T < 1 or T > R:
-        raise ValueError("forward_windows: window length T=%d does not fit a pool of %d frames" % (T, R))
-    if check and starts.numel():
-        lo, hi = torch.stack(torch.aminmax(starts)).tolist()
-        if lo < 0 or hi > R - T:
-            raise ValueError("forward_windows: starts must lie in [0, %d] (pool of %d frames, T=%d); got [%d, %d]"
-                             % (R - T, R, T, lo, hi))
+    T = int(T)
+    fastgrnn_cuda.check_starts_range(starts if check else starts[:0], pool.shape[0], T)
     return pool[starts.long()[:, None] + torch.arange(T, device=pool.device)]
 
 
@@ -185,6 +179,42 @@ class FastGRNNUnrollFunction(Function):
         if ctx.flags & _lib.FLAG_X_BFT:                 # d_input was produced as [B,F,T]: hand back the [T,B,F] view
             outputs = [outputs[0].permute(2, 0, 1) if outputs[0].numel() else outputs[0]] + list(outputs[1:])
         return _as_autograd_grads(outputs, ctx.needs_input_grad) + (None, None)
+
+
+class FastGRNNWindowsFunction(Function):
+    """Autograd glue over ``fastgrnn_cuda.forward_windows_train`` / ``backward_windows``: the unrolled cell on windows
+    of a frame pool, differentiable with respect to the parameters and the initial state.  The pool is data: it gets no
+    gradient (that would be a scatter-add over overlapping windows, which is not built), and nothing but the pool
+    itself and the ``[B]`` starts is kept of the input between the two passes."""
+
+    @staticmethod
+    def forward(ctx, pool, starts, T, bias_gate, bias_update, zeta, nu, old_h, w, u, gate_non_linearity, batch_major,
+                last_state, check):
+        old_h = old_h.contiguous()
+        if starts.dtype != torch.int32:
+            if check:                                    # (checked here, on the caller's values: the cast could wrap)
+                fastgrnn_cuda.check_starts_range(starts, pool.shape[0], int(T))
+                check = False
+            starts = starts.to(torch.int32)
+        hs, saved = fastgrnn_cuda.forward_windows_train(pool, starts, T, w, u, bias_gate, bias_update, zeta, nu, old_h,
+                                                        gate_non_linearity, batch_major=batch_major, check=check)
+        ctx.save_for_backward(pool, starts, hs, saved, zeta, nu, w, u, bias_gate, bias_update, old_h)
+        ctx.T, ctx.gate_non_linearity = int(T), gate_non_linearity
+        ctx.batch_major, ctx.last_state = bool(batch_major), bool(last_state)
+        if last_state:
+            return (hs[:, -1] if batch_major else hs[-1]).clone()
+        return hs
+
+    @staticmethod
+    def backward(ctx, grad_h):
+        pool, starts, hs, saved, zeta, nu, w, u, bias_gate, bias_update, old_h = ctx.saved_tensors
+        g = fastgrnn_cuda.backward_windows(grad_h.contiguous(), pool, starts, ctx.T, hs, saved, zeta, nu, w, u,
+                                           bias_gate, bias_update, old_h, ctx.gate_non_linearity,
+                                           batch_major=ctx.batch_major, grad_last=ctx.last_state)
+        # (pool, starts, T, bias_gate, bias_update, zeta, nu, old_h, w, u, nl, batch_major, last_state, check)
+        grads = [None, None, None, g[1], g[2], g[3], g[4], g[5], g[6], g[7]]
+        grads = [v if need else None for v, need in zip(grads, ctx.needs_input_grad[:10])]
+        return tuple(grads) + (None, None, None, None)
 
 
 def _as_autograd_grads(outputs, needs):
@@ -509,6 +539,36 @@ class FastGRNNCUDA(nn.Module):
                                                  batch_major=bm, last_state=last_state, check=check)
         windows = gather_windows(pool, starts, T, check)                       # [B,T,F]
         return self.forward(windows if bm else windows.transpose(0, 1).contiguous(), hiddenState=h0,
+                            last_state=last_state)
+
+    def unroll_windows(self, pool, starts, T, hiddenState=None, last_state=False, check=True):
+        """Training on windows of a shared frame pool (not in the reference): utterance ``b`` is the ``T`` consecutive
+        rows of ``pool:[R,F]`` from row ``starts[b]`` on, so a batch is ``B`` start rows -- no assembled ``[B,T,F]``
+        batch, and random time-shift crops are other start rows.  Returns what ``forward`` returns for the gathered
+        batch -- hs ``[T,B,H]`` (``[B,T,H]`` with ``batch_first``) or h_T ``[B,H]`` with ``last_state`` -- differentiable
+        with respect to the parameters and ``hiddenState``.  The pool is data and gets no gradient (a scatter-add over
+        overlapping windows, not built): a pool that requires grad raises ``ValueError``.  ``check`` as in
+        ``forward_windows``.  Where the training calls hold the cell (``fastgrnn_cuda.train_windows_supported``) the
+        library reads the pool itself and no ``[B,T,F]`` batch is kept; elsewhere (factorised weights, other sizes,
+        bf16, fp64) the windows are gathered and ``forward`` runs them: exactly ``forward(gather_windows(...))``."""
+        if pool.requires_grad:
+            raise ValueError("unroll_windows: the pool must not require grad -- its gradient is a scatter-add over "
+                             "overlapping windows, which is not built (the pool is a model's input data)")
+        pool = pool.to(self.device) if not pool.is_cuda else pool
+        starts = starts.to(pool.device)
+        B, H, T = starts.numel(), self._hidden_size, int(T)
+        bm = self.batch_first is True
+        flags = (_lib.FLAG_BATCH_MAJOR if bm else 0) | (_lib.FLAG_GRAD_LAST if last_state else 0)
+        if pool.is_cuda and pool.dim() == 2 and fastgrnn_cuda.train_windows_supported(
+                T, B, pool.shape[1], H, self.W1.shape[0] if self.W1.numel() else 0,
+                self.U1.shape[0] if self.U1.numel() else 0, self._gate_non_linearity, 2, pool.dtype, flags):
+            h0 = torch.zeros([B, H], dtype=pool.dtype, device=pool.device) if hiddenState is None \
+                else hiddenState.to(pool.device)
+            return FastGRNNWindowsFunction.apply(pool.contiguous(), starts, T, self.bias_gate, self.bias_update,
+                                                 self.zeta, self.nu, h0, self.W, self.U, self._gate_non_linearity,
+                                                 bm, bool(last_state), bool(check))
+        windows = gather_windows(pool, starts, T, check)                       # [B,T,F]
+        return self.forward(windows if bm else windows.transpose(0, 1).contiguous(), hiddenState=hiddenState,
                             last_state=last_state)
 
     def getVars(self):
