@@ -292,7 +292,9 @@ __global__ __launch_bounds__(512) void fwd_scan_split_w8(
   // does not bound h at all).  For those,  |h_t| <= z|h_{t-1}| + sigma(zeta)(1-z) + sigma(nu)
   //                                              <= max(|h_{t-1}|, sigma(zeta)) + sigma(nu),
   // i.e. |h_t| <= max(|h0|, 1) + t: the workgroup checks its own 16 rows of h0 against that bound here and
-  // falls back to the three-bf16-plane product (no range limit) when a user-supplied h0 is too large (or NaN).
+  // falls back to the three-bf16-plane product (no range limit) when a user-supplied h0 is too large, or NaN in all
+  // four units of a lane (a whole row, say).  A lone NaN is dropped by the fmaxf over the lane's units and the tile keeps
+  // the fp16 form; the NaN goes through its utterance's fp16 planes and makes that utterance NaN there as well.
   // Two planes resolve 2^-22 of the value anywhere in range (lo subnormal below 2^-14: absolute 2^-24), and U is
   // pre-scaled per wave by an exact power of two that puts its largest element in [2^12, 2^13), undone by one
   // fma in the epilogue.  W.x keeps the three bf16 planes: x is unbounded user data.

@@ -13,24 +13,31 @@ SHAPES = [(99, 64, 256, 128, 1), (99, 50, 256, 128, 1), (23, 37, 256, 128, 0), (
           (8, 33, 128, 128, 1), (7, 50, 256, 128, 0), (7, 32, 64, 128, 1), (7, 33, 32, 128, 1), (7, 33, 32, 128, 0),
           # low-rank (6th entry = rank) and H=256 ragged batches
           (9, 33, 32, 256, 1, 16), (7, 50, 32, 256, 1, 8), (8, 17, 32, 256, 1, 16), (9, 33, 32, 256, 1), (8, 50, 32, 256, 0),
-          (7, 37, 32, 256, 1, 32)]                     # rank 32: factors multiplied out, dense H=256 kernels
+          (7, 37, 32, 256, 1, 32),                     # rank 32: factors multiplied out, dense H=256 kernels
+          # dense H=256 with a mixed h0 (7th entry): the middle tile of 16 utterances is outside fp16's range, so the fp16
+          # launch (MODE 1) hands that workgroup to the three-bf16-plane launch behind it (MODE 2); U is scaled to match
+          (5, 37, 32, 256, 1, 0, "mixed_h0")]
 if os.environ.get("REPRO_BIG"):
     # full-size ragged batches (255 full workgroups + one with 10 utterances): what the last batch of an epoch looks like
     SHAPES += [(99, 4090, 32, 128, 1), (99, 4090, 32, 128, 0), (99, 4090, 256, 128, 1), (99, 4090, 32, 256, 1),
                (99, 4090, 32, 256, 1, 16), (99, 4096, 32, 128, 1), (99, 4096, 32, 256, 1, 16)]
 
 
-def make(T, B, F, H, seed, r=0):
+def make(T, B, F, H, seed, r=0, mixed_h0=False):
     torch.manual_seed(seed)
     if r:
         fac = dict(w=e, u=e, w1=0.1 * torch.randn(r, F, device=dev), w2=0.1 * torch.randn(H, r, device=dev),
                    u1=0.1 * torch.randn(r, H, device=dev), u2=0.1 * torch.randn(H, r, device=dev))
     else:
         fac = dict(w=0.1 * torch.randn(H, F, device=dev), u=0.1 * torch.randn(H, H, device=dev), w1=e, w2=e, u1=e, u2=e)
-    return dict(fac,
+    d = dict(fac,
                 bz=torch.randn(1, H, device=dev), bh=torch.randn(1, H, device=dev), zeta=torch.ones(1, 1, device=dev),
                 nu=-4 * torch.ones(1, 1, device=dev), x=torch.randn(T, B, F, device=dev),
                 h0=0.3 * torch.randn(B, H, device=dev), G=torch.randn(T, B, H, device=dev))
+    if mixed_h0:                                   # (drawn last: the other shapes keep the data they always had)
+        d["h0"][16:32] = 1e5 * torch.where(torch.randn(16, H, device=dev) < 0, -1.0, 1.0)
+        d["u"] = d["u"] * 1e-5
+    return d
 
 
 def run(d, fl):
@@ -50,7 +57,7 @@ if BF16:
 if os.environ.get("REPRO_SHORT"):
     SHAPES = SHAPES[:15]
 POISON = [int(v, 0) for v in os.environ.get("REPRO_POISON", "").split(",") if v]
-data = [make(sh[0], sh[1], sh[2], sh[3], 10 + k, sh[5] if len(sh) > 5 else 0) for k, sh in enumerate(SHAPES)]
+data = [make(sh[0], sh[1], sh[2], sh[3], 10 + k, sh[5] if len(sh) > 5 else 0, len(sh) > 6) for k, sh in enumerate(SHAPES)]
 if BF16:
     for d_ in data:
         d_["x"], d_["G"] = d_["x"].to(torch.bfloat16), d_["G"].to(torch.bfloat16)
