@@ -27,7 +27,7 @@ from torch.autograd import Function
 
 from . import _lib
 from .batchnorm import FastGRNNBatchNorm
-from .fastgrnn_cuda import _ptr, _stream, _workspace
+from .fastgrnn_cuda import _call, _params, _pool_plan, _ptr
 
 _warned = set()
 
@@ -43,16 +43,17 @@ def _bn_struct(cell, forward=True):
     return _lib.BnParams(*(_bn_layer(bn, forward) for bn in (cell.bn_w, cell.bn_u, cell.bn_gate, cell.bn_update)))
 
 
-def _desc(T, B, F, H, gate_code, batch_major):
+def _plan(T, B, F, H, gate_code, batch_major):
+    """The cached descriptor of a training step with what the library answers for it (fastgrnn_cuda._pool_plan)."""
     flags = _lib.FLAG_BN_TRAIN | (_lib.FLAG_BATCH_MAJOR if batch_major else 0)
-    return _lib.Desc(T, B, F, H, 0, 0, int(gate_code), 2, _lib.F32, flags)
+    return _pool_plan((T, B, F, H, 0, 0, int(gate_code), 2, _lib.F32, flags), "bn_train")
 
 
 def bn_train_supported(T, B, F, H, gate_code=0, dtype=torch.float32, batch_major=False):
     """True where the training step runs on the fused kernels (fastgrnn_hip_bn_train_supported)."""
     if dtype != torch.float32:
         return False
-    return bool(_lib.load().fastgrnn_hip_bn_train_supported(C.byref(_desc(T, B, F, H, gate_code, batch_major))))
+    return _plan(T, B, F, H, gate_code, batch_major).supported
 
 
 class _BatchNormTrain(Function):
@@ -66,22 +67,20 @@ class _BatchNormTrain(Function):
         else:
             T, B, F = x.shape
         H = cell._hidden_size
-        desc = _desc(T, B, F, H, cell._gate_code, batch_major)
+        plan = _plan(T, B, F, H, cell._gate_code, batch_major)
         dev = x.device
         w = W.detach().t().contiguous()
         u = U.detach().t().contiguous()
         bgate, bupd = bias_gate.detach().contiguous(), bias_update.detach().contiguous()
-        params = _lib.Params(_ptr(w), _ptr(u), None, None, None, None, _ptr(bgate), _ptr(bupd), _ptr(zeta), _ptr(nu))
+        params = _params(False, False, w, u, None, None, None, None, bgate, bupd, zeta, nu)
         bnp = _bn_struct(cell, True)
         with torch.cuda.device(dev):
             hs = torch.empty(tuple(x.shape[:2]) + (H,), dtype=x.dtype, device=dev)
             saved = torch.empty(T, B, H, dtype=torch.float32, device=dev)
             stats = torch.empty(T, 9 * H, dtype=torch.float64, device=dev)
-            nbytes = int(lib.fastgrnn_hip_bn_train_forward_workspace_bytes(C.byref(desc)))
-            _, wsp = _workspace(nbytes, dev)
-            _lib.check(lib.fastgrnn_hip_bn_train_forward(C.byref(desc), C.byref(params), C.byref(bnp), _ptr(x),
-                                                         _ptr(h0), _ptr(hs), _ptr(saved), _ptr(stats), wsp, nbytes,
-                                                         _stream(dev)), "fastgrnn_hip_bn_train_forward")
+            _call(lib.fastgrnn_hip_bn_train_forward, "fastgrnn_hip_bn_train_forward", None, dev, plan.ws_forward,
+                  C.byref(plan.desc), C.byref(params), C.byref(bnp), _ptr(x), _ptr(h0), _ptr(hs), _ptr(saved),
+                  _ptr(stats))
             with torch.no_grad():
                 for bn in (cell.bn_w, cell.bn_u, cell.bn_gate, cell.bn_update):
                     bn.num_batches_tracked.add_(T)
@@ -95,10 +94,10 @@ class _BatchNormTrain(Function):
         lib = _lib.load()
         x, h0, hs, saved, stats, w, u, bgate, bupd, zeta, nu, gw, bw, gu, bu, gg, bg, gc, bc = ctx.saved_tensors
         T, B, F, H, gate_code, batch_major = ctx.desc_args
-        desc = _desc(T, B, F, H, gate_code, batch_major)
+        plan = _plan(T, B, F, H, gate_code, batch_major)
         dev = x.device
         grad_hs = grad_hs.contiguous()
-        params = _lib.Params(_ptr(w), _ptr(u), None, None, None, None, _ptr(bgate), _ptr(bupd), _ptr(zeta), _ptr(nu))
+        params = _params(False, False, w, u, None, None, None, None, bgate, bupd, zeta, nu)
         layers = []
         for (g_, b_), (eps, mom) in zip(((gw, bw), (gu, bu), (gg, bg), (gc, bc)), ctx.eps_mom):
             layers.append(_lib.BnLayer(_ptr(g_), _ptr(b_), None, None, None, float(eps),
@@ -113,12 +112,9 @@ class _BatchNormTrain(Function):
             grads = _lib.Grads(_ptr(d_x), _ptr(d_bg), _ptr(d_bu), _ptr(d_zeta), _ptr(d_nu), _ptr(d_h0), _ptr(d_w),
                                _ptr(d_u), None, None, None, None)
             bgr = _lib.BnGrads(*(_ptr(t) for t in dbn))
-            nbytes = int(lib.fastgrnn_hip_bn_train_backward_workspace_bytes(C.byref(desc)))
-            _, wsp = _workspace(nbytes, dev)
-            _lib.check(lib.fastgrnn_hip_bn_train_backward(C.byref(desc), C.byref(params), C.byref(bnp), _ptr(grad_hs),
-                                                          _ptr(x), _ptr(hs), _ptr(saved), _ptr(stats), _ptr(h0),
-                                                          C.byref(grads), C.byref(bgr), wsp, nbytes, _stream(dev)),
-                       "fastgrnn_hip_bn_train_backward")
+            _call(lib.fastgrnn_hip_bn_train_backward, "fastgrnn_hip_bn_train_backward", None, dev, plan.ws_backward,
+                  C.byref(plan.desc), C.byref(params), C.byref(bnp), _ptr(grad_hs), _ptr(x), _ptr(hs), _ptr(saved),
+                  _ptr(stats), _ptr(h0), C.byref(grads), C.byref(bgr))
         return (None, d_x, d_h0, None, d_w.t(), d_u.t(), d_bg.reshape(bgate.shape), d_bu.reshape(bupd.shape),
                 d_zeta.reshape(zeta.shape), d_nu.reshape(nu.shape), *dbn)
 

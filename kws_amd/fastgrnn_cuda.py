@@ -49,13 +49,14 @@ class _Timed:
         self.tag, self.device = tag, device
 
     def __enter__(self):
-        if _timing is not None:
+        self.on = _timing is not None and self.tag is not None     # (tag None: a call that records no sample)
+        if self.on:
             self.e0 = torch.cuda.Event(enable_timing=True)
             self.e1 = torch.cuda.Event(enable_timing=True)
             self.e0.record(torch.cuda.current_stream(self.device))
 
     def __exit__(self, *exc):
-        if _timing is not None:
+        if self.on:
             self.e1.record(torch.cuda.current_stream(self.device))
             _timing.append((self.tag, self.e0, self.e1))
         return False
@@ -139,21 +140,45 @@ def _seq_dims(input, flags):
     return T, B, F
 
 
+def _seq_shape(T, B, H, batch_major, last):
+    """The shape of an unrolled call's hidden states: every state in the input's layout, or the last one alone."""
+    return (B, H) if last else (B, T, H) if batch_major else (T, B, H)
+
+
+def _desc(T, B, F, H, rw, ru, gate_nl, update_nl, dtype_code, flags):
+    """The C descriptor (the one place it is built); its arguments are the key of every per-descriptor cache."""
+    return _lib.Desc(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), dtype_code, int(flags))
+
+
+def _key(d):
+    return d.T, d.B, d.F, d.H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, d.flags
+
+
 # Scratch workspace, kept per (device, stream) and grown on demand: its contents never outlive a call and every use
 # is stream-ordered, so consecutive calls on one stream can share it (a fresh torch.empty per call was a few
 # microseconds of host time per step; the 8-GPU step adds the collective's latency on top of whatever the host spends)
 _ws_cache = {}
 
+_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or \
+    (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
 
-def _workspace(nbytes, device):
-    if nbytes == 0:
-        return None, C.c_void_p(None)
-    key = (device.index, _raw_stream(device))
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-        _ws_cache[key] = ws
-    return ws, C.c_void_p(ws.data_ptr())
+
+def _call(fn, what, tag, dev, nbytes, *args):
+    """The launch path of every C-ABI call: ``fn(*args, workspace, nbytes, stream)`` on torch's current stream of
+    ``dev`` (``nbytes=None``: ``fn(*args, stream)``, a call without a workspace), timed under ``tag`` (``_timing``) and
+    its status checked as ``what``.  Callers allocate their outputs under ``torch.cuda.device(dev)`` around it."""
+    idx = dev.index
+    # (the raw-stream query is one C call; building a torch.cuda.Stream object for it cost ~5 us per operator call)
+    stream = _get_raw_stream(torch.cuda.current_device() if idx is None else idx)
+    if nbytes is not None:
+        ws = _ws_cache.get((idx, stream)) if nbytes else None
+        if nbytes and (ws is None or ws.numel() < nbytes):
+            ws = _ws_cache[idx, stream] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        # (ws stays referenced until fn has enqueued; reuse by the next call is stream-ordered behind these launches)
+        args += (ws.data_ptr() if nbytes else None, nbytes)
+    with _Timed(tag, dev):
+        st = fn(*args, stream)
+    _lib.check(st, what)
 
 
 # What the library decides from a descriptor alone (include/fastgrnn_hip.h, fastgrnn_plan): the kernel family and the
@@ -167,7 +192,7 @@ def _plan(T, B, F, H, rw, ru, gate_nl, update_nl, dtype_code, flags):
     for it (a pure function of the descriptor in the C ABI, one call).  One dictionary lookup per operator call
     instead of a ctypes round trip.  ``zext`` is the ``_lib.ZextPlan``: all zero where FLAG_ZERO_EXTEND does not take
     the padded route."""
-    desc = _lib.Desc(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), dtype_code, int(flags))
+    desc = _desc(T, B, F, H, rw, ru, gate_nl, update_nl, dtype_code, flags)
     out = _lib.Plan()
     st = _lib.load().fastgrnn_hip_plan(C.byref(desc), C.byref(out))
     if flags & _lib.FLAG_ZERO_EXTEND:
@@ -186,7 +211,7 @@ def _warn_fallback(plan, direction):
     d = plan.desc
     if plan.path[direction] != 0 or d.T * d.B < 4096 or (d.flags & _lib.FLAG_FORCE_GENERIC):
         return
-    key = (d.T, d.B, d.F, d.H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, d.flags, direction)
+    key = _key(d) + (direction,)
     if key in _cliff_warned:
         return
     _cliff_warned.add(key)
@@ -196,21 +221,6 @@ def _warn_fallback(plan, direction):
                   "include/fastgrnn_hip.h (fastgrnn_hip_kernel_path) for the shapes those cover"
                   % ("backward" if direction else "forward", d.T, d.B, d.F, d.H, d.w_rank, d.u_rank, d.dtype, d.flags),
                   RuntimeWarning, stacklevel=4)
-
-
-def _raw_stream(device):
-    """The current stream's handle as an integer (the raw-stream query is one C call; building a torch.cuda.Stream
-    object for it cost ~5 us, twice per operator call)."""
-    idx = device.index
-    return _get_raw_stream(torch.cuda.current_device() if idx is None else idx)
-
-
-_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or \
-    (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
-
-
-def _stream(device):
-    return C.c_void_p(_raw_stream(device))
 
 
 def kernel_path(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=torch.float32,
@@ -237,11 +247,19 @@ _seen = {}
 _use_seen = True                 # (tools/host_overhead.py switches it off for its A/B)
 
 
-def _all_dense_cuda(*ts):
+def _all_dense_on(dev, *ts):
+    """What the validated-signature path re-checks: every non-empty operand is contiguous on the input's device."""
     for t in ts:
-        if t.numel() and not (t.is_cuda and t.is_contiguous()):
+        if t.numel() and not (t.device == dev and t.is_contiguous()):
             return False
     return True
+
+
+def _check_devices(dev, named, meta_ok=False):
+    """Every present operand is on the input's device: its pointer is launched there."""
+    for t, n in named:
+        if _present(t) and t.device != dev and not (meta_ok and t.device.type == "meta"):
+            raise RuntimeError("%s is on %s, but input is on %s" % (n, t.device, dev))
 
 
 def _launch_forward(lib, plan, ent, unrolled, preact, want_gates, input, h0, params):
@@ -258,14 +276,10 @@ def _launch_forward(lib, plan, ent, unrolled, preact, want_gates, input, h0, par
         cs = torch.empty(oshape, dtype=pdt, device=dev) if (want_gates and not preact) else None
         if rank_space_shape:
             cs = torch.empty(rank_space_shape, dtype=pdt, device=dev)
-        ws, wsp = _workspace(nbytes, dev)
-        fn = lib.fastgrnn_hip_forward_unroll if unrolled else lib.fastgrnn_hip_forward
-        with _Timed("forward", dev):
-            st = fn(C.byref(plan.desc), C.byref(params), _ptr(input), _ptr(h0), _ptr(hs), _ptr(zs), _ptr(cs),
-                    wsp, nbytes, _stream(dev))
-        _lib.check(st, "fastgrnn forward_unroll" if unrolled else "fastgrnn forward")
-        del ws                   # (cached per stream: reuse by the next call is stream-ordered behind these launches)
-    if preact:                   # zs holds the pre-activation W.x + U.h
+        _call(lib.fastgrnn_hip_forward_unroll if unrolled else lib.fastgrnn_hip_forward,
+              "fastgrnn forward_unroll" if unrolled else "fastgrnn forward", "forward", dev, nbytes,
+              C.byref(plan.desc), C.byref(params), _ptr(input), _ptr(h0), _ptr(hs), _ptr(zs), _ptr(cs))
+    if preact:                  # zs holds the pre-activation W.x + U.h
         return [hs, zs] if cs is None else [hs, zs, cs]
     return [hs, zs, cs] if want_gates else [hs]
 
@@ -279,14 +293,14 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
            (w if w.numel() else w1).dtype, (u if u.numel() else u1).dtype, bias_gate.dtype, bias_update.dtype,
            zeta.dtype, nu.dtype, gate_nl, update_nl, flags, want_gates, input.device.index)
     ent = _seen.get(sig) if _use_seen else None
-    if ent is not None and _all_dense_cuda(input, h0, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu):
+    if ent is not None and _all_dense_on(input.device, input, h0, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta,
+                                         nu):
         plan, w_lr, u_lr, tail = ent
         return _launch_forward(lib, plan, tail, unrolled, preact, want_gates, input, h0,
                                _params(w_lr, u_lr, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu))
     _check_input(input, "input")
     _check_input(bias_gate, "bias_gate"); _check_input(bias_update, "bias_update")
     _check_input(h0, "initial_h" if unrolled else "old_h")
-    batch_major = bool(flags & _lib.FLAG_BATCH_MAJOR)
     if unrolled:
         if input.dim() != 3:
             raise RuntimeError("input must be [timesteps, batch, features]")
@@ -306,8 +320,11 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
                            else "bfloat16 sequences take a float32 hidden state")
     plan, params, w_lr, u_lr = _describe(T, B, F, H, w, u, w1, w2, u1, u2, bias_gate, bias_update, zeta, nu,
                                          input.dtype, gate_nl, update_nl, flags)
+    _check_devices(input.device, ((h0, "initial_h" if unrolled else "old_h"), (w, "w"), (u, "u"), (w1, "w1"),
+                                  (w2, "w2"), (u1, "u1"), (u2, "u2"), (bias_gate, "bias_gate"),
+                                  (bias_update, "bias_update"), (zeta, "zeta"), (nu, "nu")))
     _warn_fallback(plan, 0)
-    oshape = ((B, T, H) if batch_major else (T, B, H)) if unrolled else (B, H)
+    oshape = _seq_shape(T, B, H, flags & _lib.FLAG_BATCH_MAJOR, not unrolled)
     hs_last = bool(unrolled and (flags & _lib.FLAG_HS_LAST))
     if hs_last and (want_gates or preact):
         raise RuntimeError("FLAG_HS_LAST is an inference mode: nothing can be saved for a backward "
@@ -330,7 +347,7 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
 
 def _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_h, z, h_prime, rank_space, h0,
                      w, u, w1, w2, u1, u2, b0, b1, zeta, nu, need_dx):
-    """Allocate the 12 outputs (the parameter gradients as views of ONE flat buffer) and launch."""
+    """Allocate the 12 outputs (the parameter gradients through ``_flat_grads``) and launch."""
     w_lr, u_lr, shapes, sizes, dx_optional, B, H = ent
     desc = plan.desc
     dev = input.device
@@ -338,45 +355,37 @@ def _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_
     pdt = h0.dtype
     params = _params(w_lr, u_lr, w, u, w1, w2, u1, u2, b0, b1, zeta, nu)
     with torch.cuda.device(dev):
-        none = _NONE
         # the input's gradient is optional on these shapes (fastgrnn_hip.h, fastgrnn_grads.d_x): skipped when autograd
         # does not ask for it (a model's first layer)
-        d_input = none if (dx_optional and not need_dx) else torch.empty(input.shape, dtype=dt, device=dev)
+        d_input = _NONE if (dx_optional and not need_dx) else torch.empty(input.shape, dtype=dt, device=dev)
         d_old_h = torch.empty((B, H), dtype=pdt, device=dev)
-        # The parameter gradients are views of ONE flat buffer, laid out in the order the modules register
-        # their parameters (W | W1,W2 ; U | U1,U2 ; bias_gate ; bias_update ; zeta ; nu).  autograd adopts
-        # them as the .grad tensors, so a data-parallel step can all-reduce that buffer in place
-        # (kws_amd.dp.GradBucket) instead of packing and unpacking six tensors.
-        flat = torch.empty(sum(sizes), dtype=pdt, device=dev)
-        views = [v.view(sh) for v, sh in zip(flat.split(sizes), shapes)]
-        nw = 2 if w_lr else 1
-        nu_ = 2 if u_lr else 1
-        d_w = none if w_lr else views[0]
-        d_w1, d_w2 = (views[0], views[1]) if w_lr else (none, none)
-        d_u = none if u_lr else views[nw]
-        d_u1, d_u2 = (views[nw], views[nw + 1]) if u_lr else (none, none)
-        d_bz, d_bh, d_zeta, d_nu = views[nw + nu_:nw + nu_ + 4]
-        del flat, views
-        grads = _lib.Grads(_ptr(d_input), _ptr(d_bz), _ptr(d_bh), _ptr(d_zeta), _ptr(d_nu), _ptr(d_old_h),
-                           _ptr(d_w), _ptr(d_u), _ptr(d_w1), _ptr(d_w2), _ptr(d_u1), _ptr(d_u2))
-        nbytes = plan.ws[1]
-        ws, wsp = _workspace(nbytes, dev)
-        with _Timed("backward", dev):
-            if unrolled:
-                st = lib.fastgrnn_hip_backward_unroll(C.byref(desc), C.byref(params), _ptr(grad_h), _ptr(input),
-                                                      _ptr(hs_or_old_h), _ptr(z),
-                                                      _ptr(rank_space if preact else h_prime),
-                                                      _ptr(h0), C.byref(grads), wsp, nbytes, _stream(dev))
-            else:
-                st = lib.fastgrnn_hip_backward(C.byref(desc), C.byref(params), _ptr(grad_h), _ptr(input),
-                                               _ptr(h0), _ptr(z), _ptr(h_prime), C.byref(grads), wsp, nbytes,
-                                               _stream(dev))
-        _lib.check(st, "fastgrnn backward_unroll" if unrolled else "fastgrnn backward")
-        del ws                   # (cached per stream: reuse by the next call is stream-ordered behind these launches)
-    return [d_input, d_bz, d_bh, d_zeta, d_nu, d_old_h, d_w, d_u, d_w1, d_w2, d_u1, d_u2]
+        views, slots = _flat_grads(w_lr, u_lr, shapes, sizes, pdt, dev)
+        out = [d_input, *views[-4:], d_old_h, *slots]        # (the 12-tuple is in the order of the C grads struct)
+        grads = _lib.Grads(*map(_ptr, out))
+        if unrolled:
+            _call(lib.fastgrnn_hip_backward_unroll, "fastgrnn backward_unroll", "backward", dev, plan.ws[1],
+                  C.byref(desc), C.byref(params), _ptr(grad_h), _ptr(input), _ptr(hs_or_old_h), _ptr(z),
+                  _ptr(rank_space if preact else h_prime), _ptr(h0), C.byref(grads))
+        else:
+            _call(lib.fastgrnn_hip_backward, "fastgrnn backward", "backward", dev, plan.ws[1], C.byref(desc),
+                  C.byref(params), _ptr(grad_h), _ptr(input), _ptr(h0), _ptr(z), _ptr(h_prime), C.byref(grads))
+    return out
 
 
 _NONE = torch.empty(0)           # the reference's placeholder for operands / gradients that do not apply
+
+
+def _flat_grads(w_lr, u_lr, shapes, sizes, dtype, device):
+    """The parameter gradients as views of ONE flat buffer, laid out in the order the modules register their
+    parameters (W | W1,W2 ; U | U1,U2 ; bias_gate ; bias_update ; zeta ; nu).  autograd adopts them as the .grad
+    tensors, so a data-parallel step can all-reduce that buffer in place (kws_amd.dp.GradBucket) instead of packing
+    and unpacking six tensors.  Returns (the views in that order, the ``d_w, d_u, d_w1, d_w2, d_u1, d_u2`` slots of
+    the 12-tuple with ``_NONE`` where the cell has no such operand)."""
+    views = [v.view(sh) for v, sh in zip(torch.empty(sum(sizes), dtype=dtype, device=device).split(sizes), shapes)]
+    nw = 2 if w_lr else 1
+    d_w, d_w1, d_w2 = (_NONE, views[0], views[1]) if w_lr else (views[0], _NONE, _NONE)
+    d_u, d_u1, d_u2 = (_NONE, views[nw], views[nw + 1]) if u_lr else (views[nw], _NONE, _NONE)
+    return views, (d_w, d_u, d_w1, d_w2, d_u1, d_u2)
 
 
 def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w1, w2, u1, u2, gate_nl,
@@ -395,8 +404,9 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
            None if bias_update is None else (bias_update.shape, bias_update.dtype),
            gate_nl, update_nl, flags, input.device.index)
     ent = _seen.get(sig) if _use_seen else None
-    if ent is not None and _all_dense_cuda(grad_h, input, hs_or_old_h, z, h_prime, h0, w, u, w1, w2, u1, u2, zeta, nu) \
-            and (not preact or _all_dense_cuda(bias_gate, bias_update)):
+    dev = input.device
+    if ent is not None and _all_dense_on(dev, grad_h, input, hs_or_old_h, z, h_prime, h0, w, u, w1, w2, u1, u2, zeta,
+                                         nu) and (not preact or _all_dense_on(dev, bias_gate, bias_update)):
         plan, rs, tail = ent
         return _launch_backward(lib, plan, tail, unrolled, preact, grad_h, input, hs_or_old_h, z,
                                 z if preact else h_prime, h_prime if rs else None, h0, w, u, w1, w2, u1, u2,
@@ -438,6 +448,10 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
     plan, params, w_lr, u_lr = _describe(T, B, F, H, w, u, w1, w2, u1, u2,
                                          bias_gate if preact else zeta, bias_update if preact else zeta,
                                          zeta, nu, dt, gate_nl, update_nl, flags)
+    _check_devices(dev, ((grad_h, "grad_h"), (hs_or_old_h, "hidden_states" if unrolled else "old_h"), (z, "z"),
+                         (h_prime, "h_prime"), (rank_space, "rank_space"), (h0, "initial_h"), (w, "w"), (u, "u"),
+                         (w1, "w1"), (w2, "w2"), (u1, "u1"), (u2, "u2"), (zeta, "zeta"), (nu, "nu"))
+                   + (((bias_gate, "bias_gate"), (bias_update, "bias_update")) if preact else ()), meta_ok=preact)
     zx = plan.zext
     if zsaved and not (zx.backward and z.numel() == zx.saved_bytes):
         raise RuntimeError("fastgrnn backward: z is not the saved buffer of a FLAG_ZERO_EXTEND forward of this shape")
@@ -470,9 +484,8 @@ def frame_gemm(x, w):
     _expect(w, (H, F), "w")
     p = torch.empty((rows, H), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        with _Timed("frame_gemm", x.device):
-            st = _lib.load().fastgrnn_hip_frame_gemm(rows, H, F, _ptr(x), _ptr(w), _ptr(p), _DTYPES[x.dtype], _stream(x.device))
-    _lib.check(st, "fastgrnn frame_gemm")
+        _call(_lib.load().fastgrnn_hip_frame_gemm, "fastgrnn frame_gemm", "frame_gemm", x.device, None,
+              rows, H, F, _ptr(x), _ptr(w), _ptr(p), _DTYPES[x.dtype])
     return p
 
 
@@ -532,27 +545,41 @@ def forward_unroll_affine(input, w, u, bias_gate, bias_update, zeta, nu, gate_sc
                                    input.dtype, z_non_linearity, update_non_linearity, flags)
     _warn_fallback(plan, 0)
     dev = input.device
-    hs_shape = (B, H) if flags & _lib.FLAG_HS_LAST else ((B, T, H) if flags & _lib.FLAG_BATCH_MAJOR else (T, B, H))
     with torch.cuda.device(dev):
-        hs = torch.empty(hs_shape, dtype=input.dtype, device=dev)
-        ws, wsp = _workspace(plan.ws[0], dev)
-        with _Timed("forward_affine", dev):
-            st = lib.fastgrnn_hip_forward_unroll_affine(C.byref(plan.desc), C.byref(params), _ptr(gate_scale),
-                                                        _ptr(update_scale), _ptr(input), _ptr(initial_h), _ptr(hs),
-                                                        wsp, plan.ws[0], _stream(dev))
-        _lib.check(st, "fastgrnn forward_unroll_affine")
-        del ws
+        hs = torch.empty(_seq_shape(T, B, H, flags & _lib.FLAG_BATCH_MAJOR, flags & _lib.FLAG_HS_LAST),
+                         dtype=input.dtype, device=dev)
+        _call(lib.fastgrnn_hip_forward_unroll_affine, "fastgrnn forward_unroll_affine", "forward_affine", dev,
+              plan.ws[0], C.byref(plan.desc), C.byref(params), _ptr(gate_scale), _ptr(update_scale), _ptr(input),
+              _ptr(initial_h), _ptr(hs))
     return hs
 
 
+# What the library answers for a descriptor in one family of calls that goes beyond ``_plan``: whether the family holds
+# it, and the workspace of its forward and its backward (0 where there is none, or where the family does not hold it)
+_PoolPlan = collections.namedtuple("_PoolPlan", "desc supported ws_forward ws_backward")
+
+# family -> the C ABI's queries (supported, forward workspace, backward workspace)
+_FAMILIES = {
+    "windows": ("fastgrnn_hip_windows_supported", "fastgrnn_hip_forward_windows_workspace_bytes", None),
+    "train_windows": ("fastgrnn_hip_train_windows_supported", "fastgrnn_hip_train_windows_forward_workspace_bytes",
+                      "fastgrnn_hip_train_windows_backward_workspace_bytes"),
+    "bn_train": ("fastgrnn_hip_bn_train_supported", "fastgrnn_hip_bn_train_forward_workspace_bytes",
+                 "fastgrnn_hip_bn_train_backward_workspace_bytes"),
+}
+
+
 @functools.lru_cache(maxsize=1024)
-def _windows_plan(T, B, F, H, rw, ru, gate_nl, update_nl, dtype_code, flags, rows):
-    """(descriptor, windowed scans hold it, workspace bytes for a pool of ``rows`` frames): pure functions of the
-    descriptor in the C ABI, asked once per signature like ``_plan``."""
-    desc = _lib.Desc(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), dtype_code, int(flags))
+def _pool_plan(key, family, rows=None):
+    """The ``_PoolPlan`` of the descriptor ``_desc(*key)`` in a family of ``_FAMILIES``, for a pool of ``rows`` frames
+    (None: the family's workspace queries take the descriptor alone).  Pure functions of the descriptor in the C ABI,
+    asked once per signature like ``_plan``."""
+    desc = _desc(*key)
     lib = _lib.load()
-    ok = bool(lib.fastgrnn_hip_windows_supported(C.byref(desc)))
-    return desc, ok, int(lib.fastgrnn_hip_forward_windows_workspace_bytes(C.byref(desc), rows)) if ok else 0
+    supported, *sizes = (q and getattr(lib, q) for q in _FAMILIES[family])
+    if not supported(C.byref(desc)):
+        return _PoolPlan(desc, False, 0, 0)
+    rest = () if rows is None else (rows,)
+    return _PoolPlan(desc, True, *(int(q(C.byref(desc), *rest)) if q else 0 for q in sizes))
 
 
 def windows_supported(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=torch.float32, flags=0):
@@ -561,7 +588,8 @@ def windows_supported(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dt
     forward.  ``flags``: FLAG_BATCH_MAJOR / FLAG_HS_LAST / FLAG_PREACT_AFFINE."""
     if dtype not in _DTYPES:
         return False
-    return _windows_plan(T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype], int(flags), T)[1]
+    return _pool_plan((T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype], int(flags)),
+                      "windows", T).supported
 
 
 def forward_windows(pool, starts, T, w, u, bias_gate, bias_update, zeta, nu, initial_h, z_non_linearity,
@@ -580,61 +608,20 @@ def forward_windows(pool, starts, T, w, u, bias_gate, bias_update, zeta, nu, ini
     affine = gate_scale is not None or update_scale is not None
     if affine and (gate_scale is None or update_scale is None):
         raise RuntimeError("forward_windows: gate_scale and update_scale go together")
-    named = [(pool, "pool"), (starts, "starts"), (initial_h, "initial_h"), (bias_gate, "bias_gate"),
-             (bias_update, "bias_update")] + ([(gate_scale, "gate_scale"), (update_scale, "update_scale")] if affine else [])
-    for t, n in named:
-        _check_input(t, n)
-    if pool.dim() != 2:
-        raise RuntimeError("pool must be [frames, features]")
-    if starts.dim() != 1 or starts.dtype not in (torch.int32, torch.int64):
-        raise RuntimeError("starts must be a 1-D int32 or int64 tensor")
-    if starts.device != pool.device:
-        raise RuntimeError("starts must be on the pool's device")
-    R, F = pool.shape
-    B, T = starts.numel(), int(T)
-    H = initial_h.shape[-1]
-    _expect(initial_h, (B, H), "initial_h")
-    check_starts_range(starts if check else starts[:0], R, T)
-    for t, n in named[3:]:
-        if t.numel() != H:
-            raise RuntimeError("%s must hold H=%d elements" % (n, H))
-    for t in (initial_h,) + ((gate_scale, update_scale) if affine else ()):
-        if t.dtype != _param_dtype(pool.dtype):
-            raise RuntimeError("fastgrnn: all operands must share dtype %s (got %s)" % (_param_dtype(pool.dtype), t.dtype))
-    if starts.dtype != torch.int32:
-        starts = starts.to(torch.int32)
+    scales = ((gate_scale, "gate_scale"), (update_scale, "update_scale")) if affine else ()
+    R, F, B, T, H, starts = _windows_operands(pool, starts, T, initial_h, bias_gate, bias_update, check, scales)
     flags = (_lib.FLAG_BATCH_MAJOR if batch_major else 0) | (_lib.FLAG_HS_LAST if last_state else 0) | \
         (_lib.FLAG_PREACT_AFFINE if affine else 0)
     plan, params, w_lr, u_lr = _describe(T, B, F, H, w, u, None, None, None, None, bias_gate, bias_update, zeta, nu,
                                          pool.dtype, z_non_linearity, update_non_linearity, flags)
     d = plan.desc
-    _, _, nbytes = _windows_plan(T, B, F, H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, flags, R)
     dev = pool.device
-    hs_shape = (B, H) if last_state else ((B, T, H) if batch_major else (T, B, H))
     with torch.cuda.device(dev):
-        hs = torch.empty(hs_shape, dtype=pool.dtype, device=dev)
-        ws, wsp = _workspace(nbytes, dev)
-        with _Timed("forward_windows", dev):
-            st = lib.fastgrnn_hip_forward_windows(C.byref(d), C.byref(params), _ptr(gate_scale), _ptr(update_scale),
-                                                  _ptr(pool), R, _ptr(starts), _ptr(initial_h), _ptr(hs), wsp, nbytes,
-                                                  _stream(dev))
-        _lib.check(st, "fastgrnn forward_windows")
-        del ws
+        hs = torch.empty(_seq_shape(T, B, H, batch_major, last_state), dtype=pool.dtype, device=dev)
+        _call(lib.fastgrnn_hip_forward_windows, "fastgrnn forward_windows", "forward_windows", dev,
+              _pool_plan(_key(d), "windows", R).ws_forward, C.byref(d), C.byref(params), _ptr(gate_scale),
+              _ptr(update_scale), _ptr(pool), R, _ptr(starts), _ptr(initial_h), _ptr(hs))
     return hs
-
-
-@functools.lru_cache(maxsize=1024)
-def _train_windows_plan(T, B, F, H, rw, ru, gate_nl, update_nl, dtype_code, flags, rows):
-    """(descriptor, the training calls over windows hold it, forward workspace bytes, backward workspace bytes) for a
-    pool of ``rows`` frames: pure functions of the descriptor in the C ABI, asked once per signature like ``_plan``.
-    ``flags``: FLAG_BATCH_MAJOR, and FLAG_GRAD_LAST for a backward that takes the last state's gradient."""
-    desc = _lib.Desc(T, B, F, H, rw, ru, int(gate_nl), int(update_nl), dtype_code, int(flags))
-    lib = _lib.load()
-    ok = bool(lib.fastgrnn_hip_train_windows_supported(C.byref(desc)))
-    if not ok:
-        return desc, False, 0, 0
-    return (desc, True, int(lib.fastgrnn_hip_train_windows_forward_workspace_bytes(C.byref(desc), rows)),
-            int(lib.fastgrnn_hip_train_windows_backward_workspace_bytes(C.byref(desc), rows)))
 
 
 def train_windows_supported(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=torch.float32, flags=0):
@@ -643,7 +630,8 @@ def train_windows_supported(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl
     and calls the existing forward.  ``flags``: FLAG_BATCH_MAJOR / FLAG_GRAD_LAST."""
     if dtype not in _DTYPES:
         return False
-    return _train_windows_plan(T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype], int(flags), T)[1]
+    return _pool_plan((T, B, F, H, w_rank, u_rank, int(gate_nl), int(update_nl), _DTYPES[dtype], int(flags)),
+                      "train_windows", T).supported
 
 
 def check_starts_range(starts, R, T):
@@ -659,11 +647,11 @@ def check_starts_range(starts, R, T):
                              % (R - T, R, T, lo, hi))
 
 
-def _windows_operands(pool, starts, T, initial_h, bias_gate, bias_update, check):
-    """The argument checks the windowed training calls share (those of ``forward_windows``); (R, F, B, T, H, starts
-    as int32)."""
+def _windows_operands(pool, starts, T, initial_h, bias_gate, bias_update, check, extra=()):
+    """The argument checks every windowed call shares; (R, F, B, T, H, starts as int32).  ``extra``: further named
+    per-unit vectors (the two scales of the affine forward), checked like the biases and held to the parameter dtype."""
     named = [(pool, "pool"), (starts, "starts"), (initial_h, "initial_h"), (bias_gate, "bias_gate"),
-             (bias_update, "bias_update")]
+             (bias_update, "bias_update"), *extra]
     for t, n in named:
         _check_input(t, n)
     if pool.dim() != 2:
@@ -680,8 +668,9 @@ def _windows_operands(pool, starts, T, initial_h, bias_gate, bias_update, check)
     for t, n in named[3:]:
         if t.numel() != H:
             raise RuntimeError("%s must hold H=%d elements" % (n, H))
-    if initial_h.dtype != _param_dtype(pool.dtype):
-        raise RuntimeError("fastgrnn: all operands must share dtype %s (got %s)" % (_param_dtype(pool.dtype), initial_h.dtype))
+    for t in (initial_h, *(t for t, _ in extra)):
+        if t.dtype != _param_dtype(pool.dtype):
+            raise RuntimeError("fastgrnn: all operands must share dtype %s (got %s)" % (_param_dtype(pool.dtype), t.dtype))
     if starts.dtype != torch.int32:
         starts = starts.to(torch.int32)
     return R, F, B, T, H, starts
@@ -702,19 +691,14 @@ def forward_windows_train(pool, starts, T, w, u, bias_gate, bias_update, zeta, n
     plan, params, _, _ = _describe(T, B, F, H, w, u, None, None, None, None, bias_gate, bias_update, zeta, nu,
                                    pool.dtype, z_non_linearity, update_non_linearity, flags)
     d = plan.desc
-    _, _, nbytes, _ = _train_windows_plan(T, B, F, H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, flags, R)
     dev = pool.device
-    shape = (B, T, H) if batch_major else (T, B, H)
+    shape = _seq_shape(T, B, H, batch_major, False)
     with torch.cuda.device(dev):
         hs = torch.empty(shape, dtype=pool.dtype, device=dev)
         saved = torch.empty(shape, dtype=torch.float32, device=dev)
-        ws, wsp = _workspace(nbytes, dev)
-        with _Timed("forward_windows_train", dev):
-            st = lib.fastgrnn_hip_forward_windows_train(C.byref(d), C.byref(params), _ptr(pool), R, _ptr(starts),
-                                                        _ptr(initial_h), _ptr(hs), _ptr(saved), wsp, nbytes,
-                                                        _stream(dev))
-        _lib.check(st, "fastgrnn forward_windows_train")
-        del ws
+        _call(lib.fastgrnn_hip_forward_windows_train, "fastgrnn forward_windows_train", "forward_windows_train", dev,
+              _pool_plan(_key(d), "train_windows", R).ws_forward, C.byref(d), C.byref(params), _ptr(pool), R,
+              _ptr(starts), _ptr(initial_h), _ptr(hs), _ptr(saved))
     return hs, saved
 
 
@@ -739,27 +723,18 @@ def backward_windows(grad_h, pool, starts, T, hidden_states, saved, zeta, nu, w,
     plan, params, _, _ = _describe(T, B, F, H, w, u, None, None, None, None, bias_gate, bias_update, zeta, nu,
                                    pool.dtype, z_non_linearity, update_non_linearity, flags)
     d = plan.desc
-    _, _, _, nbytes = _train_windows_plan(T, B, F, H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, flags, R)
     dev = pool.device
     pdt = initial_h.dtype
     shapes = [(H, F), (H, H), (1, H), (1, H), (1, 1), (1, 1)]
-    sizes = [a * b for a, b in shapes]
     with torch.cuda.device(dev):
-        none = _NONE
         d_old_h = torch.empty((B, H), dtype=pdt, device=dev)
-        flat = torch.empty(sum(sizes), dtype=pdt, device=dev)
-        d_w, d_u, d_bz, d_bh, d_zeta, d_nu = [v.view(sh) for v, sh in zip(flat.split(sizes), shapes)]
-        del flat
-        grads = _lib.Grads(_ptr(none), _ptr(d_bz), _ptr(d_bh), _ptr(d_zeta), _ptr(d_nu), _ptr(d_old_h),
-                           _ptr(d_w), _ptr(d_u), _ptr(none), _ptr(none), _ptr(none), _ptr(none))
-        ws, wsp = _workspace(nbytes, dev)
-        with _Timed("backward_windows", dev):
-            st = lib.fastgrnn_hip_backward_windows(C.byref(d), C.byref(params), _ptr(grad_h), _ptr(pool), R,
-                                                   _ptr(starts), _ptr(hidden_states), _ptr(saved), _ptr(initial_h),
-                                                   C.byref(grads), wsp, nbytes, _stream(dev))
-        _lib.check(st, "fastgrnn backward_windows")
-        del ws
-    return [none, d_bz, d_bh, d_zeta, d_nu, d_old_h, d_w, d_u, none, none, none, none]
+        views, slots = _flat_grads(False, False, shapes, [a * b for a, b in shapes], pdt, dev)
+        out = [_NONE, *views[-4:], d_old_h, *slots]
+        grads = _lib.Grads(*map(_ptr, out))
+        _call(lib.fastgrnn_hip_backward_windows, "fastgrnn backward_windows", "backward_windows", dev,
+              _pool_plan(_key(d), "train_windows", R).ws_backward, C.byref(d), C.byref(params), _ptr(grad_h),
+              _ptr(pool), R, _ptr(starts), _ptr(hidden_states), _ptr(saved), _ptr(initial_h), C.byref(grads))
+    return out
 
 
 def backward_unroll(grad_h, input, hidden_states, zeta, nu, w, u, z, h_prime, initial_h, w1, w2, u1, u2,

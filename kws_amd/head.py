@@ -7,14 +7,12 @@ on ``hs[T-1]`` (model.py:86-88, 226-227), ``F.log_softmax(dim=1)`` (model.py:229
 parameters under the reference's names so a ``RNNClassifierModel`` state dict loads unchanged
 (``hidden2keyword.weight`` / ``.bias``).
 """
-import ctypes as C
-
 import torch
 from torch import nn
 from torch.autograd import Function
 
 from . import _lib
-from .fastgrnn_cuda import _check_input, _ptr, _stream, _workspace
+from .fastgrnn_cuda import _call, _check_input, _ptr
 
 
 def head_xent(h_last, weight, bias, labels, want_log_probs=False):
@@ -39,11 +37,8 @@ def head_xent(h_last, weight, bias, labels, want_log_probs=False):
         d_w = torch.empty_like(weight)
         d_b = torch.empty(Cn, dtype=torch.float32, device=dev)
         nbytes = lib.fastgrnn_hip_head_workspace_bytes(B, H, Cn)
-        ws, wsp = _workspace(nbytes, dev)
-        st = lib.fastgrnn_hip_head_xent(B, H, Cn, _ptr(h_last), _ptr(weight), _ptr(bias), _ptr(labels), _ptr(loss),
-                                        _ptr(logp), _ptr(d_h), _ptr(d_w), _ptr(d_b), wsp, nbytes, _stream(dev))
-        _lib.check(st, "fastgrnn head_xent")
-        del ws
+        _call(lib.fastgrnn_hip_head_xent, "fastgrnn head_xent", None, dev, nbytes, B, H, Cn, _ptr(h_last), _ptr(weight),
+              _ptr(bias), _ptr(labels), _ptr(loss), _ptr(logp), _ptr(d_h), _ptr(d_w), _ptr(d_b))
     return loss, logp, d_h, d_w, d_b
 
 

@@ -93,7 +93,7 @@ def main():
                 ta.append(e0.elapsed_time(e1)); tb.append(e1.elapsed_time(e2))
             ws_a = fastgrnn_cuda._plan(T, B, F, H, 0, 0, 0, 2, _lib.F32,
                                        _lib.FLAG_SAVE_PREACT | _lib.FLAG_ZERO_EXTEND | _lib.FLAG_NO_INPUT_GRAD).ws[1]
-            ws_b = fastgrnn_cuda._train_windows_plan(T, B, F, H, 0, 0, 0, 2, _lib.F32, 0, R)[3]
+            ws_b = fastgrnn_cuda._pool_plan((T, B, F, H, 0, 0, 0, 2, _lib.F32, 0), "train_windows", R).ws_backward
             layer[kind] = {
                 "gather_route_ms": stat(ta), "windows_route_ms": stat(tb),
                 "windows_over_gather": pct(tb, 0.5) / pct(ta, 0.5),

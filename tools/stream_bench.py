@@ -83,7 +83,7 @@ def main():
             ta.append(e0.elapsed_time(e1)); tg.append(e0.elapsed_time(em)); tb.append(e1.elapsed_time(e2))
         med = lambda ts: pct(ts, 0.5)                                      # noqa: E731
         ws_a = fastgrnn_cuda._plan(T, B, F, H, 0, 0, 0, 2, _lib.F32, _lib.FLAG_BATCH_MAJOR | _lib.FLAG_ZERO_EXTEND).ws[0]
-        ws_b = fastgrnn_cuda._windows_plan(T, B, F, H, 0, 0, 0, 2, _lib.F32, _lib.FLAG_BATCH_MAJOR, L)[2]
+        ws_b = fastgrnn_cuda._pool_plan((T, B, F, H, 0, 0, 0, 2, _lib.F32, _lib.FLAG_BATCH_MAJOR), "windows", L).ws_forward
         res["layers"]["%d->%d" % (F, H)] = {
             "gather_route_ms": {"median": med(ta), "p10": pct(ta, 0.1), "p90": pct(ta, 0.9)},
             "windows_route_ms": {"median": med(tb), "p10": pct(tb, 0.1), "p90": pct(tb, 0.9)},
