@@ -463,6 +463,39 @@ int fastgrnn_hip_head_xent(int32_t B, int32_t H, int32_t C, const void *h_last, 
                            void *d_h_last, void *d_fc_w, void *d_fc_b,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* head_predict -- the inference counterpart of head_xent: what the reference does with a batch of scores outside
+ * training, in one call and without gradients:
+ *   keyword_scores = F.log_softmax(self.hidden2keyword(hs[T-1]), dim=1)     (model.py:86-88, 226-230)
+ *   predicted_index = torch.argmax(...)                                      (inferencetry.py:213-214)
+ *   passed += (scores[i].argmax() == labels[i])  for every i                 (trainClassifier.py:54-65, batch_accuracy)
+ * fp32, operands as in head_xent.  Writes log_probs:[B,C] (may be NULL: not stored) -- the same bits head_xent writes
+ * for the same operands --, pred:[B] int32 = the argmax of the logits by torch.argmax's rules (the lowest index among
+ * equal maxima; a NaN is the maximum and the first NaN wins), and, when labels:[B] int64 is given, n_correct[1] int32 =
+ * the number of rows with pred[b] == labels[b] (required iff labels; a label of -100 or any other value outside [0,C)
+ * never matches).  The count is an integer sum of per-workgroup counts: exact, repeatable, and the call may be captured
+ * in a graph.  H <= 256, C <= 64, else FASTGRNN_ERR_UNSUPPORTED.
+ * workspace: fastgrnn_hip_head_predict_workspace_bytes(B,H,C) when labels is given (it holds the per-workgroup counts);
+ * without labels it is not used and may be NULL.  The largest heads (more than 64 KB of LDS, e.g. H = 256 with C = 64)
+ * opt in to their LDS size with an attribute call in front of the launch, as head_xent does; that call is not a
+ * stream operation and the whole call captures in a graph at those sizes too. */
+size_t fastgrnn_hip_head_predict_workspace_bytes(int32_t B, int32_t H, int32_t C);
+int fastgrnn_hip_head_predict(int32_t B, int32_t H, int32_t C, const void *h_last, const void *fc_w,
+                              const void *fc_b, const int64_t *labels, void *log_probs, int32_t *pred,
+                              int32_t *n_correct, void *workspace, size_t workspace_bytes, void *stream);
+
+/* vote_windows -- the bookkeeping of the reference's detector (inferencetry.py:217-227) for S independent streams of Nw
+ * consecutive window predictions, each from an empty vote list and no previous detection.  pred:[S,Nw] int32.  For
+ * window w of stream s, votes = pred[s, max(0, w-K+1) .. w] (K = num_windows, NUM_WINDOWS = 10 in the reference), (m, f)
+ * the most frequent value among them and its frequency -- on equal frequency the value whose first occurrence in votes
+ * is earliest, which is Counter(votes).most_common(1) --, and with M = majority (MAJORITY = 5):
+ *   majority_out[s,w] = m if f >= M else -1
+ *   event_out[s,w]    = m if f >= M and m != previous else -1;  previous becomes m when an event fires
+ * (the reference prints "Detected keyword" exactly where event_out >= 0).  A negative entry of pred is a vote for no
+ * class: it holds its slot in the list and is never m.  1 <= M <= K, else FASTGRNN_ERR_BAD_SHAPE; K <= 64, else
+ * FASTGRNN_ERR_UNSUPPORTED.  No workspace. */
+int fastgrnn_hip_vote_windows(int32_t S, int32_t Nw, int32_t num_windows, int32_t majority, const int32_t *pred,
+                              int32_t *majority_out, int32_t *event_out, void *stream);
+
 /* frame_gemm -- the one genuinely dense, non-recurrent contraction of a layer, as a call of its own:
  *   P[rows, H] = X[rows, F] . W^T,   W:[H,F]  (rows = T*B; the reference computes it per step, `mm` at .cu:356).
  * forward_unroll runs exactly this launch in front of the scan for layers whose input is wider than 32 (the scan of a

@@ -6,7 +6,7 @@ from . import _lib  # noqa: F401
 from . import fastgrnn_cuda  # noqa: F401
 from . import utils  # noqa: F401
 from . import head  # noqa: F401
-from .head import KeywordHead, keyword_loss  # noqa: F401
+from .head import KeywordHead, head_predict, keyword_loss, vote_windows  # noqa: F401
 from .rnn import (FastGRNNCUDA, FastGRNNCUDACell, FastGRNNFunction,  # noqa: F401
                   FastGRNNUnrollFunction)
 from .batchnorm import FastGRNNBatchNorm, FastGRNNBatchNormCell, fold_batchnorm  # noqa: F401
@@ -15,5 +15,5 @@ from .model import RNNClassifierModel  # noqa: F401
 from .graph import GraphedStep  # noqa: F401
 
 __all__ = ["fastgrnn_cuda", "utils", "head", "FastGRNNCUDA", "FastGRNNCUDACell", "FastGRNNFunction",
-           "FastGRNNUnrollFunction", "KeywordHead", "keyword_loss", "RNNClassifierModel", "GraphedStep",
+           "FastGRNNUnrollFunction", "KeywordHead", "keyword_loss", "head_predict", "vote_windows", "RNNClassifierModel", "GraphedStep",
            "FastGRNNBatchNorm", "FastGRNNBatchNormCell", "fold_batchnorm", "FastGRNNBatchNormCUDA"]

@@ -48,6 +48,7 @@ EXPORTS = (
     "fastgrnn_hip_train_windows_supported", "fastgrnn_hip_train_windows_forward_workspace_bytes",
     "fastgrnn_hip_train_windows_backward_workspace_bytes", "fastgrnn_hip_forward_windows_train",
     "fastgrnn_hip_backward_windows",
+    "fastgrnn_hip_head_predict_workspace_bytes", "fastgrnn_hip_head_predict", "fastgrnn_hip_vote_windows",
 )
 
 
@@ -145,6 +146,12 @@ def load():
     lib.fastgrnn_hip_head_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.fastgrnn_hip_head_xent.restype = i32
     lib.fastgrnn_hip_head_xent.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.fastgrnn_hip_head_predict_workspace_bytes.restype = sz
+    lib.fastgrnn_hip_head_predict_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.fastgrnn_hip_head_predict.restype = i32
+    lib.fastgrnn_hip_head_predict.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.fastgrnn_hip_vote_windows.restype = i32
+    lib.fastgrnn_hip_vote_windows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.fastgrnn_hip_frame_gemm.restype = i32
     lib.fastgrnn_hip_frame_gemm.argtypes = [sz, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp]
     BP, BG = C.POINTER(BnParams), C.POINTER(BnGrads)

@@ -442,6 +442,31 @@ int fastgrnn_hip_head_xent(int32_t B, int32_t H, int32_t C, const void* h_last, 
                    reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t fastgrnn_hip_head_predict_workspace_bytes(int32_t B, int32_t H, int32_t C) {
+  return head_supported(B, H, C) ? head_predict_ws_bytes(B) : 0;
+}
+
+int fastgrnn_hip_head_predict(int32_t B, int32_t H, int32_t C, const void* h_last, const void* fc_w, const void* fc_b,
+                              const int64_t* labels, void* log_probs, int32_t* pred, int32_t* n_correct,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (B < 1 || H < 1 || C < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  if (!head_supported(B, H, C)) return FASTGRNN_ERR_UNSUPPORTED;
+  if (!h_last || !fc_w || !fc_b || !pred || (labels && !n_correct)) return FASTGRNN_ERR_NULL_POINTER;
+  int st = check_ws(workspace, workspace_bytes, labels ? head_predict_ws_bytes(B) : 0);   // (only the count uses it)
+  if (st) return st;
+  return head_predict(B, H, C, h_last, fc_w, fc_b, labels, log_probs, pred, n_correct, workspace,
+                      reinterpret_cast<hipStream_t>(stream));
+}
+
+int fastgrnn_hip_vote_windows(int32_t S, int32_t Nw, int32_t num_windows, int32_t majority, const int32_t* pred,
+                              int32_t* majority_out, int32_t* event_out, void* stream) {
+  if (S < 1 || Nw < 1 || num_windows < 1 || majority < 1 || majority > num_windows) return FASTGRNN_ERR_BAD_SHAPE;
+  if ((double)S * Nw > 1099511627776.0) return FASTGRNN_ERR_BAD_SHAPE;     // (element offsets are size_t; as check_desc)
+  if (!vote_supported(num_windows)) return FASTGRNN_ERR_UNSUPPORTED;
+  if (!pred || !majority_out || !event_out) return FASTGRNN_ERR_NULL_POINTER;
+  return vote_windows(S, Nw, num_windows, majority, pred, majority_out, event_out, reinterpret_cast<hipStream_t>(stream));
+}
+
 int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void* x, const void* w, void* p, int32_t dtype,
                             void* stream) {
   if (!x || !w || !p) return FASTGRNN_ERR_NULL_POINTER;

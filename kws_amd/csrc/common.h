@@ -172,6 +172,13 @@ bool head_supported(int B, int H, int C);
 size_t head_ws_bytes(int B, int H, int C);
 int head_xent(int B, int H, int C, const void* h_last, const void* fc_w, const void* fc_b, const void* labels,
               void* loss, void* logp, void* d_h, void* d_w, void* d_b, void* ws, hipStream_t s);
+// ... its inference counterpart: scores (logp may be NULL), pred = argmax of the logits, and with labels the count of
+// pred == labels in n_correct[1] (labels NULL: neither ws nor n_correct is touched); the detector's majority vote
+size_t head_predict_ws_bytes(int B);
+int head_predict(int B, int H, int C, const void* h_last, const void* fc_w, const void* fc_b, const void* labels,
+                 void* logp, int32_t* pred, int32_t* n_correct, void* ws, hipStream_t s);
+bool vote_supported(int K);
+int vote_windows(int S, int Nw, int K, int M, const int32_t* pred, int32_t* majority, int32_t* event, hipStream_t s);
 
 // training-mode BatchNorm cell (kernels_bn_train.hip): FASTGRNN_FLAG_BN_TRAIN
 bool bn_train_supported(const fastgrnn_desc& d);

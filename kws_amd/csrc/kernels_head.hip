@@ -5,6 +5,8 @@
 // The loss is always differentiated in training, so the backward is computed beside the forward (the classic
 // fused softmax-cross-entropy): one launch produces log-probabilities, the loss and d_h / d_W / d_b per
 // workgroup, a second one reduces the per-workgroup partials in a fixed order (deterministic, no atomics).
+// The inference tail lives here too: head_predict (scores, argmax, correct count) and vote_windows (the detector's
+// majority vote), further down.
 // HBM-bound integer/float byte work: B*H*4 bytes in, B*H*4 out; nothing here belongs on the matrix pipe
 // (2*B*H*C flops, C ~ 12).
 #include "common.h"
@@ -155,6 +157,152 @@ __global__ __launch_bounds__(256) void head_reduce(int nwg, int n, int CH, int C
   }
 }
 
+// ---- inference head (head_predict): the scores, their argmax and the count of correct rows, no gradient work.
+//   reference: model.py:226-230 (scores), inferencetry.py:213-214 (argmax of the window's scores),
+//   trainClassifier.py:54-65 (batch_accuracy: scores[i].argmax() == labels[i], counted).
+// Staging, tiling and the fmaf / exp / log order are head_xent_fwd_bwd's: logp holds the same bits as that kernel's.
+// dynamic LDS: hT[HEAD_UTT][H+1] | W[C][H+1] | logits[HEAD_UTT][C+1]
+__global__ __launch_bounds__(HEAD_THREADS) void head_predict_fwd(
+    int B, int H, int C, const float* __restrict__ h_last, const float* __restrict__ fc_w,
+    const float* __restrict__ fc_b, const long long* __restrict__ labels, float* __restrict__ logp,
+    int* __restrict__ pred, int* __restrict__ part) {
+  extern __shared__ float lds[];
+  const int HP = H + 1, CP = C + 1;
+  float* sh = lds;                               // [HEAD_UTT][HP]
+  float* sw = sh + HEAD_UTT * HP;                // [C][HP]
+  float* sdl = sw + C * HP;                      // [HEAD_UTT][CP]: logits
+  __shared__ int s_hit[HEAD_UTT];
+  const int tid = threadIdx.x;
+  const int b0 = blockIdx.x * HEAD_UTT;
+  const int nu = min(HEAD_UTT, B - b0);
+
+  for (int e = tid; e < HEAD_UTT * H; e += HEAD_THREADS) {
+    const int u = e / H, n = e - u * H;
+    sh[u * HP + n] = (u < nu) ? h_last[(size_t)(b0 + u) * H + n] : 0.f;
+    lds_writes_landed();                           // (second rule of DESIGN.md 4.0: the next iteration's load)
+  }
+  for (int e = tid; e < C * H; e += HEAD_THREADS) {
+    const int c = e / H, n = e - c * H;
+    sw[c * HP + n] = fc_w[e];
+    lds_writes_landed();                           // (second rule of DESIGN.md 4.0: the next iteration's load)
+  }
+  __syncthreads();
+  // ---- logits[u][c] = b[c] + W[c,:] . h[u,:]            (model.py:227)
+  for (int e = tid; e < HEAD_UTT * C; e += HEAD_THREADS) {
+    const int u = e / C, c = e - u * C;
+    float acc = fc_b[c];
+    const float* hp = sh + u * HP;
+    const float* wp = sw + c * HP;
+    for (int n = 0; n < H; ++n) acc = fmaf(wp[n], hp[n], acc);
+    sdl[u * CP + c] = acc;
+    lds_writes_landed();                           // (second rule of DESIGN.md 4.0: the next iteration's load)
+  }
+  __syncthreads();
+  // ---- per utterance: log_softmax (model.py:229), argmax of the logits, label match
+  if (tid < HEAD_UTT) {
+    const int u = tid;
+    const float* row = sdl + u * CP;
+    float m = row[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(row[c] - m);
+    const float lse = m + logf(s);
+    // torch.argmax: the lowest index among equal maxima; a NaN is the maximum and the first NaN wins
+    float best = row[0];
+    int bi = 0;
+    for (int c = 1; c < C; ++c) {
+      const float v = row[c];
+      if (best == best && (v > best || v != v)) { best = v; bi = c; }
+    }
+    int hit = 0;
+    if (u < nu) {
+      if (logp)
+        for (int c = 0; c < C; ++c) logp[(size_t)(b0 + u) * C + c] = row[c] - lse;
+      pred[b0 + u] = bi;
+      // (a label of -100, or any other value outside [0,C), never equals a class index)
+      if (labels) hit = labels[b0 + u] == (long long)bi ? 1 : 0;
+    }
+    s_hit[u] = hit;
+  }
+  __syncthreads();
+  if (tid == 0 && part) {
+    int n = 0;
+#pragma unroll
+    for (int u = 0; u < HEAD_UTT; ++u) n += s_hit[u];
+    part[blockIdx.x] = n;
+  }
+}
+
+// n_correct[0] = sum of the workgroups' counts (integers: exact in any order)
+__global__ __launch_bounds__(256) void head_count_reduce(int nwg, const int* __restrict__ part,
+                                                         int* __restrict__ n_correct) {
+  __shared__ int s_cnt[256 / 64];
+  const int tid = threadIdx.x;
+  int cnt = 0;
+  for (int w = tid; w < nwg; w += 256) cnt += part[w];
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) cnt += __shfl_xor(cnt, m);
+  if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+  __syncthreads();
+  if (tid == 0) n_correct[0] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// ---- the detector's vote (vote_windows): inferencetry.py:217-227 per stream, from an empty vote list.
+// One workgroup per stream walks Nw in chunks of VOTE_CHUNK windows, one thread per window.  Window w's vote list is
+// pred[max(0, w-K+1) .. w]: the thread compares the list with itself (K <= 64) and scans the candidates in list order
+// with a strict >, which is Counter(votes).most_common(1)'s first maximum in insertion order.  `previous` at window w is
+// the most recent earlier majority that qualified (an event sets previous = m, and without an event a qualifying m
+// already equals previous), so the events are a last-valid-value scan over the majorities with one carried value per
+// chunk.
+constexpr int VOTE_CHUNK = 256, VOTE_MAX_K = 64;
+
+__global__ __launch_bounds__(VOTE_CHUNK) void vote_windows_k(int Nw, int K, int M, const int* __restrict__ pred,
+                                                             int* __restrict__ majority, int* __restrict__ event) {
+  __shared__ int sp[VOTE_MAX_K - 1 + VOTE_CHUNK];   // pred[w0-(K-1) .. w0+VOTE_CHUNK-1]; -1 outside [0,Nw)
+  __shared__ int smaj[VOTE_CHUNK];
+  __shared__ int s_carry;                           // the last qualifying majority of the chunks so far, else -1
+  const int tid = threadIdx.x;
+  const size_t base = (size_t)blockIdx.x * (size_t)Nw;
+  if (tid == 0) s_carry = -1;
+  for (long long w0 = 0; w0 < Nw; w0 += VOTE_CHUNK) {      // (64-bit: w0 + VOTE_CHUNK may pass 2^31)
+    for (int i = tid; i < K - 1 + VOTE_CHUNK; i += VOTE_CHUNK) {
+      const long long w = w0 - (K - 1) + i;
+      sp[i] = (w >= 0 && w < Nw) ? pred[base + w] : -1;
+      lds_writes_landed();                           // (second rule of DESIGN.md 4.0: the next iteration's load)
+    }
+    __syncthreads();
+    const long long w = w0 + tid;
+    int maj = -1;
+    if (w < Nw) {
+      const int hi = tid + K - 1;                    // sp index of window w
+      const int lo = hi - (int)min(w, (long long)(K - 1));             // ... of the oldest vote in the list
+      int bf = 0, bm = -1;
+      for (int i = lo; i <= hi; ++i) {
+        const int v = sp[i];
+        int f = 0;
+        for (int j = lo; j <= hi; ++j) f += (sp[j] == v) ? 1 : 0;
+        if (v >= 0 && f > bf) { bf = f; bm = v; }    // (a negative vote holds its slot and is never the majority)
+      }
+      if (bf >= M) maj = bm;
+    }
+    smaj[tid] = maj;
+    __syncthreads();
+    int prev = -1, j = tid - 1;
+    for (; j >= 0; --j) {
+      prev = smaj[j];
+      if (prev != -1) break;
+    }
+    if (j < 0) prev = s_carry;
+    if (w < Nw) {
+      majority[base + w] = maj;
+      event[base + w] = (maj != -1 && maj != prev) ? maj : -1;
+    }
+    __syncthreads();
+    if (tid == VOTE_CHUNK - 1) s_carry = (maj != -1) ? maj : prev;
+    lds_writes_landed();                             // (second rule of DESIGN.md 4.0: the next chunk's loads)
+  }
+}
+
 size_t head_lds_bytes(int H, int C) {
   return (size_t)(HEAD_UTT * (H + 1) + C * (H + 1) + HEAD_UTT * (C + 1) + HEAD_UTT) * sizeof(float);
 }
@@ -183,6 +331,31 @@ int head_xent(int B, int H, int C, const void* h_last, const void* fc_w, const v
   const int n = C * H + C + 1;
   hipLaunchKernelGGL(head_reduce, dim3((n + 31) / 32), dim3(256), 0, s, nwg, n, C * H, C, (const float*)part,
                      (float*)d_w, (float*)d_b, (float*)loss);
+  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+}
+
+size_t head_predict_ws_bytes(int B) { return align256((size_t)((B + HEAD_UTT - 1) / HEAD_UTT) * sizeof(int)); }
+
+int head_predict(int B, int H, int C, const void* h_last, const void* fc_w, const void* fc_b, const void* labels,
+                 void* logp, int32_t* pred, int32_t* n_correct, void* ws, hipStream_t s) {
+  const int nwg = (B + HEAD_UTT - 1) / HEAD_UTT;
+  // (head_xent's LDS image without the loss column: the same opt-in above 64 KB)
+  const size_t lds = head_lds_bytes(H, C) - HEAD_UTT * sizeof(float);
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_predict_fwd),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  int* part = labels ? reinterpret_cast<int*>(ws) : nullptr;
+  hipLaunchKernelGGL(head_predict_fwd, dim3(nwg), dim3(HEAD_THREADS), lds, s, B, H, C, (const float*)h_last,
+                     (const float*)fc_w, (const float*)fc_b, (const long long*)labels, (float*)logp, pred, part);
+  if (labels)
+    hipLaunchKernelGGL(head_count_reduce, dim3(1), dim3(256), 0, s, nwg, (const int*)part, n_correct);
+  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+}
+
+bool vote_supported(int K) { return K <= VOTE_MAX_K; }
+
+int vote_windows(int S, int Nw, int K, int M, const int32_t* pred, int32_t* majority, int32_t* event, hipStream_t s) {
+  hipLaunchKernelGGL(vote_windows_k, dim3(S), dim3(VOTE_CHUNK), 0, s, Nw, K, M, pred, majority, event);
   return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
 }
 

@@ -23,6 +23,9 @@ Same constructor arguments, attribute and parameter names as the reference (``rn
 * ``rnn_name="FastGRNNBatchNormCUDA"`` builds ``kws_amd.FastGRNNBatchNormCUDA`` layers: the same model trained on the
   GPU (training-mode BatchNorm; ``model.train()`` / ``model.eval()`` pick the mode as for ``"FastGRNNBatchNorm"``),
   and ``loss()`` trains it through the fused head;
+* ``predict`` / ``batch_accuracy`` / ``evaluate`` (trainClassifier.py:54-65, 286-316) and ``detect_stream``
+  (inferencetry.py:213-227) end in the fused inference head and the majority vote: scores, argmax, the count of
+  correct rows and the detector's vote stay on the device;
 * the shadow ``rnn_list_`` / ``tracking`` ONNX-export path (model.py:72-84,187-195) is not built (export is
   disabled in the reference, trainClassifier.py:42-52), nor are the rolling hidden-state bags
   (model.py:135-148: data-loader bookkeeping, no arithmetic).
@@ -35,7 +38,7 @@ import torch.nn.functional as F
 
 from .batchnorm import FastGRNNBatchNorm
 from .batchnorm_train import FastGRNNBatchNormCUDA
-from .head import keyword_loss
+from .head import head_predict, keyword_loss, vote_windows
 from .fastgrnn_cuda import check_starts_range
 from .rnn import FastGRNNCUDA, gather_windows
 
@@ -134,16 +137,9 @@ class RNNClassifierModel(nn.Module):
             model_output = F.log_softmax(model_output, dim=1)
         return model_output
 
-    @torch.no_grad()
-    def score_stream(self, stream, hop=1, window=99):
-        """Score every window of continuous audio, as the reference's detector does one window at a time
-        (inferencetry.py:165-227: a 99-frame window slid over the stream, the model run from a zero state on each).
-        ``stream``: ``[S,L,F]`` (or ``[L,F]``: one stream) -> ``[S,Nw,C]`` scores, ``Nw = (L - window) // hop + 1``,
-        window ``w`` of stream ``s`` being frames ``w*hop .. w*hop + window - 1``.  Layer 0 reads the stream in place
-        (``forward_windows``: the window is the batch dimension, no ``window/hop``-fold copy); the layers above and
-        the head run as ``forward`` does under ``torch.no_grad()``.  Every window starts from a zero state:
-        ``hidden_states`` is neither read nor written.  Majority voting over consecutive windows is bookkeeping on
-        ``argmax`` and stays the caller's.  BatchNorm models: eval mode only."""
+    def _window_states(self, stream, hop, window):
+        """The layer chain of ``score_stream`` / ``detect_stream``: ``stream`` -> ``(h, S, Nw)``, ``h:[S*Nw,H_top]`` the
+        top layer's last state of every window, each from a zero state."""
         if stream.dim() == 2:
             stream = stream[None]
         if stream.dim() != 3:
@@ -163,12 +159,93 @@ class RNNClassifierModel(nn.Module):
         out = self.rnn_list[0].forward_windows(pool, starts, window, last_state=(top == 0), check=False, **kw)
         for l in range(1, self.num_layers):
             out = self.rnn_list[l](out, hiddenState=None, last_state=(l == top), **kw)
+        return out, S, nw
+
+    @torch.no_grad()
+    def score_stream(self, stream, hop=1, window=99):
+        """Score every window of continuous audio, as the reference's detector does one window at a time
+        (inferencetry.py:165-227: a 99-frame window slid over the stream, the model run from a zero state on each).
+        ``stream``: ``[S,L,F]`` (or ``[L,F]``: one stream) -> ``[S,Nw,C]`` scores, ``Nw = (L - window) // hop + 1``,
+        window ``w`` of stream ``s`` being frames ``w*hop .. w*hop + window - 1``.  Layer 0 reads the stream in place
+        (``forward_windows``: the window is the batch dimension, no ``window/hop``-fold copy); the layers above and
+        the head run as ``forward`` does under ``torch.no_grad()``.  Every window starts from a zero state:
+        ``hidden_states`` is neither read nor written.  ``detect_stream`` adds the argmax and the detector's majority
+        vote over consecutive windows on the device.  BatchNorm models: eval mode only."""
+        out, S, nw = self._window_states(stream, hop, window)
         out = out.float()
         if self.linear:
             out = self.hidden2keyword(out)
         if self.apply_softmax:
             out = F.log_softmax(out, dim=1)
         return out.reshape(S, nw, -1)
+
+    @torch.no_grad()
+    def detect_stream(self, stream, hop=1, window=99, num_windows=10, majority=5):
+        """The reference's detector over continuous audio (inferencetry.py:165-227) without leaving the device:
+        ``score_stream``'s chain with the fused inference head and the majority vote as its tail.  Returns
+        ``(pred, majority, event)``, each ``[S,Nw]`` int32 on the device: ``pred`` the argmax of every window's scores
+        (inferencetry.py:213-214), ``majority`` the most common of the last ``num_windows`` predictions where it has
+        at least ``majority`` votes, else -1, and ``event`` that keyword at the windows where the reference prints
+        "Detected keyword" (it differs from the last one reported, inferencetry.py:224-227), else -1.  Read detections
+        out with ``event >= 0``: ``s, w = (event >= 0).nonzero(as_tuple=True)``, keyword ``event[s, w]``, window ``w``
+        starting at frame ``w * hop``.  Streams vote independently, each from an empty list.  Needs ``linear=True``;
+        BatchNorm models: eval mode only."""
+        if not self.linear:
+            raise RuntimeError("detect_stream() needs the Linear head (linear=True)")
+        h, S, nw = self._window_states(stream, hop, window)
+        pred, _, _ = head_predict(h.float().contiguous(), self.hidden2keyword.weight.contiguous(),
+                                  self.hidden2keyword.bias.contiguous(), want_log_probs=False)
+        pred = pred.reshape(S, nw)
+        maj, event = vote_windows(pred, num_windows, majority)
+        return pred, maj, event
+
+    def _predict(self, input, labels=None, want_log_probs=True):
+        if not self.linear:
+            raise RuntimeError("predict() / batch_accuracy() / evaluate() need the Linear head (linear=True)")
+        h_last = self._last_state(input)
+        if labels is not None:
+            labels = labels.to(device=h_last.device, dtype=torch.int64).contiguous()
+        return head_predict(h_last.contiguous(), self.hidden2keyword.weight.contiguous(),
+                            self.hidden2keyword.bias.contiguous(), labels, want_log_probs)
+
+    @torch.no_grad()
+    def predict(self, input):
+        """``(pred, log_probs)``: ``forward``'s keyword scores ``[B,C]`` (log-probabilities, model.py:226-230) and
+        their argmax ``[B]`` int32, from the fused inference head.  Same layer chain and ``hidden_states`` carry as
+        ``forward``, under ``torch.no_grad()``.  Needs ``linear=True``.  ``log_probs`` are log-probabilities whatever
+        ``apply_softmax`` says: on a model built with ``apply_softmax=False``, whose ``forward`` returns the raw
+        logits, they are ``log_softmax`` of those (the argmax is the same)."""
+        pred, logp, _ = self._predict(input)
+        return pred, logp
+
+    @torch.no_grad()
+    def batch_accuracy(self, input, labels):
+        """The reference's ``batch_accuracy`` (trainClassifier.py:54-65) from the batch itself: runs ``predict`` on
+        ``input`` and returns ``(percent, passed, results)`` -- ``results`` the predicted class of every utterance,
+        ``passed`` how many equal ``labels``.  The reference compares row by row on the host (one sync per
+        utterance); here the comparison and the count happen in the head kernel and one device-to-host copy at the
+        end fetches both."""
+        pred, _, n_correct = self._predict(input, labels, want_log_probs=False)
+        host = torch.cat((n_correct, pred)).cpu().tolist()
+        passed, results = host[0], host[1:]
+        return (float(passed) * 100.0 / float(len(results)), passed, results)
+
+    @torch.no_grad()
+    def evaluate(self, batches):
+        """The reference's ``evaluate`` (trainClassifier.py:286-316) over an iterable of ``(input, labels)``, ``input``
+        in the layout ``forward`` takes: eval mode, ``init_hidden()`` before every batch (trainClassifier.py:304), the
+        correct predictions counted by the head kernel and added up on the device; one sync, at the end.  Returns
+        ``passed / total``."""
+        self.eval()                                                     # trainClassifier.py:290
+        passed, total = None, 0
+        for input, labels in batches:
+            self.init_hidden()
+            _, _, n_correct = self._predict(input, labels, want_log_probs=False)
+            passed = n_correct.to(torch.int64) if passed is None else passed + n_correct
+            total += labels.numel()
+        if total == 0:
+            raise ValueError("evaluate: no batches")
+        return int(passed) / total
 
     def loss(self, input, labels):
         """``nn.NLLLoss()(self(input), labels)`` (trainClassifier.py:233-236) with the fused head."""
