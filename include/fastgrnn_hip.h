@@ -496,6 +496,55 @@ int fastgrnn_hip_head_predict(int32_t B, int32_t H, int32_t C, const void *h_las
 int fastgrnn_hip_vote_windows(int32_t S, int32_t Nw, int32_t num_windows, int32_t majority, const int32_t *pred,
                               int32_t *majority_out, int32_t *event_out, void *stream);
 
+/* train_update -- the end of a trainer iteration in one call: optimizer.step() (trainClassifier.py:249) for every
+ * parameter tensor of a model, then the IHT phase of trainClassifier.py:251-259 on the tensors marked for it.  One
+ * launch per FASTGRNN_UPDATE_MAX_SEGS tensors ("segments"), one workgroup per segment; the segment table travels in
+ * the kernel arguments, so the call allocates nothing, copies nothing and never synchronises, and it may be captured
+ * in a graph.  fp32 tensors, fp32 arithmetic:
+ *   algo 0, torch.optim.Adam (amsgrad=False, maximize=False; weight_decay is L2, not AdamW), t = step[0]:
+ *     g' = g + wd p;  m' = beta1 m + (1-beta1) g';  v' = beta2 v + (1-beta2) g'^2
+ *     p' = p - (lr / (1-beta1^t)) m' / (sqrt(v') / sqrt(1-beta2^t) + eps)      (the bias corrections in double)
+ *   algo 1, torch.optim.SGD, mu = momentum, tau = dampening:
+ *     g' = g + wd p;  b' = g' if t == 1 else mu b + (1-tau) g';  d = g' + mu b' with nesterov, else b';  p' = p - lr d
+ *     (mu = 0: d = g' and the buffer is left alone, as torch keeps none)
+ * Then, on segments with iht != 0, by the device scalar iht_mode[0]:
+ *   1: th = the element of 0-based rank keep_rank among the ascending |p'|, found exactly (radix select on the bit
+ *      patterns); p' = 0 where |p'| < th -- ties with th survive, as numpy.percentile(..., 'higher') in utils.py:53-64
+ *      leaves them; keep_rank = 0 zeroes nothing.  support[i] = (p'[i] != 0), one byte per element, is written for
+ *      every such segment.
+ *   2: p' = 0 where support[i] == 0 (utils.py:66-81); support is only read.
+ *   0 or any other value: nothing.  The moments m, v, b are never masked (torch keeps updating them for zeroed entries).
+ * NaN parameters: the update propagates them; their place in the threshold's order is not specified.
+ * lr[1] (float), step[1] (int64: the 1-based number of THIS step, incremented by the caller, only read here) and
+ * iht_mode[1] (int32; NULL = 0) are DEVICE scalars: a replayed graph picks up new values.  segs is a HOST array, read
+ * before the call returns.  Repeatable bit for bit (the histogram's integer sums do not depend on order).
+ * Errors, all before any launch: FASTGRNN_ERR_NULL_POINTER (h, segs, lr, step; a segment's param, grad or state0;
+ * state1 under Adam; support on a segment with iht != 0, and iht_mode when there is such a segment),
+ * FASTGRNN_ERR_UNSUPPORTED (algo other than 0, 1), FASTGRNN_ERR_BAD_SHAPE (n_segs < 1; n outside 1..2^22; keep_rank
+ * outside 0..n-1; beta1, beta2 or momentum outside [0,1); eps <= 0 under Adam; weight_decay < 0; nesterov with zero
+ * momentum or non-zero dampening, torch's own rule).  No workspace. */
+#define FASTGRNN_UPDATE_MAX_SEGS 32
+#define FASTGRNN_UPDATE_MAX_N (1 << 22)
+typedef struct fastgrnn_update_seg {
+  void *param; const void *grad;      /* [n] fp32, device */
+  void *state0, *state1;              /* Adam: exp_avg, exp_avg_sq; SGD: momentum buffer, NULL */
+  uint8_t *support;                   /* [n], required iff iht != 0 */
+  int64_t n;                          /* 1 .. 2^22 */
+  int64_t keep_rank;                  /* 0 .. n-1: ceil((1-s)(n-1)), computed by the caller in double as
+                                         numpy's percentile index; 0 = everything survives */
+  int32_t iht, reserved;              /* 1: this tensor takes part in the IHT phases */
+} fastgrnn_update_seg;
+
+typedef struct fastgrnn_update_hyper {
+  int32_t algo;                       /* 0 Adam, 1 SGD */
+  int32_t nesterov;
+  double beta1_or_momentum, beta2_or_dampening, eps, weight_decay;
+} fastgrnn_update_hyper;
+
+int fastgrnn_hip_train_update(const fastgrnn_update_hyper *h, const fastgrnn_update_seg *segs /* HOST array */,
+                              int32_t n_segs, const float *lr, const int64_t *step, const int32_t *iht_mode,
+                              void *stream);
+
 /* frame_gemm -- the one genuinely dense, non-recurrent contraction of a layer, as a call of its own:
  *   P[rows, H] = X[rows, F] . W^T,   W:[H,F]  (rows = T*B; the reference computes it per step, `mm` at .cu:356).
  * forward_unroll runs exactly this launch in front of the scan for layers whose input is wider than 32 (the scan of a

@@ -49,6 +49,7 @@ EXPORTS = (
     "fastgrnn_hip_train_windows_backward_workspace_bytes", "fastgrnn_hip_forward_windows_train",
     "fastgrnn_hip_backward_windows",
     "fastgrnn_hip_head_predict_workspace_bytes", "fastgrnn_hip_head_predict", "fastgrnn_hip_vote_windows",
+    "fastgrnn_hip_train_update",
 )
 
 
@@ -97,6 +98,25 @@ class Plan(C.Structure):
     _fields_ = [("path", C.c_int32 * 2), ("forward_ws_optional", C.c_int32), ("dx_optional", C.c_int32),
                 ("rank_space_cols", C.c_int32), ("reserved", C.c_int32), ("workspace_bytes", C.c_size_t * 2),
                 ("zext", ZextPlan)]
+
+
+UPDATE_MAX_SEGS = 32            # FASTGRNN_UPDATE_MAX_SEGS: segments per launch of fastgrnn_hip_train_update
+UPDATE_MAX_N = 1 << 22          # FASTGRNN_UPDATE_MAX_N: elements per segment
+ADAM, SGD = 0, 1                # fastgrnn_update_hyper.algo
+IHT_NONE, IHT_THRESHOLD, IHT_SUPPORT = 0, 1, 2     # the device scalar iht_mode
+
+
+class UpdateSeg(C.Structure):
+    """fastgrnn_update_seg: one parameter tensor of fastgrnn_hip_train_update."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state0", C.c_void_p), ("state1", C.c_void_p),
+                ("support", C.c_void_p), ("n", C.c_int64), ("keep_rank", C.c_int64), ("iht", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class UpdateHyper(C.Structure):
+    """fastgrnn_update_hyper."""
+    _fields_ = [("algo", C.c_int32), ("nesterov", C.c_int32), ("beta1_or_momentum", C.c_double),
+                ("beta2_or_dampening", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double)]
 
 
 class FastGRNNLibraryError(RuntimeError):
@@ -152,6 +172,8 @@ def load():
     lib.fastgrnn_hip_head_predict.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.fastgrnn_hip_vote_windows.restype = i32
     lib.fastgrnn_hip_vote_windows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+    lib.fastgrnn_hip_train_update.restype = i32
+    lib.fastgrnn_hip_train_update.argtypes = [C.POINTER(UpdateHyper), C.POINTER(UpdateSeg), C.c_int32, vp, vp, vp, vp]
     lib.fastgrnn_hip_frame_gemm.restype = i32
     lib.fastgrnn_hip_frame_gemm.argtypes = [sz, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp]
     BP, BG = C.POINTER(BnParams), C.POINTER(BnGrads)

@@ -467,6 +467,28 @@ int fastgrnn_hip_vote_windows(int32_t S, int32_t Nw, int32_t num_windows, int32_
   return vote_windows(S, Nw, num_windows, majority, pred, majority_out, event_out, reinterpret_cast<hipStream_t>(stream));
 }
 
+int fastgrnn_hip_train_update(const fastgrnn_update_hyper* h, const fastgrnn_update_seg* segs, int32_t n_segs,
+                              const float* lr, const int64_t* step, const int32_t* iht_mode, void* stream) {
+  if (!h || !segs || !lr || !step) return FASTGRNN_ERR_NULL_POINTER;
+  if (h->algo != 0 && h->algo != 1) return FASTGRNN_ERR_UNSUPPORTED;
+  if (n_segs < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  const bool adam = h->algo == 0;
+  const double b1 = h->beta1_or_momentum, b2 = h->beta2_or_dampening;
+  // (written so that a NaN fails every range check)
+  if (!(b1 >= 0.0 && b1 < 1.0) || !(h->weight_decay >= 0.0)) return FASTGRNN_ERR_BAD_SHAPE;
+  if (adam && (!(b2 >= 0.0 && b2 < 1.0) || !(h->eps > 0.0))) return FASTGRNN_ERR_BAD_SHAPE;
+  if (!adam && h->nesterov && (b1 <= 0.0 || b2 != 0.0)) return FASTGRNN_ERR_BAD_SHAPE;   // torch.optim.SGD's rule
+  if (!adam && !(b2 == b2)) return FASTGRNN_ERR_BAD_SHAPE;
+  for (int32_t k = 0; k < n_segs; ++k) {
+    const fastgrnn_update_seg& sg = segs[k];
+    if (!sg.param || !sg.grad || !sg.state0 || (adam && !sg.state1)) return FASTGRNN_ERR_NULL_POINTER;
+    if (sg.iht && (!sg.support || !iht_mode)) return FASTGRNN_ERR_NULL_POINTER;
+    if (sg.n < 1 || sg.n > FASTGRNN_UPDATE_MAX_N || sg.keep_rank < 0 || sg.keep_rank >= sg.n)
+      return FASTGRNN_ERR_BAD_SHAPE;
+  }
+  return train_update(*h, segs, n_segs, lr, step, iht_mode, reinterpret_cast<hipStream_t>(stream));
+}
+
 int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void* x, const void* w, void* p, int32_t dtype,
                             void* stream) {
   if (!x || !w || !p) return FASTGRNN_ERR_NULL_POINTER;

@@ -180,6 +180,10 @@ int head_predict(int B, int H, int C, const void* h_last, const void* fc_w, cons
 bool vote_supported(int K);
 int vote_windows(int S, int Nw, int K, int M, const int32_t* pred, int32_t* majority, int32_t* event, hipStream_t s);
 
+// optimizer step + IHT phase for every parameter tensor (kernels_update.hip); arguments already checked, segs on the host
+int train_update(const fastgrnn_update_hyper& h, const fastgrnn_update_seg* segs, int n_segs, const float* lr,
+                 const int64_t* step, const int32_t* iht_mode, hipStream_t s);
+
 // training-mode BatchNorm cell (kernels_bn_train.hip): FASTGRNN_FLAG_BN_TRAIN
 bool bn_train_supported(const fastgrnn_desc& d);
 size_t bn_train_forward_ws(const fastgrnn_desc& d);

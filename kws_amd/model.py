@@ -40,6 +40,7 @@ from .batchnorm import FastGRNNBatchNorm
 from .batchnorm_train import FastGRNNBatchNormCUDA
 from .head import head_predict, keyword_loss, vote_windows
 from .fastgrnn_cuda import check_starts_range
+from .optim import _FusedOptimizer
 from .rnn import FastGRNNCUDA, gather_windows
 
 _RNN_CLASSES = {"FastGRNNCUDA": FastGRNNCUDA, "FastGRNNBatchNorm": FastGRNNBatchNorm,     # model.py:12-15
@@ -255,6 +256,32 @@ class RNNClassifierModel(nn.Module):
             raise RuntimeError("loss() is the Linear + log_softmax + NLLLoss tail (linear=True, apply_softmax=True)")
         h_last = self._last_state(input)
         return keyword_loss(h_last, self.hidden2keyword.weight, self.hidden2keyword.bias, labels)
+
+    def train_step(self, input, labels, optimizer, iht="none", bucket=None):
+        """One trainer iteration (trainClassifier.py:230-259) on the device: gradients set to None, ``loss()``,
+        ``backward()``, the gradient all-reduce of ``bucket`` (a ``kws_amd.dp.GradBucket``) if given, then
+        ``optimizer.step(iht)``.  ``optimizer`` must be a ``kws_amd.FusedAdam`` / ``FusedSGD`` (``TypeError`` otherwise:
+        a torch optimizer's ``step()`` has no IHT phase): the update of every parameter and the IHT
+        phase ``iht`` (``"none"``, ``"threshold"``, ``"support"``: what ``kws_amd.iht_phase`` returns for the
+        iteration, or ``None`` to leave the optimizer's ``iht_t`` as it is) in one library call.  Returns the detached
+        loss.  Nothing here synchronises, so the whole step captures in a ``GraphedStep`` (build the optimizer with
+        ``capturable=True`` and write its ``lr_t`` / ``iht_t`` between replays).
+
+        The fused optimizer owns the support masks of its IHT phases (``optimizer.support(param)``); it neither reads
+        nor writes a layer's ``oldmats``, and ``sparsify()`` / ``sparsifyWithSupport()`` stay as they are.  The two
+        mechanisms are not meant to be mixed within one run."""
+        if not isinstance(optimizer, _FusedOptimizer):
+            raise TypeError("train_step() needs a kws_amd.FusedAdam or kws_amd.FusedSGD (got %s): a torch optimizer's "
+                            "step() has no IHT phase -- call loss(), backward(), optimizer.step() and sparsify() yourself"
+                            % type(optimizer).__name__)
+        for p in self.parameters():
+            p.grad = None
+        loss = self.loss(input, labels)
+        loss.backward()
+        if bucket is not None:
+            bucket.all_reduce_()
+        optimizer.step(iht)
+        return loss.detach()
 
     def loss_windows(self, pool, starts, labels, window=99):
         """``loss()`` on the batch whose utterance ``b`` is the ``window`` consecutive rows of ``pool:[R,F]`` from row
