@@ -545,6 +545,55 @@ int fastgrnn_hip_train_update(const fastgrnn_update_hyper *h, const fastgrnn_upd
                               int32_t n_segs, const float *lr, const int64_t *step, const int32_t *iht_mode,
                               void *stream);
 
+/* mfcc -- the reference's featuriser, librosa.feature.mfcc + librosa.feature.delta at librosa 0.10.2's defaults as
+ * data_pipeline/mfccProcessor.py:43-58 calls them, then the pad / cut and the normalisation of preprocessing.py:79-88 and
+ * inferencetry.py:165-200, from raw audio in one launch.  sr = 16000, n_fft = win_length = 400, hop = 160, n_mels = 128
+ * are fixed.  Per clip y of len samples:
+ *   1. fp32 samples, or int16 PCM times 2^-15; with FASTGRNN_MFCC_PEAK_NORMALIZE y /= max|y| (fp32) if that is > 0.
+ *   2. center=True, pad_mode="constant": 200 zeros on each side, n = 1 + len / 160 frames, periodic Hann window.
+ *   3. power |rfft|^2 (201 bins);  4. Slaney mel weights (fmin 0, fmax 8000, norm="slaney"; fp64 rounded to fp32).
+ *   5. dB = 10 log10(max(1e-10, M)), then max(dB, max over the clip's n frames and 128 mels - top_db)  (top_db < 0:
+ *      no clip).   6. DCT-II, norm="ortho", the first n_mfcc coefficients.
+ *   7. order >= 1: delta = savgol(width, polyorder 1, deriv 1, mode="interp"), taps k / sum k^2; order 2 adds
+ *      delta-delta = savgol(width, polyorder 2, deriv 2) OF THE MFCC, taps 2 (w k^2 - sum k^2) / (w sum k^4 - (sum k^2)^2);
+ *      k = -h..h, h = width / 2; the first h frames take frame h's value, the last h frame n-1-h's (deriv == polyorder
+ *      makes the interp edges constant).   8. rows [mfcc; delta; delta2]: F = n_mfcc (order + 1) features.
+ *   9. pad with zeros or cut to max_len frames (after 5 and 7 have seen all n frames).
+ *  10. with mean / std ([F] fp32, both or neither): (f - mean) / std; padded frames become -mean / std.
+ * audio: clip b starts at ELEMENT b * clip_stride (fp32 or int16; no alignment beyond the element's is assumed);
+ * clip_stride < L gives overlapping clips of one recording without a copy.  lengths: NULL (every clip is L long) or [B]
+ * int32 on the device with 1280 <= lengths[b] <= L; the kernel clamps into that range, so no value makes it read or
+ * write outside its buffers.  feats: [B, max_len, F] fp32, contiguous and fully written -- a frame pool for
+ * fastgrnn_hip_forward_windows (clip b = rows b max_len ..).  tables: fastgrnn_hip_mfcc_tables_bytes() bytes that
+ * fastgrnn_hip_mfcc_init_tables filled once (window-folded DFT basis, mel weights, DCT, taps: computed on the device in
+ * fp64 with exact integer angle reduction, rounded to fp32); the library allocates nothing.  Arithmetic: the three
+ * products on the exact-fp32 matrix instruction (a k-ordered fmaf chain), accurate log10f, no atomics: repeatable bit
+ * for bit, and a clip's rows do not depend on its neighbours.  One launch on `stream`, no host decision on device data:
+ * the call may be captured in a graph.
+ * Supported: 1280 <= L <= 16000, 1 <= n_mfcc <= 64, order 0 / 1 / 2, width odd in 3..15 with L >= 160 (width - 1),
+ * flags = 0 or FASTGRNN_MFCC_PEAK_NORMALIZE; else FASTGRNN_ERR_UNSUPPORTED.  FASTGRNN_ERR_BAD_SHAPE: B, L, clip_stride,
+ * max_len or n_mfcc < 1, top_db NaN, size overflow; FASTGRNN_ERR_BAD_DTYPE: audio_dtype; FASTGRNN_ERR_NULL_POINTER: d,
+ * audio, tables, feats, exactly one of mean / std; FASTGRNN_ERR_WORKSPACE as everywhere (the query answers 0 today).
+ * All before any launch. */
+#define FASTGRNN_MFCC_PEAK_NORMALIZE 1u
+#define FASTGRNN_MFCC_AUDIO_F32 0
+#define FASTGRNN_MFCC_AUDIO_I16 1
+typedef struct fastgrnn_mfcc_desc {
+  int32_t B, L;                       /* clips, samples per clip */
+  int64_t clip_stride;                /* elements between the starts of consecutive clips, >= 1 */
+  int32_t audio_dtype;                /* FASTGRNN_MFCC_AUDIO_F32 / _I16 */
+  int32_t n_mfcc, order, width, max_len;
+  float top_db;
+  uint32_t flags;
+} fastgrnn_mfcc_desc;
+
+size_t fastgrnn_hip_mfcc_tables_bytes(void);
+int fastgrnn_hip_mfcc_init_tables(void *tables, void *stream);
+size_t fastgrnn_hip_mfcc_workspace_bytes(const fastgrnn_mfcc_desc *d);
+int fastgrnn_hip_mfcc(const fastgrnn_mfcc_desc *d, const void *audio, const int32_t *lengths, const void *tables,
+                      const float *mean, const float *std, void *feats, void *workspace, size_t workspace_bytes,
+                      void *stream);
+
 /* frame_gemm -- the one genuinely dense, non-recurrent contraction of a layer, as a call of its own:
  *   P[rows, H] = X[rows, F] . W^T,   W:[H,F]  (rows = T*B; the reference computes it per step, `mm` at .cu:356).
  * forward_unroll runs exactly this launch in front of the scan for layers whose input is wider than 32 (the scan of a

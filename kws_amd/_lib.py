@@ -50,6 +50,8 @@ EXPORTS = (
     "fastgrnn_hip_backward_windows",
     "fastgrnn_hip_head_predict_workspace_bytes", "fastgrnn_hip_head_predict", "fastgrnn_hip_vote_windows",
     "fastgrnn_hip_train_update",
+    "fastgrnn_hip_mfcc_tables_bytes", "fastgrnn_hip_mfcc_init_tables", "fastgrnn_hip_mfcc_workspace_bytes",
+    "fastgrnn_hip_mfcc",
 )
 
 
@@ -119,6 +121,18 @@ class UpdateHyper(C.Structure):
                 ("beta2_or_dampening", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double)]
 
 
+MFCC_PEAK_NORMALIZE = 1         # FASTGRNN_MFCC_PEAK_NORMALIZE
+MFCC_AUDIO_F32, MFCC_AUDIO_I16 = 0, 1
+MFCC_MIN_SAMPLES, MFCC_MAX_SAMPLES = 1280, 16000     # the clip lengths fastgrnn_hip_mfcc takes
+
+
+class MfccDesc(C.Structure):
+    """fastgrnn_mfcc_desc."""
+    _fields_ = [("B", C.c_int32), ("L", C.c_int32), ("clip_stride", C.c_int64), ("audio_dtype", C.c_int32),
+                ("n_mfcc", C.c_int32), ("order", C.c_int32), ("width", C.c_int32), ("max_len", C.c_int32),
+                ("top_db", C.c_float), ("flags", C.c_uint32)]
+
+
 class FastGRNNLibraryError(RuntimeError):
     pass
 
@@ -174,6 +188,15 @@ def load():
     lib.fastgrnn_hip_vote_windows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.fastgrnn_hip_train_update.restype = i32
     lib.fastgrnn_hip_train_update.argtypes = [C.POINTER(UpdateHyper), C.POINTER(UpdateSeg), C.c_int32, vp, vp, vp, vp]
+    MD = C.POINTER(MfccDesc)
+    lib.fastgrnn_hip_mfcc_tables_bytes.restype = sz
+    lib.fastgrnn_hip_mfcc_tables_bytes.argtypes = []
+    lib.fastgrnn_hip_mfcc_init_tables.restype = i32
+    lib.fastgrnn_hip_mfcc_init_tables.argtypes = [vp, vp]
+    lib.fastgrnn_hip_mfcc_workspace_bytes.restype = sz
+    lib.fastgrnn_hip_mfcc_workspace_bytes.argtypes = [MD]
+    lib.fastgrnn_hip_mfcc.restype = i32
+    lib.fastgrnn_hip_mfcc.argtypes = [MD, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.fastgrnn_hip_frame_gemm.restype = i32
     lib.fastgrnn_hip_frame_gemm.argtypes = [sz, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp]
     BP, BG = C.POINTER(BnParams), C.POINTER(BnGrads)

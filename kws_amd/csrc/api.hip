@@ -489,6 +489,43 @@ int fastgrnn_hip_train_update(const fastgrnn_update_hyper* h, const fastgrnn_upd
   return train_update(*h, segs, n_segs, lr, step, iht_mode, reinterpret_cast<hipStream_t>(stream));
 }
 
+// FASTGRNN_OK or the refusal of a featuriser descriptor (include/fastgrnn_hip.h lists the supported range)
+static int check_mfcc_desc(const fastgrnn_mfcc_desc* d) {
+  if (!d) return FASTGRNN_ERR_NULL_POINTER;
+  if (d->B < 1 || d->L < 1 || d->clip_stride < 1 || d->max_len < 1 || d->n_mfcc < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  if (!(d->top_db == d->top_db)) return FASTGRNN_ERR_BAD_SHAPE;
+  if (d->audio_dtype != FASTGRNN_MFCC_AUDIO_F32 && d->audio_dtype != FASTGRNN_MFCC_AUDIO_I16) return FASTGRNN_ERR_BAD_DTYPE;
+  if (d->L < 1280 || d->L > 16000 || d->n_mfcc > 64 || d->order < 0 || d->order > 2) return FASTGRNN_ERR_UNSUPPORTED;
+  if (d->width < 3 || d->width > 15 || !(d->width & 1) || d->L < 160 * (d->width - 1)) return FASTGRNN_ERR_UNSUPPORTED;
+  if (d->flags & ~(uint32_t)FASTGRNN_MFCC_PEAK_NORMALIZE) return FASTGRNN_ERR_UNSUPPORTED;
+  // (element offsets are size_t and the workgroup's block of the output is indexed in 32 bits)
+  const double per_clip = (double)d->max_len * d->n_mfcc * (d->order + 1);
+  if (per_clip > 1073741824.0 || per_clip * d->B > 1099511627776.0) return FASTGRNN_ERR_BAD_SHAPE;
+  return FASTGRNN_OK;
+}
+
+size_t fastgrnn_hip_mfcc_tables_bytes(void) { return mfcc_tables_bytes(); }
+
+int fastgrnn_hip_mfcc_init_tables(void* tables, void* stream) {
+  if (!tables) return FASTGRNN_ERR_NULL_POINTER;
+  return mfcc_init_tables(tables, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t fastgrnn_hip_mfcc_workspace_bytes(const fastgrnn_mfcc_desc* d) {
+  (void)d;
+  return 0;                                      // (everything between the samples and the rows stays in LDS)
+}
+
+int fastgrnn_hip_mfcc(const fastgrnn_mfcc_desc* d, const void* audio, const int32_t* lengths, const void* tables,
+                      const float* mean, const float* std, void* feats, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+  int st = check_mfcc_desc(d);
+  if (st) return st;
+  if (!audio || !tables || !feats || (!mean != !std)) return FASTGRNN_ERR_NULL_POINTER;
+  if ((st = check_ws(workspace, workspace_bytes, fastgrnn_hip_mfcc_workspace_bytes(d)))) return st;
+  return mfcc_run(*d, audio, lengths, tables, mean, std, feats, reinterpret_cast<hipStream_t>(stream));
+}
+
 int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void* x, const void* w, void* p, int32_t dtype,
                             void* stream) {
   if (!x || !w || !p) return FASTGRNN_ERR_NULL_POINTER;

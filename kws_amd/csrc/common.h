@@ -184,6 +184,12 @@ int vote_windows(int S, int Nw, int K, int M, const int32_t* pred, int32_t* majo
 int train_update(const fastgrnn_update_hyper& h, const fastgrnn_update_seg* segs, int n_segs, const float* lr,
                  const int64_t* step, const int32_t* iht_mode, hipStream_t s);
 
+// MFCC + delta features from raw audio (kernels_mfcc.hip); arguments already checked
+size_t mfcc_tables_bytes();
+int mfcc_init_tables(void* tables, hipStream_t s);
+int mfcc_run(const fastgrnn_mfcc_desc& d, const void* audio, const int32_t* lengths, const void* tables, const float* mean,
+             const float* stdv, void* feats, hipStream_t s);
+
 // training-mode BatchNorm cell (kernels_bn_train.hip): FASTGRNN_FLAG_BN_TRAIN
 bool bn_train_supported(const fastgrnn_desc& d);
 size_t bn_train_forward_ws(const fastgrnn_desc& d);

@@ -200,6 +200,34 @@ class RNNClassifierModel(nn.Module):
         maj, event = vote_windows(pred, num_windows, majority)
         return pred, maj, event
 
+    @torch.no_grad()
+    def detect_audio(self, recording, frontend, hop_samples=800, num_windows=10, majority=5, clip=16000):
+        """The reference's live loop (inferencetry.py:165-227) end to end on raw audio: every ``hop_samples`` (50 ms)
+        the last ``clip`` samples of the 1-D ``recording`` (fp32 or int16 PCM) are peak-normalised and featurised by
+        ``frontend`` (a ``kws_amd.MFCCFrontend``; its ``mean`` / ``std`` and ``max_len`` are the model's), the model
+        runs each clip from a zero state, and the majority vote runs over consecutive clips.  The clips are a strided
+        view of the recording (``MFCCFrontend.clips_of``) and layer 0 reads the feature pool in place where the
+        windowed scans hold the cell (``forward_windows`` with ``starts = arange(B) * max_len``; gathered elsewhere),
+        so nothing is copied between the samples and the vote.  Returns what ``detect_stream`` returns for one stream:
+        ``(pred, majority, event)``, each ``[1, B]`` int32 on the device, ``B = (N - clip) // hop_samples + 1``.
+        ``hidden_states`` is neither read nor written.  Needs ``linear=True``; BatchNorm models: eval mode only."""
+        if not self.linear:
+            raise RuntimeError("detect_audio() needs the Linear head (linear=True)")
+        if frontend.num_features != self.input_dim:
+            raise ValueError("the front end gives %d features, the model takes %d" % (frontend.num_features, self.input_dim))
+        clips = frontend.clips_of(recording.to(self.rnn_list[0].device), hop_samples, clip)
+        peak, frontend.peak_normalize = frontend.peak_normalize, True        # inferencetry.py:172-175
+        try:
+            feats = frontend(clips)                                          # [B, max_len, F]: the frame pool
+        finally:
+            frontend.peak_normalize = peak
+        h, B, _ = self._window_states(feats, 1, feats.shape[1])              # (one window per clip: starts = b * max_len)
+        pred, _, _ = head_predict(h.float().contiguous(), self.hidden2keyword.weight.contiguous(),
+                                  self.hidden2keyword.bias.contiguous(), want_log_probs=False)
+        pred = pred.reshape(1, B)
+        maj, event = vote_windows(pred, num_windows, majority)
+        return pred, maj, event
+
     def _predict(self, input, labels=None, want_log_probs=True):
         if not self.linear:
             raise RuntimeError("predict() / batch_accuracy() / evaluate() need the Linear head (linear=True)")
