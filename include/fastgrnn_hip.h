@@ -594,6 +594,82 @@ int fastgrnn_hip_mfcc(const fastgrnn_mfcc_desc *d, const void *audio, const int3
                       const float *mean, const float *std, void *feats, void *workspace, size_t workspace_bytes,
                       void *stream);
 
+/* mfcc_augment -- the featuriser reading an AUDIO BANK through per-clip augmentation records: the reference's
+ * data_pipeline/audioAugmentation.py (background noise at a gain, wrapped to the clip's length) plus the time shift of
+ * preprocessing.py:13's to-do, applied while the clip is loaded; the augmented clip is never written to memory.
+ * d is a fastgrnn_mfcc_desc whose B is the number of OUTPUT clips (= records) and whose clip_stride is the bank's.
+ * audio: the bank, clip c at element c * clip_stride, c < bank->n_clips.  lengths: NULL or [n_clips], indexed by src.
+ * noise: bank->n_noise rows of the audio's dtype, row k at element k * noise_stride; noise_lengths: [n_noise] int32 on
+ * the device; the buffer holds (n_noise - 1) * noise_stride + noise_len_max elements.  aug: [B] records on the device.
+ * For output clip b with record r:  c = r.src clamped into 0 .. n_clips-1;  len = lengths[c] clamped into 1280 .. L
+ * (L without lengths);  and, when r.noise >= 0 and n_noise > 0:  k = min(r.noise, n_noise-1),  nlen = noise_lengths[k]
+ * clamped into 1 .. noise_len_max,  off = r.noise_off mod nlen (the non-negative remainder).  For 0 <= i < len
+ *   y'[i] = fl( fl(r.gain * y[i - r.shift]) + fl(r.noise_gain * nz[(off + i) mod nlen]) )
+ * with y = clip c as step 1 of mfcc reads it (fp32, or int16 times 2^-15: exact), y[j] = 0 outside 0 .. len-1, and the
+ * three fp32 operations rounded to nearest one by one (no fused multiply-add): numpy and torch reproduce the samples
+ * bit for bit.  r.shift is any int32 (the difference does not overflow; |shift| >= len leaves no sample of y).  With
+ * r.noise < 0 (or n_noise = 0) the noise term is ABSENT, y'[i] = fl(r.gain * y[i - r.shift]): the noise bank is not
+ * read, so nothing in it -- NaN, inf -- can leak.  The wrap is numpy.pad(noise, mode='wrap')[:len]
+ * (audioAugmentation.py:47-49) generalised by a start offset; gain = 0 gives the reference's noise-only clips.  The clip
+ * keeps len samples, hence its frame count.  Steps 1 (the peak normalisation, if flagged, of y') to 10 of mfcc follow
+ * unchanged; feats: [B, max_len, F].  The clamps above are the DEFINED behaviour for records outside their ranges: no
+ * record value moves a read or a write outside the buffers.  One launch, no workspace, capturable.
+ * Errors, all before any launch: everything mfcc refuses for d;  FASTGRNN_ERR_NULL_POINTER: bank, aug, audio, tables,
+ * feats, one of mean / std, noise or noise_lengths while n_noise > 0;  FASTGRNN_ERR_BAD_SHAPE: n_clips < 1, n_noise < 0,
+ * noise_stride < 1 while n_noise > 0 (clip_stride < 1 as in mfcc);  FASTGRNN_ERR_UNSUPPORTED: noise_len_max outside
+ * 1 .. 2^24 while n_noise > 0. */
+typedef struct fastgrnn_mfcc_aug {      /* one per OUTPUT clip, device array [B] */
+  int32_t src;        /* bank clip to read, 0 .. n_clips-1 */
+  int32_t shift;      /* samples; y'[i] = y[i - shift], zero outside 0 .. len-1 */
+  int32_t noise;      /* noise bank row, or < 0: none */
+  int32_t noise_off;  /* first noise sample, 0 .. nlen-1 */
+  float   gain, noise_gain;
+} fastgrnn_mfcc_aug;
+
+#define FASTGRNN_MFCC_NOISE_LEN_MAX (1 << 24)
+typedef struct fastgrnn_mfcc_bank {
+  int32_t n_clips;                    /* clips in the audio bank, >= 1 */
+  int32_t n_noise;                    /* rows of the noise bank, >= 0 */
+  int64_t noise_stride;               /* elements between the starts of consecutive noise rows, >= 1 */
+  int32_t noise_len_max;              /* 1 .. 2^24: the bound the kernel holds every noise length to */
+  int32_t reserved;
+} fastgrnn_mfcc_bank;
+
+int fastgrnn_hip_mfcc_augment(const fastgrnn_mfcc_desc *d, const fastgrnn_mfcc_bank *bank, const void *audio,
+                              const int32_t *lengths, const void *noise, const int32_t *noise_lengths,
+                              const fastgrnn_mfcc_aug *aug, const void *tables, const float *mean, const float *std,
+                              void *feats, void *workspace, size_t workspace_bytes, void *stream);
+
+/* augment_draw -- the records of mfcc_augment from a counter-based generator, in one small launch: nothing is drawn on
+ * the host, and a graph captured once draws new augmentations on every replay as step advances.  seed is a HOST value;
+ * step[1] (int64) is a DEVICE scalar that is only read, like train_update's; index: [B] int32 on the device, copied to
+ * src.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key = (seed_lo,
+ * seed_hi); block j of clip b has the counter (b, step_lo, step_hi, j); x0..x3 = block 0, x4..x7 = block 1.  With
+ * u(x) = (x >> 8) * 2^-24 and r(x, n) = ((uint64)x * n) >> 32:
+ *   augment    = u(x0) < p_augment
+ *   shift      = r(x1, 2 max_shift + 1) - max_shift
+ *   gain       = fl(gain_lo + fl(fl(gain_hi - gain_lo) * u(x2)))
+ *   with_noise = augment && n_noise > 0 && u(x3) < p_noise
+ *   noise      = r(x4, n_noise)
+ *   noise_off  = r(x5, nlen[noise]),   nlen = noise_lengths clamped into 1 .. noise_len_max
+ *   noise_gain = fl(noise_gain_lo + fl(fl(noise_gain_hi - noise_gain_lo) * u(x6)))
+ * A clip that is not augmented gets (src, 0, -1, 0, 1.0f, 0.0f); one augmented without noise gets noise = -1,
+ * noise_off = 0 and noise_gain = 0.  Record b depends on (seed, step, b) alone: not on B, not on the launch geometry.
+ * The reference's settings are p_noise = 0.5 and noise_gain_lo = noise_gain_hi = 0.1.
+ * Errors, all before any launch: FASTGRNN_ERR_NULL_POINTER (r, step, index, aug; noise_lengths while n_noise > 0),
+ * FASTGRNN_ERR_BAD_SHAPE (B < 1; n_noise < 0; a probability outside [0,1] or NaN; lo > hi or a non-finite bound),
+ * FASTGRNN_ERR_UNSUPPORTED (max_shift outside 0 .. 2^20; noise_len_max outside 1 .. 2^24 while n_noise > 0). */
+#define FASTGRNN_AUGMENT_MAX_SHIFT (1 << 20)
+typedef struct fastgrnn_augment_ranges {
+  float p_augment, p_noise;
+  int32_t max_shift, reserved;
+  float gain_lo, gain_hi, noise_gain_lo, noise_gain_hi;
+} fastgrnn_augment_ranges;
+
+int fastgrnn_hip_augment_draw(int32_t B, uint64_t seed, const int64_t *step, const int32_t *index,
+                              const fastgrnn_augment_ranges *r, int32_t n_noise, int32_t noise_len_max,
+                              const int32_t *noise_lengths, fastgrnn_mfcc_aug *aug, void *stream);
+
 /* frame_gemm -- the one genuinely dense, non-recurrent contraction of a layer, as a call of its own:
  *   P[rows, H] = X[rows, F] . W^T,   W:[H,F]  (rows = T*B; the reference computes it per step, `mm` at .cu:356).
  * forward_unroll runs exactly this launch in front of the scan for layers whose input is wider than 32 (the scan of a

@@ -51,7 +51,7 @@ EXPORTS = (
     "fastgrnn_hip_head_predict_workspace_bytes", "fastgrnn_hip_head_predict", "fastgrnn_hip_vote_windows",
     "fastgrnn_hip_train_update",
     "fastgrnn_hip_mfcc_tables_bytes", "fastgrnn_hip_mfcc_init_tables", "fastgrnn_hip_mfcc_workspace_bytes",
-    "fastgrnn_hip_mfcc",
+    "fastgrnn_hip_mfcc", "fastgrnn_hip_mfcc_augment", "fastgrnn_hip_augment_draw",
 )
 
 
@@ -133,6 +133,29 @@ class MfccDesc(C.Structure):
                 ("top_db", C.c_float), ("flags", C.c_uint32)]
 
 
+MFCC_NOISE_LEN_MAX = 1 << 24     # FASTGRNN_MFCC_NOISE_LEN_MAX
+AUGMENT_MAX_SHIFT = 1 << 20      # FASTGRNN_AUGMENT_MAX_SHIFT
+
+
+class MfccAug(C.Structure):
+    """fastgrnn_mfcc_aug: one augmentation record (a row of the ``[B, 6]`` int32 tensors of ``kws_amd.augment``)."""
+    _fields_ = [("src", C.c_int32), ("shift", C.c_int32), ("noise", C.c_int32), ("noise_off", C.c_int32),
+                ("gain", C.c_float), ("noise_gain", C.c_float)]
+
+
+class MfccBank(C.Structure):
+    """fastgrnn_mfcc_bank."""
+    _fields_ = [("n_clips", C.c_int32), ("n_noise", C.c_int32), ("noise_stride", C.c_int64),
+                ("noise_len_max", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AugmentRanges(C.Structure):
+    """fastgrnn_augment_ranges."""
+    _fields_ = [("p_augment", C.c_float), ("p_noise", C.c_float), ("max_shift", C.c_int32), ("reserved", C.c_int32),
+                ("gain_lo", C.c_float), ("gain_hi", C.c_float), ("noise_gain_lo", C.c_float),
+                ("noise_gain_hi", C.c_float)]
+
+
 class FastGRNNLibraryError(RuntimeError):
     pass
 
@@ -197,6 +220,11 @@ def load():
     lib.fastgrnn_hip_mfcc_workspace_bytes.argtypes = [MD]
     lib.fastgrnn_hip_mfcc.restype = i32
     lib.fastgrnn_hip_mfcc.argtypes = [MD, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.fastgrnn_hip_mfcc_augment.restype = i32
+    lib.fastgrnn_hip_mfcc_augment.argtypes = [MD, C.POINTER(MfccBank), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.fastgrnn_hip_augment_draw.restype = i32
+    lib.fastgrnn_hip_augment_draw.argtypes = [C.c_int32, C.c_uint64, vp, vp, C.POINTER(AugmentRanges), C.c_int32,
+                                              C.c_int32, vp, vp, vp]
     lib.fastgrnn_hip_frame_gemm.restype = i32
     lib.fastgrnn_hip_frame_gemm.argtypes = [sz, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp]
     BP, BG = C.POINTER(BnParams), C.POINTER(BnGrads)

@@ -526,6 +526,46 @@ int fastgrnn_hip_mfcc(const fastgrnn_mfcc_desc* d, const void* audio, const int3
   return mfcc_run(*d, audio, lengths, tables, mean, std, feats, reinterpret_cast<hipStream_t>(stream));
 }
 
+// the noise bank's sizes, as both augmentation calls read them
+static int check_noise_bank(int32_t n_noise, int32_t noise_len_max, const int32_t* noise_lengths) {
+  if (n_noise < 0) return FASTGRNN_ERR_BAD_SHAPE;
+  if (n_noise > 0 && !noise_lengths) return FASTGRNN_ERR_NULL_POINTER;
+  if (n_noise > 0 && (noise_len_max < 1 || noise_len_max > FASTGRNN_MFCC_NOISE_LEN_MAX)) return FASTGRNN_ERR_UNSUPPORTED;
+  return FASTGRNN_OK;
+}
+
+int fastgrnn_hip_mfcc_augment(const fastgrnn_mfcc_desc* d, const fastgrnn_mfcc_bank* bank, const void* audio,
+                              const int32_t* lengths, const void* noise, const int32_t* noise_lengths,
+                              const fastgrnn_mfcc_aug* aug, const void* tables, const float* mean, const float* std,
+                              void* feats, void* workspace, size_t workspace_bytes, void* stream) {
+  int st = check_mfcc_desc(d);
+  if (st) return st;
+  if (!bank || !aug || !audio || !tables || !feats || (!mean != !std)) return FASTGRNN_ERR_NULL_POINTER;
+  if (bank->n_clips < 1 || bank->n_noise < 0 || (bank->n_noise > 0 && bank->noise_stride < 1)) return FASTGRNN_ERR_BAD_SHAPE;
+  if (bank->n_noise > 0 && !noise) return FASTGRNN_ERR_NULL_POINTER;
+  if ((st = check_noise_bank(bank->n_noise, bank->noise_len_max, noise_lengths))) return st;
+  if ((st = check_ws(workspace, workspace_bytes, fastgrnn_hip_mfcc_workspace_bytes(d)))) return st;
+  return mfcc_augment_run(*d, *bank, audio, lengths, noise, noise_lengths, aug, tables, mean, std, feats,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
+int fastgrnn_hip_augment_draw(int32_t B, uint64_t seed, const int64_t* step, const int32_t* index,
+                              const fastgrnn_augment_ranges* r, int32_t n_noise, int32_t noise_len_max,
+                              const int32_t* noise_lengths, fastgrnn_mfcc_aug* aug, void* stream) {
+  if (!r || !step || !index || !aug) return FASTGRNN_ERR_NULL_POINTER;
+  if (B < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  int st = check_noise_bank(n_noise, noise_len_max, noise_lengths);
+  if (st) return st;
+  // (written so that a NaN fails every range check; lo <= hi, both and their difference finite)
+  if (!(r->p_augment >= 0.f && r->p_augment <= 1.f) || !(r->p_noise >= 0.f && r->p_noise <= 1.f)) return FASTGRNN_ERR_BAD_SHAPE;
+  const float inf = __builtin_huge_valf();
+  if (!(r->gain_lo <= r->gain_hi && r->gain_lo > -inf && r->gain_hi - r->gain_lo < inf)) return FASTGRNN_ERR_BAD_SHAPE;
+  if (!(r->noise_gain_lo <= r->noise_gain_hi && r->noise_gain_lo > -inf && r->noise_gain_hi - r->noise_gain_lo < inf)) return FASTGRNN_ERR_BAD_SHAPE;
+  if (r->max_shift < 0 || r->max_shift > FASTGRNN_AUGMENT_MAX_SHIFT) return FASTGRNN_ERR_UNSUPPORTED;
+  return augment_draw_run(B, seed, step, index, *r, n_noise, noise_len_max, noise_lengths, aug,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
 int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void* x, const void* w, void* p, int32_t dtype,
                             void* stream) {
   if (!x || !w || !p) return FASTGRNN_ERR_NULL_POINTER;

@@ -189,6 +189,12 @@ size_t mfcc_tables_bytes();
 int mfcc_init_tables(void* tables, hipStream_t s);
 int mfcc_run(const fastgrnn_mfcc_desc& d, const void* audio, const int32_t* lengths, const void* tables, const float* mean,
              const float* stdv, void* feats, hipStream_t s);
+// ... reading an audio bank through augmentation records, and the records' draw (kernels_augment.hip)
+int mfcc_augment_run(const fastgrnn_mfcc_desc& d, const fastgrnn_mfcc_bank& bank, const void* audio, const int32_t* lengths,
+                     const void* noise, const int32_t* noise_lengths, const fastgrnn_mfcc_aug* aug, const void* tables,
+                     const float* mean, const float* stdv, void* feats, hipStream_t s);
+int augment_draw_run(int B, uint64_t seed, const int64_t* step, const int32_t* index, const fastgrnn_augment_ranges& r,
+                     int n_noise, int noise_len_max, const int32_t* noise_lengths, fastgrnn_mfcc_aug* aug, hipStream_t s);
 
 // training-mode BatchNorm cell (kernels_bn_train.hip): FASTGRNN_FLAG_BN_TRAIN
 bool bn_train_supported(const fastgrnn_desc& d);

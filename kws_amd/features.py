@@ -7,7 +7,9 @@ frames, normalised with ``mean`` / ``std``).  ``mfcc_features`` is that chain in
 librosa 0.10.2's defaults restated in include/fastgrnn_hip.h -- and ``MFCCFrontend`` the module that keeps its
 settings, the constant tables and the normalisation statistics.  Its output ``[B, max_len, F]`` is a frame pool:
 ``RNNClassifierModel.detect_audio`` and ``loss_windows(feats.view(B * T, F), starts, labels)`` read it in place.
-There is no host fallback: without the library every call raises.
+With ``augment=records`` the same call reads an audio BANK through per-clip augmentation records (``kws_amd.augment``;
+``fastgrnn_hip_mfcc_augment``): shift, gain and noise are applied while a clip is loaded and no augmented audio is
+written.  There is no host fallback: without the library every call raises.
 """
 from __future__ import annotations
 
@@ -51,6 +53,30 @@ def _mfcc_plan(B, L, clip_stride, audio_dtype, n_mfcc, order, width, max_len, to
     return desc, int(_lib.load().fastgrnn_hip_mfcc_workspace_bytes(C.byref(desc)))
 
 
+@functools.lru_cache(maxsize=256)
+def _augment_plan(B, L, clip_stride, audio_dtype, n_mfcc, order, width, max_len, top_db, flags, n_clips, n_noise,
+                  noise_stride, noise_len_max):
+    """``_mfcc_plan`` for the augmented call: the descriptor, the bank's sizes and the workspace size."""
+    desc, nbytes = _mfcc_plan(B, L, clip_stride, audio_dtype, n_mfcc, order, width, max_len, top_db, flags)
+    return desc, _lib.MfccBank(n_clips, n_noise, noise_stride, noise_len_max, 0), nbytes
+
+
+def check_augment_range(augment, n_clips, noise_lengths=None):
+    """The one host range check of an augmented call: every ``src`` in ``0..n_clips-1``, every ``noise`` below the
+    number of noises, every ``noise_off`` of a record with a noise in ``0..nlen-1``; one device reduction, one
+    device-to-host copy, ``ValueError`` otherwise.  (The kernel clamps whatever it is given; this tells the caller that
+    it would have.)"""
+    src, noise, off = augment[:, 0], augment[:, 2], augment[:, 3]
+    n_noise = 0 if noise_lengths is None else noise_lengths.numel()
+    bad = (src < 0) | (src >= n_clips) | (noise >= n_noise)
+    if n_noise:
+        nlen = noise_lengths[noise.clamp(0, n_noise - 1).long()]
+        bad = bad | ((noise >= 0) & ((off < 0) | (off >= nlen)))
+    if bool(bad.any()):
+        raise ValueError("augment: a record lies outside its range (src in [0, %d), noise < %d, 0 <= noise_off < the "
+                         "noise's length)" % (n_clips, n_noise))
+
+
 def _order_of(feature_type):
     if feature_type not in FEATURE_TYPES:
         raise ValueError("Unknown feature type: %r (mfcc, delta, delta_delta)" % (feature_type,))
@@ -76,7 +102,8 @@ def _check_settings(n_mfcc, order, width, max_len, L=None):
 
 
 def mfcc_features(audio, lengths=None, *, n_mfcc=32, feature_type="delta", width=9, max_len=99, top_db=80.0,
-                  mean=None, std=None, peak_normalize=False, tables=None):
+                  mean=None, std=None, peak_normalize=False, tables=None, augment=None, noise=None, noise_lengths=None,
+                  check=True):
     """``audio:[B,L]`` fp32 samples or int16 PCM on the device -> ``[B, max_len, F]`` fp32 features,
     ``F = n_mfcc * (order + 1)`` with ``feature_type`` ``"mfcc"`` / ``"delta"`` / ``"delta_delta"`` = order 0 / 1 / 2:
     ``[mfcc; delta; delta2]`` of every clip as ``MFCCProcessor.compute_features`` stacks them (transposed: time-major
@@ -87,7 +114,15 @@ def mfcc_features(audio, lengths=None, *, n_mfcc=32, feature_type="delta", width
     ``[B]`` int32 on the device, ``1280 <= lengths[b] <= L`` (the caller's obligation; the kernel clamps): clip ``b`` is
     its first ``lengths[b]`` samples and has ``1 + lengths[b] // 160`` frames.  ``peak_normalize`` divides every clip by
     its ``max|y|`` first (inferencetry.py:172-175).  ``top_db=None`` (or negative) switches the dB clip off.  One launch
-    on the current stream; nothing synchronises."""
+    on the current stream; nothing synchronises.
+
+    With ``augment`` (``[B, 6]`` int32 records on the device: ``kws_amd.pack_augment`` / ``AudioAugment.draw``) ``audio``
+    is a BANK ``[N, L]``, ``lengths`` is ``[N]``, and output clip ``b`` is bank clip ``src[b]`` shifted, scaled and mixed
+    with a noise while it is loaded (``fastgrnn_hip_mfcc_augment``; ``AudioAugment.apply`` is the same definition in
+    torch ops): the output has ``B = augment.shape[0]`` clips and no augmented audio is ever written.  ``noise``:
+    ``[n_noise, noise_len_max]`` of ``audio``'s dtype with unit stride along the samples, ``noise_lengths``: ``[n_noise]``
+    int32, both or neither.  ``check=True`` validates the records' ranges (``check_augment_range``: one reduction and one
+    synchronisation); pass ``check=False`` in a captured step -- the kernel clamps every record into its range."""
     lib = _lib.load()
     order = _order_of(feature_type)
     if not isinstance(audio, torch.Tensor):
@@ -98,11 +133,11 @@ def mfcc_features(audio, lengths=None, *, n_mfcc=32, feature_type="delta", width
         raise RuntimeError("audio must be [B, L] (got %d dimensions)" % audio.dim())
     if audio.dtype not in _AUDIO_DTYPES:
         raise RuntimeError("audio must be float32 samples or int16 PCM (got %s)" % audio.dtype)
-    B, L = audio.shape
-    if B < 1:
+    N, L = audio.shape                                   # (N: the clips of audio -- the batch, or the bank under augment)
+    if N < 1:
         raise RuntimeError("audio holds no clips")
     n_mfcc, width, max_len = _check_settings(n_mfcc, order, width, max_len, L)
-    if audio.stride(1) != 1 or (B > 1 and audio.stride(0) < 1):
+    if audio.stride(1) != 1 or (N > 1 and audio.stride(0) < 1):
         raise RuntimeError("audio needs unit stride along the samples and a positive row stride (got strides %s)"
                            % (tuple(audio.stride()),))
     dev = audio.device
@@ -116,21 +151,65 @@ def mfcc_features(audio, lengths=None, *, n_mfcc=32, feature_type="delta", width
                 raise RuntimeError("%s must be float32 [%d] on %s" % (name, F, dev))
     if lengths is not None:
         _check_input(lengths, "lengths")
-        if lengths.dtype != torch.int32 or lengths.numel() != B or lengths.device != dev:
-            raise RuntimeError("lengths must be int32 [%d] on %s" % (B, dev))
+        if lengths.dtype != torch.int32 or lengths.numel() != N or lengths.device != dev:
+            raise RuntimeError("lengths must be int32 [%d] on %s" % (N, dev))
+    B = N
+    if augment is None:
+        if noise is not None or noise_lengths is not None:
+            raise RuntimeError("noise and noise_lengths go with augment")
+    else:
+        B, n_noise, noise_stride, noise_len_max = _check_augment_operands(augment, noise, noise_lengths, audio)
+        if check:
+            check_augment_range(augment, N, noise_lengths)
     if tables is None:
         tables = mfcc_tables(dev)
     elif tables.device != dev or tables.dtype != torch.float32 or tables.numel() * 4 < lib.fastgrnn_hip_mfcc_tables_bytes():
         raise RuntimeError("tables must be the float32 tensor of mfcc_tables() on %s" % dev)
     top = -1.0 if top_db is None else float(top_db)
     flags = _lib.MFCC_PEAK_NORMALIZE if peak_normalize else 0
-    desc, nbytes = _mfcc_plan(B, L, int(audio.stride(0)) if B > 1 else L, _AUDIO_DTYPES[audio.dtype], n_mfcc, order,
-                              width, max_len, top, flags)
+    plan = (B, L, int(audio.stride(0)) if N > 1 else L, _AUDIO_DTYPES[audio.dtype], n_mfcc, order, width, max_len, top,
+            flags)
     with torch.cuda.device(dev):
         feats = torch.empty((B, max_len, F), dtype=torch.float32, device=dev)
-        _call(lib.fastgrnn_hip_mfcc, "fastgrnn mfcc", "mfcc", dev, nbytes, C.byref(desc), _ptr(audio), _ptr(lengths),
-              _ptr(tables), _ptr(mean), _ptr(std), _ptr(feats))
+        if augment is None:
+            desc, nbytes = _mfcc_plan(*plan)
+            _call(lib.fastgrnn_hip_mfcc, "fastgrnn mfcc", "mfcc", dev, nbytes, C.byref(desc), _ptr(audio),
+                  _ptr(lengths), _ptr(tables), _ptr(mean), _ptr(std), _ptr(feats))
+        else:
+            desc, bank, nbytes = _augment_plan(*plan, N, n_noise, noise_stride, noise_len_max)
+            _call(lib.fastgrnn_hip_mfcc_augment, "fastgrnn mfcc_augment", "mfcc_augment", dev, nbytes, C.byref(desc),
+                  C.byref(bank), _ptr(audio), _ptr(lengths), _ptr(noise), _ptr(noise_lengths), _ptr(augment),
+                  _ptr(tables), _ptr(mean), _ptr(std), _ptr(feats))
     return feats
+
+
+def _check_augment_operands(augment, noise, noise_lengths, audio):
+    """The argument errors of the augmented call; ``(B, n_noise, noise_stride, noise_len_max)``."""
+    dev = audio.device
+    _check_input(augment, "augment")
+    if augment.dtype != torch.int32 or augment.dim() != 2 or augment.shape[1] != 6 or augment.shape[0] < 1:
+        raise RuntimeError("augment must be int32 records [B, 6] (got %s %s)" % (augment.dtype, tuple(augment.shape)))
+    if augment.device != dev:
+        raise RuntimeError("augment must be on the audio's device")
+    if (noise is None) != (noise_lengths is None):
+        raise RuntimeError("noise and noise_lengths go together")
+    if noise is None:
+        return augment.shape[0], 0, 1, 1
+    if not isinstance(noise, torch.Tensor) or not noise.is_cuda or noise.device != dev:
+        raise RuntimeError("noise must be a CUDA tensor on the audio's device")
+    if noise.dtype != audio.dtype:
+        raise RuntimeError("noise must have the audio's dtype %s (got %s)" % (audio.dtype, noise.dtype))
+    if noise.dim() != 2 or noise.shape[0] < 1 or not 1 <= noise.shape[1] <= _lib.MFCC_NOISE_LEN_MAX:
+        raise RuntimeError("noise must be [n_noise, noise_len_max] with 1 <= noise_len_max <= 2^24 (got %s)"
+                           % (tuple(noise.shape),))
+    if noise.stride(1) != 1 or (noise.shape[0] > 1 and noise.stride(0) < 1):
+        raise RuntimeError("noise needs unit stride along the samples and a positive row stride (got strides %s)"
+                           % (tuple(noise.stride()),))
+    _check_input(noise_lengths, "noise_lengths")
+    if noise_lengths.dtype != torch.int32 or noise_lengths.numel() != noise.shape[0] or noise_lengths.device != dev:
+        raise RuntimeError("noise_lengths must be int32 [%d] on %s" % (noise.shape[0], dev))
+    n_noise, nmax = noise.shape
+    return augment.shape[0], n_noise, int(noise.stride(0)) if n_noise > 1 else nmax, nmax
 
 
 class MFCCFrontend(nn.Module):
@@ -172,9 +251,10 @@ class MFCCFrontend(nn.Module):
         self.mean = mean.clone() if dev is None else mean.to(dev)
         self.std = std.clone() if dev is None else std.to(dev)
 
-    def forward(self, audio, lengths=None, normalize=True):
+    def forward(self, audio, lengths=None, normalize=True, augment=None, noise=None, noise_lengths=None, check=True):
         """``audio:[B,L]`` on the device -> ``[B, max_len, F]``; ``normalize=False`` leaves ``mean`` / ``std`` out (the
-        raw features ``fit_normalization`` takes)."""
+        raw features ``fit_normalization`` takes).  ``augment`` (with ``noise`` / ``noise_lengths`` / ``check``): the
+        augmented call of ``mfcc_features`` -- ``audio`` is the bank, the output has one clip per record."""
         if self.tables is None or self.tables.device != audio.device:
             self.tables = mfcc_tables(audio.device)
         use = normalize and self.mean is not None
@@ -183,7 +263,8 @@ class MFCCFrontend(nn.Module):
         mean, std = (self.mean, self.std) if use else (None, None)
         return mfcc_features(audio, lengths, n_mfcc=self.n_mfcc, feature_type=self.feature_type, width=self.width,
                              max_len=self.max_len, top_db=self.top_db, mean=mean, std=std,
-                             peak_normalize=self.peak_normalize, tables=self.tables)
+                             peak_normalize=self.peak_normalize, tables=self.tables, augment=augment, noise=noise,
+                             noise_lengths=noise_lengths, check=check)
 
     @staticmethod
     def clips_of(recording, hop_samples=800, clip=16000):

@@ -311,6 +311,50 @@ class RNNClassifierModel(nn.Module):
         optimizer.step(iht)
         return loss.detach()
 
+    def train_step_audio(self, audio, lengths, labels, index, frontend, augment, optimizer, iht="none", bucket=None,
+                         check=False):
+        """``train_step`` from raw audio that lives on the device: ``audio:[N,L]`` is the dataset as an audio bank
+        (float32 samples or int16 PCM), ``lengths:[N]`` int32 or None, ``labels:[N]``; the batch is ``index:[B]`` int32
+        clip indices, freshly augmented.  ``records = augment.draw(index, optimizer.step_t)`` (a ``kws_amd.AudioAugment``;
+        the step scalar is read as it stands BEFORE this step's update), the features come from ``frontend`` (a
+        ``kws_amd.MFCCFrontend``) reading the bank through the records under ``torch.no_grad()`` -- no augmented audio
+        and no gathered batch is written --, ``labels[index]`` is gathered on the device, and the rest is exactly
+        ``train_step`` on those features: layer 0 reads the ``[B, max_len, F]`` feature pool in place where
+        ``loss_windows`` can (``starts = arange(B) * max_len``), ``hidden_states`` is carried as there.  Returns the
+        detached loss.  Nothing synchronises with ``check=False`` (``check=True`` validates ``index`` and the records on
+        the host first), so the step captures in a ``GraphedStep``: ``index`` is a captured input that the caller
+        overwrites between replays, and every replay draws new augmentations as ``step_t`` advances."""
+        if not isinstance(optimizer, _FusedOptimizer):
+            raise TypeError("train_step_audio() needs a kws_amd.FusedAdam or kws_amd.FusedSGD (got %s)"
+                            % type(optimizer).__name__)
+        if self.rnn_name == "FastGRNNBatchNorm":
+            raise NotImplementedError("loss() trains FastGRNNCUDA models; FastGRNNBatchNorm runs in eval mode only")
+        if not (self.linear and self.apply_softmax):
+            raise RuntimeError("loss() is the Linear + log_softmax + NLLLoss tail (linear=True, apply_softmax=True)")
+        if frontend.num_features != self.input_dim:
+            raise ValueError("the front end gives %d features, the model takes %d" % (frontend.num_features, self.input_dim))
+        records = augment.draw(index, optimizer.step_t)
+        with torch.no_grad():
+            feats = frontend(audio, lengths, augment=records, noise=augment.noise, noise_lengths=augment.noise_lengths,
+                             check=check)                                    # [B, max_len, F]: the frame pool
+            target = labels.index_select(0, index)
+        for p in self.parameters():
+            p.grad = None
+        B, T, Fn = feats.shape
+        if self._batchnorm:
+            h_last = self._last_state(feats if self.batch_first else feats.transpose(0, 1).contiguous())
+        else:
+            key = (B, T, feats.device)
+            if getattr(self, "_audio_starts", (None,))[0] != key:            # (built once per batch shape)
+                self._audio_starts = (key, torch.arange(B, device=feats.device, dtype=torch.int32) * T)
+            h_last = self._last_state(None, windows=(feats.view(B * T, Fn), self._audio_starts[1], T))
+        loss = keyword_loss(h_last, self.hidden2keyword.weight, self.hidden2keyword.bias, target)
+        loss.backward()
+        if bucket is not None:
+            bucket.all_reduce_()
+        optimizer.step(iht)
+        return loss.detach()
+
     def loss_windows(self, pool, starts, labels, window=99):
         """``loss()`` on the batch whose utterance ``b`` is the ``window`` consecutive rows of ``pool:[R,F]`` from row
         ``starts[b]`` on -- a training step from a frame pool that lives on the device: the batch is ``B`` start rows
