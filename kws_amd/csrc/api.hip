@@ -105,7 +105,11 @@ int resolve(const fastgrnn_desc* d, route* r) {
   // d_x may be NULL (the input's gradient is not wanted) where it is a GEMM of its own behind the scan, and under
   // FASTGRNN_FLAG_NO_INPUT_GRAD where the scan can leave its d_x product out
   const bool nograd = (d->flags & FASTGRNN_FLAG_NO_INPUT_GRAD) != 0;
-  const auto dx_optional = [nograd](const fastgrnn_desc& c) { return split_dx_optional(c) || (nograd && split_dx_skippable(c)); };
+  const auto dx_optional = [nograd](const fastgrnn_desc& c) {
+    const family* f = family_of(c);
+    return (f && f->dx_optional) || (nograd && split_dx_skippable(c));
+  };
+  const family* fu = family_of(u);
   fastgrnn_plan& o = r->plan;
   fastgrnn_zext_plan& z = o.zext;
   if (zext_route(d, r)) {
@@ -125,9 +129,9 @@ int resolve(const fastgrnn_desc* d, route* r) {
   o.workspace_bytes[0] = (z.forward && (preact || r->zneed[0] > r->need[0])) ? r->zneed[0] : r->need[0];
   o.workspace_bytes[1] = z.backward ? r->zneed[1] : r->need[1];
   // (path 2 only needs its workspace when no auxiliary output is requested: see split_forward_ws)
-  o.forward_ws_optional = !affine && r->path[0] == 2 && split_forward_ws_optional(u);
+  o.forward_ws_optional = !affine && r->path[0] == 2 && fu && fu->forward_ws_optional;
   o.dx_optional = z.backward ? z.dx_optional : (r->path[1] == 2 && dx_optional(u));
-  o.rank_space_cols = (preact && lowrank_shape(u) && (r->path[0] == 2 || r->path[1] == 2)) ? 32 : 0;
+  o.rank_space_cols = (preact && fu == &lowrank_family() && (r->path[0] == 2 || r->path[1] == 2)) ? 32 : 0;
   return FASTGRNN_OK;
 }
 

@@ -43,6 +43,23 @@ template <typename T> __device__ __forceinline__ T dact(T y, int nl) {
 
 static inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
+// the status of a launcher that has enqueued its kernels
+static inline int launch_status() { return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH; }
+
+// Every call with a workspace has ONE layout function that walks its regions with a Carve (256-byte aligned each):
+// given NULL it yields the byte count (off) and NULL pointers, given the caller's pointer the typed pointers.  The size
+// query and the launcher both call it; nobody else computes an offset.
+struct Carve {
+  char* base;
+  size_t off = 0;
+  explicit Carve(void* b) : base((char*)b) {}
+  template <typename T> T* take(size_t n) {
+    T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += align256(n * sizeof(T));
+    return r;
+  }
+};
+
 // ---- internal launchers (implemented in kernels_generic.hip / kernels_mfma.hip) ---------
 size_t generic_forward_ws(const fastgrnn_desc& d);
 size_t generic_backward_ws(const fastgrnn_desc& d);
@@ -70,26 +87,47 @@ int mfma_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
                   const void* hs, const void* zs, const void* cs, const void* h0,
                   const fastgrnn_grads& g, void* ws, hipStream_t s);
 
-// split-precision (3 x bf16 planes, 6 MFMA terms) scan on the bf16 matrix pipe (kernels_split.hip)
-bool split_supported(const fastgrnn_desc& d, int direction);
-size_t split_forward_ws(const fastgrnn_desc& d);
-size_t split_backward_ws(const fastgrnn_desc& d);
-bool split_forward_ws_optional(const fastgrnn_desc& d);   // the forward workspace is only used when z_s is NULL
-bool split_dx_optional(const fastgrnn_desc& d);           // the backward accepts d_x == NULL (no input gradient)
-bool split_dx_skippable(const fastgrnn_desc& d);          // ... under FASTGRNN_FLAG_NO_INPUT_GRAD as well
-// the per-unit scaled forward (sg, sc non-NULL, zs = cs = NULL) on the shapes affine_supported() admits
-bool affine_supported(const fastgrnn_desc& d);
+// split-precision (3 x bf16 planes, 6 MFMA terms) scans on the bf16 matrix pipe: kernel path 2.  Its cell families are
+// the rows of ONE ordered table (family_of, kernels_split.hip: the first row whose shape holds, NULL where path 2 has
+// none); every query and call below is a lookup in that row.
 // fastgrnn_hip_forward_windows: utterance b is the T consecutive rows from row start[b] of a frame pool [rows, F]
 // (x then points at the pool); start: [B] int32 on the device, 0 <= start[b] <= rows - T
 struct window_src { const int32_t* start; size_t rows; };
+struct family {
+  bool (*shape)(const fastgrnn_desc& d);
+  bool (*supported)(const fastgrnn_desc& d, int direction);
+  size_t (*forward_ws)(const fastgrnn_desc& d);
+  size_t (*backward_ws)(const fastgrnn_desc& d);
+  // sg, sc: FASTGRNN_FLAG_PREACT_AFFINE (affine_supported); win: the windowed calls (windows_supported)
+  int (*forward)(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
+                 void* cs, void* ws, hipStream_t s, const float* sg, const float* sc, const window_src* win);
+  int (*backward)(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
+                  const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s);
+  size_t (*windows_ws)(const fastgrnn_desc& d, size_t pool_rows);   // NULL: the windowed forward needs no workspace
+  bool forward_ws_optional;   // the forward workspace is only used when z_s is NULL
+  bool dx_optional;           // d_x is a GEMM of its own behind the scan: the backward accepts d_x == NULL
+};
+const family* family_of(const fastgrnn_desc& d);
+// dense H = 256 with F = 32 / 64 / 128 (kernels_h256.hip); H = 256 / F = 32 with both ranks in 1..16 (kernels_lowrank.hip);
+// every other factorised cell on a dense shape, multiplied out per call (kernels_densify.hip); the two dense H = 128
+// rows, F = 64 / 128 / 256 and F = 32, are kernels_split.hip's own
+const family& h256_family();
+const family& lowrank_family();
+const family& densified_family();
+
+bool split_supported(const fastgrnn_desc& d, int direction);
+size_t split_forward_ws(const fastgrnn_desc& d);
+size_t split_backward_ws(const fastgrnn_desc& d);
+bool split_dx_skippable(const fastgrnn_desc& d);          // d_x == NULL under FASTGRNN_FLAG_NO_INPUT_GRAD (beyond family::dx_optional)
+// the per-unit scaled forward (sg, sc non-NULL, zs = cs = NULL) on the shapes affine_supported() admits
+bool affine_supported(const fastgrnn_desc& d);
 bool windows_supported(const fastgrnn_desc& d);                  // the windowed scans hold this cell (path 2 only)
 size_t windows_ws(const fastgrnn_desc& d, size_t pool_rows);
 // fastgrnn_hip_forward_windows_train / fastgrnn_hip_backward_windows: d carries FASTGRNN_FLAG_BATCH_MAJOR and (backward)
-// FASTGRNN_FLAG_GRAD_LAST at most; the calls run it with FASTGRNN_FLAG_SAVE_PREACT added.  The backward gathers the
-// windows into the LAST align256(T*B*F*4) bytes of its workspace (train_windows_gather_bytes) and runs the existing
-// route on that copy.
+// FASTGRNN_FLAG_GRAD_LAST at most; the calls run it with FASTGRNN_FLAG_SAVE_PREACT added.  Where no scan reads the pool
+// in place (every backward; the H = 128 forward) the windows are gathered into the call's workspace and the existing
+// route runs on that copy.
 bool train_windows_supported(const fastgrnn_desc& d);
-size_t train_windows_gather_bytes(const fastgrnn_desc& d);
 size_t train_windows_forward_ws(const fastgrnn_desc& d, size_t pool_rows);
 size_t train_windows_backward_ws(const fastgrnn_desc& d);
 int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0,
@@ -103,7 +141,8 @@ int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
 //   rows_gemm:   C[R,N] = A[R,K] . Wt^T, Wt[n][k] = trans_w ? W[k*N + n] : W[n*K + k]; A / C may be bf16 sequences
 //   tn_gemm_big: C[M,N] (row stride ldc) = A[R,M]^T . B[R,N]; rows of B below shiftB come from B0, the rest from B1
 //                shifted down by shiftB rows; part: tn_gemm_big_ws(R, M, N) bytes (bf_b with 0 < shiftB < R:
-//                tn_gemm_big_ws(R, M, N, shiftB) -- the head and the body are cut into chunks independently)
+//                tn_gemm_big_ws(R, M, N, shiftB) -- the head and the body are cut into chunks independently).  The query
+//                and both runs cut the rows with one plan (tnb_plan).
 bool rows_gemm_supported(int N, int K, bool trans_w);
 int rows_gemm(size_t R, int N, int K, bool trans_w, const void* A, const float* W, void* C, bool bf_in, bool bf_out,
               hipStream_t s);
@@ -114,47 +153,24 @@ int rows_gemm_bft(int B, int T, int N, int K, const float* A, const float* W, fl
 // [T,B,F] or, batch_major, [B,T,F]; F = 32 / 64
 int gather_windows(int T, int B, int F, bool batch_major, const float* pool, const int32_t* start, float* out,
                    hipStream_t s);
-bool tn_gemm_big_supported(int M, int N);
 size_t tn_gemm_big_ws(size_t R, int M, int N, size_t bf_shiftB = 0);
 int tn_gemm_big_run(size_t R, int M, int N, const float* A, int lda, const float* B0, const void* B1, size_t shiftB,
                     int ldb, float* part, float* C, int ldc, hipStream_t s, bool bf_b = false);   // bf_b: B1 holds bf16
 // ... with row r of B = B0[r / period] where r is a multiple of period, else B1[r - 1] (N = 256 only)
 int tn_gemm_big_run_periodic(size_t R, int M, int N, const float* A, int lda, const float* B0, const void* B1, size_t period,
                              int ldb, float* part, float* C, int ldc, hipStream_t s, bool bf_b = false);
+// [B,F,T] frames (FASTGRNN_FLAG_X_BFT) <-> time-major [T,B,F] rows (kernels_lowrank.hip): F = 32 with 2- or 4-byte
+// elements, F = 64 / 128 / 256 with 4-byte ones
+int bft_transpose_run(int B, int T, int F, size_t esize, const void* src, void* dst, bool to_time_major, hipStream_t s);
 
-// dense H = 256 / F = 32 scans (kernels_h256.hip), dispatched through split_supported / split_forward / split_backward
-bool h256_shape(const fastgrnn_desc& d);
-bool h256_supported(const fastgrnn_desc& d, int direction);
-size_t h256_forward_ws(const fastgrnn_desc& d);
-size_t h256_backward_ws(const fastgrnn_desc& d);
-int h256_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                 void* cs, void* ws, hipStream_t s, const float* sg = nullptr, const float* sc = nullptr,
-                 const window_src* win = nullptr);
-size_t h256_windows_ws(const fastgrnn_desc& d, size_t pool_rows);
-int h256_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
-                  const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s);
-
-// low-rank H = 256 / F = 32 scans, ranks <= 16 (kernels_lowrank.hip), dispatched like the H = 256 dense ones
-void bft_transpose_f32(int B, int T, const float* src, float* dst, bool to_time_major, hipStream_t s, int F = 32);   // F: 32 / 64 / 128 / 256
-bool lowrank_shape(const fastgrnn_desc& d);
-bool lowrank_supported(const fastgrnn_desc& d, int direction);
-size_t lowrank_forward_ws(const fastgrnn_desc& d);
-size_t lowrank_backward_ws(const fastgrnn_desc& d);
-int lowrank_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                    void* cs, void* ws, hipStream_t s);
-int lowrank_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
-                     const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s);
-
-// other factorised H = 256 / F = 32 cells (rank above 16, or only one of W, U factorised) on the dense H = 256 scans:
-// the factors are multiplied out per call and the dense gradients projected back (kernels_densify.hip)
-bool densified_shape(const fastgrnn_desc& d);
-bool densified_supported(const fastgrnn_desc& d, int direction);
-size_t densified_forward_ws(const fastgrnn_desc& d);
-size_t densified_backward_ws(const fastgrnn_desc& d);
-int densified_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                      void* cs, void* ws, hipStream_t s);
-int densified_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
-                       const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s);
+// A backward whose scan leaves d_pre[T*B, H] behind (dense H = 128 with a wide input, dense H = 256).  Workspace: the
+// workgroups' slabs, d_pre + 16 sink rows for the lanes beyond a ragged batch, the partial sums of the weight-gradient
+// GEMMs (du_gemm: dU is one; bf16 sequences split it at the B rows of h0), under FASTGRNN_FLAG_X_BFT a time-major copy
+// of x.  dpre_bwd_tail: dW = d_pre^T . X, where g.d_x is wanted d_x = d_pre . W, the [B,F,T] transposes around them.
+struct DpreBwdWs { float *part, *dpre, *tn, *xtm; size_t bytes; };
+DpreBwdWs dpre_bwd_ws(const fastgrnn_desc& d, size_t slab_floats, bool du_gemm, void* base);
+int dpre_bwd_tail(const fastgrnn_desc& d, const float* dpre, float* tn, float* xtm, const void* x, const void* w,
+                  const fastgrnn_grads& g, hipStream_t s);
 
 // FASTGRNN_FLAG_ZERO_EXTEND (kernels_zext.hip): the cell d run as the padded cell e (e.H, e.F = Hp, Fp; a path-2
 // descriptor) -- padded copies of the operands, the split-precision code on them, the results compacted back

@@ -104,7 +104,7 @@ int mfcc_augment_run(const fastgrnn_mfcc_desc& d, const fastgrnn_mfcc_bank& bank
     hipLaunchKernelGGL(mfcc_aug_k<short>, dim3(d.B), dim3(MF_THREADS), 0, s, a);
   else
     hipLaunchKernelGGL(mfcc_aug_k<float>, dim3(d.B), dim3(MF_THREADS), 0, s, a);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 int augment_draw_run(int B, uint64_t seed, const int64_t* step, const int32_t* index, const fastgrnn_augment_ranges& r,
@@ -121,7 +121,7 @@ int augment_draw_run(int B, uint64_t seed, const int64_t* step, const int32_t* i
   a.n_noise = n_noise;
   a.noise_len_max = noise_len_max;
   hipLaunchKernelGGL(aug_draw_k, dim3((B + 255) / 256), dim3(256), 0, s, a);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace fastgrnn

@@ -628,24 +628,13 @@ BnConst make_const(const fastgrnn_bn_params& bn, const fastgrnn_params& p) {
   return k;
 }
 
-// workspace carving: every piece 256-byte aligned
-struct Carve {
-  char* base;
-  size_t off = 0;
-  template <typename T> T* take(size_t n) {
-    T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += align256(n * sizeof(T));
-    return r;
-  }
-};
-
 int frame_product(const fastgrnn_desc& d, const void* x, const float* w, float* wc, hipStream_t s) {
   const size_t R = (size_t)d.T * d.B;
   if (d.F == 32) {
     const dim3 grid((unsigned)((R + BNT_CHUNK - 1) / BNT_CHUNK));
     if (d.H == 128) hipLaunchKernelGGL(bnt_frame_f32<128>, grid, dim3(256), 0, s, R, (const float*)x, w, wc);
     else hipLaunchKernelGGL(bnt_frame_f32<256>, grid, dim3(256), 0, s, R, (const float*)x, w, wc);
-    return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+    return launch_status();
   }
   return rows_gemm(R, d.H, d.F, false, x, w, wc, false, false, s);
 }
@@ -659,7 +648,7 @@ struct FwdWs {
 
 FwdWs fwd_ws(const fastgrnn_desc& d, void* base) {
   const Layout l = layout(d.B, d.H);
-  Carve c{(char*)base};
+  Carve c(base);
   FwdWs w;
   w.ut = c.take<float>((size_t)d.H * d.H);
   w.wc = c.take<float>((size_t)d.T * d.B * d.H);
@@ -681,7 +670,7 @@ BwdWs bwd_ws(const fastgrnn_desc& d, void* base) {
   const bool bm = (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0;
   const size_t R = (size_t)d.T * d.B, Ru = bm ? R + d.B : R, BH = (size_t)d.B * d.H;
   const size_t g1 = tn_gemm_big_ws(Ru, d.H, d.H), g2 = tn_gemm_big_ws(R, d.H, d.F);
-  Carve c{(char*)base};
+  Carve c(base);
   BwdWs w;
   w.wc = c.take<float>(R * d.H);
   w.duc = c.take<float>(Ru * d.H);
@@ -751,7 +740,7 @@ int bn_train_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const fas
   }
   hipLaunchKernelGGL(bnt_running, dim3(4), dim3(d.H), 0, s, d.T, d.B, d.H, k, (const float*)p.bias_gate,
                      (const float*)p.bias_update, (const double*)st, rs);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 int bn_train_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const fastgrnn_bn_params& bn,
@@ -788,10 +777,8 @@ int bn_train_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const fa
                            (float*)g.d_u, d.H, s)))
     return r;
   // d_w[j][f] = sum d wC[j] . x[f];  d_x = d wC . w
-  if ((r = tn_gemm_big_run(R, d.H, d.F, w.dwc, d.H, (const float*)x, x, 0, d.F, w.gpart, (float*)g.d_w, d.F, s)))
-    return r;
-  if (g.d_x && (r = rows_gemm(R, d.F, d.H, true, w.dwc, (const float*)p.w, g.d_x, false, false, s))) return r;
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  if ((r = dpre_bwd_tail(d, w.dwc, w.gpart, nullptr, x, p.w, g, s))) return r;
+  return launch_status();
 }
 
 }  // namespace fastgrnn

@@ -69,7 +69,7 @@ int debug_poison(unsigned pattern, hipStream_t s) {
   }
   // several workgroups per CU in turn: every CU is visited however the dispatcher places them
   hipLaunchKernelGGL(poison_cu_state, dim3(256 * 8), dim3(256), 160 * 1024, s, pattern, (unsigned*)nullptr);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace fastgrnn

@@ -32,41 +32,38 @@ fastgrnn_desc dense_desc(const fastgrnn_desc& d) {
   return e;
 }
 
-struct DenseWs { size_t wd, ud, dwd, dud, inner, total; };
-DenseWs layout(const fastgrnn_desc& d, bool backward) {
+// the dense W and U, for the backward their dense gradients, then the workspace of the dense call
+struct DenseWs { float *wd, *ud, *dwd, *dud; char* inner; size_t bytes; };
+DenseWs layout(const fastgrnn_desc& d, bool backward, void* base) {
   const size_t H2 = d.H, F2 = d.F;
-  DenseWs L; size_t o = 0;
-  L.wd = o; o += align256(H2 * F2 * 4);
-  L.ud = o; o += align256(H2 * H2 * 4);
-  L.dwd = o; if (backward) o += align256(H2 * F2 * 4);
-  L.dud = o; if (backward) o += align256(H2 * H2 * 4);
-  L.inner = o;
   const fastgrnn_desc e = dense_desc(d);
-  o += backward ? split_backward_ws(e) : split_forward_ws(e);
-  L.total = o;
+  Carve c(base);
+  DenseWs L{};
+  L.wd = c.take<float>(H2 * F2);
+  L.ud = c.take<float>(H2 * H2);
+  if (backward) { L.dwd = c.take<float>(H2 * F2); L.dud = c.take<float>(H2 * H2); }
+  L.inner = c.take<char>(backward ? split_backward_ws(e) : split_forward_ws(e));
+  L.bytes = c.off;
   return L;
 }
 
 // the dense matrices of the cell: multiplied out into the workspace, or the caller's own where it is dense already
-void densify(const fastgrnn_desc& d, const fastgrnn_params& p, char* base, const DenseWs& L, fastgrnn_params& q,
-             hipStream_t s) {
+void densify(const fastgrnn_desc& d, const fastgrnn_params& p, const DenseWs& L, fastgrnn_params& q, hipStream_t s) {
   const int H2 = d.H, F2 = d.F;
   q = p;
   if (d.w_rank) {                                    // W[H,F] = W2[H,r] . W1[r,F]
-    gemm(H2, F2, d.w_rank, (const float*)p.w2, d.w_rank, 1, (const float*)p.w1, F2, 1, (float*)(base + L.wd), s);
-    q.w = base + L.wd;
+    gemm(H2, F2, d.w_rank, (const float*)p.w2, d.w_rank, 1, (const float*)p.w1, F2, 1, L.wd, s);
+    q.w = L.wd;
   }
   if (d.u_rank) {                                    // U[H,H] = U2[H,r] . U1[r,H]
-    gemm(H2, H2, d.u_rank, (const float*)p.u2, d.u_rank, 1, (const float*)p.u1, H2, 1, (float*)(base + L.ud), s);
-    q.u = base + L.ud;
+    gemm(H2, H2, d.u_rank, (const float*)p.u2, d.u_rank, 1, (const float*)p.u1, H2, 1, L.ud, s);
+    q.u = L.ud;
   }
   q.w1 = q.w2 = q.u1 = q.u2 = nullptr;
 }
 
-}  // namespace
-
 bool densified_shape(const fastgrnn_desc& d) {
-  return (d.w_rank > 0 || d.u_rank > 0) && d.w_rank <= d.H && d.u_rank <= d.H && !lowrank_shape(d) &&
+  return (d.w_rank > 0 || d.u_rank > 0) && d.w_rank <= d.H && d.u_rank <= d.H && !lowrank_family().shape(d) &&
          ((d.H == 256 && (d.F == 32 || d.F == 64 || d.F == 128)) ||
           (d.H == 128 && (d.F == 32 || d.F == 64 || d.F == 128 || d.F == 256)));
 }
@@ -77,47 +74,53 @@ bool densified_supported(const fastgrnn_desc& d, int direction) {
   return split_supported(dense_desc(d), direction);
 }
 
-size_t densified_forward_ws(const fastgrnn_desc& d) { return layout(d, false).total; }
-size_t densified_backward_ws(const fastgrnn_desc& d) { return layout(d, true).total; }
+size_t densified_forward_ws(const fastgrnn_desc& d) { return layout(d, false, nullptr).bytes; }
+size_t densified_backward_ws(const fastgrnn_desc& d) { return layout(d, true, nullptr).bytes; }
 
 int densified_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                      void* cs, void* ws, hipStream_t s) {
+                      void* cs, void* ws, hipStream_t s, const float*, const float*, const window_src*) {
   if (!ws) return FASTGRNN_ERR_WORKSPACE;
-  const DenseWs L = layout(d, false);
-  char* base = reinterpret_cast<char*>(ws);
+  const DenseWs L = layout(d, false, ws);
   fastgrnn_params q;
-  densify(d, p, base, L, q, s);
+  densify(d, p, L, q, s);
   // (under FASTGRNN_FLAG_SAVE_PREACT the dense contract saves the pre-activation alone: c_s is not used)
-  return split_forward(dense_desc(d), q, x, h0, hs, zs, (d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? nullptr : cs, base + L.inner, s);
+  return split_forward(dense_desc(d), q, x, h0, hs, zs, (d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? nullptr : cs, L.inner, s);
 }
 
 int densified_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
                        const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
   if (!ws) return FASTGRNN_ERR_WORKSPACE;
-  const DenseWs L = layout(d, true);
-  char* base = reinterpret_cast<char*>(ws);
+  const DenseWs L = layout(d, true, ws);
   fastgrnn_params q;
-  densify(d, p, base, L, q, s);
+  densify(d, p, L, q, s);
   fastgrnn_grads gd = g;
-  gd.d_w = d.w_rank ? (void*)(base + L.dwd) : g.d_w;
-  gd.d_u = d.u_rank ? (void*)(base + L.dud) : g.d_u;
+  gd.d_w = d.w_rank ? (void*)L.dwd : g.d_w;
+  gd.d_u = d.u_rank ? (void*)L.dud : g.d_u;
   gd.d_w1 = gd.d_w2 = gd.d_u1 = gd.d_u2 = nullptr;
-  const int st = split_backward(dense_desc(d), q, ghs, x, hs, zs, cs, h0, gd, base + L.inner, s);
+  const int st = split_backward(dense_desc(d), q, ghs, x, hs, zs, cs, h0, gd, L.inner, s);
   if (st != FASTGRNN_OK) return st;
   const int H2 = d.H, F2 = d.F;
   if (d.w_rank) {
-    const float* dW = (const float*)(base + L.dwd);
+    const float* dW = L.dwd;
     // dW1[r,F] = W2^T . dW :  A[m=i][k=h] = W2[h*r + i],  B[k=h][n=f] = dW[h*F + f]
     gemm(d.w_rank, F2, H2, (const float*)p.w2, 1, d.w_rank, dW, F2, 1, (float*)g.d_w1, s);
     // dW2[H,r] = dW . W1^T :  A[m=h][k=f] = dW[h*F + f],  B[k=f][n=i] = W1[i*F + f]
     gemm(H2, d.w_rank, F2, dW, F2, 1, (const float*)p.w1, 1, F2, (float*)g.d_w2, s);
   }
   if (d.u_rank) {
-    const float* dU = (const float*)(base + L.dud);
+    const float* dU = L.dud;
     gemm(d.u_rank, H2, H2, (const float*)p.u2, 1, d.u_rank, dU, H2, 1, (float*)g.d_u1, s);     // dU1[r,H] = U2^T . dU
     gemm(H2, d.u_rank, H2, dU, H2, 1, (const float*)p.u1, 1, H2, (float*)g.d_u2, s);           // dU2[H,r] = dU . U1^T
   }
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
+}
+
+}  // namespace
+
+const family& densified_family() {
+  static const family f = {densified_shape, densified_supported, densified_forward_ws, densified_backward_ws,
+                           densified_forward, densified_backward, nullptr, false, false};
+  return f;
 }
 
 }  // namespace fastgrnn

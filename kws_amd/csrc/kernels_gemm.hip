@@ -742,7 +742,7 @@ int gather_windows(int T, int B, int F, bool batch_major, const float* pool, con
   const unsigned gy = T < 65535 ? (unsigned)T : 65535u;
   if (F == 32) hipLaunchKernelGGL(gather_windows_rows<32>, dim3((B + 31) / 32, gy), dim3(256), 0, s, T, B, oT, oB, pool, start, out);
   else hipLaunchKernelGGL(gather_windows_rows<64>, dim3((B + 15) / 16, gy), dim3(256), 0, s, T, B, oT, oB, pool, start, out);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 bool rows_gemm_supported(int N, int K, bool trans_w) {
@@ -760,7 +760,7 @@ int rows_gemm(size_t R, int N, int K, bool trans_w, const void* A, const float* 
   if (N == n && K == k) {                                                                 \
     if (trans_w) launch_rows_gemm<n / 16, k / 32, true>(R, A, W, C, bf_in, bf_out, s);    \
     else launch_rows_gemm<n / 16, k / 32, false>(R, A, W, C, bf_in, bf_out, s);           \
-    return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;           \
+    return launch_status();           \
   }
   if (!rows_gemm_supported(N, K, trans_w)) return FASTGRNN_ERR_UNSUPPORTED;
   RG_CASE(128, 64) RG_CASE(128, 128) RG_CASE(128, 256)
@@ -777,7 +777,7 @@ int rows_gemm_bft(int B, int T, int N, int K, const float* A, const float* W, fl
 #define RGB_CASE(n, k)                                                                              \
   if (N == n && K == k) {                                                                           \
     launch_rows_gemm_bft<n / 16, k / 32>(B, T, A, W, C, (unsigned)cT, (unsigned)cB, s);             \
-    return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;                     \
+    return launch_status();                     \
   }
   RGB_CASE(128, 64) RGB_CASE(128, 128) RGB_CASE(128, 256) RGB_CASE(256, 64) RGB_CASE(256, 128)
 #undef RGB_CASE
@@ -793,89 +793,108 @@ static inline int tnb_chunks(size_t R, int nblk, int* spw) {
   return (int)((nstages + *spw - 1) / *spw);
 }
 
+// How a product over R rows is cut: nch chunks of spw stages, each with partial sums of its own (nblk blocks of 128 rows
+// of C).  bf16 rows of B behind fp32 ones (0 < bf_shiftB < R: the rows that pair with h0) make a head over the first
+// bf_shiftB rows and a body over the rest, each cut on ITS row count -- the body can make more chunks than R does
+// (R = 4131, bf_shiftB = 1377, M = 256: 87 + 44 against 2 * 65) -- the head's partials behind the body's, one reduction
+// over both.  bytes: twice the chunks of the unsplit product, or what the split one writes where that is more.
+struct TnbPlan { int nblk, spw, nch, spw0, nch0; size_t head_off, bytes; };   // head_off: floats
+static TnbPlan tnb_plan(size_t R, int M, int N, size_t bf_shiftB) {
+  TnbPlan P{};
+  P.nblk = M / 128;
+  P.nch = tnb_chunks(R, P.nblk, &P.spw);
+  size_t slots = (size_t)2 * P.nch;
+  if (bf_shiftB > 0 && bf_shiftB < R) {
+    P.nch = tnb_chunks(R - bf_shiftB, P.nblk, &P.spw);
+    P.nch0 = tnb_chunks(bf_shiftB, P.nblk, &P.spw0);
+    if ((size_t)P.nch + P.nch0 > slots) slots = (size_t)P.nch + P.nch0;
+  }
+  const size_t chunk = (size_t)P.nblk * 128 * N;
+  P.head_off = P.nch * chunk;
+  P.bytes = align256(slots * chunk * sizeof(float));
+  return P;
+}
+
 int tn_gemm_big_run_periodic(size_t R, int M, int N, const float* A, int lda, const float* B0, const void* B1, size_t period,
                              int ldb, float* part, float* C, int ldc, hipStream_t s, bool bf_b) {
   // (bf16 rows with the periodic mapping: the instantiation spills inside its loop -- spill reloads are loads, operand
   // rule -- and is not built; h256_supported keeps batch-major bf16 backwards off this path)
   if (N != 256 || (M != 128 && M != 256) || period == 0 || R >= ((size_t)1 << 32) || bf_b) return FASTGRNN_ERR_UNSUPPORTED;
-  int spw;
-  const int nblk = M / 128, nch = tnb_chunks(R, nblk, &spw);
-  dim3 grid(((nch + 7) / 8) * 8 * nblk);
-  hipLaunchKernelGGL((tn_gemm_big<16, true>), grid, dim3(512), 0, s, R, spw, nblk, nch, A, lda, B0, (const float*)B1, period, ldb, part);
-  hipLaunchKernelGGL(tn_big_reduce, dim3((M * N + 63) / 64), dim3(1024), 0, s, nch, nblk, N, (const float*)part, C, ldc);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  const TnbPlan P = tnb_plan(R, M, N, 0);
+  dim3 grid(((P.nch + 7) / 8) * 8 * P.nblk);
+  hipLaunchKernelGGL((tn_gemm_big<16, true>), grid, dim3(512), 0, s, R, P.spw, P.nblk, P.nch, A, lda, B0, (const float*)B1, period, ldb, part);
+  hipLaunchKernelGGL(tn_big_reduce, dim3((M * N + 63) / 64), dim3(1024), 0, s, P.nch, P.nblk, N, (const float*)part, C, ldc);
+  return launch_status();
 }
 
-bool tn_gemm_big_supported(int M, int N) { return (M == 128 || M == 256) && (N == 32 || N == 64 || N == 128 || N == 256); }
-
-size_t tn_gemm_big_ws(size_t R, int M, int N, size_t bf_shiftB) {
-  int spw;
-  const int nblk = M / 128, nch = tnb_chunks(R, nblk, &spw);
-  // (twice the chunks of the product: with bf16 rows of B the rows that pair with fp32 h0 are a product of their own,
-  // its partials behind the others')
-  size_t slots = (size_t)2 * nch;
-  // ... and the two products are cut on their own row counts: the body's R - shiftB rows can fall below a step of
-  // stages-per-chunk that R is above and make MORE chunks than R does (R = 4131, shiftB = 1377, M = 256: 87 + 44
-  // against 2 * 65), so the caller that splits names its shiftB and gets room for exactly what tn_gemm_big_run writes
-  if (bf_shiftB > 0 && bf_shiftB < R) {
-    const size_t split = (size_t)tnb_chunks(R - bf_shiftB, nblk, &spw) + (size_t)tnb_chunks(bf_shiftB, nblk, &spw);
-    if (split > slots) slots = split;
-  }
-  return align256(slots * nblk * 128 * N * sizeof(float));
-}
+size_t tn_gemm_big_ws(size_t R, int M, int N, size_t bf_shiftB) { return tnb_plan(R, M, N, bf_shiftB).bytes; }
 
 int tn_gemm_big_run(size_t R, int M, int N, const float* A, int lda, const float* B0, const void* B1v, size_t shiftB,
                     int ldb, float* part, float* C, int ldc, hipStream_t s, bool bf_b) {
-  if (!tn_gemm_big_supported(M, N)) return FASTGRNN_ERR_UNSUPPORTED;
-  int spw;
-  const int nblk = M / 128;
-  int nch = tnb_chunks(R, nblk, &spw);
+  if ((M != 128 && M != 256) || (N != 32 && N != 64 && N != 128 && N != 256)) return FASTGRNN_ERR_UNSUPPORTED;
+  const TnbPlan P = tnb_plan(R, M, N, bf_b ? shiftB : 0);
+  const int spw = P.spw, nblk = P.nblk, nch = P.nch;
   dim3 grid(((nch + 7) / 8) * 8 * nblk);
   const float* B1 = (const float*)B1v;
   // bf16 rows of B: with shiftB = 0 every row is bf16 (the PURE variant: three MFMA terms); otherwise the first
-  // shiftB rows pair with fp32 rows of B0 (h0) -- a product of its own over those rows, its partials behind the
-  // others' in the workspace, one reduction over both
-  int nch0 = 0;                                      // chunks of the fp32 head product
-  if (bf_b && shiftB > 0 && shiftB < R) {
-    const size_t R0 = shiftB, Rb = R - shiftB;
-    // the bf16 body: rows shiftB .. R-1 of A against rows 0 .. of B1
-    nch = tnb_chunks(Rb, nblk, &spw);
-    grid = dim3(((nch + 7) / 8) * 8 * nblk);
-    int spw0;
-    nch0 = tnb_chunks(R0, nblk, &spw0);
-    float* part0 = part + (size_t)nch * nblk * 128 * N;      // (behind the body's partials: one reduction over both)
-    dim3 grid0(((nch0 + 7) / 8) * 8 * nblk);
+  // shiftB rows pair with fp32 rows of B0 (h0) -- the plan's head, a product of its own over those rows
+  if (P.nch0) {
+    const size_t R0 = shiftB;
+    dim3 grid0(((P.nch0 + 7) / 8) * 8 * nblk);
 #define TNB_HEAD(n) \
-    if (N == n) hipLaunchKernelGGL((tn_gemm_big<n / 16>), grid0, dim3(512), 0, s, R0, spw0, nblk, nch0, A, lda, B0, B0, R0, ldb, part0);
+    if (N == n) hipLaunchKernelGGL((tn_gemm_big<n / 16>), grid0, dim3(512), 0, s, R0, P.spw0, nblk, P.nch0, A, lda, B0, B0, R0, ldb, part + P.head_off);
     TNB_HEAD(32) TNB_HEAD(64) TNB_HEAD(128) TNB_HEAD(256)
 #undef TNB_HEAD
+    // the bf16 body: rows shiftB .. R-1 of A against rows 0 .. of B1
     A += R0 * (size_t)lda;
-    R = Rb;
+    R -= R0;
     shiftB = 0;
   }
   const bool pure = bf_b && shiftB == 0;
+  // N = 256, fp32: tn_gemm_w4, where a stage takes its rows of B from ONE source
+  const bool w4 = N == 256 && !bf_b && (shiftB == 0 || shiftB >= R || shiftB % TNB_STAGE == 0);
+  if (w4) hipLaunchKernelGGL((tn_gemm_w4<16, TNW4_PRE>), grid, dim3(256), 0, s, R, spw, nblk, nch, A, lda, B0, B1, shiftB, ldb, part);
 #define TNB_CASE(n)                                                                                                               \
-  if (N == n) {                                                                                                                   \
+  if (N == n && !w4) {                                                                                                            \
     if (pure) hipLaunchKernelGGL((tn_gemm_big<n / 16, false, true, true>), grid, dim3(512), 0, s, R, spw, nblk, nch, A, lda, B0, B1, shiftB, ldb, part); \
     else if (bf_b) hipLaunchKernelGGL((tn_gemm_big<n / 16, false, true>), grid, dim3(512), 0, s, R, spw, nblk, nch, A, lda, B0, B1, shiftB, ldb, part); \
     else hipLaunchKernelGGL((tn_gemm_big<n / 16>), grid, dim3(512), 0, s, R, spw, nblk, nch, A, lda, B0, B1, shiftB, ldb, part);   \
   }
-  TNB_CASE(32) TNB_CASE(64) TNB_CASE(128)
+  TNB_CASE(32) TNB_CASE(64) TNB_CASE(128) TNB_CASE(256)
 #undef TNB_CASE
-  if (N == 256) {
-    // (a stage of tn_gemm_w4 takes its rows of B from ONE source, fp32)
-    if (pure)
-      hipLaunchKernelGGL((tn_gemm_big<16, false, true, true>), grid, dim3(512), 0, s, R, spw, nblk, nch, A, lda, B0, B1, shiftB, ldb, part);
-    else if (bf_b)
-      hipLaunchKernelGGL((tn_gemm_big<16, false, true>), grid, dim3(512), 0, s, R, spw, nblk, nch, A, lda, B0, B1, shiftB, ldb, part);
-    else if (shiftB == 0 || shiftB >= R || shiftB % TNB_STAGE == 0)
-      hipLaunchKernelGGL((tn_gemm_w4<16, TNW4_PRE>), grid, dim3(256), 0, s, R, spw, nblk, nch, A, lda, B0, B1, shiftB, ldb, part);
-    else
-      hipLaunchKernelGGL((tn_gemm_big<16>), grid, dim3(512), 0, s, R, spw, nblk, nch, A, lda, B0, B1, shiftB, ldb, part);
+  hipLaunchKernelGGL(tn_big_reduce, dim3((M * N + 63) / 64), dim3(1024), 0, s, nch + P.nch0, nblk, N, (const float*)part, C, ldc);
+  return launch_status();
+}
+
+DpreBwdWs dpre_bwd_ws(const fastgrnn_desc& d, size_t slab_floats, bool du_gemm, void* base) {
+  const size_t TB = (size_t)d.T * d.B, nwg = (d.B + 15) / 16;
+  const size_t tn_w = tn_gemm_big_ws(TB, d.H, d.F);
+  const size_t tn_u = du_gemm ? tn_gemm_big_ws(TB, d.H, d.H, d.dtype == FASTGRNN_BF16_IO ? (size_t)d.B : 0) : 0;
+  Carve c(base);
+  DpreBwdWs L{};
+  L.part = c.take<float>(nwg * slab_floats);
+  L.dpre = c.take<float>((TB + 16) * d.H);
+  L.tn = c.take<float>((tn_u > tn_w ? tn_u : tn_w) / sizeof(float));
+  if (d.flags & FASTGRNN_FLAG_X_BFT) L.xtm = c.take<float>(TB * d.F);   // the d_x GEMM writes over it, then the result is transposed back
+  L.bytes = c.off;
+  return L;
+}
+
+int dpre_bwd_tail(const fastgrnn_desc& d, const float* dpre, float* tn, float* xtm, const void* x, const void* w,
+                  const fastgrnn_grads& g, hipStream_t s) {
+  const size_t TB = (size_t)d.T * d.B;
+  const bool bf = d.dtype == FASTGRNN_BF16_IO;       // (x and d_x are bf16 then; d_pre is fp32 always)
+  const bool bft = (d.flags & FASTGRNN_FLAG_X_BFT) != 0;   // (fp32, time-major sequences: the families' supported())
+  int st;
+  if (bft) {
+    if ((st = bft_transpose_run(d.B, d.T, d.F, 4, x, xtm, true, s))) return st;
+    x = xtm;
   }
-  const int total = M * N;
-  hipLaunchKernelGGL(tn_big_reduce, dim3((total + 63) / 64), dim3(1024), 0, s, nch + nch0, nblk, N, (const float*)part, C, ldc);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  if ((st = tn_gemm_big_run(TB, d.H, d.F, dpre, d.H, (const float*)x, x, (size_t)0, d.F, tn, (float*)g.d_w, d.F, s, bf))) return st;
+  if (!g.d_x) return FASTGRNN_OK;                    // (NULL: not wanted -- the first layer of a model, whose input is data)
+  // d_x[T*B,F] = d_pre . W   (W is [H,F] = [K,N])
+  if ((st = rows_gemm(TB, d.F, d.H, true, dpre, (const float*)w, bft ? (void*)xtm : g.d_x, false, bf, s))) return st;
+  return bft ? bft_transpose_run(d.B, d.T, d.F, 4, xtm, g.d_x, false, s) : FASTGRNN_OK;
 }
 
 }  // namespace fastgrnn

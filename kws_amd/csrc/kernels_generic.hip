@@ -480,7 +480,7 @@ int generic_forward_t(const fastgrnn_desc& d, const fastgrnn_params& p, const vo
                        reinterpret_cast<T*>(hs), reinterpret_cast<T*>(zs), reinterpret_cast<T*>(cs));
   };
   if (sg) go(fwd_scan_generic<T, true>); else go(fwd_scan_generic<T, false>);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 template <typename T>
@@ -543,7 +543,7 @@ int generic_backward_t(const fastgrnn_desc& d, const fastgrnn_params& p, const v
   } else {
     launch_tn<T>(TB, H, H, dpre, h0, hs, shiftH, splitk, reinterpret_cast<T*>(g.d_u), s);  // .cu:540
   }
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace

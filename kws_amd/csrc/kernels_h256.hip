@@ -798,25 +798,20 @@ __global__ __launch_bounds__(1024) void reduce_h256_small(int nwg, const float* 
   }
 }
 
-static inline size_t h256_flag_bytes(const fastgrnn_desc& d) { return align256((size_t)((d.B + 15) / 16) * sizeof(unsigned)); }
-// fastgrnn_hip_forward_windows: the flag words of the largest batch the shape takes (h256_shape: B < 2^21), so that the
-// workspace of a pool depends on its rows alone and one allocation serves every set of windows cut from it
-constexpr size_t H256_WIN_FLAG_BYTES = (size_t)(1 << 21) / 16 * sizeof(unsigned);
-
-struct H256BwdWs { size_t part, dpre, tn, xtm, total; };
-H256BwdWs h256_bwd_layout(const fastgrnn_desc& d) {
-  const size_t TB = (size_t)d.T * d.B, nwg = (d.B + 15) / 16;
-  H256BwdWs L; size_t o = 0;
-  L.part = o; o += align256(nwg * SLAB2 * 4);
-  L.dpre = o; o += align256((TB + 16) * H2 * 4);     // + 16 sink rows for the lanes beyond a ragged batch
-  // (bf16 sequences: the dU product runs as an fp32 head over the B rows of h0 and a bf16 body)
-  const size_t tn_u = tn_gemm_big_ws(TB, H2, H2, d.dtype == FASTGRNN_BF16_IO ? (size_t)d.B : 0);
-  const size_t tn_w = tn_gemm_big_ws(TB, H2, d.F);
-  L.tn = o; o += tn_u > tn_w ? tn_u : tn_w;
-  // FASTGRNN_FLAG_X_BFT: the time-major copy of x for the dW GEMM; the d_x GEMM then writes over it and the result is
-  // transposed into the caller's [B,F,T] tensor
-  L.xtm = o; if (d.flags & FASTGRNN_FLAG_X_BFT) o += align256(TB * (size_t)d.F * 4);
-  L.total = o;
+// The forward's workspace: one word per workgroup, "my rows of h0 are outside the fp16 path's range" (fwd_scan_h256
+// MODE 1 -> MODE 2) -- windowed: the words of the largest batch the shape takes (h256_shape: B < 2^21), so that the
+// workspace of a pool depends on its rows alone and one allocation serves every set of windows cut from it;
+// under FASTGRNN_FLAG_X_BFT with F = 32 the time-major copy of x; for F = 64 / 128 the frame product P[rows, 256] (the
+// frame GEMM reads [B,F,T] frames in place: no copy of x), rows = T*B or, windowed, the pool's
+struct H256FwdWs { unsigned* flags; float *xtm, *P; size_t bytes; };
+H256FwdWs h256_fwd_ws(const fastgrnn_desc& d, bool windowed, size_t pool_rows, void* base) {
+  const size_t TB = (size_t)d.T * d.B;
+  Carve c(base);
+  H256FwdWs L{};
+  L.flags = c.take<unsigned>(windowed ? (size_t)(1 << 21) / 16 : (size_t)((d.B + 15) / 16));
+  if ((d.flags & FASTGRNN_FLAG_X_BFT) && d.F == F2) L.xtm = c.take<float>(TB * F2);
+  if (d.F != F2) L.P = c.take<float>((windowed ? pool_rows : TB) * H2);
+  L.bytes = c.off;
   return L;
 }
 
@@ -824,31 +819,32 @@ H256BwdWs h256_bwd_layout(const fastgrnn_desc& d) {
 struct FwdH256 { int gate, aux; bool ragged, f16h, prein, bf, aff, win; };
 
 // win: x is the frame pool and win->start the utterances' first rows (the WIN variants)
-// false: the library holds no kernel for this call (fwd_h256_built), no scan was launched
-bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                void* cs, void* ws, hipStream_t s, const float* sg, const float* sc, const window_src* win) {
+// FASTGRNN_ERR_UNSUPPORTED: the library holds no kernel for this call (fwd_h256_built), no scan was launched
+int h256_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
+                 void* cs, void* ws, hipStream_t s, const float* sg, const float* sc, const window_src* win) {
+  if (!ws) return FASTGRNN_ERR_WORKSPACE;
   dim3 grid((d.B + 15) / 16), block(512);
-  unsigned* flags = reinterpret_cast<unsigned*>(ws);
+  const H256FwdWs L = h256_fwd_ws(d, win != nullptr, win ? win->rows : 0, ws);
+  const bool prein = d.F != F2, bf = d.dtype == FASTGRNN_BF16_IO;
+  const bool bm_hs = (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0;
+  int st;
   // FASTGRNN_FLAG_X_BFT: the loader's [B,F,T] frames are transposed into the workspace first (25 us at B = 4096; a
   // lane's frame-by-frame read of [B,F,T] in place touches 64 cache lines per wave load and cost the scan 120 us)
   // (F = 32 only: a wider layer's frames are consumed by the frame GEMM, which reads [B,F,T] in place)
-  const bool prein = d.F != F2, bf = d.dtype == FASTGRNN_BF16_IO;
-  const bool bm_hs = (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0;
-  if ((d.flags & FASTGRNN_FLAG_X_BFT) && !prein) {
-    float* xtm = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + h256_flag_bytes(d));
-    bft_transpose_f32(d.B, d.T, (const float*)x, xtm, true, s);
-    x = xtm;
+  if (L.xtm) {
+    if ((st = bft_transpose_run(d.B, d.T, F2, 4, x, L.xtm, true, s))) return st;
+    x = L.xtm;
   }
   // a wider input (F = 64 / 128): the batched frame GEMM  P = X . W^T  into the workspace, then the PREIN scan on P
   if (prein) {
-    float* P = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + (win ? H256_WIN_FLAG_BYTES : h256_flag_bytes(d)));
     if (win)                                         // one row of P per pool frame, whatever the windows share
-      rows_gemm(win->rows, H2, d.F, false, x, (const float*)p.w, P, false, false, s);
+      st = rows_gemm(win->rows, H2, d.F, false, x, (const float*)p.w, L.P, false, false, s);
     else if (d.flags & FASTGRNN_FLAG_X_BFT)               // (fp32: h256_supported) rows of P land in the order of hs
-      rows_gemm_bft(d.B, d.T, H2, d.F, (const float*)x, (const float*)p.w, P, bm_hs ? 1 : (size_t)d.B, bm_hs ? (size_t)d.T : 1, s);
+      st = rows_gemm_bft(d.B, d.T, H2, d.F, (const float*)x, (const float*)p.w, L.P, bm_hs ? 1 : (size_t)d.B, bm_hs ? (size_t)d.T : 1, s);
     else
-      rows_gemm((size_t)d.T * d.B, H2, d.F, false, x, (const float*)p.w, P, bf, false, s);   // (bf16 frames, fp32 P)
-    x = P;
+      st = rows_gemm((size_t)d.T * d.B, H2, d.F, false, x, (const float*)p.w, L.P, bf, false, s);   // (bf16 frames, fp32 P)
+    if (st) return st;
+    x = L.P;
   }
   // strides of the sequences (elements): FASTGRNN_FLAG_BATCH_MAJOR lays hs / zs / cs and x out as [B,T,*]; the
   // workspace copy of [B,F,T] frames is time-major whatever the flag says; P's rows follow the order of x's
@@ -858,14 +854,15 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
   auto go = [&](auto kern) __attribute__((always_inline)) {
     hipLaunchKernelGGL(kern, grid, block, 0, s, d.T, d.B, hsT, hsB, xsT, xsB, (const float*)x, (const float*)h0, (const float*)p.w,
                        (const float*)p.u, (const float*)p.bias_gate, (const float*)p.bias_update, (const float*)p.zeta,
-                       (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, flags, sg, sc, win ? win->start : nullptr);
+                       (const float*)p.nu, (float*)hs, (float*)zs, (float*)cs, L.flags, sg, sc, win ? win->start : nullptr);
   };
   // fp16 two-plane state product only for gates that keep z in [0,1] (see fwd_scan_split_w8): the fp16 launch, then
   // the bf16 one for the workgroups it turned down; FWD_BF16X3: A/B
   const int aux = (d.flags & FASTGRNN_FLAG_HS_LAST) ? 3 : (zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1));
   const FwdH256 v{d.gate_nl, aux, (d.B % 16) != 0, gate_bounds_state(d.gate_nl) && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3),
                   prein, bf, sg != nullptr, win != nullptr};
-  return pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
+  const bool launched =
+         pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
          return pick_int<0, 1, 2, 3>(v.aux, [&](auto A_) {
          return pick_bool(v.f16h, [&](auto FH_) {
          return pick_bool(v.prein, [&](auto PI_) {
@@ -882,17 +879,17 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
              return true;
            } else return false;
          }); }); }); }); }); }); }); });
+  return launched ? launch_status() : FASTGRNN_ERR_UNSUPPORTED;
 }
 
 // run-time values of bwd_scan_h256's template parameters
 struct BwdH256 { int gate; bool preact, ragged, bf; };
 
-// false: the library holds no kernel for this call (bwd_h256_built), nothing was launched
-bool launch_bwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
-                const void* a0, const void* a1, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
-  const H256BwdWs L = h256_bwd_layout(d);
-  char* base = reinterpret_cast<char*>(ws);
-  float* part = (float*)(base + L.part); float* dpre = (float*)(base + L.dpre); float* tn = (float*)(base + L.tn);
+// FASTGRNN_ERR_UNSUPPORTED: the library holds no kernel for this call (bwd_h256_built), nothing was launched
+int h256_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
+                  const void* a0, const void* a1, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
+  const DpreBwdWs L = dpre_bwd_ws(d, SLAB2, true, ws);
+  float* const part = L.part, * const dpre = L.dpre, * const tn = L.tn;
   const int nwg = (d.B + 15) / 16;
   const bool bm = (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0;
   const unsigned hsT = bm ? H2 : (unsigned)d.B * H2, hsB = bm ? (unsigned)d.T * H2 : H2;
@@ -914,29 +911,17 @@ bool launch_bwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* gh
         if constexpr (bwd_h256_built(G, PA, BF)) { go(bwd_scan_h256<G, PA, RG, BF>); return true; }
         else return false;
       }); }); }); });
-  if (!launched) return false;
+  if (!launched) return FASTGRNN_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(reduce_h256_small, dim3((2 * H2 + 2 + 63) / 64), dim3(1024), 0, s, nwg, part, (const float*)p.zeta,
                      (const float*)p.nu, (float*)g.d_bias_gate, (float*)g.d_bias_update, (float*)g.d_zeta, (float*)g.d_nu);
   const size_t TB = (size_t)d.T * d.B;
-  // dU = d_pre^T . H_prev (rows of t = 0 are h0, the rest hs[t-1]);  dW = d_pre^T . X   (.cu:539-540 over all steps)
+  // dU = d_pre^T . H_prev (rows of t = 0 are h0, the rest hs[t-1])   (.cu:540 over all steps)
   // (batch-major: row b*T + t of d_pre pairs with hs row b*T + t - 1, every T-th row with h0[b])
-  if (bm) tn_gemm_big_run_periodic(TB, H2, H2, dpre, H2, (const float*)h0, hs, (size_t)d.T, H2, tn, (float*)g.d_u, H2, s, bf);
-  else tn_gemm_big_run(TB, H2, H2, dpre, H2, (const float*)h0, hs, (size_t)d.B, H2, tn, (float*)g.d_u, H2, s, bf);
-  const bool bft = (d.flags & FASTGRNN_FLAG_X_BFT) != 0;
-  float* xtm = (float*)(base + L.xtm);
-  if (bft) bft_transpose_f32(d.B, d.T, (const float*)x, xtm, true, s, d.F);
-  const float* xr = bft ? xtm : (const float*)x;
-  tn_gemm_big_run(TB, H2, d.F, dpre, H2, xr, xr, (size_t)0, d.F, tn, (float*)g.d_w, d.F, s, bf);
-  // d_x = d_pre . W   (.cu:538; W is [H,F] = [K,N]); skipped when the caller does not want the input's gradient
-  // (g.d_x == NULL: the first layer of a model, whose input is data)
-  if (g.d_x) {
-    rows_gemm(TB, d.F, H2, true, dpre, (const float*)p.w, bft ? (void*)xtm : g.d_x, false, bf, s);   // (bf16 d_x)
-    if (bft) bft_transpose_f32(d.B, d.T, xtm, (float*)g.d_x, false, s, d.F);
-  }
-  return true;
+  int st = bm ? tn_gemm_big_run_periodic(TB, H2, H2, dpre, H2, (const float*)h0, hs, (size_t)d.T, H2, tn, (float*)g.d_u, H2, s, bf)
+              : tn_gemm_big_run(TB, H2, H2, dpre, H2, (const float*)h0, hs, (size_t)d.B, H2, tn, (float*)g.d_u, H2, s, bf);
+  if (st || (st = dpre_bwd_tail(d, dpre, tn, L.xtm, x, p.w, g, s))) return st;
+  return launch_status();
 }
-
-}  // namespace
 
 bool h256_shape(const fastgrnn_desc& d) {
   // B < 2^21: a step's rows are addressed with 32-bit lane offsets (B*H*4 bytes < 2^31)
@@ -966,31 +951,16 @@ bool h256_supported(const fastgrnn_desc& d, int direction) {
   return d.gate_nl <= FASTGRNN_NL_TANH || direction == 0 || preact;
 }
 
-size_t h256_backward_ws(const fastgrnn_desc& d) { return h256_bwd_layout(d).total; }
-// one word per workgroup: "my rows of h0 are outside the fp16 path's range" (fwd_scan_h256 MODE 1 -> MODE 2)
-// + under FASTGRNN_FLAG_X_BFT with F = 32 the time-major copy of x
-// + for F = 64 / 128 the frame product P[T*B, 256] (the frame GEMM reads [B,F,T] frames in place: no copy of x)
-size_t h256_forward_ws(const fastgrnn_desc& d) {
-  return h256_flag_bytes(d) + (((d.flags & FASTGRNN_FLAG_X_BFT) && d.F == F2) ? align256((size_t)d.T * d.B * F2 * 4) : 0) +
-         (d.F != F2 ? align256((size_t)d.T * d.B * H2 * 4) : 0);
-}
+size_t h256_forward_ws(const fastgrnn_desc& d) { return h256_fwd_ws(d, false, 0, nullptr).bytes; }
+size_t h256_windows_ws(const fastgrnn_desc& d, size_t pool_rows) { return h256_fwd_ws(d, true, pool_rows, nullptr).bytes; }
+size_t h256_backward_ws(const fastgrnn_desc& d) { return dpre_bwd_ws(d, SLAB2, true, nullptr).bytes; }
 
-// the flag words + for F = 64 the frame product of the pool, P_pool[R, 256]
-size_t h256_windows_ws(const fastgrnn_desc& d, size_t pool_rows) {
-  return H256_WIN_FLAG_BYTES + (d.F != F2 ? align256(pool_rows * H2 * 4) : 0);
-}
+}  // namespace
 
-int h256_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                 void* cs, void* ws, hipStream_t s, const float* sg, const float* sc, const window_src* win) {
-  if (!ws) return FASTGRNN_ERR_WORKSPACE;
-  if (!launch_fwd(d, p, x, h0, hs, zs, cs, ws, s, sg, sc, win)) return FASTGRNN_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
-}
-
-int h256_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
-                  const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
-  if (!launch_bwd(d, p, ghs, x, hs, zs, cs, h0, g, ws, s)) return FASTGRNN_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+const family& h256_family() {
+  static const family f = {h256_shape, h256_supported, h256_forward_ws, h256_backward_ws, h256_forward, h256_backward,
+                           h256_windows_ws, false, true};
+  return f;
 }
 
 }  // namespace fastgrnn

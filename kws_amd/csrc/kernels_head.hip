@@ -311,9 +311,15 @@ size_t head_lds_bytes(int H, int C) {
 
 bool head_supported(int B, int H, int C) { return B >= 1 && H >= 1 && H <= HEAD_MAX_H && C >= 1 && C <= HEAD_MAX_C; }
 
-size_t head_ws_bytes(int B, int H, int C) {
-  return align256((size_t)((B + HEAD_UTT - 1) / HEAD_UTT) * (C * H + C + 1) * sizeof(float));
+// one row of partial sums per workgroup: head_xent's d_w | d_b | loss, head_predict's count of correct rows
+template <typename T> struct HeadWs { T* part; size_t bytes; };
+template <typename T> static HeadWs<T> head_ws(int B, size_t per_wg, void* base) {
+  Carve c(base);
+  T* part = c.take<T>((size_t)((B + HEAD_UTT - 1) / HEAD_UTT) * per_wg);
+  return {part, c.off};
 }
+
+size_t head_ws_bytes(int B, int H, int C) { return head_ws<float>(B, C * H + C + 1, nullptr).bytes; }
 
 int head_xent(int B, int H, int C, const void* h_last, const void* fc_w, const void* fc_b, const void* labels,
               void* loss, void* logp, void* d_h, void* d_w, void* d_b, void* ws, hipStream_t s) {
@@ -324,17 +330,17 @@ int head_xent(int B, int H, int C, const void* h_last, const void* fc_w, const v
   if (lds > 64 * 1024)                              // (what this launch needs, not the CU's 160 KB: the kernel also has static LDS)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_xent_fwd_bwd),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  float* part = reinterpret_cast<float*>(ws);
+  float* part = head_ws<float>(B, C * H + C + 1, ws).part;
   hipLaunchKernelGGL(head_xent_fwd_bwd, dim3(nwg), dim3(HEAD_THREADS), lds, s, B, H, C, (const float*)h_last,
                      (const float*)fc_w, (const float*)fc_b, (const long long*)labels, (float*)logp,
                      (float*)d_h, part);
   const int n = C * H + C + 1;
   hipLaunchKernelGGL(head_reduce, dim3((n + 31) / 32), dim3(256), 0, s, nwg, n, C * H, C, (const float*)part,
                      (float*)d_w, (float*)d_b, (float*)loss);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
-size_t head_predict_ws_bytes(int B) { return align256((size_t)((B + HEAD_UTT - 1) / HEAD_UTT) * sizeof(int)); }
+size_t head_predict_ws_bytes(int B) { return head_ws<int>(B, 1, nullptr).bytes; }
 
 int head_predict(int B, int H, int C, const void* h_last, const void* fc_w, const void* fc_b, const void* labels,
                  void* logp, int32_t* pred, int32_t* n_correct, void* ws, hipStream_t s) {
@@ -344,19 +350,19 @@ int head_predict(int B, int H, int C, const void* h_last, const void* fc_w, cons
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_predict_fwd),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  int* part = labels ? reinterpret_cast<int*>(ws) : nullptr;
+  int* part = labels ? head_ws<int>(B, 1, ws).part : nullptr;
   hipLaunchKernelGGL(head_predict_fwd, dim3(nwg), dim3(HEAD_THREADS), lds, s, B, H, C, (const float*)h_last,
                      (const float*)fc_w, (const float*)fc_b, (const long long*)labels, (float*)logp, pred, part);
   if (labels)
     hipLaunchKernelGGL(head_count_reduce, dim3(1), dim3(256), 0, s, nwg, (const int*)part, n_correct);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 bool vote_supported(int K) { return K <= VOTE_MAX_K; }
 
 int vote_windows(int S, int Nw, int K, int M, const int32_t* pred, int32_t* majority, int32_t* event, hipStream_t s) {
   hipLaunchKernelGGL(vote_windows_k, dim3(S), dim3(VOTE_CHUNK), 0, s, Nw, K, M, pred, majority, event);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace fastgrnn

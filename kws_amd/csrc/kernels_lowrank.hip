@@ -782,48 +782,45 @@ __global__ __launch_bounds__(256) void bft_transpose(int B, int T, const E* __re
 
 static inline size_t esz(const fastgrnn_desc& d) { return d.dtype == FASTGRNN_BF16_IO ? 2 : 4; }
 
-struct LowrankBwdWs { size_t part, sink, xt, dxt, total; };
-LowrankBwdWs lowrank_bwd_layout(const fastgrnn_desc& d) {
+// the backward's slabs of partial sums (one per workgroup) and the d_x rows of the lanes beyond a ragged batch; under
+// FASTGRNN_FLAG_X_BFT the time-major copy of x and, for the backward, of d_x
+struct LowrankWs { float *part, *sink; char *xt, *dxt; size_t bytes; };
+LowrankWs lowrank_ws(const fastgrnn_desc& d, bool backward, void* base) {
   const size_t TB = (size_t)d.T * d.B, nwg = (d.B + 15) / 16;
-  LowrankBwdWs L; size_t o = 0;
-  L.part = o; o += align256(nwg * SLAB_LR * 4);      // one slab of partial sums per workgroup
-  L.sink = o; o += align256(16 * 32 * 4);            // d_x rows of the lanes beyond a ragged batch
-  L.xt = L.dxt = o;
-  if (d.flags & FASTGRNN_FLAG_X_BFT) {               // time-major copies of x and d_x
-    L.xt = o; o += align256(TB * 32 * esz(d));
-    L.dxt = o; o += align256(TB * 32 * esz(d));
+  Carve c(base);
+  LowrankWs L{};
+  if (backward) { L.part = c.take<float>(nwg * SLAB_LR); L.sink = c.take<float>(16 * 32); }
+  if (d.flags & FASTGRNN_FLAG_X_BFT) {
+    L.xt = c.take<char>(TB * 32 * esz(d));
+    if (backward) L.dxt = c.take<char>(TB * 32 * esz(d));
   }
-  L.total = o;
+  L.bytes = c.off;
   return L;
 }
 
-// false: the library holds no kernel for this call (bwd_lowrank_built), no scan was launched
-bool launch_bwd_lowrank(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x,
-                        const void* hs, const void* pre_s, const void* m_s, const void* h0,
-                        const fastgrnn_grads& g, void* ws, hipStream_t s) {
-  const LowrankBwdWs L = lowrank_bwd_layout(d);
-  char* base = reinterpret_cast<char*>(ws);
-  float* part = (float*)(base + L.part);
-  float* sink = (float*)(base + L.sink);
+// FASTGRNN_ERR_UNSUPPORTED: the library holds no kernel for this call (bwd_lowrank_built), no scan was launched
+int lowrank_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x,
+                     const void* hs, const void* pre_s, const void* m_s, const void* h0,
+                     const fastgrnn_grads& g, void* ws, hipStream_t s) {
+  if (!m_s || !pre_s) return FASTGRNN_ERR_NULL_POINTER;  // the rank-space vector and the pre-activation saved by the forward
+  const LowrankWs L = lowrank_ws(d, true, ws);
   const int nwg = (d.B + 15) / 16;
   const bool bf = d.dtype == FASTGRNN_BF16_IO, bft = (d.flags & FASTGRNN_FLAG_X_BFT) != 0;
   const int rsT = row_stride_t(d), rsB = row_stride_b(d);
   const int xsT = bft ? d.B : rsT, xsB = bft ? 1 : rsB;               // x / d_x rows (time-major copies under X_BFT)
   const void* xs = x;
   void* dxs = g.d_x;
+  int st;
   if (bft) {
-    xs = base + L.xt; dxs = base + L.dxt;
-    if (bf) hipLaunchKernelGGL((bft_transpose<unsigned short, true>), dim3(d.B), dim3(256), 0, s, d.B, d.T,
-                               (const unsigned short*)x, (unsigned short*)(base + L.xt));
-    else hipLaunchKernelGGL((bft_transpose<float, true>), dim3(d.B), dim3(256), 0, s, d.B, d.T, (const float*)x,
-                            (float*)(base + L.xt));
+    xs = L.xt; dxs = L.dxt;
+    if ((st = bft_transpose_run(d.B, d.T, 32, esz(d), x, L.xt, true, s))) return st;
   }
   auto go = [&](auto kern) __attribute__((always_inline)) {
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), 0, s, d.T, d.B, rsT, rsB, xsT, xsB, d.w_rank, d.u_rank,
                        (d.flags & FASTGRNN_FLAG_GRAD_LAST) ? 1 : 0, (const float*)ghs, (const float*)xs, (const float*)hs,
                        (const float*)pre_s, (const float*)m_s, (const float*)h0, (const float*)p.w1, (const float*)p.w2,
                        (const float*)p.u1, (const float*)p.u2, (const float*)p.bias_gate, (const float*)p.bias_update,
-                       (const float*)p.zeta, (const float*)p.nu, (float*)dxs, (float*)g.d_h0, sink, part);
+                       (const float*)p.zeta, (const float*)p.nu, (float*)dxs, (float*)g.d_h0, L.sink, L.part);
   };
   // 8 waves (two per SIMD) for full and ragged batches alike (lanes beyond a ragged batch only get a zero gradient,
   // which needs no extra registers; the first ragged variant masked five values per element and spilled)
@@ -835,35 +832,35 @@ bool launch_bwd_lowrank(const fastgrnn_desc& d, const fastgrnn_params& p, const 
         if constexpr (bwd_lowrank_built(G)) { go(bwd_scan_lowrank_split<G, decltype(RG_)::value, decltype(BF_)::value>); return true; }
         else return false;
       }); }); });
-  if (!launched) return false;
-  if (bft) {
-    if (bf) hipLaunchKernelGGL((bft_transpose<unsigned short, false>), dim3(d.B), dim3(256), 0, s, d.B, d.T,
-                               (const unsigned short*)(base + L.dxt), (unsigned short*)g.d_x);
-    else hipLaunchKernelGGL((bft_transpose<float, false>), dim3(d.B), dim3(256), 0, s, d.B, d.T,
-                            (const float*)(base + L.dxt), (float*)g.d_x);
-  }
+  if (!launched) return FASTGRNN_ERR_UNSUPPORTED;
+  if (bft && (st = bft_transpose_run(d.B, d.T, 32, esz(d), L.dxt, g.d_x, false, s))) return st;
   // every parameter gradient is a sum over the workgroups' slabs (.cu:544-555, factorised)
-  hipLaunchKernelGGL(reduce_lowrank_slabs, dim3((SL_ZN + 2 + 63) / 64), dim3(1024), 0, s, nwg, part, (const float*)p.zeta,
+  hipLaunchKernelGGL(reduce_lowrank_slabs, dim3((SL_ZN + 2 + 63) / 64), dim3(1024), 0, s, nwg, L.part, (const float*)p.zeta,
                      (const float*)p.nu, d.u_rank, d.w_rank, (float*)g.d_u1, (float*)g.d_u2, (float*)g.d_w1,
                      (float*)g.d_w2, (float*)g.d_bias_gate, (float*)g.d_bias_update, (float*)g.d_zeta, (float*)g.d_nu);
-  return true;
+  return launch_status();
 }
 
 // run-time values of fwd_scan_lowrank_split's template parameters
 struct FwdLowrank { int gate, aux; bool ragged, bf, last; };
 
-// false: the library holds no kernel for this call (fwd_lowrank_built), no scan was launched
-bool launch_fwd_lowrank(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                        void* zs, void* cs, void* ws, hipStream_t s) {
+// FASTGRNN_ERR_UNSUPPORTED: the library holds no kernel for this call (fwd_lowrank_built), no scan was launched
+int lowrank_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
+                    void* cs, void* ws, hipStream_t s, const float*, const float*, const window_src*) {
+  const bool preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
+  if (preact && (!cs || !zs) && !(d.flags & FASTGRNN_FLAG_HS_LAST)) return FASTGRNN_ERR_NULL_POINTER;   // pre-activation and rank-space vector
+  if ((d.flags & FASTGRNN_FLAG_HS_LAST) && (zs || (preact && cs))) return FASTGRNN_ERR_UNSUPPORTED;
+  if (d.dtype == FASTGRNN_BF16_IO && zs && !preact) return FASTGRNN_ERR_UNSUPPORTED;
+  if ((d.flags & FASTGRNN_FLAG_X_BFT) && !ws) return FASTGRNN_ERR_WORKSPACE;
   dim3 grid((d.B + 15) / 16), block(512);
   const bool ragged = (d.B % 16) != 0, bf = d.dtype == FASTGRNN_BF16_IO, bft = (d.flags & FASTGRNN_FLAG_X_BFT) != 0;
   const int rsT = row_stride_t(d), rsB = row_stride_b(d);
   const int xsT = bft ? d.B : rsT, xsB = bft ? 1 : rsB;
   if (bft) {
-    if (bf) hipLaunchKernelGGL((bft_transpose<unsigned short, true>), dim3(d.B), dim3(256), 0, s, d.B, d.T,
-                               (const unsigned short*)x, (unsigned short*)ws);
-    else hipLaunchKernelGGL((bft_transpose<float, true>), dim3(d.B), dim3(256), 0, s, d.B, d.T, (const float*)x, (float*)ws);
-    x = ws;
+    const LowrankWs L = lowrank_ws(d, false, ws);
+    const int st = bft_transpose_run(d.B, d.T, 32, esz(d), x, L.xt, true, s);
+    if (st) return st;
+    x = L.xt;
   }
   auto go = [&](auto kern) __attribute__((always_inline)) {
     hipLaunchKernelGGL(kern, grid, block, 0, s, d.T, d.B, rsT, rsB, xsT, xsB, d.w_rank, d.u_rank, (const float*)x,
@@ -873,7 +870,8 @@ bool launch_fwd_lowrank(const fastgrnn_desc& d, const fastgrnn_params& p, const 
   };
   const FwdLowrank v{d.gate_nl, zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1), ragged, bf,
                      (d.flags & FASTGRNN_FLAG_HS_LAST) != 0};   // (last: inference, no auxiliary output -- lowrank_forward)
-  return pick_int<0, 1, 2>(v.gate, [&](auto G_) {
+  const bool launched =
+         pick_int<0, 1, 2>(v.gate, [&](auto G_) {
          return pick_int<0, 1, 2>(v.aux, [&](auto A_) {
          return pick_bool(v.bf, [&](auto BF_) {
          return pick_bool(v.last, [&](auto LS_) {
@@ -883,12 +881,11 @@ bool launch_fwd_lowrank(const fastgrnn_desc& d, const fastgrnn_params& p, const 
            if constexpr (fwd_lowrank_built(G, A, BF, LS)) { go(fwd_scan_lowrank_split<G, A, RG, BF, LS>); return true; }
            else return false;
          }); }); }); }); });
+  return launched ? launch_status() : FASTGRNN_ERR_UNSUPPORTED;
 }
 
-}  // namespace
-
 // H = 256, F = 32, both factorisations with rank 1..16 (zero-extended to 16 in the kernels).  Larger ranks and
-// half-factorised cells (only W or only U low-rank, rnn.py:783-798) stay on the generic scan.
+// half-factorised cells (only W or only U low-rank, rnn.py:783-798) are densified (kernels_densify.hip).
 bool lowrank_shape(const fastgrnn_desc& d) {
   return d.H == 256 && d.F == 32 && d.w_rank >= 1 && d.w_rank <= 16 && d.u_rank >= 1 && d.u_rank <= 16;
 }
@@ -906,43 +903,27 @@ bool lowrank_supported(const fastgrnn_desc& d, int direction) {
   return preact;
 }
 
-size_t lowrank_forward_ws(const fastgrnn_desc& d) {
-  return (d.flags & FASTGRNN_FLAG_X_BFT) ? align256((size_t)d.T * d.B * 32 * esz(d)) : 0;
+size_t lowrank_forward_ws(const fastgrnn_desc& d) { return lowrank_ws(d, false, nullptr).bytes; }
+size_t lowrank_backward_ws(const fastgrnn_desc& d) { return lowrank_ws(d, true, nullptr).bytes; }
+
+}  // namespace
+
+const family& lowrank_family() {
+  static const family f = {lowrank_shape, lowrank_supported, lowrank_forward_ws, lowrank_backward_ws,
+                           lowrank_forward, lowrank_backward, nullptr, false, false};
+  return f;
 }
 
-size_t lowrank_backward_ws(const fastgrnn_desc& d) { return lowrank_bwd_layout(d).total; }
-
-int lowrank_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
-                    void* cs, void* ws, hipStream_t s) {
-  const bool preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
-  if (preact && (!cs || !zs) && !(d.flags & FASTGRNN_FLAG_HS_LAST)) return FASTGRNN_ERR_NULL_POINTER;   // pre-activation and rank-space vector
-  if ((d.flags & FASTGRNN_FLAG_HS_LAST) && (zs || (preact && cs))) return FASTGRNN_ERR_UNSUPPORTED;
-  if (d.dtype == FASTGRNN_BF16_IO && zs && !preact) return FASTGRNN_ERR_UNSUPPORTED;
-  if ((d.flags & FASTGRNN_FLAG_X_BFT) && !ws) return FASTGRNN_ERR_WORKSPACE;
-  if (!launch_fwd_lowrank(d, p, x, h0, hs, zs, cs, ws, s)) return FASTGRNN_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
-}
-
-int lowrank_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
-                     const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
-  if (!cs || !zs) return FASTGRNN_ERR_NULL_POINTER;  // the rank-space vector and the pre-activation saved by the forward
-  if (!launch_bwd_lowrank(d, p, ghs, x, hs, zs, cs, h0, g, ws, s)) return FASTGRNN_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
-}
-
-// fp32 [B,32,T] <-> [T,B,32] for the dense H = 256 layer's backward (kernels_h256.hip): its dW GEMM and d_x GEMM work on
-// time-major rows
-void bft_transpose_f32(int B, int T, const float* src, float* dst, bool to_time_major, hipStream_t s, int F) {
-#define BFT_WIDE(fw)                                                                                                  \
-  if (F == fw) {                                                                                                      \
-    if (to_time_major) hipLaunchKernelGGL((bft_transpose<float, true, fw>), dim3(B, fw / 32), dim3(256), 0, s, B, T, src, dst); \
-    else hipLaunchKernelGGL((bft_transpose<float, false, fw>), dim3(B, fw / 32), dim3(256), 0, s, B, T, src, dst);    \
-    return;                                                                                                           \
+int bft_transpose_run(int B, int T, int F, size_t esize, const void* src, void* dst, bool to_time_major, hipStream_t s) {
+#define BFT_CASE(E, fw)                                                                                               \
+  if (F == fw && esize == sizeof(E)) {                                                                                \
+    if (to_time_major) hipLaunchKernelGGL((bft_transpose<E, true, fw>), dim3(B, fw / 32), dim3(256), 0, s, B, T, (const E*)src, (E*)dst); \
+    else hipLaunchKernelGGL((bft_transpose<E, false, fw>), dim3(B, fw / 32), dim3(256), 0, s, B, T, (const E*)src, (E*)dst); \
+    return launch_status();                                                                                           \
   }
-  BFT_WIDE(64) BFT_WIDE(128) BFT_WIDE(256)
-#undef BFT_WIDE
-  if (to_time_major) hipLaunchKernelGGL((bft_transpose<float, true>), dim3(B), dim3(256), 0, s, B, T, src, dst);
-  else hipLaunchKernelGGL((bft_transpose<float, false>), dim3(B), dim3(256), 0, s, B, T, src, dst);
+  BFT_CASE(unsigned short, 32) BFT_CASE(float, 32) BFT_CASE(float, 64) BFT_CASE(float, 128) BFT_CASE(float, 256)
+#undef BFT_CASE
+  return FASTGRNN_ERR_UNSUPPORTED;
 }
 
 }  // namespace fastgrnn

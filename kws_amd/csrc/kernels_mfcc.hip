@@ -81,7 +81,7 @@ size_t mfcc_tables_bytes() { return align256(TB_END * sizeof(float)); }
 
 int mfcc_init_tables(void* tables, hipStream_t s) {
   hipLaunchKernelGGL(mfcc_tables_k, dim3(512), dim3(256), 0, s, reinterpret_cast<float*>(tables));
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 int mfcc_run(const fastgrnn_mfcc_desc& d, const void* audio, const int32_t* lengths, const void* tables, const float* mean,
@@ -105,7 +105,7 @@ int mfcc_run(const fastgrnn_mfcc_desc& d, const void* audio, const int32_t* leng
     hipLaunchKernelGGL(mfcc_k<short>, dim3(d.B), dim3(MF_THREADS), 0, s, a);
   else
     hipLaunchKernelGGL(mfcc_k<float>, dim3(d.B), dim3(MF_THREADS), 0, s, a);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace fastgrnn

@@ -719,7 +719,7 @@ int launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, 
         else return false;
       }); }); });
   if (!launched) return FASTGRNN_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 template <int H, int F>
@@ -746,7 +746,7 @@ int launch_bwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs
   hipLaunchKernelGGL(reduce_slabs, dim3((ntot + 63) / 64), dim3(1024), 0, s, nwg, H, F, slab_stride(H, F), part,
                      (const float*)p.zeta, (const float*)p.nu, (float*)g.d_u, (float*)g.d_w,
                      (float*)g.d_bias_gate, (float*)g.d_bias_update, (float*)g.d_zeta, (float*)g.d_nu);
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 bool shape_ok(int H, int F) { return (H == 128 && F == 32) || (H == 64 && F == 32) || (H == 128 && F == 64); }

@@ -1060,32 +1060,48 @@ bool dense_wide_shape(const fastgrnn_desc& d) {
          // 32-bit byte offsets inside a tensor (see split_supported), the d_pre workspace's 16 sink rows included
          ((double)d.T * d.B + 16.0) * (d.F > 128 ? d.F : 128) * 4.0 < 4294967296.0;
 }
-struct WideBwdWs { size_t slabs, dpre, tn, xtm, total; };
-WideBwdWs wide_bwd_layout(const fastgrnn_desc& d) {
-  const size_t TB = (size_t)d.T * d.B, nwg = (d.B + 15) / 16;
-  WideBwdWs L; size_t o = 0;
-  L.slabs = o; o += align256(nwg * SLAB * 4);
-  L.dpre = o; o += align256((TB + 16) * 128 * 4);    // + 16 sink rows for the lanes beyond a ragged batch
-  L.tn = o; o += tn_gemm_big_ws(TB, 128, d.F);
-  // FASTGRNN_FLAG_X_BFT: the time-major copy of x for the dW GEMM (its rows follow d_pre's); the d_x GEMM then writes
-  // over it and the result is transposed into the caller's [B,F,T] tensor (as kernels_h256.hip)
-  L.xtm = o; if (d.flags & FASTGRNN_FLAG_X_BFT) o += align256(TB * (size_t)d.F * 4);
-  L.total = o;
+// F = 32 keeps everything in the scan: ranks 0, the sequences addressed with 32-bit offsets
+bool dense_f32_shape(const fastgrnn_desc& d) { return d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && seq_fits32(d); }
+
+// the backward's workspace: the workgroups' slabs and, for a wide layer, what dpre_bwd_tail works on
+DpreBwdWs w8_bwd_ws(const fastgrnn_desc& d, void* base) {
+  if (dense_wide_shape(d)) return dpre_bwd_ws(d, SLAB, false, base);
+  Carve c(base);
+  DpreBwdWs L{};
+  L.part = c.take<float>((size_t)((d.B + 15) / 16) * SLAB);
+  L.bytes = c.off;
   return L;
+}
+// a wide layer's forward: the frame product P = X.W^T goes to the auxiliary output the caller passes (z_s under
+// SAVE_PREACT, c_s otherwise); a forward without auxiliary outputs needs room for it.  The query cannot see the
+// pointers, so it answers for that case; forward-only callers (HS_LAST or no gates) are the ones that pay.
+struct WideFwdWs { float* P; size_t bytes; };
+WideFwdWs wide_fwd_ws(const fastgrnn_desc& d, void* base) {
+  Carve c(base);
+  float* P = c.take<float>((size_t)d.T * d.B * 128);
+  return {P, c.off};
+}
+// the training calls over windows where no scan reads the pool in place: the route's own workspace (inner_bytes: none
+// for the H = 128 / F = 32 forward), then the gathered copy of x
+struct GatherWs { char* inner; float* xg; size_t bytes; };
+GatherWs gather_ws(const fastgrnn_desc& d, size_t inner_bytes, void* base) {
+  Carve c(base);
+  char* inner = c.take<char>(inner_bytes);
+  float* xg = c.take<float>((size_t)d.T * d.B * d.F);
+  return {inner, xg, c.off};
 }
 
 // run-time values of bwd_scan_split_w8's template parameters
 struct BwdW8 { int gate; bool preact, ragged, bf, nox, uq, nodx; };
 
-// false: the library holds no kernel for this call (bwd_w8_built), nothing was launched
-bool launch_bwd_w8(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
-                   const void* a0, const void* a1, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
+// FASTGRNN_ERR_UNSUPPORTED: the library holds no kernel for this call (bwd_w8_built), nothing was launched
+int launch_bwd_w8(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
+                  const void* a0, const void* a1, const void* h0, const fastgrnn_grads& g, void* ws, hipStream_t s) {
   const int nwg = (d.B + 15) / 16;
   dim3 grid(nwg);
   const bool wide = dense_wide_shape(d);
-  const WideBwdWs L = wide ? wide_bwd_layout(d) : WideBwdWs{0, 0, 0, 0, 0};
-  float* part = reinterpret_cast<float*>(ws);
-  float* dpre = wide ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.dpre) : nullptr;
+  const DpreBwdWs L = w8_bwd_ws(d, ws);
+  float* const part = L.part, * const dpre = L.dpre;
   auto go8 = [&](auto kern) __attribute__((always_inline)) {     // 8-wave kernels also take the x layout
     hipLaunchKernelGGL(kern, grid, dim3(512), 0, s, d.T, d.B, row_stride_t(d), row_stride_b(d),
                        ((d.flags & FASTGRNN_FLAG_X_BFT) ? 1 : 0) | ((d.flags & FASTGRNN_FLAG_GRAD_LAST) ? 2 : 0), (const float*)ghs,
@@ -1113,27 +1129,16 @@ bool launch_bwd_w8(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
         if constexpr (bwd_w8_built(G, PA, BF, NX, UQ, ND)) { go8(bwd_scan_split_w8<G, PA, RG, BF, NX, UQ, ND>); return true; }
         else return false;
       }); }); }); }); }); }); });
-  if (!launched) return false;
+  if (!launched) return FASTGRNN_ERR_UNSUPPORTED;
   const int ntot = 128 * 128 + 128 * 32 + 2 * 128 + 2;
   hipLaunchKernelGGL(reduce_slabs_split, dim3((ntot + 63) / 64), dim3(1024), 0, s, nwg, part, (const float*)p.zeta,
                      (const float*)p.nu, (float*)g.d_u, wide ? (float*)nullptr : (float*)g.d_w, (float*)g.d_bias_gate,
                      (float*)g.d_bias_update, (float*)g.d_zeta, (float*)g.d_nu);
   if (wide) {
-    const size_t TB = (size_t)d.T * d.B;
-    // dW[H,F] = d_pre^T . X   (.cu:539 summed over the steps)
-    const bool bfw = d.dtype == FASTGRNN_BF16_IO;    // (x and d_x are bf16 then; d_pre is fp32 always)
-    const bool bft = (d.flags & FASTGRNN_FLAG_X_BFT) != 0;   // (fp32, time-major sequences: split_supported)
-    float* xtm = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.xtm);
-    if (bft) { bft_transpose_f32(d.B, d.T, (const float*)x, xtm, true, s, d.F); x = xtm; }
-    tn_gemm_big_run(TB, 128, d.F, dpre, 128, (const float*)x, x, (size_t)0, d.F,
-                    reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.tn), (float*)g.d_w, d.F, s, bfw);
-    // d_x[T*B,F] = d_pre . W   (.cu:538 for every step at once; W is [H,F] = [K,N])
-    if (g.d_x) {                                     // (NULL: not wanted)
-      rows_gemm(TB, d.F, 128, true, dpre, (const float*)p.w, bft ? (void*)xtm : g.d_x, false, bfw, s);
-      if (bft) bft_transpose_f32(d.B, d.T, xtm, (float*)g.d_x, false, s, d.F);
-    }
+    const int st = dpre_bwd_tail(d, dpre, L.tn, L.xtm, x, p.w, g, s);
+    if (st) return st;
   }
-  return true;
+  return launch_status();
 }
 
 // run-time values of fwd_scan_split_w8's template parameters
@@ -1143,10 +1148,10 @@ struct FwdW8 { int gate, aux; bool ragged, bf, f16h, prein, uq, aff, win; };
 // reference's outputs) or, when the caller wants no auxiliary tensor, to the workspace pws
 // sg, sc: FASTGRNN_FLAG_PREACT_AFFINE -- the AFF variants (gates sigmoid / relu / tanh, fp32, hs only or h_T alone)
 // win: x is the frame pool and win->start the utterances' first rows (the WIN variants)
-// false: the library holds no kernel for this call (fwd_w8_built), nothing was launched
-bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
-                void* zs, void* cs, hipStream_t s, void* pws, const float* sg, const float* sc,
-                const window_src* win = nullptr) {
+// FASTGRNN_ERR_UNSUPPORTED: the library holds no kernel for this call (fwd_w8_built), nothing was launched
+int launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
+               void* zs, void* cs, hipStream_t s, void* pws, const float* sg, const float* sc,
+               const window_src* win = nullptr) {
   dim3 grid((d.B + 15) / 16), block(256);
   const bool ragged = (d.B % 16) != 0, bf = d.dtype == FASTGRNN_BF16_IO, prein = pws != nullptr;
   const int aux = zs == nullptr ? 0 : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? 2 : 1);
@@ -1173,7 +1178,7 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
            return pick_bool(ragged, [&](auto RG_) {
              go(fwd_scan_split<decltype(G_)::value, decltype(A_)::value, decltype(RG_)::value>);
              return true;
-           }); }); });
+           }); }); }) ? launch_status() : FASTGRNN_ERR_UNSUPPORTED;
   // default: the 8-wave shape.  aux 3 = h_T alone (inference).  fp16 two-plane state product (F16H) only for gates
   // that keep z in [0,1] -- they bound the growth of h to sigma(nu) per step, and the kernel itself checks h0 (see
   // fwd_scan_split_w8); relu / tanh / quantTanh gates always run the three-bf16-plane product, as does
@@ -1181,7 +1186,8 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
   const FwdW8 v{d.gate_nl, (d.flags & FASTGRNN_FLAG_HS_LAST) ? 3 : aux, ragged, bf,
                 gate_bounds_state(d.gate_nl) && !(d.flags & FASTGRNN_FLAG_FWD_BF16X3), prein,
                 d.update_nl == FASTGRNN_NL_QUANT_TANH, sg != nullptr, win != nullptr};
-  return pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
+  const bool launched =
+         pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
          return pick_int<0, 1, 2, 3>(v.aux, [&](auto A_) {
          return pick_bool(v.bf, [&](auto BF_) {
          return pick_bool(v.f16h, [&](auto FH_) {
@@ -1197,9 +1203,70 @@ bool launch_fwd(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x,
            if constexpr (fwd_w8_built(G, A, BF, FH, PI, UQ, AF, WN)) { go8(fwd_scan_split_w8<G, A, RG, BF, FH, PI, UQ, AF, WN>); return true; }
            else return false;
          }); }); }); }); }); }); }); }); });
+  return launched ? launch_status() : FASTGRNN_ERR_UNSUPPORTED;
+}
+
+// dense H = 128 with a wider input (F = 64 / 128 / 256; the reference's second layer): recurrence-only scans +
+// batched GEMMs.  fp32 sequences, time- or batch-major, every gate, full or last-state outputs / gradients.
+bool wide_supported(const fastgrnn_desc& d, int direction) {
+  const bool preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
+  // the loader's [B,F,T] batches: fp32; the frame GEMM reads them in place, the backward takes a time-major workspace
+  // copy, which rows of batch-major d_pre would not match
+  if ((d.flags & FASTGRNN_FLAG_X_BFT) &&
+      (d.dtype != FASTGRNN_F32 || (direction == 1 && (d.flags & FASTGRNN_FLAG_BATCH_MAJOR)))) return false;
+  if (d.dtype == FASTGRNN_BF16_IO)                 // bf16 sequences (round 3): the reference's three gates, no last-state
+    return d.gate_nl <= FASTGRNN_NL_TANH &&        // flags, the backward under the one-saved-tensor contract
+           !(d.flags & (FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_GRAD_LAST)) && (direction == 0 || preact);
+  if (direction == 0 && preact && (d.flags & FASTGRNN_FLAG_HS_LAST)) return false;
+  return d.gate_nl <= FASTGRNN_NL_TANH || direction == 0 || preact;
+}
+
+bool dense_f32_supported(const fastgrnn_desc& d, int direction) {
+  const bool preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
+  // quantised gates (rnn.py:53-60) and the [B,F,T] input layout: 8-wave kernels only, i.e. the backward under the
+  // SAVE_PREACT contract
+  if (d.gate_nl > FASTGRNN_NL_TANH || (d.flags & FASTGRNN_FLAG_X_BFT)) return direction == 0 || preact;
+  // last-state-only outputs / gradients (the classifier's view of the last layer, model.py:227): 8-wave kernels
+  if (direction == 0 && preact && (d.flags & FASTGRNN_FLAG_HS_LAST)) return false;
+  // bf16 sequences: the backward only under the SAVE_PREACT contract (8-wave kernel)
+  return d.dtype != FASTGRNN_BF16_IO || direction == 0 || preact;
+}
+
+size_t wide_forward_ws(const fastgrnn_desc& d) { return wide_fwd_ws(d, nullptr).bytes; }
+size_t no_forward_ws(const fastgrnn_desc&) { return 0; }
+size_t w8_backward_ws(const fastgrnn_desc& d) { return w8_bwd_ws(d, nullptr).bytes; }
+
+int w8_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs, void* zs,
+               void* cs, void* ws, hipStream_t s, const float* sg, const float* sc, const window_src* win) {
+  void* pws = nullptr;
+  if (dense_wide_shape(d)) {
+    // P[T*B,H] = X . W^T, the one genuinely dense contraction of the layer (.cu:356 per step), into the buffer the
+    // scan reads it from: z_s (SAVE_PREACT: overwritten by the pre-activation), c_s (overwritten by h_prime), or
+    // the workspace when the caller wants neither
+    pws = zs == nullptr ? wide_fwd_ws(d, ws).P : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? zs : cs);
+    if (!pws) return FASTGRNN_ERR_WORKSPACE;
+    // (FASTGRNN_FLAG_X_BFT: the [B,F,T] frames are read in place; the rows of P land in the order of hs)
+    const int st = (d.flags & FASTGRNN_FLAG_X_BFT)
+        ? rows_gemm_bft(d.B, d.T, 128, d.F, (const float*)x, (const float*)p.w, (float*)pws, (size_t)row_stride_t(d), (size_t)row_stride_b(d), s)
+        : rows_gemm((size_t)d.T * d.B, 128, d.F, false, x, (const float*)p.w, pws, d.dtype == FASTGRNN_BF16_IO, false, s);
+    if (st != FASTGRNN_OK) return st;
+  }
+  return launch_fwd(d, p, x, h0, hs, zs, cs, s, pws, sg, sc, win);
 }
 
 }  // namespace
+
+// The cell families of kernel path 2, in the order they are asked (common.h)
+const family* family_of(const fastgrnn_desc& d) {
+  static const family dense_wide = {dense_wide_shape, wide_supported, wide_forward_ws, w8_backward_ws, w8_forward,
+                                    launch_bwd_w8, nullptr, true, true};
+  static const family dense_f32 = {dense_f32_shape, dense_f32_supported, no_forward_ws, w8_backward_ws, w8_forward,
+                                   launch_bwd_w8, nullptr, false, false};
+  static const family* const table[] = {&h256_family(), &lowrank_family(), &densified_family(), &dense_wide, &dense_f32};
+  for (const family* f : table)
+    if (f->shape(d)) return f;
+  return nullptr;
+}
 
 bool split_supported(const fastgrnn_desc& d, int direction) {
   if ((d.dtype != FASTGRNN_F32 && d.dtype != FASTGRNN_BF16_IO) ||
@@ -1208,39 +1275,12 @@ bool split_supported(const fastgrnn_desc& d, int direction) {
     return false;
   if (d.update_nl == FASTGRNN_NL_QUANT_TANH) {
     // quantTanh update (rnn.py:57-58,292-293): dense H = 128 / F = 32, fp32, hs only or the one-saved-tensor contract
-    const bool shape = d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && d.dtype == FASTGRNN_F32 && seq_fits32(d);
-    if (!shape || (d.flags & (FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_FWD_4WAVE))) return false;
+    if (!dense_f32_shape(d) || d.dtype != FASTGRNN_F32 ||
+        (d.flags & (FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_FWD_4WAVE))) return false;
     return direction == 0 || (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
   }
-  const bool dense = d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && seq_fits32(d);
-  const bool preact = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
-  if (h256_shape(d)) return h256_supported(d, direction);      // dense H = 256 / F = 32: kernels_h256.hip
-  if (lowrank_shape(d)) return lowrank_supported(d, direction); // H = 256 / F = 32, ranks <= 16: kernels_lowrank.hip
-  if (densified_shape(d)) return densified_supported(d, direction);   // every other factorised cell on a dense shape: kernels_densify.hip
-  // dense H = 128 with a wider input (F = 64 / 128 / 256; the reference's second layer): recurrence-only scans +
-  // batched GEMMs.  fp32 sequences, time- or batch-major, every gate, full or last-state outputs / gradients.
-  if (dense_wide_shape(d)) {
-    // the loader's [B,F,T] batches: fp32; the frame GEMM reads them in place, the backward takes a time-major workspace
-    // copy, which rows of batch-major d_pre would not match
-    if ((d.flags & FASTGRNN_FLAG_X_BFT) &&
-        (d.dtype != FASTGRNN_F32 || (direction == 1 && (d.flags & FASTGRNN_FLAG_BATCH_MAJOR)))) return false;
-    if (d.dtype == FASTGRNN_BF16_IO)                 // bf16 sequences (round 3): the reference's three gates, no last-state
-      return d.gate_nl <= FASTGRNN_NL_TANH &&        // flags, the backward under the one-saved-tensor contract
-             !(d.flags & (FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_GRAD_LAST)) && (direction == 0 || preact);
-    if (direction == 0 && preact && (d.flags & FASTGRNN_FLAG_HS_LAST)) return false;
-    return d.gate_nl <= FASTGRNN_NL_TANH || direction == 0 || preact;
-  }
-  // quantised gates (rnn.py:53-60) and the [B,F,T] input layout: 8-wave dense kernels only, i.e. the backward
-  // under the SAVE_PREACT contract
-  if (d.gate_nl > FASTGRNN_NL_TANH || (d.flags & FASTGRNN_FLAG_X_BFT)) return dense && (direction == 0 || preact);
-  // last-state-only outputs / gradients (the classifier's view of the last layer, model.py:227): 8-wave dense kernels
-  if (d.flags & (FASTGRNN_FLAG_GRAD_LAST | FASTGRNN_FLAG_HS_LAST)) {
-    if (!dense) return false;
-    if (direction == 0 && (d.flags & FASTGRNN_FLAG_SAVE_PREACT) && (d.flags & FASTGRNN_FLAG_HS_LAST)) return false;
-  }
-  // bf16 sequences: dense shape only; the backward only under the SAVE_PREACT contract (8-wave kernel)
-  if (d.dtype == FASTGRNN_BF16_IO) return dense && (direction == 0 || preact);
-  return dense;
+  const family* f = family_of(d);
+  return f && f->supported(d, direction);
 }
 
 // FASTGRNN_FLAG_PREACT_AFFINE on kernel path 2: fp32 sequences, gates sigmoid / relu / tanh, update tanh, dense
@@ -1248,10 +1288,11 @@ bool split_supported(const fastgrnn_desc& d, int direction) {
 bool affine_supported(const fastgrnn_desc& d) {
   if (d.dtype != FASTGRNN_F32 || d.gate_nl > FASTGRNN_NL_TANH || d.update_nl != FASTGRNN_NL_TANH) return false;
   if (d.flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_GRAD_LAST)) return false;
+  const bool h256 = h256_family().shape(d);
   // [B,F,T] frames: only where the frame product is a GEMM of its own (the scaled F = 32 scans read time-major frames)
-  if ((d.flags & FASTGRNN_FLAG_X_BFT) && !((h256_shape(d) && d.F != 32) || dense_wide_shape(d))) return false;
-  if (h256_shape(d)) return h256_supported(d, 0);
-  return (d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32 && seq_fits32(d)) || dense_wide_shape(d);
+  if ((d.flags & FASTGRNN_FLAG_X_BFT) && !((h256 && d.F != 32) || dense_wide_shape(d))) return false;
+  if (h256) return h256_family().supported(d, 0);
+  return dense_f32_shape(d) || dense_wide_shape(d);
 }
 
 // fastgrnn_hip_forward_windows on kernel path 2: fp32, dense, gates sigmoid / relu / tanh, update tanh; H = 128 with
@@ -1265,7 +1306,10 @@ bool windows_supported(const fastgrnn_desc& d) {
 }
 
 // the H = 256 scans' flag words and, for F = 64, the frame product of the whole pool P_pool[R, 256]; 0 for H = 128
-size_t windows_ws(const fastgrnn_desc& d, size_t pool_rows) { return h256_shape(d) ? h256_windows_ws(d, pool_rows) : 0; }
+size_t windows_ws(const fastgrnn_desc& d, size_t pool_rows) {
+  const family* f = family_of(d);
+  return f && f->windows_ws ? f->windows_ws(d, pool_rows) : 0;
+}
 
 // fastgrnn_hip_forward_windows_train / fastgrnn_hip_backward_windows: the plain cells the windowed scans hold, under the
 // one-saved-tensor contract in both directions; FASTGRNN_FLAG_BATCH_MAJOR, and FASTGRNN_FLAG_GRAD_LAST for the backward
@@ -1279,46 +1323,25 @@ bool train_windows_supported(const fastgrnn_desc& d) {
   return split_supported(f, 0) && split_supported(b, 1);
 }
 
-// bytes of the gathered copy of x: at the end of the backward's workspace for every shape (the backward scans read no
-// pool in place) and, for H = 128, at the start of the forward's
-size_t train_windows_gather_bytes(const fastgrnn_desc& d) { return align256((size_t)d.T * d.B * d.F * 4); }
-
 // the training forward: the H = 256 scans read the pool in place (windows_ws); H = 128 runs the plain forward on a
-// gathered copy of x at the start of the workspace (this file holds no WIN scan that saves the pre-activation)
+// gathered copy of x in the workspace (this file holds no WIN scan that saves the pre-activation)
 size_t train_windows_forward_ws(const fastgrnn_desc& d, size_t pool_rows) {
-  return h256_shape(d) ? h256_windows_ws(d, pool_rows) : train_windows_gather_bytes(d);
+  const family* f = family_of(d);
+  return f && f->windows_ws ? f->windows_ws(d, pool_rows) : gather_ws(d, 0, nullptr).bytes;
 }
 
+// the backward scans read no pool in place: every shape gathers, behind the route's own workspace
 size_t train_windows_backward_ws(const fastgrnn_desc& d) {
   fastgrnn_desc b = d;
   b.flags |= FASTGRNN_FLAG_SAVE_PREACT;
-  return split_backward_ws(b) + train_windows_gather_bytes(d);
+  return gather_ws(b, split_backward_ws(b), nullptr).bytes;
 }
 
-size_t split_forward_ws(const fastgrnn_desc& d) {
-  // wide layers: the frame product P = X.W^T goes to the auxiliary output the caller passes (z_s under SAVE_PREACT,
-  // c_s otherwise); a forward without auxiliary outputs needs room for it.  The query cannot see the pointers, so
-  // it answers for that case; forward-only callers (HS_LAST or no gates) are the ones that pay.
-  if (dense_wide_shape(d)) return align256((size_t)d.T * d.B * 128 * 4);
-  if (h256_shape(d)) return h256_forward_ws(d);
-  if (lowrank_shape(d)) return lowrank_forward_ws(d);
-  if (densified_shape(d)) return densified_forward_ws(d);
-  return 0;
-}
+size_t split_forward_ws(const fastgrnn_desc& d) { const family* f = family_of(d); return f ? f->forward_ws(d) : 0; }
+size_t split_backward_ws(const fastgrnn_desc& d) { const family* f = family_of(d); return f ? f->backward_ws(d) : 0; }
 
-bool split_forward_ws_optional(const fastgrnn_desc& d) { return dense_wide_shape(d); }
-// shapes whose d_x is a GEMM of its own behind the scan: the caller may pass d_x = NULL to skip it
-bool split_dx_optional(const fastgrnn_desc& d) { return dense_wide_shape(d) || h256_shape(d); }
-// ... and where the scan can leave its d_x product out (bwd_scan_split_w8<..., NODX>): under FASTGRNN_FLAG_NO_INPUT_GRAD
+// where the scan can leave its d_x product out (bwd_scan_split_w8<..., NODX>): under FASTGRNN_FLAG_NO_INPUT_GRAD
 bool split_dx_skippable(const fastgrnn_desc& d) { return d.w_rank == 0 && d.u_rank == 0 && d.H == 128 && d.F == 32; }
-
-size_t split_backward_ws(const fastgrnn_desc& d) {
-  if (h256_shape(d)) return h256_backward_ws(d);
-  if (dense_wide_shape(d)) return wide_bwd_layout(d).total;
-  if (lowrank_shape(d)) return lowrank_backward_ws(d);
-  if (densified_shape(d)) return densified_backward_ws(d);
-  return align256((size_t)((d.B + 15) / 16) * SLAB * 4);
-}
 
 int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
                    const void* zs, const void* cs, const void* h0, const fastgrnn_grads& g, void* ws,
@@ -1328,31 +1351,31 @@ int split_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const void*
     c.flags &= ~FASTGRNN_FLAG_SAVE_PREACT;
     if (g.d_x || !(d.flags & FASTGRNN_FLAG_SAVE_PREACT) || !train_windows_supported(c)) return FASTGRNN_ERR_UNSUPPORTED;
     // the windows as a copy of x behind the route's own workspace; the existing dispatch runs on it
-    float* xg = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + split_backward_ws(d));
-    const int st = gather_windows(d.T, d.B, d.F, (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0, (const float*)x, win->start, xg, s);
+    const GatherWs L = gather_ws(d, split_backward_ws(d), ws);
+    const int st = gather_windows(d.T, d.B, d.F, (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0, (const float*)x, win->start, L.xg, s);
     if (st != FASTGRNN_OK) return st;
-    x = xg;
+    x = L.xg;
+    ws = L.inner;
   }
-  if (h256_shape(d)) return h256_backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s);
-  if (lowrank_shape(d)) return lowrank_backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s);
-  if (densified_shape(d)) return densified_backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s);
-  if (!launch_bwd_w8(d, p, ghs, x, hs, zs, cs, h0, g, ws, s)) return FASTGRNN_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  const family* f = family_of(d);
+  return f ? f->backward(d, p, ghs, x, hs, zs, cs, h0, g, ws, s) : FASTGRNN_ERR_UNSUPPORTED;
 }
 
 int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
                   void* zs, void* cs, void* ws, hipStream_t s, const void* sg_, const void* sc_, const window_src* win) {
+  const family* f = family_of(d);
   if (win) {
     // fastgrnn_hip_forward_windows: nothing saved; fastgrnn_hip_forward_windows_train: the pre-activation through zs
     fastgrnn_desc c = d;
     c.flags &= ~FASTGRNN_FLAG_SAVE_PREACT;
     const bool train = (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
     if (cs || (zs != nullptr) != train || !(train ? train_windows_supported(c) : windows_supported(d))) return FASTGRNN_ERR_UNSUPPORTED;
-    if (train && !h256_shape(d)) {                   // H = 128: the plain forward on a gathered copy of x in the workspace
+    if (train && !f->windows_ws) {                   // H = 128: the plain forward on a gathered copy of x in the workspace
       if (!ws) return FASTGRNN_ERR_WORKSPACE;
-      const int st = gather_windows(d.T, d.B, d.F, (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0, (const float*)x, win->start, (float*)ws, s);
+      const GatherWs L = gather_ws(d, 0, ws);
+      const int st = gather_windows(d.T, d.B, d.F, (d.flags & FASTGRNN_FLAG_BATCH_MAJOR) != 0, (const float*)x, win->start, L.xg, s);
       if (st != FASTGRNN_OK) return st;
-      x = ws;
+      x = L.xg;
       win = nullptr;
     }
   }
@@ -1361,24 +1384,7 @@ int split_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
   const float* sg = reinterpret_cast<const float*>(sg_);
   const float* sc = reinterpret_cast<const float*>(sc_);
   if (sg && (zs || !affine_supported(d))) return FASTGRNN_ERR_UNSUPPORTED;
-  if (h256_shape(d)) return h256_forward(d, p, x, h0, hs, zs, cs, ws, s, sg, sc, win);
-  if (lowrank_shape(d)) return lowrank_forward(d, p, x, h0, hs, zs, cs, ws, s);
-  if (densified_shape(d)) return densified_forward(d, p, x, h0, hs, zs, cs, ws, s);
-  void* pws = nullptr;
-  if (dense_wide_shape(d)) {
-    // P[T*B,H] = X . W^T, the one genuinely dense contraction of the layer (.cu:356 per step), into the buffer the
-    // scan reads it from: z_s (SAVE_PREACT: overwritten by the pre-activation), c_s (overwritten by h_prime), or
-    // the workspace when the caller wants neither
-    pws = zs == nullptr ? ws : ((d.flags & FASTGRNN_FLAG_SAVE_PREACT) ? zs : cs);
-    if (!pws) return FASTGRNN_ERR_WORKSPACE;
-    // (FASTGRNN_FLAG_X_BFT: the [B,F,T] frames are read in place; the rows of P land in the order of hs)
-    const int st = (d.flags & FASTGRNN_FLAG_X_BFT)
-        ? rows_gemm_bft(d.B, d.T, 128, d.F, (const float*)x, (const float*)p.w, (float*)pws, (size_t)row_stride_t(d), (size_t)row_stride_b(d), s)
-        : rows_gemm((size_t)d.T * d.B, 128, d.F, false, x, (const float*)p.w, pws, d.dtype == FASTGRNN_BF16_IO, false, s);
-    if (st != FASTGRNN_OK) return st;
-  }
-  if (!launch_fwd(d, p, x, h0, hs, zs, cs, s, pws, sg, sc, win)) return FASTGRNN_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return f ? f->forward(d, p, x, h0, hs, zs, cs, ws, s, sg, sc, win) : FASTGRNN_ERR_UNSUPPORTED;
 }
 
 }  // namespace fastgrnn

@@ -201,7 +201,7 @@ int train_update(const fastgrnn_update_hyper& h, const fastgrnn_update_seg* segs
     hipLaunchKernelGGL(train_update_k, dim3(cnt), dim3(UPD_THREADS), 0, s, tab, hy, lr, (const long long*)step,
                        (const int*)iht_mode);
   }
-  return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace fastgrnn

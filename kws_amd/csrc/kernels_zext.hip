@@ -150,7 +150,7 @@ ZSaved zsaved(const fastgrnn_desc& d, const fastgrnn_desc& e) {
   S.pre = o; o += align256(TB * Hp * 4);
   S.hs = NONE; S.cs = NONE;
   if (d.H != e.H) { S.hs = o; o += align256(TB * Hp * seq_esz(d)); }
-  if (lowrank_shape(e)) { S.cs = o; o += align256(TB * 32 * 4); }
+  if (family_of(e) == &lowrank_family()) { S.cs = o; o += align256(TB * 32 * 4); }
   S.total = o;
   return S;
 }
@@ -251,7 +251,7 @@ int zext_backward(const fastgrnn_desc& d, const fastgrnn_desc& e, const fastgrnn
   // the padded gradients: into the workspace where their shape differs, else straight into the caller's
   fastgrnn_grads ge = g;
   auto out = [&](void* own, size_t off) -> void* { return off == NONE ? own : at(ws, off); };
-  ge.d_x = g.d_x ? out(g.d_x, L.dx) : nullptr;   // (NULL: split_dx_optional(e), not wanted)
+  ge.d_x = g.d_x ? out(g.d_x, L.dx) : nullptr;   // (NULL: family::dx_optional, not wanted)
   ge.d_h0 = out(g.d_h0, L.dh0);
   ge.d_w = out(g.d_w, L.dw);
   ge.d_w1 = out(g.d_w1, L.dw1);

@@ -58,7 +58,7 @@ SWEEP = PC.SHAPES + [(99, 4096), (99, 64), (31, 37), (3, 1377), (3, 1381), (5, 9
 
 @pytest.mark.parametrize("T,B", SWEEP, ids=lambda v: str(v))
 def test_tn_chunk_rule_matches_the_workspace_the_library_asks_for(lib, T, B):
-    """h256_bwd_layout (kws_amd/csrc/kernels_h256.hip): the slabs depend on B alone, d_pre is (T*B + 16) * 1024 bytes, the
+    """dpre_bwd_ws (kws_amd/csrc/kernels_gemm.hip), the H = 256 backward's layout: the slabs depend on B alone, d_pre is (T*B + 16) * 1024 bytes, the
     TN partials are 2 * nch * SLOT bytes (tn_gemm_big_ws): at fixed B the workspace grows from T = 1 by exactly
     1024 * B * dT + 2 * SLOT * dnch."""
     assert B < (1 << 21)
