@@ -1,5 +1,8 @@
 // Diagnostic harness for the split-precision scan kernels (not part of the product build).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o /tmp/diag_split tools/diag_split.hip && /tmp/diag_split
+// After `make -C kws_amd/csrc` (the scans call into the library's other sources; link their objects):
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-gpu-rdc -c tools/diag_split.hip -o /tmp/diag_split.o
+//   hipcc --offload-arch=gfx950 -o /tmp/diag_split /tmp/diag_split.o $(ls kws_amd/csrc/*.o | grep -v kernels_split.o)
+//   /tmp/diag_split
 #define FASTGRNN_DIAG_STAMPS 1
 #include "../kws_amd/csrc/kernels_split.hip"
 #include <algorithm>
@@ -13,7 +16,8 @@ static float* dev_rand(size_t n, float scale) {
   float* d; (void)hipMalloc(&d, n * 4); (void)hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice);
   return d;
 }
-template <bool PREACT>
+// NODX: the headline step's backward (FASTGRNN_FLAG_NO_INPUT_GRAD: no d_x)
+template <bool PREACT, bool NODX>
 void run_bwd_w8(int T, int B) {
   constexpr int H = 128, F = 32;
   float *x = dev_rand((size_t)T * B * F, 1.f), *h0 = dev_rand((size_t)B * H, 0.f), *w = dev_rand(H * F, 0.17f);
@@ -26,22 +30,24 @@ void run_bwd_w8(int T, int B) {
   std::vector<float> ts;
   for (int rep = 0; rep < 10; ++rep) {
     (void)hipEventRecord(e0);
-    hipLaunchKernelGGL((bwd_scan_split_w8<0, PREACT, false>), dim3((B + 15) / 16), dim3(512), 0, 0, T, B, B, 1, 0, ghs, x, hs, a0, a1,
-                       h0, w, u, bz, bh, zeta, nu, dx, dh0, part);
+    hipLaunchKernelGGL((bwd_scan_split_w8<0, PREACT, false, false, false, false, NODX>), dim3((B + 15) / 16), dim3(512), 0, 0, T, B, B, 1,
+                       0, ghs, x, hs, a0, a1, h0, w, u, bz, bh, zeta, nu, NODX ? (float*)nullptr : dx, dh0, part);
     (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
     float ms; (void)hipEventElapsedTime(&ms, e0, e1);
     if (rep >= 2) ts.push_back(ms);
   }
   std::sort(ts.begin(), ts.end());
-  printf("bwd_scan_split_w8 PREACT=%d: %.1f us (%.2f us/step)\n", (int)PREACT, ts[ts.size() / 2] * 1e3, ts[ts.size() / 2] * 1e3 / T);
+  printf("bwd_scan_split_w8 PREACT=%d NODX=%d: %.1f us (%.2f us/step)\n", (int)PREACT, (int)NODX, ts[ts.size() / 2] * 1e3,
+         ts[ts.size() / 2] * 1e3 / T);
   unsigned long long h[8][8];
   (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_sdiag), sizeof(h));
-  const char* names[5] = {"(glue)", "dB reads + chain + ew_pre", "ew_post + publish", "weight_grads (every other iteration)", "barrier"};
+  const char* names[6] = {"(glue)", "dB read issue + landing", "chain + ew_pre", "ew_post + publish + requests",
+                          "weight_grads (every other iteration)", "barrier"};
   for (int wv = 0; wv < 8; wv += 4) {
     unsigned long long tot = 0;
-    for (int k = 0; k < 5; ++k) tot += h[wv][k];
+    for (int k = 0; k < 6; ++k) tot += h[wv][k];
     printf("   wave %d: %.0f cycles/step:", wv, (double)tot / T);
-    for (int k = 0; k < 5; ++k) printf("  [%s] %.0f", names[k], (double)h[wv][k] / T);
+    for (int k = 0; k < 6; ++k) printf("  [%s] %.0f", names[k], (double)h[wv][k] / T);
     printf("\n");
   }
 }
@@ -112,7 +118,8 @@ int main(int argc, char** argv) {
   run_fwd_w8<2>(99, B);
   run_fwd_w8<0>(99, B);
   run_fwd<1>(99, B);
-  run_bwd_w8<true>(99, B);
-  run_bwd_w8<false>(99, B);
+  run_bwd_w8<true, true>(99, B);
+  run_bwd_w8<true, false>(99, B);
+  run_bwd_w8<false, false>(99, B);
   return 0;
 }
