@@ -35,20 +35,12 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _lib, fastgrnn_cuda
+from . import _lib, _route, fastgrnn_cuda
 from .rnn import NON_LINEARITY, _resolve_device, _sparsify, _sparsify_with_support, gather_windows
 
 _TRAINING_MSG = ("FastGRNNBatchNorm runs in eval mode only (training=False / model.eval()): training-mode BatchNorm "
                  "normalises every frame with the statistics of the whole batch at that frame, which needs a "
                  "grid-wide reduction inside every step of the fused scan")
-
-
-def _affine_on_path2(cell, x, T, B, flags):
-    """The scaled forward of this call (FLAG_PREACT_AFFINE added to ``flags``) is on kernel path 2: the sibling of
-    ``rnn._on_path2`` for the dense BatchNorm cell, whose update nonlinearity is its own."""
-    return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)
-            and fastgrnn_cuda.kernel_path(T, B, x.shape[-1], cell._hidden_size, 0, 0, cell._gate_code,
-                                          cell._update_code, x.dtype, 0, flags | _lib.FLAG_PREACT_AFFINE) == 2)
 
 
 def _bn_affine(bn):
@@ -245,35 +237,23 @@ class FastGRNNBatchNorm(nn.Module):
         input = input.to(dev)
         if input.dtype != cell.W.dtype:
             raise RuntimeError("input dtype %s differs from the parameters' %s" % (input.dtype, cell.W.dtype))
-        bf = self.batch_first is True
-        Bn, Tn = (input.shape[0], input.shape[1]) if bf else (input.shape[1], input.shape[0])
-        H = cell._hidden_size
+        route = _route.route(_route.Signature(
+            _route.AFFINE, input.shape, input.stride(), input.dtype, input.is_cuda, cell._hidden_size, 0, 0,
+            cell._gate_code, cell._update_code, self.batch_first is True, bool(last_state), None))
+        Bn, H = route.dims[1], cell._hidden_size
         if hiddenState is None:
-            h0 = torch.zeros(Bn, H, dtype=input.dtype, device=dev)
+            h0 = _route.zero_state(Bn, H, input.dtype, dev)
         else:
             h0 = hiddenState.to(dev).reshape(Bn, H).contiguous()
-        flags = _lib.FLAG_HS_LAST if last_state else 0
-        # batch_first in place where the kernels index [B,T,.] (kernel path 2), else transposed as BaseRNN does
-        in_place = bf and _affine_on_path2(cell, input, Tn, Bn, flags | _lib.FLAG_BATCH_MAJOR)
-        x = input
-        if in_place:
-            flags |= _lib.FLAG_BATCH_MAJOR
-        elif bf:
-            x = input.transpose(0, 1)
-        # the trainer's permuted view of the loader's [B,F,T] batch (trainClassifier.py:299): its base as it is where the
-        # scaled forward takes FLAG_X_BFT (the layers whose frame product is a GEMM of its own), else a copy
-        if (not bf and x.dim() == 3 and not x.is_contiguous() and x.permute(1, 2, 0).is_contiguous()
-                and _affine_on_path2(cell, x, Tn, Bn, flags | _lib.FLAG_X_BFT)):
-            return _BatchNormInference.apply(cell, x.permute(1, 2, 0), h0, flags | _lib.FLAG_X_BFT, *cell._fold_tensors())
-        x = x.contiguous()
-        if last_state and not _affine_on_path2(cell, x, Tn, Bn, flags):
-            flags &= ~_lib.FLAG_HS_LAST               # (kernel path 0 writes every state; the last one is taken)
-            hs = _BatchNormInference.apply(cell, x, h0, flags, *cell._fold_tensors())
-            return hs[:, -1] if (flags & _lib.FLAG_BATCH_MAJOR) else hs[-1]
-        hs = _BatchNormInference.apply(cell, x, h0, flags, *cell._fold_tensors())
-        if bf and not in_place and not last_state:
-            hs = hs.transpose(0, 1)
-        return hs
+        # batch_first in place where the kernels index [B,T,.] (kernel path 2), else transposed as BaseRNN does; the
+        # trainer's view of the loader's [B,F,T] batch (trainClassifier.py:299) as its base under FLAG_X_BFT, else a copy
+        if route.present == _route.TRANSPOSE_COPY:
+            input = input.transpose(0, 1)
+        x = input.permute(1, 2, 0) if route.present == _route.BFT_BASE else input.contiguous()
+        hs = _BatchNormInference.apply(cell, x, h0, route.flags, *cell._fold_tensors())
+        if route.post == _route.LAST_STEP:
+            return _route.last_step(hs, route.flags)
+        return hs.transpose(0, 1) if route.post == _route.TRANSPOSE_BACK else hs
 
     @torch.no_grad()
     def forward_windows(self, pool, starts, T, hiddenState=None, last_state=False, check=True, training=False):
@@ -291,7 +271,7 @@ class FastGRNNBatchNorm(nn.Module):
         if pool.dtype != cell.W.dtype:
             raise RuntimeError("pool dtype %s differs from the parameters' %s" % (pool.dtype, cell.W.dtype))
         B, H, T = starts.numel(), cell._hidden_size, int(T)
-        h0 = torch.zeros(B, H, dtype=pool.dtype, device=dev) if hiddenState is None else \
+        h0 = _route.zero_state(B, H, pool.dtype, dev) if hiddenState is None else \
             hiddenState.to(dev).reshape(B, H).contiguous()
         bm = self.batch_first is True
         flags = (_lib.FLAG_BATCH_MAJOR if bm else 0) | (_lib.FLAG_HS_LAST if last_state else 0) | _lib.FLAG_PREACT_AFFINE
@@ -301,6 +281,5 @@ class FastGRNNBatchNorm(nn.Module):
             return fastgrnn_cuda.forward_windows(pool.contiguous(), starts, T, w, u, bg, bu, cell.zeta, cell.nu, h0,
                                                  cell._gate_code, sg, sc, batch_major=bm, last_state=last_state,
                                                  update_non_linearity=cell._update_code, check=check)
-        windows = gather_windows(pool, starts, T, check)                       # [B,T,F]
-        return FastGRNNBatchNorm.forward(self, windows if bm else windows.transpose(0, 1).contiguous(),
-                                         hiddenState=h0, training=False, last_state=last_state)
+        return FastGRNNBatchNorm.forward(self, gather_windows(pool, starts, T, check, bm), hiddenState=h0,
+                                         training=False, last_state=last_state)

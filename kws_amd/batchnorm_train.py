@@ -25,7 +25,7 @@ import warnings
 import torch
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, _route
 from .batchnorm import FastGRNNBatchNorm
 from .fastgrnn_cuda import _call, _params, _pool_plan, _ptr
 
@@ -62,10 +62,7 @@ class _BatchNormTrain(Function):
     @staticmethod
     def forward(ctx, cell, x, h0, batch_major, W, U, bias_gate, bias_update, zeta, nu, gw, bw, gu, bu, gg, bg, gc, bc):
         lib = _lib.load()
-        if batch_major:
-            B, T, F = x.shape
-        else:
-            T, B, F = x.shape
+        T, B, F = _route.seq_dims(x.shape, batch_major)
         H = cell._hidden_size
         plan = _plan(T, B, F, H, cell._gate_code, batch_major)
         dev = x.device
@@ -128,7 +125,7 @@ class FastGRNNBatchNormCUDA(FastGRNNBatchNorm):
         bns = (cell.bn_w, cell.bn_u, cell.bn_gate, cell.bn_update)
         if not all(bn.training and bn.affine and bn.track_running_stats for bn in bns):
             return False
-        T, F = (x.shape[1], x.shape[2]) if batch_major else (x.shape[0], x.shape[2])
+        T, _, F = _route.seq_dims(x.shape, batch_major)
         return bn_train_supported(T, B, F, cell._hidden_size, cell._gate_code, x.dtype, batch_major) and \
             cell.W.dtype == torch.float32
 
@@ -154,7 +151,7 @@ class FastGRNNBatchNormCUDA(FastGRNNBatchNorm):
             raise ValueError("FastGRNNBatchNormCUDA: training-mode BatchNorm needs more than 1 utterance per batch "
                              "(got B=%d)" % B)
         H = cell._hidden_size
-        h0 = torch.zeros(B, H, dtype=input.dtype, device=dev) if hiddenState is None else \
+        h0 = _route.zero_state(B, H, input.dtype, dev) if hiddenState is None else \
             hiddenState.to(dev, input.dtype).reshape(B, H).contiguous()
         x = input.contiguous()
         if self._fused(x, bf, B):
@@ -164,9 +161,7 @@ class FastGRNNBatchNormCUDA(FastGRNNBatchNorm):
                                        cell.bn_update.bias)
         else:
             hs = self._torch_ops(x, h0, bf)
-        if last_state:
-            return hs[:, -1] if bf else hs[-1]
-        return hs
+        return _route.last_step(hs, _lib.FLAG_BATCH_MAJOR if bf else 0) if last_state else hs
 
     def forward_windows(self, pool, starts, T, hiddenState=None, last_state=False, check=True, training=False):
         """``FastGRNNBatchNorm.forward_windows`` (eval mode only), folding again on every call as ``forward`` does."""

@@ -244,7 +244,14 @@ def zero_extend_plan(T, B, F, H, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dty
 # signature is re-checked (device, contiguity), and the checks that are pure functions of the signature are skipped --
 # half of the host time of a step (tools/host_overhead.py: the host's enqueue time is within reach of the GPU's).
 _seen = {}
+_SEEN_MAX = 1024                 # (the bound of _plan: a loader with variable T or a ragged last batch keeps adding)
 _use_seen = True                 # (tools/host_overhead.py switches it off for its A/B)
+
+
+def _remember(sig, ent):
+    if len(_seen) >= _SEEN_MAX:  # (cleared when full, as the default states of _route are)
+        _seen.clear()
+    _seen[sig] = ent
 
 
 def _all_dense_on(dev, *ts):
@@ -341,7 +348,7 @@ def _forward_impl(input, w, u, bias_gate, bias_update, zeta, nu, h0, gate_nl, w1
     # include/fastgrnn_hip.h, forward workspace)
     nbytes = 0 if (plan.forward_ws_optional and (want_gates or preact)) else plan.ws[0]
     tail = (oshape, (B, H) if hs_last else oshape, rank_space_shape, nbytes, zsaved)
-    _seen[sig] = (plan, w_lr, u_lr, tail)
+    _remember(sig, (plan, w_lr, u_lr, tail))
     return _launch_forward(lib, plan, tail, unrolled, preact, want_gates, input, h0, params)
 
 
@@ -469,7 +476,7 @@ def _backward_impl(grad_h, input, hs_or_old_h, zeta, nu, w, u, z, h_prime, h0, w
              ([tuple(u1.shape), tuple(u2.shape)] if u_lr else [(H, H)]) + [(1, H), (1, H), (1, 1), (1, 1)]
     sizes = [a * b for a, b in shapes]
     ent = (w_lr, u_lr, shapes, sizes, plan.dx_optional, B, H)
-    _seen[sig] = (plan, rank_space is not None, ent)
+    _remember(sig, (plan, rank_space is not None, ent))
     return _launch_backward(lib, plan, ent, unrolled, preact, grad_h, input, hs_or_old_h, z, h_prime,
                             rank_space, h0, w, u, w1, w2, u1, u2,
                             bias_gate if preact else zeta, bias_update if preact else zeta, zeta, nu, need_dx)

@@ -369,8 +369,8 @@ class RNNClassifierModel(nn.Module):
             raise RuntimeError("loss() is the Linear + log_softmax + NLLLoss tail (linear=True, apply_softmax=True)")
         window = int(window)
         if self._batchnorm:
-            x = gather_windows(pool.to(self.rnn_list[0].device), starts.to(self.rnn_list[0].device), window)
-            h_last = self._last_state(x if self.batch_first else x.transpose(0, 1).contiguous())
+            h_last = self._last_state(gather_windows(pool.to(self.rnn_list[0].device), starts.to(self.rnn_list[0].device),
+                                                     window, batch_first=self.batch_first))
         else:
             if pool.requires_grad:
                 raise ValueError("loss_windows: the pool must not require grad (unroll_windows)")

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _lib, fastgrnn_cuda, utils
+from . import _lib, _route, fastgrnn_cuda, utils
 
 NON_LINEARITY = {"sigmoid": 0, "relu": 1, "tanh": 2}   # rnn.py:478,751
 
@@ -60,33 +60,14 @@ class FastGRNNFunction(Function):
         return _as_autograd_grads(outputs, ctx.needs_input_grad)
 
 
-def _is_bft_view(input):
-    """``input`` is what the trainer hands over: permute(2,0,1) of the loader's [B,F,T] batch (trainClassifier.py:204,
-    299), a [T,B,F] view whose base the kernels can take under FLAG_X_BFT."""
-    return (input.is_cuda and input.dim() == 3 and not input.is_contiguous()
-            and input.permute(1, 2, 0).is_contiguous())
-
-
-def _on_path2(input, T, B, F, H, w1, u1, gate_non_linearity, direction, flags):
-    """This call is on kernel path 2 (the split-precision scans): a GPU tensor of a dtype they take and the library's
-    answer for the descriptor.  ``w1`` / ``u1``: the cell's W1 / U1, whose leading sizes are the ranks (empty = dense)."""
-    return (input.is_cuda and input.dtype in (torch.float32, torch.bfloat16)
-            and fastgrnn_cuda.kernel_path(T, B, F, H, w1.shape[0] if w1.numel() else 0,
-                                          u1.shape[0] if u1.numel() else 0, gate_non_linearity, 2, input.dtype,
-                                          direction, flags) == 2)
-
-
-def gather_windows(pool, starts, T, check=True):
+def gather_windows(pool, starts, T, check=True, batch_first=True):
     """``[B,T,F]``: window ``b`` = rows ``starts[b] .. starts[b]+T-1`` of ``pool:[R,F]``, materialised (what
-    ``forward_windows`` avoids where the windowed scans hold the cell)."""
+    ``forward_windows`` avoids where the windowed scans hold the cell).  ``batch_first=False``: its ``[T,B,F]`` copy,
+    what a module that is not ``batch_first`` takes."""
     T = int(T)
     fastgrnn_cuda.check_starts_range(starts if check else starts[:0], pool.shape[0], T)
-    return pool[starts.long()[:, None] + torch.arange(T, device=pool.device)]
-
-
-_unroll_decisions = {}
-_zero_states = {}        # (B, H, dtype, device) -> the default h0
-_inference_ok = {}       # call signature -> "the hs-only forward is on kernel path 2"
+    windows = pool[starts.long()[:, None] + torch.arange(T, device=pool.device)]
+    return windows if batch_first else windows.transpose(0, 1).contiguous()
 
 
 class FastGRNNUnrollFunction(Function):
@@ -97,88 +78,51 @@ class FastGRNNUnrollFunction(Function):
 
     @staticmethod
     def forward(ctx, input, bias_gate, bias_update, zeta, nu, old_h, w, u, w1, w2, u1, u2, gate_non_linearity,
-                batch_major=False, last_state=False):
+                batch_major=False, last_state=False, route=None):
         """``batch_major`` (not in the reference signature): ``input`` / the result are [B,T,.] and the
         kernels index them in place (FLAG_BATCH_MAJOR) instead of working on transposed copies.
         ``last_state``: return h_T [B,H] alone -- what the classifier head reads
         (model.py:227) -- so that the backward receives a [B,H] gradient instead of the dense, all-but-one-
-        step-zero [T,B,H] tensor autograd builds for ``hs[-1]`` (FLAG_GRAD_LAST: not written, not read)."""
+        step-zero [T,B,H] tensor autograd builds for ``hs[-1]`` (FLAG_GRAD_LAST: not written, not read).
+        ``route``: the ``_route.Route`` of this call where the module has looked it up already."""
         old_h = old_h.contiguous()
-        # Which contract / layout flags this call runs under is a pure function of its shapes, dtype and strides:
-        # decided once per signature (three descriptor look-ups), then one dictionary hit per step.
-        key = (input.shape, input.stride(), input.dtype, input.is_cuda, old_h.shape, w1.shape, u1.shape,
-               gate_non_linearity, batch_major, last_state)
-        dec = _unroll_decisions.get(key)
-        if dec is None:
-            if batch_major:
-                B, T, F = input.shape
-            else:
-                T, B, F = input.shape
-            H = old_h.shape[1]
-            # The trainer hands over permute(2,0,1) of the loader's [B,F,T] batch (trainClassifier.py:204,299), a
-            # [T,B,F] VIEW; the reference copies it here with .contiguous().  Where the kernels can read [B,F,T]
-            # in place (FLAG_X_BFT) the view's base is passed instead and d_input comes back as the same view.
-            call = (input, T, B, F, H, w1, u1, gate_non_linearity)
-            x_bft = (not batch_major and _is_bft_view(input)
-                     and _on_path2(*call, 1, _lib.FLAG_SAVE_PREACT | _lib.FLAG_X_BFT))
-            # (FLAG_ZERO_EXTEND: hidden sizes up to 256 that no kernel-path-2 shape covers run zero-padded to one)
-            preact = _on_path2(*call, 1, _lib.FLAG_SAVE_PREACT | _lib.FLAG_ZERO_EXTEND)
-            flags = (_lib.FLAG_SAVE_PREACT | _lib.FLAG_ZERO_EXTEND) if preact else 0
-            if batch_major:
-                flags |= _lib.FLAG_BATCH_MAJOR
-            if x_bft:
-                flags |= _lib.FLAG_X_BFT
-            grad_last = bool(last_state and _on_path2(*call, 1, flags | _lib.FLAG_GRAD_LAST))
-            dec = _unroll_decisions[key] = (x_bft, preact, flags, grad_last)
-        x_bft, preact, flags, grad_last = dec
-        input = input.permute(1, 2, 0) if x_bft else input.contiguous()
-        ctx.flags = flags
+        if route is None:
+            route = _route.route(_route.Signature(
+                _route.PLAIN, input.shape, input.stride(), input.dtype, input.is_cuda, old_h.shape[1],
+                *_route.ranks(w1, u1), gate_non_linearity, 2, bool(batch_major), bool(last_state), _route.APPLY))
+        # (the trainer's [T,B,F] view of a [B,F,T] batch: the reference copies it here; under FLAG_X_BFT its base goes)
+        input = input.permute(1, 2, 0) if route.present == _route.BFT_BASE else input.contiguous()
         outputs = fastgrnn_cuda.forward_unroll(input, w, u, bias_gate, bias_update, zeta, nu, old_h,
-                                               gate_non_linearity, w1, w2, u1, u2, flags=flags)
+                                               gate_non_linearity, w1, w2, u1, u2, flags=route.flags)
         hidden_states = outputs[0]
-        if preact:
-            # outputs[2] (factorised operands only): the rank-space vector [U1.h | W1.x] per step
-            aux2 = outputs[2] if len(outputs) > 2 else outputs[1]
-            variables = [input, hidden_states, zeta, nu, w, u, outputs[1], aux2, bias_gate, bias_update,
-                         old_h, w1, w2, u1, u2]
-        else:
-            variables = [input, hidden_states, zeta, nu, w, u] + outputs[1:] + [old_h, w1, w2, u1, u2]
-        ctx.save_for_backward(*variables)
-        ctx.gate_non_linearity = gate_non_linearity
-        ctx.preact = preact
-        ctx.last_state = bool(last_state)
-        if last_state:
-            ctx.grad_last = grad_last
-            return (hidden_states[:, -1] if batch_major else hidden_states[-1]).clone()
+        # saved beside hs: (pre-activation, the factorised cells' rank-space vector [U1.h | W1.x]) + biases, or (z_s, h_prime_s)
+        biases = [bias_gate, bias_update] if route.saved == _route.PREACT else []
+        ctx.save_for_backward(input, hidden_states, zeta, nu, w, u, outputs[1], outputs[-1], old_h, w1, w2, u1, u2,
+                              *biases)
+        ctx.gate_non_linearity, ctx.route = gate_non_linearity, route
+        if route.post == _route.LAST_STEP:
+            return _route.last_step(hidden_states, route.flags).clone()
         return hidden_states
 
     @staticmethod
     def backward(ctx, grad_h):
-        flags = ctx.flags
-        if ctx.last_state:
-            if ctx.grad_last:
+        route, flags = ctx.route, ctx.route.flags
+        input, hidden_states, zeta, nu, w, u, z_s, aux2, old_h, w1, w2, u1, u2, *biases = ctx.saved_tensors
+        if route.post == _route.LAST_STEP:
+            if route.grad_last:
                 flags |= _lib.FLAG_GRAD_LAST            # the kernel takes the [B,H] gradient as it is
             else:                                        # other kernel paths: the dense form autograd would build
-                hs_saved = ctx.saved_tensors[1]
-                dense = torch.zeros_like(hs_saved)
-                (dense[:, -1] if flags & _lib.FLAG_BATCH_MAJOR else dense[-1]).copy_(grad_h)
+                dense = torch.zeros_like(hidden_states)
+                _route.last_step(dense, flags).copy_(grad_h)
                 grad_h = dense
-        if ctx.preact:
-            (input, hidden_states, zeta, nu, w, u, pre_s, aux2, bias_gate, bias_update, old_h,
-             w1, w2, u1, u2) = ctx.saved_tensors
-            outputs = fastgrnn_cuda.backward_unroll(grad_h.contiguous(), input, hidden_states, zeta, nu, w, u,
-                                                    pre_s, aux2, old_h, w1, w2, u1, u2, ctx.gate_non_linearity,
-                                                    flags=flags, bias_gate=bias_gate,
-                                                    bias_update=bias_update, need_dx=ctx.needs_input_grad[0])
-        else:
-            (input, hidden_states, zeta, nu, w, u, z_s, h_prime_s, old_h, w1, w2, u1, u2) = ctx.saved_tensors
-            outputs = fastgrnn_cuda.backward_unroll(grad_h.contiguous(), input, hidden_states, zeta, nu, w, u,
-                                                    z_s, h_prime_s, old_h, w1, w2, u1, u2,
-                                                    ctx.gate_non_linearity, flags=flags,
-                                                    need_dx=ctx.needs_input_grad[0])
-        if ctx.flags & _lib.FLAG_X_BFT:                 # d_input was produced as [B,F,T]: hand back the [T,B,F] view
+        bias_gate, bias_update = biases or (None, None)
+        outputs = fastgrnn_cuda.backward_unroll(grad_h.contiguous(), input, hidden_states, zeta, nu, w, u, z_s, aux2,
+                                                old_h, w1, w2, u1, u2, ctx.gate_non_linearity, flags=flags,
+                                                bias_gate=bias_gate, bias_update=bias_update,
+                                                need_dx=ctx.needs_input_grad[0])
+        if flags & _lib.FLAG_X_BFT:                     # d_input was produced as [B,F,T]: hand back the [T,B,F] view
             outputs = [outputs[0].permute(2, 0, 1) if outputs[0].numel() else outputs[0]] + list(outputs[1:])
-        return _as_autograd_grads(outputs, ctx.needs_input_grad) + (None, None)
+        return _as_autograd_grads(outputs, ctx.needs_input_grad) + (None, None, None)
 
 
 class FastGRNNWindowsFunction(Function):
@@ -426,95 +370,29 @@ class FastGRNNCUDA(nn.Module):
         hidden-state sequence is not written at all (FLAG_HS_LAST)."""
         if not input.is_cuda:
             input = input.to(self.device)
-        # batch_first: the reference transposes to [T,B,F] and back (rnn.py:812-813,823-825); where the
-        # kernels can index [B,T,.] in place (FLAG_BATCH_MAJOR) no copy is made at all
-        in_place = False
-        if self.batch_first is True:
-            Bn, Tn, Fn = input.shape
-            in_place = self._on_path2(input, Tn, Bn, Fn, 1,
-                                      _lib.FLAG_SAVE_PREACT | _lib.FLAG_BATCH_MAJOR | _lib.FLAG_ZERO_EXTEND)
-            if not in_place:
-                input = input.transpose(0, 1).contiguous()
-        nbatch = input.shape[0] if in_place else input.shape[1]
+        route = _route.route(_route.Signature(
+            _route.PLAIN, input.shape, input.stride(), input.dtype, input.is_cuda, self._hidden_size,
+            *_route.ranks(self.W1, self.U1), self._gate_non_linearity, 2, self.batch_first is True, bool(last_state),
+            _route.grad_mode()))
+        if route.present == _route.TRANSPOSE_COPY:
+            input = input.transpose(0, 1).contiguous()
         if hiddenState is None:
             # bf16 sequences (BASELINE config "bf16 with fp32 master grads") keep an fp32 state and parameters
-            hdt = torch.float32 if input.dtype == torch.bfloat16 else input.dtype
-            # (the default state is read-only to every kernel and never handed out: one tensor per shape instead of a
-            # fill launch per call)
-            zkey = (nbatch, self._hidden_size, hdt, input.device)
-            hiddenState = None if torch.is_inference_mode_enabled() else _zero_states.get(zkey)
-            if hiddenState is None:
-                hiddenState = torch.zeros([nbatch, self._hidden_size], dtype=hdt, device=input.device)
-                if not torch.is_inference_mode_enabled():   # (an inference tensor could not be saved for a backward later)
-                    if len(_zero_states) >= 16:
-                        _zero_states.clear()
-                    _zero_states[zkey] = hiddenState
+            hiddenState = _route.zero_state(route.dims[1], self._hidden_size, fastgrnn_cuda._param_dtype(input.dtype),
+                                            input.device)
         if not hiddenState.is_cuda:
             hiddenState = hiddenState.to(self.device)
-        if last_state and not torch.is_grad_enabled():
-            out = self._last_state_inference(input, hiddenState, in_place)
-            if out is not None:
-                return out
-        if not last_state and not torch.is_grad_enabled():
-            out = self._inference_forward(input, hiddenState, in_place)
-            if out is not None:
-                return out.transpose(0, 1) if (self.batch_first is True and not in_place) else out
-        result = FastGRNNUnrollFunction.apply(input, self.bias_gate, self.bias_update, self.zeta, self.nu,
-                                              hiddenState, self.W, self.U, self.W1, self.W2, self.U1, self.U2,
-                                              self._gate_non_linearity, in_place, bool(last_state))
-        if self.batch_first is True and not in_place and not last_state:
-            return result.transpose(0, 1)
-        return result
-
-    def _on_path2(self, input, T, B, F, direction, flags):
-        return _on_path2(input, T, B, F, self._hidden_size, self.W1, self.U1, self._gate_non_linearity, direction, flags)
-
-    def _inference_forward(self, input, hiddenState, batch_major):
-        """hs alone when nothing will be differentiated (torch.no_grad()): no tensor is saved for a backward, so the
-        scan writes one [T,B,H] tensor instead of two.  None where the kernels have no such variant (the caller then
-        goes through the autograd function as before)."""
-        # the trainer's permuted view of a [B,F,T] batch (evaluate(), trainClassifier.py:299): its base is passed under
-        # FLAG_X_BFT where the kernels take it (not beside FLAG_ZERO_EXTEND: such a view goes the autograd function's way)
-        bft = not batch_major and _is_bft_view(input)
-        if not (input.is_cuda and (input.is_contiguous() or bft) and input.dtype in (torch.float32, torch.bfloat16)):
-            return None
-        key = (input.shape, input.dtype, batch_major, self._hidden_size, self.W1.shape, self.U1.shape,
-               self._gate_non_linearity, input.device.index, bft)
-        ok = _inference_ok.get(key)
-        flags = _lib.FLAG_X_BFT if bft else (_lib.FLAG_ZERO_EXTEND | (_lib.FLAG_BATCH_MAJOR if batch_major else 0))
-        if ok is None:
-            if batch_major:
-                Bn, Tn, Fn = input.shape
-            else:
-                Tn, Bn, Fn = input.shape
-            ok = _inference_ok[key] = self._on_path2(input, Tn, Bn, Fn, 0, flags)
-        if not ok:
-            return None
-        if bft:
-            input = input.permute(1, 2, 0)
-        return fastgrnn_cuda.forward_unroll(input, self.W, self.U, self.bias_gate, self.bias_update, self.zeta, self.nu,
-                                            hiddenState.contiguous(), self._gate_non_linearity, self.W1, self.W2,
-                                            self.U1, self.U2, want_gates=False, flags=flags)[0]
-
-    def _last_state_inference(self, input, hiddenState, batch_major):
-        """h_T without writing hs[T,B,H] (FLAG_HS_LAST); None where the kernels cannot (other shapes / paths)."""
-        if batch_major:
-            Bn, Tn, Fn = input.shape
+        if route.saved is None:                          # nothing will be differentiated: hs, or h_T, alone
+            input = input.permute(1, 2, 0) if route.present == _route.BFT_BASE else input.contiguous()
+            result = fastgrnn_cuda.forward_unroll(input, self.W, self.U, self.bias_gate, self.bias_update, self.zeta,
+                                                  self.nu, hiddenState.contiguous(), self._gate_non_linearity, self.W1,
+                                                  self.W2, self.U1, self.U2, want_gates=False, flags=route.flags)[0]
         else:
-            Tn, Bn, Fn = input.shape
-        flags = _lib.FLAG_HS_LAST | _lib.FLAG_ZERO_EXTEND | (_lib.FLAG_BATCH_MAJOR if batch_major else 0)
-        if (not batch_major and _is_bft_view(input)
-                and self._on_path2(input, Tn, Bn, Fn, 0, _lib.FLAG_HS_LAST | _lib.FLAG_X_BFT)):
-            # the trainer's permuted view: the [B,F,T] base as it is (a view on a zero-extended shape is copied below)
-            return fastgrnn_cuda.forward_unroll(input.permute(1, 2, 0), self.W, self.U, self.bias_gate,
-                                                self.bias_update, self.zeta, self.nu, hiddenState.contiguous(),
-                                                self._gate_non_linearity, self.W1, self.W2, self.U1, self.U2,
-                                                want_gates=False, flags=_lib.FLAG_HS_LAST | _lib.FLAG_X_BFT)[0]
-        if not self._on_path2(input, Tn, Bn, Fn, 0, flags):
-            return None
-        return fastgrnn_cuda.forward_unroll(input.contiguous(), self.W, self.U, self.bias_gate, self.bias_update,
-                                            self.zeta, self.nu, hiddenState.contiguous(), self._gate_non_linearity,
-                                            self.W1, self.W2, self.U1, self.U2, want_gates=False, flags=flags)[0]
+            result = FastGRNNUnrollFunction.apply(input, self.bias_gate, self.bias_update, self.zeta, self.nu,
+                                                  hiddenState, self.W, self.U, self.W1, self.W2, self.U1, self.U2,
+                                                  self._gate_non_linearity, bool(route.flags & _lib.FLAG_BATCH_MAJOR),
+                                                  bool(last_state), route)
+        return result.transpose(0, 1) if route.post == _route.TRANSPOSE_BACK else result
 
     @torch.no_grad()
     def forward_windows(self, pool, starts, T, hiddenState=None, last_state=False, check=True):
@@ -527,19 +405,16 @@ class FastGRNNCUDA(nn.Module):
         pool = pool.to(self.device) if not pool.is_cuda else pool
         starts = starts.to(pool.device)
         B, H, T = starts.numel(), self._hidden_size, int(T)
-        h0 = torch.zeros([B, H], dtype=fastgrnn_cuda._param_dtype(pool.dtype), device=pool.device) \
-            if hiddenState is None else hiddenState.to(pool.device).contiguous()
+        h0 = _route.zero_state(B, H, fastgrnn_cuda._param_dtype(pool.dtype), pool.device) if hiddenState is None \
+            else hiddenState.to(pool.device).contiguous()
         bm = self.batch_first is True
         flags = (_lib.FLAG_BATCH_MAJOR if bm else 0) | (_lib.FLAG_HS_LAST if last_state else 0)
-        if pool.dim() == 2 and fastgrnn_cuda.windows_supported(
-                T, B, pool.shape[1], H, self.W1.shape[0] if self.W1.numel() else 0,
-                self.U1.shape[0] if self.U1.numel() else 0, self._gate_non_linearity, 2, pool.dtype, flags):
+        if pool.dim() == 2 and fastgrnn_cuda.windows_supported(T, B, pool.shape[1], H, *_route.ranks(self.W1, self.U1),
+                                                               self._gate_non_linearity, 2, pool.dtype, flags):
             return fastgrnn_cuda.forward_windows(pool.contiguous(), starts, T, self.W, self.U, self.bias_gate,
                                                  self.bias_update, self.zeta, self.nu, h0, self._gate_non_linearity,
                                                  batch_major=bm, last_state=last_state, check=check)
-        windows = gather_windows(pool, starts, T, check)                       # [B,T,F]
-        return self.forward(windows if bm else windows.transpose(0, 1).contiguous(), hiddenState=h0,
-                            last_state=last_state)
+        return self.forward(gather_windows(pool, starts, T, check, bm), hiddenState=h0, last_state=last_state)
 
     def unroll_windows(self, pool, starts, T, hiddenState=None, last_state=False, check=True):
         """Training on windows of a shared frame pool (not in the reference): utterance ``b`` is the ``T`` consecutive
@@ -560,16 +435,12 @@ class FastGRNNCUDA(nn.Module):
         bm = self.batch_first is True
         flags = (_lib.FLAG_BATCH_MAJOR if bm else 0) | (_lib.FLAG_GRAD_LAST if last_state else 0)
         if pool.is_cuda and pool.dim() == 2 and fastgrnn_cuda.train_windows_supported(
-                T, B, pool.shape[1], H, self.W1.shape[0] if self.W1.numel() else 0,
-                self.U1.shape[0] if self.U1.numel() else 0, self._gate_non_linearity, 2, pool.dtype, flags):
-            h0 = torch.zeros([B, H], dtype=pool.dtype, device=pool.device) if hiddenState is None \
-                else hiddenState.to(pool.device)
+                T, B, pool.shape[1], H, *_route.ranks(self.W1, self.U1), self._gate_non_linearity, 2, pool.dtype, flags):
+            h0 = _route.zero_state(B, H, pool.dtype, pool.device) if hiddenState is None else hiddenState.to(pool.device)
             return FastGRNNWindowsFunction.apply(pool.contiguous(), starts, T, self.bias_gate, self.bias_update,
                                                  self.zeta, self.nu, h0, self.W, self.U, self._gate_non_linearity,
                                                  bm, bool(last_state), bool(check))
-        windows = gather_windows(pool, starts, T, check)                       # [B,T,F]
-        return self.forward(windows if bm else windows.transpose(0, 1).contiguous(), hiddenState=hiddenState,
-                            last_state=last_state)
+        return self.forward(gather_windows(pool, starts, T, check, bm), hiddenState=hiddenState, last_state=last_state)
 
     def getVars(self):
         return _get_vars(self)

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from kws_amd import FastGRNNCUDA, GraphedStep, RNNClassifierModel, _lib, fastgrnn_cuda
-    from kws_amd import rnn as _rnn
+    from kws_amd import _route
 DEV = "cuda:0"
 SP, BM, GL, HL, ZE = 4, 16, 256, 512, 4096
 GATE = {"sigmoid": 0, "relu": 1, "tanh": 2, "quantTanh": 3, "quantSigm": 4, "quantSigm4": 5}
@@ -457,8 +457,13 @@ def test_inference_cache_key_tells_h128_from_h100():
         with torch.no_grad():
             outs[H] = (m, m(x))
         assert outs[H][1].shape == (T, B, H)
-    keys = [k for k in _rnn._inference_ok if k[0] == x.shape]
-    assert len({k[3] for k in keys} & {100, 128}) == 2 and all(_rnn._inference_ok[k] for k in keys)
+    sigs = [_route.Signature(_route.PLAIN, x.shape, x.stride(), x.dtype, True, H, 0, 0, 0, 2, False, False, _route.NO_GRAD)
+            for H in (128, 100)]
+    hits = _route.route.cache_info().hits
+    routes = [_route.route(s) for s in sigs]          # (both were entered by the calls above: two hits, two entries)
+    assert _route.route.cache_info().hits == hits + 2 and sigs[0] != sigs[1]
+    assert all(r.saved is None and r.flags & ZE and r.post == _route.AS_IS for r in routes)
+    assert [fastgrnn_cuda.kernel_path(T, B, F, H, flags=r.flags) for H, r in zip((128, 100), routes)] == [2, 2]
     for H, (m, hs) in outs.items():        # each equals its own autograd forward
         assert (hs - m(x).detach()).abs().max() <= 1e-6, H
 

@@ -39,7 +39,7 @@ def gpu_time(fn, iters, warmup=2):
 
 
 def make_step(F, H, dt, B, T, dev, plain=False):
-    from kws_amd import FastGRNNCUDA, rnn
+    from kws_amd import FastGRNNCUDA, _route, rnn
     torch.manual_seed(0)
     m = FastGRNNCUDA(F, H, device=dev)
     x = torch.randn(T, B, F, device=dev).to(dt)
@@ -59,12 +59,12 @@ def make_step(F, H, dt, B, T, dev, plain=False):
         def step():
             saved = rnn._lib.FLAG_ZERO_EXTEND
             rnn._lib.FLAG_ZERO_EXTEND = 0
-            rnn._unroll_decisions.clear()
+            _route.route.cache_clear()
             try:
                 key_step()
             finally:
                 rnn._lib.FLAG_ZERO_EXTEND = saved
-                rnn._unroll_decisions.clear()
+                _route.route.cache_clear()
     return step
 
 
