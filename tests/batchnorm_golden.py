@@ -8,6 +8,7 @@ import torch
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "batchnorm")
 HIDDEN = [256, 128, 128]
 CLASSES = 12
+DEV = torch.device("cuda:0")
 
 
 def load(name):
@@ -86,3 +87,49 @@ def model_oracle(sd, x, gate="sigmoid"):
         rin = hs
     logits = rin[-1] @ sd["hidden2keyword.weight"].double().t() + sd["hidden2keyword.bias"].double()
     return hT, torch.log_softmax(logits, dim=1)
+
+
+# ---- random eval-mode cells of the GPU tests and their scans in torch ------------------------------------------------
+
+def random_bn(F, H, gate, seed):
+    """A cell with hostile statistics: negative gammas, running variances at 0 (a = gamma / sqrt(eps)), and bn_u
+    scales spanning 10^4 within every 16 consecutive units."""
+    from kws_amd import FastGRNNBatchNorm
+    torch.manual_seed(seed)
+    m = FastGRNNBatchNorm(F, H, gate_nonlinearity=gate, device=DEV)
+    with torch.no_grad():
+        m.cell.W.mul_(0.5 / F ** 0.5 / 0.1)
+        m.cell.U.mul_((0.3 if gate == "sigmoid" else 0.05) / H ** 0.5 / 0.1)
+        m.cell.zeta.fill_(0.8); m.cell.nu.fill_(-1.5)
+        m.cell.bias_gate.normal_(0, 0.5); m.cell.bias_update.normal_(0, 0.5)
+        for bn in (m.cell.bn_w, m.cell.bn_u, m.cell.bn_gate, m.cell.bn_update):
+            bn.weight.copy_(torch.randn(H, device=DEV)); bn.bias.normal_(0, 0.3)
+            bn.running_mean.normal_(0, 0.3); bn.running_var.uniform_(0.5, 2.0)
+            bn.running_var[::11] = 0.0
+        j = torch.arange(H, device=DEV) % 16
+        span = 10.0 ** (4.0 * j / 15.0 - 2.0)                    # 1e-2 .. 1e2 inside every 16 units
+        m.cell.bn_u.running_var.fill_(1.0 - 1e-5)
+        m.cell.bn_u.weight.copy_(span * torch.where(j % 3 == 0, -1.0, 1.0))
+        if gate != "sigmoid":
+            m.cell.bn_u.weight.mul_(0.1)
+        if gate == "relu":        # an unbounded gate (h grows like the product of the z's): keep z mostly below 1
+            m.cell.bn_w.running_var.uniform_(0.5, 2.0)
+            m.cell.bn_gate.running_var.uniform_(0.5, 2.0)
+            m.cell.bn_gate.weight.normal_(0, 0.1); m.cell.bn_gate.bias.fill_(-1.0)
+    return m.eval()
+
+
+def fp64_scan(m, x_tm, h0):
+    from kws_amd import fold_batchnorm
+    w, u, bg, bu, sg, sc = fold_batchnorm(m.cell.double())
+    out = folded_scan(w, u, bg, bu, sg, sc, m.cell.zeta.reshape(()), m.cell.nu.reshape(()), x_tm.double(),
+                        h0.double(), m.cell._gate_nonlinearity)
+    m.cell.float()
+    return out
+
+
+def fp32_scan(m, x_tm, h0):
+    from kws_amd import fold_batchnorm
+    w, u, bg, bu, sg, sc = fold_batchnorm(m.cell)
+    return folded_scan(w, u, bg, bu, sg, sc, m.cell.zeta.reshape(()), m.cell.nu.reshape(()), x_tm, h0,
+                         m.cell._gate_nonlinearity)

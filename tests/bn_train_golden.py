@@ -92,3 +92,69 @@ def bound(ref64, f32_err):
     """The GPU tests' bound: 4x what the formula loses in fp32, at least 2e-6 of the tensor's scale."""
     scale = float(np.abs(ref64).max()) if np.size(ref64) else 0.0
     return max(4.0 * f32_err, 2e-6 * max(scale, 1e-30))
+
+
+# ---- the GPU tests' cases: random layers, one step on a path, the comparison under bound() ----------------------------
+
+def random_case(F, H, T, B, gate, seed, momentum=0.1):
+    g = np.random.default_rng(seed)
+    d = {"W": 0.3 * g.standard_normal((F, H)) / np.sqrt(F / 32), "U": 0.1 * g.standard_normal((H, H)),
+         "x": g.standard_normal((T, B, F)), "G": g.standard_normal((T, B, H)), "h0": 0.5 * g.standard_normal((B, H)),
+         "bias_gate": 0.5 * g.standard_normal((1, H)), "bias_update": 0.5 * g.standard_normal((1, H)),
+         "zeta": np.array([[0.7]]), "nu": np.array([[-2.5]]), "meta_gate": np.array(gate)}
+    for n in BNS:
+        d[n + "_weight"] = 1.0 + 0.5 * g.standard_normal(H)
+        d[n + "_bias"] = 0.3 * g.standard_normal(H)
+        d[n + "_running_mean"] = 0.5 * g.standard_normal(H)
+        d[n + "_running_var"] = 0.5 + g.random(H)
+        d[n + "_num_batches_tracked"] = np.int64(3)
+        d[n + "_eps"] = np.float64(1e-5)
+        d[n + "_momentum"] = np.float64(np.nan if momentum is None else momentum)
+    return d
+
+
+def run(d, dtype, batch_first=False, torch_ops=False):
+    dev = torch.device("cuda", 0)
+    m = build_layer(d, dev, dtype, batch_first=batch_first)
+    if dtype == torch.float32 and not torch_ops:     # the kernels' case must not land on the torch-op path
+        B = d["x"].shape[1]
+        probe = torch.empty((B, 1, d["W"].shape[0]) if batch_first else (1, B, d["W"].shape[0]), device=dev)
+        assert m._fused(probe, batch_first, B)
+    x, G_, h0 = (torch.from_numpy(np.asarray(d[k])).to(dev, dtype) for k in ("x", "G", "h0"))
+    if batch_first:
+        x, G_ = x.transpose(0, 1).contiguous(), G_.transpose(0, 1).contiguous()
+    out = step(m, x, h0, G_, torch_ops=torch_ops)
+    torch.cuda.synchronize()
+    hs, dx, dh0, grads, runst = out
+    if batch_first:
+        hs, dx = hs.transpose(0, 1), dx.transpose(0, 1)
+    flat = {"hs": hs, "d_x": dx, "d_h0": dh0}
+    flat.update({"grad." + k: v for k, v in grads.items()})
+    flat.update({"run." + k: v for k, v in runst.items()})
+    return {k: v.detach().double().cpu().numpy() for k, v in flat.items()}, m
+
+
+def check(got, ref64, ref32, what=""):
+    worst = 0.0
+    for k, r in ref64.items():
+        a = np.asarray(got[k]).reshape(r.shape)
+        if k.endswith("num_batches_tracked"):
+            assert np.array_equal(a, r), (what, k)
+            continue
+        err = float(np.abs(a - r).max())
+        if any(k == "grad." + z for z in ZERO_GRADS):
+            scale = max(float(np.abs(ref64["grad.U"]).max()), 1.0)
+            assert err <= 1e-5 * scale, (what, k, err)
+            continue
+        e32 = float(np.abs(np.asarray(ref32[k]).reshape(r.shape) - r).max())
+        b = bound(r, e32)
+        assert err <= b, (what, k, err, b, e32)
+        worst = max(worst, err / b)
+    return worst
+
+
+def compare(d, batch_first=False):
+    got, _ = run(d, torch.float32, batch_first=batch_first)
+    ref64, _ = run(d, torch.float64, batch_first=batch_first)            # off the kernels: the torch-op formula
+    ref32, _ = run(d, torch.float32, batch_first=batch_first, torch_ops=True)
+    return check(got, ref64, ref32, (d["W"].shape, str(d["meta_gate"]), d["x"].shape, batch_first))

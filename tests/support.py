@@ -1,0 +1,232 @@
+"""What the test files share: names of the ABI, operand builders, the only spelled-out calls of the unrolled
+operators, the bitwise comparison, the fp64 oracle preamble and the one gradient checker with its tolerance policy.
+
+A plain module (``from tests import support as S``): no conftest, nothing registered with pytest, importable without a
+GPU and without loading the library.  pytest does not rewrite the asserts of this module, so every one of them carries
+its own message with the values involved.
+
+Tolerance policy.  No function here has a default tolerance: every call site states its bound.  ``check_grads`` turns
+a bound ``tol`` into the limit ``tol * max(1, max|ref|)`` per gradient (absolute while the reference is below one,
+relative beyond), and for the two scalar gradients alone ``scalar_term_tol`` (``SCALAR_TERM_TOL`` below) raises that
+limit to a fraction of the sum of their terms' magnitudes.
+"""
+import os
+
+import numpy as np
+import torch
+
+from kws_amd import _lib, fastgrnn_cuda
+from kws_amd._lib import (FLAG_BATCH_MAJOR, FLAG_BN_TRAIN, FLAG_FORCE_F32_MFMA, FLAG_FORCE_GENERIC,  # noqa: F401
+                          FLAG_FWD_4WAVE, FLAG_FWD_BF16X3, FLAG_GRAD_LAST, FLAG_HS_LAST, FLAG_NO_INPUT_GRAD,
+                          FLAG_PREACT_AFFINE, FLAG_SAVE_PREACT, FLAG_X_BFT, FLAG_ZERO_EXTEND, NONLINEARITY)
+from oracle import fastgrnn_oracle as O
+
+DEV = "cuda:0"
+
+# the operator's twelve outputs in the ABI's order (fastgrnn_grads, include/fastgrnn_hip.h; .cu:556)
+GRAD_NAMES = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1",
+              "d_u2"]
+
+# d_zeta / d_nu are ONE scalar each: sums of T*B*H terms of either sign that cancel to a result 1e2..1e4 times smaller
+# than the sum of their magnitudes, so an fp32 evaluation (the reference's own included) is bounded relative to THAT
+# sum: 2e-7 of it (every term good to about three fp32 roundings).  The oracle reports it (diagnostics=True ->
+# ref["_abs_zeta"], ref["_abs_nu"]).  The common relative limit applies on top, and the BASELINE configurations meet
+# it on its own at full size (tests/test_hip_fullsize.py).  Round 2 applied the term bound to every layer shape,
+# because the dense H=256 backward needed it (4-5.5e-5 of the result); since round 3 its chain carries d_pre exactly
+# and the default stack's first layer (F = 32, H = 256) is held to the plain 2e-5.  What still takes the
+# conditioning-aware bound there are the layers with a wide input at full size (F = 256 / H = 128: d_nu 2.5e-5 of a
+# result that is 1e-4 of its terms' magnitudes; F = 64 / H = 256: 3.1e-5).
+SCALAR_TERM_TOL = 2e-7
+
+
+def built_library():
+    """The loaded library, built first where the shared object is missing (the ``lib`` fixtures of the CPU tests)."""
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return _lib.load()
+
+
+# ---- operands --------------------------------------------------------------------------------------------------------
+
+def to_dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def cell_tensors(p):
+    """A numpy cell dict as the operator's operand tensors, ``torch.empty(0)`` for those that do not apply."""
+    e = torch.empty(0)
+    g = lambda k: to_dev(p[k]) if k in p else e
+    return dict(w=g("w"), u=g("u"), w1=g("w1"), w2=g("w2"), u1=g("u1"), u2=g("u2"),
+                bias_gate=to_dev(p["bias_gate"]), bias_update=to_dev(p["bias_update"]), zeta=to_dev(p["zeta"]),
+                nu=to_dev(p["nu"]))
+
+
+def copy_cell_params(m, p):
+    """The numpy cell dict ``p`` into the parameters of a FastGRNNCUDA module."""
+    with torch.no_grad():
+        for k, attr in (("w", "W"), ("u", "U"), ("w1", "W1"), ("w2", "W2"), ("u1", "U1"), ("u2", "U2"),
+                        ("bias_gate", "bias_gate"), ("bias_update", "bias_update"), ("zeta", "zeta"), ("nu", "nu")):
+            if k in p:
+                getattr(m, attr).copy_(torch.from_numpy(p[k]))
+
+
+def _code(nl):
+    return NONLINEARITY[nl] if isinstance(nl, str) else nl
+
+
+# ---- operator calls: the only places in the tests that spell out the positional operand lists -------------------------
+
+def forward_unroll(x, h0, P, gate, *, update="tanh", flags=0, **kw):
+    """fastgrnn_cuda.forward_unroll on the operand dict ``P``; ``gate`` / ``update`` by name or code.  ``kw`` goes
+    through as given (``want_gates=``) and nothing is added."""
+    return fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0,
+                                        _code(gate), P["w1"], P["w2"], P["u1"], P["u2"],
+                                        update_non_linearity=_code(update), flags=flags, **kw)
+
+
+def backward_unroll(G, x, hs, z, aux, h0, P, gate, *, update="tanh", flags=0, **kw):
+    """fastgrnn_cuda.backward_unroll; ``z`` / ``aux`` are the forward's second and third output (the pre-activation
+    and, where there is one, the rank-space or saved tensor under FLAG_SAVE_PREACT).  ``kw`` goes through as given
+    (``bias_gate=``, ``bias_update=``, ``need_dx=``): a call that does not name the biases does not pass them."""
+    return fastgrnn_cuda.backward_unroll(G, x, hs, P["zeta"], P["nu"], P["w"], P["u"], z, aux, h0,
+                                         P["w1"], P["w2"], P["u1"], P["u2"], _code(gate),
+                                         update_non_linearity=_code(update), flags=flags, **kw)
+
+
+def backward_of(outs, G, x, h0, P, gate, *, update="tanh", flags=0, biases=False, **kw):
+    """backward_unroll on what a forward_unroll saved: ``outs`` is its output list (one with two entries saved one
+    tensor, given as both ``z`` and ``aux``).  ``biases=True`` names P's two biases, as a FLAG_SAVE_PREACT call must;
+    without it none are passed."""
+    if biases:
+        kw = dict(kw, bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+    return backward_unroll(G, x, outs[0], outs[1], outs[2] if len(outs) > 2 else outs[1], h0, P, gate, update=update,
+                           flags=flags, **kw)
+
+
+def fwd_bwd(x, h0, G, P, gate, *, update="tanh", flags=0, biases=False, **bwd_kw):
+    """forward_unroll, then backward_of its outputs (``biases`` and ``bwd_kw`` go to the backward alone).  Returns the
+    forward's outputs and the backward's twelve."""
+    outs = forward_unroll(x, h0, P, gate, update=update, flags=flags)
+    return outs, backward_of(outs, G, x, h0, P, gate, update=update, flags=flags, biases=biases, **bwd_kw)
+
+
+# ---- bitwise comparison ------------------------------------------------------------------------------------------------
+
+_INT_OF_SIZE = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def _bit_view(t):
+    t = t.contiguous()
+    return t if not (t.is_floating_point() or t.is_complex()) else t.view(_INT_OF_SIZE[t.element_size()])
+
+
+def bits_equal(a, b):
+    """Same shape, same dtype, same bit pattern (-0.0 is not 0.0; equal NaN payloads are equal)."""
+    return a.shape == b.shape and a.dtype == b.dtype and bool(torch.equal(_bit_view(a), _bit_view(b)))
+
+
+def assert_same_bits(a, b, what):
+    assert a.shape == b.shape, "%s: shapes %s and %s" % (what, tuple(a.shape), tuple(b.shape))
+    assert a.dtype == b.dtype, "%s: dtypes %s and %s" % (what, a.dtype, b.dtype)
+    if not torch.equal(_bit_view(a), _bit_view(b)):
+        n = int((_bit_view(a) != _bit_view(b)).sum())
+        raise AssertionError("%s: %d of %d elements differ in their bits, max |a - b| = %r"
+                             % (what, n, a.numel(), float((a.double() - b.double()).abs().max())))
+
+
+# ---- oracle ------------------------------------------------------------------------------------------------------------
+
+def _f64(p):
+    return {k: np.asarray(v, np.float64) for k, v in p.items()}
+
+
+def _h64(h0):
+    return None if h0 is None else np.asarray(h0, np.float64)      # (None: the oracle's zero state)
+
+
+def oracle64_forward(x, p, h0, gate="sigmoid", update="tanh"):
+    """The fp64 oracle's forward on the given (fp32) values: ``hs, zs, cs``."""
+    return O.unroll_forward(np.asarray(x, np.float64), _f64(p), _h64(h0), gate=gate, update=update)
+
+
+def oracle64(x, G, p, h0, gate="sigmoid", update="tanh"):
+    """The fp64 oracle on the given (fp32) values: ``hs, zs, cs, grads``; ``grads`` carries the sums of the scalar
+    gradients' term magnitudes (``_abs_zeta`` / ``_abs_nu``) for ``check_grads``."""
+    p64, x64, h64 = _f64(p), np.asarray(x, np.float64), _h64(h0)
+    hs, zs, cs = O.unroll_forward(x64, p64, h64, gate=gate, update=update)
+    grads = O.unroll_backward(np.asarray(G, np.float64), x64, hs, zs, cs, p64, h64, gate=gate, update=update,
+                              diagnostics=True)
+    return hs, zs, cs, grads
+
+
+def dense_preactivation64(x, p, h0, hs_o):
+    """W.x_t + U.h_{t-1} of a dense cell along the oracle's states ``hs_o``, in fp64: what FLAG_SAVE_PREACT saves"""
+    hprev = np.concatenate([np.asarray(h0, np.float64)[None], hs_o[:-1]], 0)
+    return np.asarray(x, np.float64) @ np.asarray(p["w"], np.float64).T + hprev @ np.asarray(p["u"], np.float64).T
+
+
+# ---- the gradient check ------------------------------------------------------------------------------------------------
+
+def _named(got):
+    """dict or the operator's list -> dict; an output the operator left empty counts as absent"""
+    items = got.items() if isinstance(got, dict) else zip(GRAD_NAMES, got)
+    return {k: v for k, v in items if (v.numel() if isinstance(v, torch.Tensor) else np.size(v))}
+
+
+def _is_f64(v):
+    return v.dtype in (torch.float64, np.float64)
+
+
+def _np64(v):
+    return v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float64)
+
+
+def check_grads(got, ref, *, tol, scalar_term_tol, tag):
+    """Every gradient of ``ref`` (keys starting with ``_`` are diagnostics, not gradients) against ``got``, a dict or
+    the operator's list, numpy or torch: ``max|got - ref| <= tol * max(1, max|ref|)``.  With ``scalar_term_tol > 0``,
+    a result that is not fp64 and a reference that carries ``_abs_zeta`` / ``_abs_nu``, the limit of ``d_zeta`` /
+    ``d_nu`` is at least ``scalar_term_tol`` times that sum (see SCALAR_TERM_TOL).  A key of ``ref`` that ``got`` lacks
+    fails.  Reports every failing entry; returns the relative errors ``max|got - ref| / max(1, max|ref|)``."""
+    got = _named(got)
+    errs, bad = {}, {}
+    for k, v in ref.items():
+        if k.startswith("_"):
+            continue
+        if k not in got:
+            bad[k] = "missing"
+            continue
+        v = np.asarray(v)
+        scale = max(1.0, float(np.abs(v).max()))
+        abs_err = float(np.abs(_np64(got[k]).reshape(v.shape) - v).max())
+        lim = tol * scale
+        if scalar_term_tol > 0 and k in ("d_zeta", "d_nu") and not _is_f64(got[k]) and ("_abs_" + k[2:]) in ref:
+            lim = max(lim, scalar_term_tol * float(ref["_abs_" + k[2:]]))
+        errs[k] = abs_err / scale
+        if not abs_err <= lim:          # (a NaN fails)
+            bad[k] = "abs err %.6g > limit %.6g (rel %.6g)" % (abs_err, lim, errs[k])
+    assert not bad, "%s: %s; relative errors of all: %s" % (tag, bad, errs)
+    return errs
+
+
+# ---- the relu kink -----------------------------------------------------------------------------------------------------
+
+def relu_gate_preactivations(p, x, h0):
+    """a = pre + b_z of the whole sequence from the fp64 oracle under a relu gate; pre is recovered from the update
+    nonlinearity's output, c = tanh(pre + b_h)"""
+    p64 = _f64(p)
+    _, _, cs = O.unroll_forward(np.asarray(x, np.float64), p64, np.asarray(h0, np.float64), gate="relu")
+    return np.arctanh(np.clip(cs, -1 + 1e-15, 1 - 1e-15)) - p64["bias_update"] + p64["bias_gate"]
+
+
+def keep_relu_gates_off_the_kink(p, x, h0, margin=1e-4):
+    """Nudge bias_gate, unit by unit, until no relu-gate pre-activation of the whole sequence lies within ``margin`` of
+    zero (fp64 oracle; the recurrence moves with the bias, so a few rounds).  Returns the moved copy of ``p``."""
+    p = {k: v.copy() for k, v in p.items()}
+    for _ in range(50):
+        a = relu_gate_preactivations(p, x, h0)
+        close = np.abs(a).reshape(-1, a.shape[-1]).min(axis=0) < 2 * margin     # units with a value near the kink
+        if not close.any():
+            return p
+        p["bias_gate"][0, close] += np.float32(7 * margin)
+    raise AssertionError("could not move the relu gates off the kink (margin %g)" % margin)

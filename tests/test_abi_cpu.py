@@ -8,16 +8,14 @@ import re
 import pytest
 
 from kws_amd import _lib
+from tests import support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
+    return S.built_library()
 
 
 def test_exports_every_declared_symbol(lib):

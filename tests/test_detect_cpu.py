@@ -8,8 +8,8 @@ import re
 
 import pytest
 
-from kws_amd import _lib
 from tests import detect_cases as D
+from tests import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, ONE = C.c_void_p(None), C.c_void_p(256)          # (a fake non-NULL, 256-byte aligned pointer: nothing is launched)
@@ -18,10 +18,7 @@ OK, NULLP, SHAPE, WS, UNSUP = 0, 1, 2, 5, 7
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
+    return support.built_library()
 
 
 def _predict(lib, B=37, H=128, Cn=12, h=ONE, w=ONE, b=ONE, labels=ONE, logp=ONE, pred=ONE, n=ONE, ws=ONE, nbytes=None):

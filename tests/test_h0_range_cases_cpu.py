@@ -3,21 +3,18 @@
 points, and the table covers the axes each family has to.  fastgrnn_hip_kernel_path is a pure function of the descriptor:
 no kernel is launched here."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from kws_amd import _lib
 from tests import h0_range_cases as HC
+from tests import support as S
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
+    return S.built_library()
 
 
 def _of(family):

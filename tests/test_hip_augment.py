@@ -14,6 +14,7 @@ import torch
 
 from tests import augment_cases as A
 from tests import mfcc_cases as M
+from tests import support as S
 
 pytestmark = pytest.mark.gpu
 
@@ -94,19 +95,15 @@ def _unfused(bank, lengths, rec, aug, *, n_mfcc=32, order=1, width=9, peak=False
                                 peak_normalize=peak, mean=mean, std=std)
 
 
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 # ---- 1. identity ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", ("f32", "i16"))
 def test_identity_records_reproduce_the_plain_call(dtype):
     bank, lengths, aug = _device(dtype)
     rec = pack_augment(torch.arange(N, device=DEV), 0, 1.0)
     want = mfcc_features(bank, lengths)
-    assert _same_bits(_fused(bank, lengths, rec, aug), want)
-    assert _same_bits(mfcc_features(bank, lengths, augment=rec), want)            # no noise bank at all
-    assert _same_bits(mfcc_features(bank, None, augment=rec), mfcc_features(bank, None))
+    assert S.bits_equal(_fused(bank, lengths, rec, aug), want)
+    assert S.bits_equal(mfcc_features(bank, lengths, augment=rec), want)            # no noise bank at all
+    assert S.bits_equal(mfcc_features(bank, None, augment=rec), mfcc_features(bank, None))
 
 
 # ---- 2. fused == unfused, bit for bit ------------------------------------------------------------------------------------
@@ -126,7 +123,7 @@ def test_the_fused_call_equals_the_unfused_chain(dtype, cfg):
     host_bank, host_noises = _host(dtype)
     oracle, olen = A.augment_batch(host_bank[1:N + 1], LENGTHS, _records(), host_noises)
     assert np.array_equal(audio.cpu().numpy().view(np.int32), oracle.view(np.int32))
-    assert got.shape == (B, 99, cfg.get("n_mfcc", 32) * (cfg.get("order", 1) + 1)) and _same_bits(got, want)
+    assert got.shape == (B, 99, cfg.get("n_mfcc", 32) * (cfg.get("order", 1) + 1)) and S.bits_equal(got, want)
     assert bool(torch.isfinite(got).all())
     # the edges did what they say: shift = len with gain 1 leaves the (one-sample) noise alone; gain 0, no noise: silence
     n1, z0 = int(LENGTHS[1]), A.as_samples(host_noises[0])[0]
@@ -143,7 +140,7 @@ def test_a_bank_that_is_a_strided_view():
     rec = torch.from_numpy(_records()).to(DEV)
     got = _fused(bank, lengths, rec, aug)
     audio, want = _unfused(bank, lengths, rec, aug)
-    assert _same_bits(got, want)
+    assert S.bits_equal(got, want)
     oracle, _ = A.augment_batch(bank.cpu().numpy(), LENGTHS, _records(), _host("i16")[1])
     assert np.array_equal(audio.cpu().numpy().view(np.int32), oracle.view(np.int32))
 
@@ -154,7 +151,7 @@ def test_an_absent_noise_reads_no_noise():
     poisoned.noise = torch.full_like(aug.noise, float("nan"))
     rec = pack_augment(torch.arange(N, device=DEV), 5, 0.5, noise=-1, noise_off=3, noise_gain=2.0)
     got = _fused(bank, lengths, rec, poisoned)
-    assert bool(torch.isfinite(got).all()) and _same_bits(got, mfcc_features(bank, lengths, augment=rec))
+    assert bool(torch.isfinite(got).all()) and S.bits_equal(got, mfcc_features(bank, lengths, augment=rec))
 
 
 def test_the_range_check():
@@ -191,16 +188,16 @@ def test_hostile_records_give_the_clamped_records_result_and_stay_inside(dtype):
     torch.cuda.synchronize()
     assert bool((out[0] == CANARY).all()) and bool((out[-1] == CANARY).all())
     want = _fused(bank, lengths, torch.from_numpy(clamped).to(DEV), aug)          # (in range: check=True passes)
-    assert _same_bits(out[1:-1], want)
-    assert _same_bits(_fused(bank, lengths, rec, aug, check=False), want)
+    assert S.bits_equal(out[1:-1], want)
+    assert S.bits_equal(_fused(bank, lengths, rec, aug, check=False), want)
     audio, unfused = _unfused(bank, lengths, rec, aug)                            # apply clamps alike
-    assert _same_bits(unfused, want)
+    assert S.bits_equal(unfused, want)
     host_bank, host_noises = _host(dtype)
     oracle, _ = A.augment_batch(host_bank[1:N + 1], LENGTHS, clamped, host_noises)
     assert np.array_equal(audio.cpu().numpy().view(np.int32), oracle.view(np.int32))
     # without noises every noise index means none
     none = A.clamp_records(hostile, N, None, 1)
-    assert _same_bits(mfcc_features(bank, lengths, augment=rec, check=False),
+    assert S.bits_equal(mfcc_features(bank, lengths, augment=rec, check=False),
                       mfcc_features(bank, lengths, augment=torch.from_numpy(none).to(DEV)))
 
 
@@ -240,8 +237,8 @@ def test_a_captured_draw_and_front_end_follow_the_step_scalar():
         step_t.fill_(s)
         got_rec, got = graphed()
         torch.cuda.synchronize()
-        assert torch.equal(got_rec, rec) and _same_bits(got, feats), s
-    assert not torch.equal(eager[0][0], eager[1][0]) and not _same_bits(eager[1][1], eager[2][1])
+        assert torch.equal(got_rec, rec) and S.bits_equal(got, feats), s
+    assert not torch.equal(eager[0][0], eager[1][0]) and not S.bits_equal(eager[1][1], eager[2][1])
     index.copy_(index.flip(0))                                                   # index is a captured input
     got_rec, _ = graphed()
     assert torch.equal(got_rec[:, 0], index)

@@ -1,11 +1,10 @@
 """FastGRNNBatchNorm eval-mode inference on the GPU: the reference's trained keyword spotter against its fp64
 evaluation, the full-size batch, random BatchNorm statistics on every kernel-path-2 shape, the generic scan in fp64,
 hidden-state carry and the refused backward."""
-import numpy as np
 import pytest
 import torch
 
-from kws_amd import FastGRNNBatchNorm, _lib, fastgrnn_cuda, fold_batchnorm
+from kws_amd import FastGRNNBatchNorm, _lib, fastgrnn_cuda
 from tests import batchnorm_golden as G
 
 pytestmark = pytest.mark.gpu
@@ -73,68 +72,27 @@ def test_trained_model_full_size():
     assert torch.equal(logp.argmax(1)[sure], ref.argmax(1)[sure])
 
 
-def _random_bn(F, H, gate, seed):
-    """A cell with hostile statistics: negative gammas, running variances at 0 (a = gamma / sqrt(eps)), and bn_u
-    scales spanning 10^4 within every 16 consecutive units."""
-    torch.manual_seed(seed)
-    m = FastGRNNBatchNorm(F, H, gate_nonlinearity=gate, device=DEV)
-    with torch.no_grad():
-        m.cell.W.mul_(0.5 / F ** 0.5 / 0.1)
-        m.cell.U.mul_((0.3 if gate == "sigmoid" else 0.05) / H ** 0.5 / 0.1)
-        m.cell.zeta.fill_(0.8); m.cell.nu.fill_(-1.5)
-        m.cell.bias_gate.normal_(0, 0.5); m.cell.bias_update.normal_(0, 0.5)
-        for bn in (m.cell.bn_w, m.cell.bn_u, m.cell.bn_gate, m.cell.bn_update):
-            bn.weight.copy_(torch.randn(H, device=DEV)); bn.bias.normal_(0, 0.3)
-            bn.running_mean.normal_(0, 0.3); bn.running_var.uniform_(0.5, 2.0)
-            bn.running_var[::11] = 0.0
-        j = torch.arange(H, device=DEV) % 16
-        span = 10.0 ** (4.0 * j / 15.0 - 2.0)                    # 1e-2 .. 1e2 inside every 16 units
-        m.cell.bn_u.running_var.fill_(1.0 - 1e-5)
-        m.cell.bn_u.weight.copy_(span * torch.where(j % 3 == 0, -1.0, 1.0))
-        if gate != "sigmoid":
-            m.cell.bn_u.weight.mul_(0.1)
-        if gate == "relu":        # an unbounded gate (h grows like the product of the z's): keep z mostly below 1
-            m.cell.bn_w.running_var.uniform_(0.5, 2.0)
-            m.cell.bn_gate.running_var.uniform_(0.5, 2.0)
-            m.cell.bn_gate.weight.normal_(0, 0.1); m.cell.bn_gate.bias.fill_(-1.0)
-    return m.eval()
-
-
-def _fp64_scan(m, x_tm, h0):
-    w, u, bg, bu, sg, sc = fold_batchnorm(m.cell.double())
-    out = G.folded_scan(w, u, bg, bu, sg, sc, m.cell.zeta.reshape(()), m.cell.nu.reshape(()), x_tm.double(),
-                        h0.double(), m.cell._gate_nonlinearity)
-    m.cell.float()
-    return out
-
-
-def _fp32_scan(m, x_tm, h0):
-    w, u, bg, bu, sg, sc = fold_batchnorm(m.cell)
-    return G.folded_scan(w, u, bg, bu, sg, sc, m.cell.zeta.reshape(()), m.cell.nu.reshape(()), x_tm, h0,
-                         m.cell._gate_nonlinearity)
-
-
 SHAPES = [(128, 32), (128, 64), (128, 128), (128, 256), (256, 32), (256, 64), (256, 128)]
 
 
 @pytest.mark.parametrize("H,F", SHAPES)
 @pytest.mark.parametrize("gate", ["sigmoid", "relu", "tanh"])
 def test_stress_path2(H, F, gate):
-    m = _random_bn(F, H, gate, seed=H + F + len(gate))
+    m = G.random_bn(F, H, gate, seed=H + F + len(gate))
     worst = 0.0
     for B in (17, 4097):
         T = 12 if (B > 1000 or gate == "relu") else 30
         g = torch.Generator(device=DEV).manual_seed(B)
         x = torch.randn(T, B, F, device=DEV, generator=g)
         h0 = 0.5 * torch.randn(B, H, device=DEV, generator=g)
-        ref = _fp64_scan(m, x, h0)
+        ref = G.fp64_scan(m, x, h0)
         assert bool(torch.isfinite(ref).all())
-        e32 = float((_fp32_scan(m, x, h0).double() - ref).abs().max())
+        e32 = float((G.fp32_scan(m, x, h0).double() - ref).abs().max())
         bound = 4 * e32 + 1e-5 * max(1.0, float(ref.abs().max()))
         for bf in (False, True):
             m.batch_first = bf
             xi = x.transpose(0, 1).contiguous() if bf else x
-            assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=G_CODES[gate], flags=A | (BM if bf else 0)) == 2
+            assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=_lib.NONLINEARITY[gate], flags=A | (BM if bf else 0)) == 2
             with torch.no_grad():
                 hs = m(xi, h0, training=False)
                 last = m(xi, h0, training=False, last_state=True)
@@ -145,9 +103,6 @@ def test_stress_path2(H, F, gate):
             assert torch.allclose(last, hs_tm[-1], rtol=0, atol=1e-6 * max(1.0, float(hs_tm[-1].abs().max()))), (B, bf)
     m.batch_first = False
     print("stress H=%d F=%d %s: worst error / bound %.3f" % (H, F, gate, worst))
-
-
-G_CODES = {"sigmoid": 0, "relu": 1, "tanh": 2}
 
 
 def test_generic_fp64_h100():

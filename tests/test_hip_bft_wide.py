@@ -11,130 +11,71 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import fastgrnn_oracle as O
+from tests import layer_cases as LC
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from kws_amd import FastGRNNBatchNorm, FastGRNNCUDA, RNNClassifierModel, _lib, fastgrnn_cuda  # noqa: F401
-DEV = "cuda:0"
-SP, BM, BFT, GL, LAST = 4, 16, 128, 256, 512
-GATE = {"sigmoid": 0, "relu": 1, "tanh": 2, "quantTanh": 3, "quantSigm": 4, "quantSigm4": 5}
-NAMES = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
+SP, BM, BFT, GL, LAST = S.FLAG_SAVE_PREACT, S.FLAG_BATCH_MAJOR, S.FLAG_X_BFT, S.FLAG_GRAD_LAST, S.FLAG_HS_LAST
 SHAPES = [(256, 64), (256, 128), (128, 64), (128, 128), (128, 256)]          # (H, F)
 # ragged and full batches; T below, at and across a 32-row stage of the frame GEMM; stages that straddle utterances
 SIZES = [(23, 37), (33, 64), (99, 16), (1, 5)]
 
 
-def _same_bits(a, b, what):
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    a, b = a.contiguous(), b.contiguous()
-    assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (what, float((a - b).abs().max()))
-
-
-def _params(F, H, seed, gate="sigmoid", w_rank=None, u_rank=None):
-    p = O.make_params(F, H, w_rank, u_rank, np.float32, seed=seed, randomize_scalars=True)
-    if gate == "relu":                          # an unbounded gate: keep z = relu(.) small so that h stays finite
-        p["bias_gate"] = (p["bias_gate"] - 1.5).astype(np.float32)
-        for k in ("u", "u1"):
-            if k in p:
-                p[k] = (0.1 * p[k]).astype(np.float32)
-    e = torch.empty(0, device=DEV)
-    t = lambda k: torch.from_numpy(np.ascontiguousarray(p[k])).to(DEV) if k in p else e
-    return {k: t(k) for k in ("w", "u", "w1", "w2", "u1", "u2", "bias_gate", "bias_update", "zeta", "nu")}
-
-
-def _forward(x, h0, P, gate, flags, want_gates=True):
-    return fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0,
-                                        GATE[gate], P["w1"], P["w2"], P["u1"], P["u2"], flags=flags,
-                                        want_gates=want_gates)
-
-
-def _backward(G, x, outs, h0, P, gate, flags, need_dx=True):
-    hs, z = outs[0], outs[1]
-    aux = outs[2] if len(outs) > 2 else outs[1]
-    g = fastgrnn_cuda.backward_unroll(G, x, hs, P["zeta"], P["nu"], P["w"], P["u"], z, aux, h0, P["w1"], P["w2"],
-                                      P["u1"], P["u2"], GATE[gate], flags=flags, bias_gate=P["bias_gate"],
-                                      bias_update=P["bias_update"], need_dx=need_dx)
-    return dict(zip(NAMES, g))
-
-
-def _data(T, B, F, H, seed=5):
-    gen = torch.Generator(device="cpu").manual_seed(seed)
-    x = torch.randn(T, B, F, generator=gen).to(DEV)                 # time-major
-    xb = x.permute(1, 2, 0).contiguous()                            # the loader's [B,F,T]
-    h0 = (0.5 * torch.randn(B, H, generator=gen)).to(DEV)
-    G = torch.randn(T, B, H, generator=gen).to(DEV)
-    return x, xb, h0, G
-
-
-def _compare_backward(G, x, xb, o_tm, o_bft, h0, P, gate, flags, tag, dx_optional=True):
-    """all eight gradients, d_x given ([B,F,T], equal to the time-major d_x permuted) and d_x == NULL (the dense
-    cells: the operator module always asks a factorised cell for d_x)"""
-    ref = _backward(G, x, o_tm, h0, P, gate, flags)
-    for need_dx in ((True, False) if dx_optional else (True,)):
-        got = _backward(G, xb, o_bft, h0, P, gate, flags | BFT, need_dx=need_dx)
-        torch.cuda.synchronize()
-        if need_dx:
-            assert got["d_x"].shape == xb.shape
-            _same_bits(got["d_x"], ref["d_x"].permute(1, 2, 0), tag + " d_x")
-        else:
-            assert got["d_x"].numel() == 0
-        for k in NAMES[1:]:
-            if ref[k].numel():
-                _same_bits(got[k], ref[k], "%s %s need_dx=%s" % (tag, k, need_dx))
-    for k in ("d_w", "d_u", "d_w1", "d_u1", "d_h0", "d_zeta"):
-        assert torch.isfinite(ref[k]).all(), (tag, k)
-
-
 @pytest.mark.parametrize("T,B", SIZES, ids=lambda v: str(v))
 @pytest.mark.parametrize("H,F", SHAPES, ids=lambda v: str(v))
 def test_operator_bitwise_equal_to_the_time_major_call(H, F, T, B):
-    x, xb, h0, G = _data(T, B, F, H)
-    P = _params(F, H, seed=11 + B % 7)
+    x, xb, h0, G = LC.bft_data(T, B, F, H)
+    P = LC.bft_params(F, H, seed=11 + B % 7)
     for direction, fl in ((0, BFT), (0, BFT | SP), (0, BFT | LAST), (0, BFT | BM), (1, BFT | SP), (1, BFT | SP | GL), (1, BFT)):
         assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=direction, flags=fl) == 2, (direction, fl)
     # hs alone
-    _same_bits(_forward(xb, h0, P, "sigmoid", BFT, False)[0], _forward(x, h0, P, "sigmoid", 0, False)[0], "hs alone")
+    hs_only = lambda xi, fl: S.forward_unroll(xi, h0, P, "sigmoid", flags=fl, want_gates=False)[0]
+    S.assert_same_bits(hs_only(xb, BFT), hs_only(x, 0), "hs alone")
     # the one-saved-tensor contract: hs, the pre-activation, every gradient
-    o_tm, o_bft = _forward(x, h0, P, "sigmoid", SP), _forward(xb, h0, P, "sigmoid", SP | BFT)
+    o_tm, o_bft = S.forward_unroll(x, h0, P, "sigmoid", flags=SP), S.forward_unroll(xb, h0, P, "sigmoid", flags=SP | BFT)
     assert len(o_tm) == len(o_bft) == 2
-    _same_bits(o_bft[0], o_tm[0], "preact hs"); _same_bits(o_bft[1], o_tm[1], "preact z")
-    _compare_backward(G, x, xb, o_tm, o_bft, h0, P, "sigmoid", SP, "preact")
+    S.assert_same_bits(o_bft[0], o_tm[0], "preact hs"); S.assert_same_bits(o_bft[1], o_tm[1], "preact z")
+    LC.compare_bft_backward(G, x, xb, o_tm, o_bft, h0, P, "sigmoid", SP, "preact")
     # ... with the gradient of the last state alone
-    _compare_backward(G[-1].contiguous(), x, xb, o_tm, o_bft, h0, P, "sigmoid", SP | GL, "grad_last")
+    LC.compare_bft_backward(G[-1].contiguous(), x, xb, o_tm, o_bft, h0, P, "sigmoid", SP | GL, "grad_last")
     # the reference's (z_s, h_prime_s) pair
-    o_tm, o_bft = _forward(x, h0, P, "sigmoid", 0), _forward(xb, h0, P, "sigmoid", BFT)
+    o_tm, o_bft = S.forward_unroll(x, h0, P, "sigmoid"), S.forward_unroll(xb, h0, P, "sigmoid", flags=BFT)
     for a, b, n in zip(o_bft, o_tm, ("hs", "z_s", "h_prime_s")):
-        _same_bits(a, b, "pair " + n)
-    _compare_backward(G, x, xb, o_tm, o_bft, h0, P, "sigmoid", 0, "pair")
+        S.assert_same_bits(a, b, "pair " + n)
+    LC.compare_bft_backward(G, x, xb, o_tm, o_bft, h0, P, "sigmoid", 0, "pair")
     # h_T alone
-    _same_bits(_forward(xb, h0, P, "sigmoid", BFT | LAST, False)[0], _forward(x, h0, P, "sigmoid", LAST, False)[0], "hs_last")
+    S.assert_same_bits(hs_only(xb, BFT | LAST), hs_only(x, LAST), "hs_last")
     # batch-major sequences from [B,F,T] frames: hs alone and with the saved pre-activation
     xbm = x.transpose(0, 1).contiguous()
-    _same_bits(_forward(xb, h0, P, "sigmoid", BFT | BM, False)[0], _forward(xbm, h0, P, "sigmoid", BM, False)[0], "bm hs")
-    o_tm, o_bft = _forward(xbm, h0, P, "sigmoid", BM | SP), _forward(xb, h0, P, "sigmoid", BFT | BM | SP)
-    _same_bits(o_bft[0], o_tm[0], "bm preact hs"); _same_bits(o_bft[1], o_tm[1], "bm preact z")
+    S.assert_same_bits(hs_only(xb, BFT | BM), hs_only(xbm, BM), "bm hs")
+    o_tm = S.forward_unroll(xbm, h0, P, "sigmoid", flags=BM | SP)
+    o_bft = S.forward_unroll(xb, h0, P, "sigmoid", flags=BFT | BM | SP)
+    S.assert_same_bits(o_bft[0], o_tm[0], "bm preact hs"); S.assert_same_bits(o_bft[1], o_tm[1], "bm preact z")
 
 
 @pytest.mark.parametrize("gate", ["relu", "tanh", "quantSigm"])
 @pytest.mark.parametrize("H,F", SHAPES, ids=lambda v: str(v))
 def test_operator_other_gates(H, F, gate):
     T, B = (6, 37) if gate == "relu" else (12, 37)           # gates that do not bound h: short sequences
-    x, xb, h0, G = _data(T, B, F, H, seed=8)
-    P = _params(F, H, seed=4, gate=gate)
-    o_tm, o_bft = _forward(x, h0, P, gate, SP), _forward(xb, h0, P, gate, SP | BFT)
-    _same_bits(o_bft[0], o_tm[0], "hs"); _same_bits(o_bft[1], o_tm[1], "z")
-    _compare_backward(G, x, xb, o_tm, o_bft, h0, P, gate, SP, gate)
-    _same_bits(_forward(xb, h0, P, gate, BFT, False)[0], _forward(x, h0, P, gate, 0, False)[0], "hs alone")
+    x, xb, h0, G = LC.bft_data(T, B, F, H, seed=8)
+    P = LC.bft_params(F, H, seed=4, gate=gate)
+    o_tm, o_bft = S.forward_unroll(x, h0, P, gate, flags=SP), S.forward_unroll(xb, h0, P, gate, flags=SP | BFT)
+    S.assert_same_bits(o_bft[0], o_tm[0], "hs"); S.assert_same_bits(o_bft[1], o_tm[1], "z")
+    LC.compare_bft_backward(G, x, xb, o_tm, o_bft, h0, P, gate, SP, gate)
+    S.assert_same_bits(S.forward_unroll(xb, h0, P, gate, flags=BFT, want_gates=False)[0],
+                       S.forward_unroll(x, h0, P, gate, want_gates=False)[0], "hs alone")
 
 
 @pytest.mark.parametrize("H,F", SHAPES, ids=lambda v: str(v))
 def test_scaled_forward_bitwise(H, F):
     """fastgrnn_hip_forward_unroll_affine (an eval-mode BatchNorm cell, folded) from [B,F,T] frames"""
     T, B = 33, 37
-    x, xb, h0, _ = _data(T, B, F, H, seed=2)
-    P = _params(F, H, seed=6)
+    x, xb, h0, _ = LC.bft_data(T, B, F, H, seed=2)
+    P = LC.bft_params(F, H, seed=6)
     gen = torch.Generator(device="cpu").manual_seed(1)
     sg = (1.0 + 0.3 * torch.randn(H, generator=gen)).to(DEV)
     sc = (1.0 + 0.3 * torch.randn(H, generator=gen)).to(DEV)
@@ -142,52 +83,52 @@ def test_scaled_forward_bitwise(H, F):
                                                               P["zeta"], P["nu"], sg, sc, h0, 0, 2, fl)
     for fl in (0, LAST):
         assert fastgrnn_cuda.kernel_path(T, B, F, H, flags=fl | BFT | _lib.FLAG_PREACT_AFFINE) == 2
-        _same_bits(run(xb, fl | BFT), run(x, fl), "affine flags=%d" % fl)
-        _same_bits(run(xb, fl | BFT | BM), run(x.transpose(0, 1).contiguous(), fl | BM), "affine bm flags=%d" % fl)
+        S.assert_same_bits(run(xb, fl | BFT), run(x, fl), "affine flags=%d" % fl)
+        S.assert_same_bits(run(xb, fl | BFT | BM), run(x.transpose(0, 1).contiguous(), fl | BM), "affine bm flags=%d" % fl)
 
 
 @pytest.mark.parametrize("H,F,w_rank,u_rank", [(128, 64, 8, None), (256, 64, 40, 40)], ids=["h128-w8", "h256-r40"])
 def test_multiplied_out_factorised_cells_inherit_the_flag(H, F, w_rank, u_rank):
     T, B = 23, 37
     assert fastgrnn_cuda.kernel_path(T, B, F, H, w_rank or 0, u_rank or 0, direction=1, flags=SP | BFT) == 2
-    x, xb, h0, G = _data(T, B, F, H, seed=3)
-    P = _params(F, H, seed=9, w_rank=w_rank, u_rank=u_rank)
-    o_tm, o_bft = _forward(x, h0, P, "sigmoid", SP), _forward(xb, h0, P, "sigmoid", SP | BFT)
-    _same_bits(o_bft[0], o_tm[0], "hs"); _same_bits(o_bft[1], o_tm[1], "z")
-    _compare_backward(G, x, xb, o_tm, o_bft, h0, P, "sigmoid", SP, "densified", dx_optional=False)
+    x, xb, h0, G = LC.bft_data(T, B, F, H, seed=3)
+    P = LC.bft_params(F, H, seed=9, w_rank=w_rank, u_rank=u_rank)
+    o_tm, o_bft = S.forward_unroll(x, h0, P, "sigmoid", flags=SP), S.forward_unroll(xb, h0, P, "sigmoid", flags=SP | BFT)
+    S.assert_same_bits(o_bft[0], o_tm[0], "hs"); S.assert_same_bits(o_bft[1], o_tm[1], "z")
+    LC.compare_bft_backward(G, x, xb, o_tm, o_bft, h0, P, "sigmoid", SP, "densified", dx_optional=False)
 
 
 def test_full_size_first_layer():
     T, B, F, H = 99, 4096, 64, 256
-    x, xb, h0, G = _data(T, B, F, H, seed=1)
-    P = _params(F, H, seed=2)
-    o_tm, o_bft = _forward(x, h0, P, "sigmoid", SP), _forward(xb, h0, P, "sigmoid", SP | BFT)
-    _same_bits(o_bft[0], o_tm[0], "hs"); _same_bits(o_bft[1], o_tm[1], "z")
-    ref = _backward(G, x, o_tm, h0, P, "sigmoid", SP, need_dx=False)
-    got = _backward(G, xb, o_bft, h0, P, "sigmoid", SP | BFT, need_dx=False)
+    x, xb, h0, G = LC.bft_data(T, B, F, H, seed=1)
+    P = LC.bft_params(F, H, seed=2)
+    o_tm, o_bft = S.forward_unroll(x, h0, P, "sigmoid", flags=SP), S.forward_unroll(xb, h0, P, "sigmoid", flags=SP | BFT)
+    S.assert_same_bits(o_bft[0], o_tm[0], "hs"); S.assert_same_bits(o_bft[1], o_tm[1], "z")
+    ref = LC.named_backward(G, x, o_tm, h0, P, "sigmoid", SP, need_dx=False)
+    got = LC.named_backward(G, xb, o_bft, h0, P, "sigmoid", SP | BFT, need_dx=False)
     torch.cuda.synchronize()
     assert got["d_x"].numel() == 0
-    for k in NAMES[1:8]:
-        _same_bits(got[k], ref[k], k)
+    for k in S.GRAD_NAMES[1:8]:
+        S.assert_same_bits(got[k], ref[k], k)
 
 
 def test_same_bits_after_cu_state_is_poisoned():
     """The new staging code reads no LDS it did not write: NaNs left in every CU's LDS and registers change nothing."""
     T, B, F, H = 33, 37, 64, 256
-    x, xb, h0, G = _data(T, B, F, H, seed=7)
-    P = _params(F, H, seed=3)
-    o_tm = _forward(x, h0, P, "sigmoid", SP)
-    ref = _backward(G, x, o_tm, h0, P, "sigmoid", SP)
+    x, xb, h0, G = LC.bft_data(T, B, F, H, seed=7)
+    P = LC.bft_params(F, H, seed=3)
+    o_tm = S.forward_unroll(x, h0, P, "sigmoid", flags=SP)
+    ref = LC.named_backward(G, x, o_tm, h0, P, "sigmoid", SP)
     torch.cuda.synchronize()
     assert _lib.load().fastgrnn_hip_debug_poison_cu_state(0x7fc00000, None) == 0
-    o_bft = _forward(xb, h0, P, "sigmoid", SP | BFT)
+    o_bft = S.forward_unroll(xb, h0, P, "sigmoid", flags=SP | BFT)
     assert _lib.load().fastgrnn_hip_debug_poison_cu_state(0x7fc00000, None) == 0
-    got = _backward(G, xb, o_bft, h0, P, "sigmoid", SP | BFT)
+    got = LC.named_backward(G, xb, o_bft, h0, P, "sigmoid", SP | BFT)
     torch.cuda.synchronize()
-    _same_bits(o_bft[0], o_tm[0], "hs"); _same_bits(o_bft[1], o_tm[1], "z")
-    _same_bits(got["d_x"], ref["d_x"].permute(1, 2, 0), "d_x")
-    for k in NAMES[1:8]:
-        _same_bits(got[k], ref[k], k)
+    S.assert_same_bits(o_bft[0], o_tm[0], "hs"); S.assert_same_bits(o_bft[1], o_tm[1], "z")
+    S.assert_same_bits(got["d_x"], ref["d_x"].permute(1, 2, 0), "d_x")
+    for k in S.GRAD_NAMES[1:8]:
+        S.assert_same_bits(got[k], ref[k], k)
 
 
 # ---- modules ------------------------------------------------------------------------------------------------
@@ -228,9 +169,9 @@ def test_module_takes_the_trainers_view_without_a_copy(F, H, monkeypatch):
     (inp, flags), = spy.calls
     assert flags & BFT and flags & SP
     assert inp.data_ptr() == a.data_ptr() and tuple(inp.shape) == (B, F, T) and inp.is_contiguous()
-    _same_bits(hs_v, hs_c, "hs"); _same_bits(dx_v, dx_c, "audio.grad")
+    S.assert_same_bits(hs_v, hs_c, "hs"); S.assert_same_bits(dx_v, dx_c, "audio.grad")
     for (name, _), u, v in zip(m.named_parameters(), g_v, g_c):
-        _same_bits(u, v, name)
+        S.assert_same_bits(u, v, name)
 
 
 @pytest.mark.parametrize("F,H", [(64, 256), (32, 128)])
@@ -250,7 +191,7 @@ def test_module_inference_takes_the_view_and_saves_nothing(F, H, last_state, mon
     assert flags & BFT and not flags & SP and bool(flags & LAST) == last_state
     assert inp.data_ptr() == audio.data_ptr() and tuple(inp.shape) == (B, F, T)
     assert tuple(out.shape) == ((B, H) if last_state else (T, B, H))
-    _same_bits(out, ref, "no_grad output")
+    S.assert_same_bits(out, ref, "no_grad output")
 
 
 def test_delta_model_training_step_from_the_view():
@@ -272,31 +213,26 @@ def test_delta_model_training_step_from_the_view():
 
     l_c, g_c = step(audio.permute(2, 0, 1).contiguous())
     l_v, g_v = step(audio.permute(2, 0, 1))
-    _same_bits(l_v.reshape(1), l_c.reshape(1), "loss")
+    S.assert_same_bits(l_v.reshape(1), l_c.reshape(1), "loss")
     for (name, _), u, v in zip(model.named_parameters(), g_v, g_c):
-        _same_bits(u, v, name)
+        S.assert_same_bits(u, v, name)
 
 
 def test_delta_layer1_against_the_reference_cell():
     """tests/golden/g13_delta64_l1_f32.npz (T=99, B=4, F=64, H=256, written from the reference's own cell), fed as
     [B,F,T] with the flag, under the bounds tests/test_hip_parity.py::test_golden_vectors holds every golden to."""
     from tests.conftest import load_golden
-    from tests.test_hip_parity import _check_grads, _scalar_abs_sums
     g = load_golden("g13_delta64_l1_f32")
     T, B, F = g["x"].shape
     H = g["h0"].shape[-1]
     assert (T, B, F, H) == (99, 4, 64, 256) and g["dtype"] != "f64"
-    p = g["params"]
-    e = torch.empty(0, device=DEV)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    P = dict(w=t(p["w"]), u=t(p["u"]), w1=e, w2=e, u1=e, u2=e, bias_gate=t(p["bias_gate"]),
-             bias_update=t(p["bias_update"]), zeta=t(p["zeta"]), nu=t(p["nu"]))
-    xb = t(g["x"]).permute(1, 2, 0).contiguous()
-    h0, G = t(g["h0"]), t(g["G"])
+    P = S.cell_tensors(g["params"])
+    xb = S.to_dev(g["x"]).permute(1, 2, 0).contiguous()
+    h0, G = S.to_dev(g["h0"]), S.to_dev(g["G"])
     for direction in (0, 1):
-        assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=GATE[g["gate"]], direction=direction, flags=BFT) == 2
-    outs = _forward(xb, h0, P, g["gate"], BFT)
-    grads = _backward(G, xb, outs, h0, P, g["gate"], BFT)
+        assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=S.NONLINEARITY[g["gate"]], direction=direction, flags=BFT) == 2
+    outs = S.forward_unroll(xb, h0, P, g["gate"], flags=BFT)
+    grads = LC.named_backward(G, xb, outs, h0, P, g["gate"], BFT)
     torch.cuda.synchronize()
     err = float(np.abs(outs[0].cpu().numpy() - g["hs"]).max())
     print("g13 [B,F,T]: max|hs - reference| %.3g (bound 1e-5)" % err)
@@ -304,8 +240,9 @@ def test_delta_layer1_against_the_reference_cell():
     got = {k: v.cpu().numpy() for k, v in grads.items() if v.numel()}
     got["d_x"] = grads["d_x"].permute(2, 0, 1).contiguous().cpu().numpy()
     ref = dict(g["dparams"]); ref["d_x"] = g["dx"]; ref["d_h0"] = g["dh0"]
-    ref.update(_scalar_abs_sums(g["G"], g["x"], g["params"], g["h0"], g["gate"], g["update"]))
-    _check_grads(got, ref, 2e-5, "g13 [B,F,T]")
+    g_o = S.oracle64(g["x"], g["G"], g["params"], g["h0"], g["gate"], g["update"])[3]
+    ref["_abs_zeta"], ref["_abs_nu"] = g_o["_abs_zeta"], g_o["_abs_nu"]
+    S.check_grads(got, ref, tol=2e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag="g13 [B,F,T]")
 
 
 def test_trained_batchnorm_model_takes_the_view_on_layer_1(monkeypatch):
@@ -327,6 +264,6 @@ def test_trained_batchnorm_model_takes_the_view_on_layer_1(monkeypatch):
     (i1, f1), (_, f2), (_, f3) = spy.calls
     assert f1 & BFT and not f2 & BFT and not f3 & BFT
     assert i1.data_ptr() == audio.data_ptr() and tuple(i1.shape) == tuple(audio.shape)
-    _same_bits(out, ref, "log-probs")
+    S.assert_same_bits(out, ref, "log-probs")
     for l, (a, b) in enumerate(zip(m.hidden_states, ref_states)):
-        _same_bits(a, b, "layer %d state" % l)
+        S.assert_same_bits(a, b, "layer %d state" % l)

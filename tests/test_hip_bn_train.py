@@ -23,83 +23,19 @@ def _dev():
     return torch.device("cuda", 0)
 
 
-def random_case(F, H, T, B, gate, seed, momentum=0.1):
-    g = np.random.default_rng(seed)
-    d = {"W": 0.3 * g.standard_normal((F, H)) / np.sqrt(F / 32), "U": 0.1 * g.standard_normal((H, H)),
-         "x": g.standard_normal((T, B, F)), "G": g.standard_normal((T, B, H)), "h0": 0.5 * g.standard_normal((B, H)),
-         "bias_gate": 0.5 * g.standard_normal((1, H)), "bias_update": 0.5 * g.standard_normal((1, H)),
-         "zeta": np.array([[0.7]]), "nu": np.array([[-2.5]]), "meta_gate": np.array(gate)}
-    for n in G.BNS:
-        d[n + "_weight"] = 1.0 + 0.5 * g.standard_normal(H)
-        d[n + "_bias"] = 0.3 * g.standard_normal(H)
-        d[n + "_running_mean"] = 0.5 * g.standard_normal(H)
-        d[n + "_running_var"] = 0.5 + g.random(H)
-        d[n + "_num_batches_tracked"] = np.int64(3)
-        d[n + "_eps"] = np.float64(1e-5)
-        d[n + "_momentum"] = np.float64(np.nan if momentum is None else momentum)
-    return d
-
-
-def run(d, dtype, batch_first=False, torch_ops=False):
-    dev = _dev()
-    m = G.build_layer(d, dev, dtype, batch_first=batch_first)
-    if dtype == torch.float32 and not torch_ops:     # the kernels' case must not land on the torch-op path
-        B = d["x"].shape[1]
-        probe = torch.empty((B, 1, d["W"].shape[0]) if batch_first else (1, B, d["W"].shape[0]), device=dev)
-        assert m._fused(probe, batch_first, B)
-    x, G_, h0 = (torch.from_numpy(np.asarray(d[k])).to(dev, dtype) for k in ("x", "G", "h0"))
-    if batch_first:
-        x, G_ = x.transpose(0, 1).contiguous(), G_.transpose(0, 1).contiguous()
-    out = G.step(m, x, h0, G_, torch_ops=torch_ops)
-    torch.cuda.synchronize()
-    hs, dx, dh0, grads, runst = out
-    if batch_first:
-        hs, dx = hs.transpose(0, 1), dx.transpose(0, 1)
-    flat = {"hs": hs, "d_x": dx, "d_h0": dh0}
-    flat.update({"grad." + k: v for k, v in grads.items()})
-    flat.update({"run." + k: v for k, v in runst.items()})
-    return {k: v.detach().double().cpu().numpy() for k, v in flat.items()}, m
-
-
-def check(got, ref64, ref32, what=""):
-    worst = 0.0
-    for k, r in ref64.items():
-        a = np.asarray(got[k]).reshape(r.shape)
-        if k.endswith("num_batches_tracked"):
-            assert np.array_equal(a, r), (what, k)
-            continue
-        err = float(np.abs(a - r).max())
-        if any(k == "grad." + z for z in G.ZERO_GRADS):
-            scale = max(float(np.abs(ref64["grad.U"]).max()), 1.0)
-            assert err <= 1e-5 * scale, (what, k, err)
-            continue
-        e32 = float(np.abs(np.asarray(ref32[k]).reshape(r.shape) - r).max())
-        b = G.bound(r, e32)
-        assert err <= b, (what, k, err, b, e32)
-        worst = max(worst, err / b)
-    return worst
-
-
-def compare(d, batch_first=False):
-    got, _ = run(d, torch.float32, batch_first=batch_first)
-    ref64, _ = run(d, torch.float64, batch_first=batch_first)            # off the kernels: the torch-op formula
-    ref32, _ = run(d, torch.float32, batch_first=batch_first, torch_ops=True)
-    return check(got, ref64, ref32, (d["W"].shape, str(d["meta_gate"]), d["x"].shape, batch_first))
-
-
 @pytest.mark.parametrize("case", G.CASES)
 def test_matches_reference_fixture(case):
     d = G.load_case(case)
-    got, m = run(d, torch.float32)
+    got, m = G.run(d, torch.float32)
     assert m._fused(torch.empty(12, d["x"].shape[1], d["W"].shape[0], device=_dev()), False, d["x"].shape[1])
-    ref32, _ = run(d, torch.float32, torch_ops=True)
+    ref32, _ = G.run(d, torch.float32, torch_ops=True)
     ehs, edx, edh0, eg, er = G.fixture_expect(d)
     ref64 = {"hs": ehs, "d_x": edx, "d_h0": edh0}
     ref64.update({"grad." + k: np.asarray(v, dtype=np.float64) for k, v in eg.items()})
     ref64.update({"run." + k: np.asarray(v) for k, v in er.items()})
-    check(got, ref64, ref32, case)
+    G.check(got, ref64, ref32, case)
     # and the fp64 torch-op formula on the GPU reproduces the fixture
-    r64, _ = run(d, torch.float64)
+    r64, _ = G.run(d, torch.float64)
     for k, v in ref64.items():
         assert np.abs(r64[k].reshape(np.shape(v)) - v).max() <= 1e-10 * max(1.0, float(np.abs(v).max())), k
 
@@ -118,20 +54,20 @@ SMALL = [pytest.param(H, F, gate, bf, B,
 @pytest.mark.parametrize("H,F,gate,batch_first,B", SMALL)
 def test_small_batches_against_fp64(H, F, gate, batch_first, B):
     i = (2, 3, 17, 128).index(B)
-    d = random_case(F, H, 7, B, gate, seed=1000 + 17 * H + F + i, momentum=None if i % 2 else 0.1)
-    compare(d, batch_first)
+    d = G.random_case(F, H, 7, B, gate, seed=1000 + 17 * H + F + i, momentum=None if i % 2 else 0.1)
+    G.compare(d, batch_first)
 
 
 @pytest.mark.parametrize("H,F", TABLE)
 def test_full_size_against_fp64(H, F):
-    d = random_case(F, H, 99, 4096, "sigmoid", seed=77 + H + F)
-    compare(d, batch_first=(F == 64))
+    d = G.random_case(F, H, 99, 4096, "sigmoid", seed=77 + H + F)
+    G.compare(d, batch_first=(F == 64))
 
 
 def test_two_calls_are_bitwise_equal():
-    d = random_case(64, 256, 20, 300, "sigmoid", seed=5)
-    a, _ = run(d, torch.float32)
-    b, _ = run(d, torch.float32)
+    d = G.random_case(64, 256, 20, 300, "sigmoid", seed=5)
+    a, _ = G.run(d, torch.float32)
+    b, _ = G.run(d, torch.float32)
     for k in a:
         assert np.array_equal(a[k], b[k]), k
 
@@ -139,7 +75,7 @@ def test_two_calls_are_bitwise_equal():
 def test_graph_replay_is_bitwise_equal_to_eager():
     from kws_amd import GraphedStep
     dev = _dev()
-    d = random_case(32, 128, 16, 200, "sigmoid", seed=9)
+    d = G.random_case(32, 128, 16, 200, "sigmoid", seed=9)
     x = torch.from_numpy(d["x"]).to(dev, torch.float32)
     Gt = torch.from_numpy(d["G"]).to(dev, torch.float32)
     m = G.build_layer(d, dev, torch.float32)
@@ -171,7 +107,7 @@ def test_graph_replay_is_bitwise_equal_to_eager():
 def test_eval_after_training_matches_fastgrnn_batchnorm():
     from kws_amd import FastGRNNBatchNorm
     dev = _dev()
-    d = random_case(64, 256, 12, 64, "sigmoid", seed=13)
+    d = G.random_case(64, 256, 12, 64, "sigmoid", seed=13)
     m = G.build_layer(d, dev, torch.float32)
     x = torch.from_numpy(d["x"]).to(dev, torch.float32)
     m(x, training=True)
@@ -190,7 +126,7 @@ def test_eval_train_eval_sees_the_new_running_statistics():
     training forward wrote (BatchNorm recalibration), like a fresh FastGRNNBatchNorm loaded from the state dict."""
     from kws_amd import FastGRNNBatchNorm
     dev = _dev()
-    d = random_case(32, 128, 12, 64, "sigmoid", seed=17)
+    d = G.random_case(32, 128, 12, 64, "sigmoid", seed=17)
     m = G.build_layer(d, dev, torch.float32)
     x = torch.from_numpy(d["x"]).to(dev, torch.float32)
     m.eval()

@@ -23,16 +23,15 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
-from tests import test_hip_parity as PAR
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from kws_amd import fastgrnn_cuda
-DEV = "cuda:0"
-SP, BFT, GL = 4, 128, 256
-NAMES = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u"]
-QT = PAR.GATE_CODE["quantTanh"]
+SP, BFT, GL = S.FLAG_SAVE_PREACT, S.FLAG_X_BFT, S.FLAG_GRAD_LAST
+NAMES = S.GRAD_NAMES[:8]
 
 #            F   gate       update       preact bf16   grad_last  [B,F,T]
 CONTRACTS = {
@@ -48,16 +47,6 @@ CONTRACTS = {
 TS = [1, 2, 3, 4, 5, 9]
 BS = [1, 16, 17, 33]
 H = 128
-
-
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
-
-
-def _same_bits(a, b, what):
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    assert torch.equal(_bits(a), _bits(b)), (what, float((a.float() - b.float()).abs().max()))
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,7 +72,7 @@ def _run(name, T, B):
     """forward once; the full backward twice and the backward without d_x once"""
     F, gate, update, preact, bf, gl, bft = CONTRACTS[name]
     p, x, G, h0 = _inputs(name, T, B)
-    P = PAR._param_tensors(p)
+    P = S.cell_tensors(p)
     dt = torch.bfloat16 if bf else torch.float32
     flags = (SP if preact else 0) | (BFT if bft else 0)
     xt = torch.from_numpy(x).to(DEV).to(dt)
@@ -91,23 +80,18 @@ def _run(name, T, B):
         xt = xt.permute(1, 2, 0).contiguous()
     Gt = torch.from_numpy(G[-1] if gl else G).to(DEV).to(dt).contiguous()
     ht = torch.from_numpy(h0).to(DEV)
-    code, ucode = PAR.GATE_CODE[gate], PAR.GATE_CODE[update]
+    code, ucode = S.NONLINEARITY[gate], S.NONLINEARITY[update]
     assert fastgrnn_cuda.kernel_path(T, B, F, H, 0, 0, code, ucode, dt, 1, flags | (GL if gl else 0)) == 2
-    outs = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], ht, code,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], update_non_linearity=ucode, flags=flags)
-    hs, a0 = outs[0], outs[1]
-    a1 = outs[2] if len(outs) > 2 else outs[1]
+    outs = S.forward_unroll(xt, ht, P, gate, update=update, flags=flags)
 
     def bwd(need_dx):
-        g = fastgrnn_cuda.backward_unroll(Gt, xt, hs, P["zeta"], P["nu"], P["w"], P["u"], a0, a1, ht, P["w1"], P["w2"],
-                                          P["u1"], P["u2"], code, update_non_linearity=ucode,
-                                          flags=flags | (GL if gl else 0), bias_gate=P["bias_gate"],
-                                          bias_update=P["bias_update"], need_dx=need_dx)
+        g = S.backward_of(outs, Gt, xt, ht, P, gate, update=update, flags=flags | (GL if gl else 0), biases=True,
+                          need_dx=need_dx)
         return dict(zip(NAMES, g[:8]))
 
     full, again, nodx = bwd(True), bwd(True), bwd(False)
     torch.cuda.synchronize()
-    return hs, a0, full, again, nodx
+    return outs[0], outs[1], full, again, nodx
 
 
 def _oracle(name, T, B, hs, pre):
@@ -144,9 +128,9 @@ def test_backward_scan_contracts_at_the_step_order_seams(name, T, B):
     # two calls, bit for bit; the call without d_x shares everything but d_x
     assert nodx["d_x"].numel() == 0
     for k in NAMES:
-        _same_bits(again[k], full[k], "second call: " + k)
+        S.assert_same_bits(again[k], full[k], "second call: " + k)
         if k != "d_x":
-            _same_bits(nodx[k], full[k], "without d_x: " + k)
+            S.assert_same_bits(nodx[k], full[k], "without d_x: " + k)
     # the oracle
     ref, tol = _oracle(name, T, B, hs, pre)
     g = dict(full)
@@ -158,5 +142,5 @@ def test_backward_scan_contracts_at_the_step_order_seams(name, T, B):
         dx = dx.to(torch.float64).cpu().numpy()
         assert (np.abs(dx - dx_ref) / np.maximum(1.0, np.abs(dx_ref))).max() <= 2.0 ** -8 + 2e-5
     else:
-        PAR._check_grads({"d_x": dx.cpu().numpy()}, {"d_x": dx_ref}, tol, (name, T, B))
-    PAR._check_grads({k: v.cpu().numpy() for k, v in g.items()}, ref, tol, (name, T, B))
+        S.check_grads({"d_x": dx}, {"d_x": dx_ref}, tol=tol, scalar_term_tol=S.SCALAR_TERM_TOL, tag=(name, T, B))
+    S.check_grads(g, ref, tol=tol, scalar_term_tol=S.SCALAR_TERM_TOL, tag=(name, T, B))

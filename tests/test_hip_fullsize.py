@@ -11,48 +11,14 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from kws_amd import _lib, fastgrnn_cuda
-DEV = "cuda:0"
 T, B, F = 99, 4096, 32
-NAMES = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _P(p):
-    e = torch.empty(0)
-    g = lambda k: _t(p[k]) if k in p else e
-    return dict(w=g("w"), u=g("u"), w1=g("w1"), w2=g("w2"), u1=g("u1"), u2=g("u2"),
-                bias_gate=_t(p["bias_gate"]), bias_update=_t(p["bias_update"]), zeta=_t(p["zeta"]), nu=_t(p["nu"]))
-
-
-def _oracle(x, G, p, h0=None):
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    x64, G64 = x.astype(np.float64), G.astype(np.float64)
-    h64 = None if h0 is None else h0.astype(np.float64)
-    hs, zs, cs = O.unroll_forward(x64, p64, h64)
-    g = O.unroll_backward(G64, x64, hs, zs, cs, p64, h64)
-    return hs, zs, cs, g
-
-
-def _rel(a, ref):
-    return float(np.abs(np.asarray(a, np.float64).reshape(ref.shape) - ref).max()) / max(1.0, float(np.abs(ref).max()))
-
-
-def _check_all(outs, g_o, tol=2e-5):
-    errs = {}
-    for n, o in zip(NAMES, outs):
-        if o.numel():
-            errs[n] = _rel(o.float().cpu().numpy(), g_o[n])
-    bad = {k: v for k, v in errs.items() if v > tol}
-    assert not bad, (bad, errs)
-    return errs
 
 
 def _inputs(H, seed, rw=None, ru=None):
@@ -68,23 +34,18 @@ def test_config2_dense_f32_full_batch_every_output_vs_fp64_oracle(contract):
     """BASELINE configs 1/2 and the metric shape: dense H=128, fp32, B=4096, both saved-tensor contracts."""
     H = 128
     p, x, G = _inputs(H, 100)
-    P = _P(p)
-    xt, Gt = _t(x), _t(G)
+    P = S.cell_tensors(p)
+    xt, Gt = S.to_dev(x), S.to_dev(G)
     h0 = torch.zeros(B, H, device=DEV)
     flags = _lib.FLAG_SAVE_PREACT if contract == "preact" else 0
     assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=1, flags=flags) == 2
-    outs = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, 0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-    gr = fastgrnn_cuda.backward_unroll(Gt, xt, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1],
-                                       outs[1] if contract == "preact" else outs[2], h0,
-                                       P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+    outs, gr = S.fwd_bwd(xt, h0, Gt, P, "sigmoid", flags=flags, biases=True)
     torch.cuda.synchronize()
-    hs_o, zs_o, cs_o, g_o = _oracle(x, G, p)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, None)
     assert np.abs(outs[0].cpu().numpy() - hs_o).max() <= 1e-5
     if contract == "reference":
         assert np.abs(outs[1].cpu().numpy() - zs_o).max() <= 1e-5 and np.abs(outs[2].cpu().numpy() - cs_o).max() <= 1e-5
-    errs = _check_all(gr, g_o)
+    errs = S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=0.0, tag="config2/" + contract)
     print("config2/%s full-size errors: %s" % (contract, {k: "%.2e" % v for k, v in errs.items()}))
 
 
@@ -94,22 +55,18 @@ def test_config3_bf16_sequences_full_batch_every_output_vs_fp64_oracle():
     oracle's values (relative 2^-8 of the element), every fp32 output to 2e-5."""
     H = 128
     p, x, G = _inputs(H, 200)
-    P = _P(p)
+    P = S.cell_tensors(p)
     xb = torch.from_numpy(x).to(torch.bfloat16)
     Gb = torch.from_numpy(G).to(torch.bfloat16)
     xt, Gt = xb.to(DEV), Gb.to(DEV)
     h0 = torch.zeros(B, H, device=DEV)
     flags = _lib.FLAG_SAVE_PREACT
     assert fastgrnn_cuda.kernel_path(T, B, F, H, dtype=torch.bfloat16, direction=1, flags=flags) == 2
-    hs, pre = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, 0,
-                                           P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-    gr = fastgrnn_cuda.backward_unroll(Gt, xt, hs, P["zeta"], P["nu"], P["w"], P["u"], pre, pre, h0,
-                                       P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+    (hs, pre), gr = S.fwd_bwd(xt, h0, Gt, P, "sigmoid", flags=flags, biases=True)
     torch.cuda.synchronize()
     xr, Gr = xb.float().numpy(), Gb.float().numpy()
     # forward: the kernel carries the state in fp32 and rounds only the stored copy
-    hs_o, zs_o, cs_o, _ = _oracle(xr, Gr, p)
+    hs_o, zs_o, cs_o = S.oracle64_forward(xr, p, None)
     hs_k = hs.float().cpu().numpy()
     assert (np.abs(hs_k - hs_o) <= 2.0 ** -8 * np.abs(hs_o) + 1e-5).all()
     # the saved pre-activation comes from the fp32 state trajectory: check it against the oracle's unrounded one
@@ -126,7 +83,8 @@ def test_config3_bf16_sequences_full_batch_every_output_vs_fp64_oracle():
     g_o = O.unroll_backward(Gr.astype(np.float64), xr.astype(np.float64), hs_r, z_r, c_r, p64)
     dx = gr[0].float().cpu().numpy()
     assert (np.abs(dx - g_o["d_x"]) <= 2.0 ** -8 * np.abs(g_o["d_x"]) + 2e-5 * max(1.0, np.abs(g_o["d_x"]).max())).all()
-    errs = _check_all([torch.empty(0)] + list(gr[1:]), g_o)
+    del g_o["d_x"]                                   # (held to bf16 rounding above)
+    errs = S.check_grads(dict(zip(S.GRAD_NAMES[1:], gr[1:])), g_o, tol=2e-5, scalar_term_tol=0.0, tag="config3")
     print("config3 full-size errors: %s" % {k: "%.2e" % v for k, v in errs.items()})
 
 
@@ -134,18 +92,14 @@ def test_config4_lowrank_full_batch_every_output_vs_fp64_oracle():
     """BASELINE config 4: H=256, wRank=uRank=16, B=4096, one-saved-tensor contract (scan + TN GEMMs)."""
     H, r = 256, 16
     p, x, G = _inputs(H, 300, r, r)
-    P = _P(p)
-    xt, Gt = _t(x), _t(G)
+    P = S.cell_tensors(p)
+    xt, Gt = S.to_dev(x), S.to_dev(G)
     h0 = torch.zeros(B, H, device=DEV)
     flags = _lib.FLAG_SAVE_PREACT
     assert fastgrnn_cuda.kernel_path(T, B, F, H, r, r, direction=1, flags=flags) == 2
-    hs, pre, m = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"],
-                                              h0, 0, P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-    gr = fastgrnn_cuda.backward_unroll(Gt, xt, hs, P["zeta"], P["nu"], P["w"], P["u"], pre, m, h0,
-                                       P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+    (hs, pre, m), gr = S.fwd_bwd(xt, h0, Gt, P, "sigmoid", flags=flags, biases=True)
     torch.cuda.synchronize()
-    hs_o, zs_o, cs_o, g_o = _oracle(x, G, p)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, None)
     assert np.abs(hs.cpu().numpy() - hs_o).max() <= 1e-5
-    errs = _check_all(gr, g_o)
+    errs = S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=0.0, tag="config4")
     print("config4 full-size errors: %s" % {k: "%.2e" % v for k, v in errs.items()})

@@ -11,12 +11,13 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
-    from kws_amd import _lib, fastgrnn_cuda
-DEV = "cuda:0"
+    from kws_amd import fastgrnn_cuda
 FAMILIES = [(32, 128, None, None), (64, 128, None, None), (256, 128, None, None), (32, 256, None, None), (32, 256, 16, 16),
             (32, 256, 7, 12), (32, 256, 32, 20), (32, 128, 8, 8), (32, 256, None, 16), (128, 128, 16, None)]
 # round 3: the reference's default first layer (64 features into 256 units), dense and factorised.  Drawn by seeds from
@@ -27,11 +28,7 @@ R3_SEEDS = list(range(200000, 200000 + 24))
 
 def _family(seed):
     return FAMILIES_R3[seed % len(FAMILIES_R3)] if seed >= 200000 else FAMILIES[seed % len(FAMILIES)]
-SAVE_PREACT, BATCH_MAJOR, X_BFT, GRAD_LAST = 4, 16, 128, 256
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+SAVE_PREACT, BATCH_MAJOR, X_BFT, GRAD_LAST = S.FLAG_SAVE_PREACT, S.FLAG_BATCH_MAJOR, S.FLAG_X_BFT, S.FLAG_GRAD_LAST
 
 
 def _block_scale(rng, n, lo=-3, hi=2):
@@ -58,7 +55,7 @@ def test_random_configuration_against_the_oracle(seed):
     F, H, rw, ru = _family(seed)
     T = int(rng.integers(1, 19)); B = int(rng.choice([1, 5, 16, 17, 33, 48, 63]))
     gate = ["sigmoid", "tanh"][int(rng.integers(0, 2))]
-    gcode = {"sigmoid": 0, "tanh": 2}[gate]
+    gcode = S.NONLINEARITY[gate]
     p = O.make_params(F, H, rw, ru, dtype=np.float32, seed=seed, randomize_scalars=True)
     for k in ("w", "u", "w2", "u2"):                       # rows in blocks
         if k in p:
@@ -90,16 +87,10 @@ def test_random_configuration_against_the_oracle(seed):
     unlay = (lambda t: t.transpose(0, 1)) if bm else (lambda t: t)
     xi = np.ascontiguousarray(x.transpose(1, 2, 0)) if bft else lay(x)
     Gi = G[-1] if gl else lay(G)
-    e = torch.empty(0)
-    P = {k: e for k in ("w", "u", "w1", "w2", "u1", "u2")}
-    P.update({k: _t(v) for k, v in p.items()})
-    outs = fastgrnn_cuda.forward_unroll(_t(xi), P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], _t(h0), gcode,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=flags & ~GRAD_LAST)
-    gr = fastgrnn_cuda.backward_unroll(_t(Gi), _t(xi), outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[-1], _t(h0),
-                                       P["w1"], P["w2"], P["u1"], P["u2"], gcode, flags=flags,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, zs_o, cs_o = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate=gate)
+    P = S.cell_tensors(p)
+    outs = S.forward_unroll(S.to_dev(xi), S.to_dev(h0), P, gate, flags=flags & ~GRAD_LAST)
+    gr = S.backward_of(outs, S.to_dev(Gi), S.to_dev(xi), S.to_dev(h0), P, gate, flags=flags, biases=True)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0, gate)
     tag = (seed, F, H, rw, ru, T, B, gate, hex(flags))
     hs = unlay(outs[0]).cpu().numpy()
     # block factors up to 4 make some draws expansive: every bound is the usual one or three times what the oracle
@@ -108,10 +99,7 @@ def test_random_configuration_against_the_oracle(seed):
     rel = lambda a: float((np.abs(a - hs_o) / np.maximum(1.0, np.abs(hs_o))).max())
     assert rel(hs) <= slack * max(2e-5, 4.0 * rel(hs_32)), (tag, rel(hs), rel(hs_32))
     g_32 = O.unroll_backward(G, x, hs_32, zs_32, cs_32, p, h0, gate=gate)
-    g_o = O.unroll_backward(G.astype(np.float64), x.astype(np.float64), hs_o, zs_o, cs_o, p64, h0.astype(np.float64), gate=gate,
-                            diagnostics=True)
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
-    g = {n: v for n, v in zip(names, gr) if v.numel()}
+    g = {n: v for n, v in zip(S.GRAD_NAMES, gr) if v.numel()}
     g["d_x"] = g["d_x"].permute(2, 0, 1) if bft else unlay(g["d_x"])
     gscale = float(np.abs(G).max())
     for k, v in g_o.items():
@@ -121,13 +109,13 @@ def test_random_configuration_against_the_oracle(seed):
         err = float(np.abs(got - v).max())
         lim = max(5e-5 * float(np.abs(v).max()), 1e-6 * gscale)
         if k in ("d_zeta", "d_nu"):
-            lim = max(lim, 2e-7 * g_o["_abs_" + k[2:]])
+            lim = max(lim, S.SCALAR_TERM_TOL * g_o["_abs_" + k[2:]])
         lim = max(lim, 4.0 * float(np.abs(g_32[k].reshape(v.shape) - v).max()))
         assert np.isfinite(got).all() and err <= slack * lim, (tag, k, err, lim)
 
 
 GATES = ["sigmoid", "relu", "tanh", "quantTanh", "quantSigm", "quantSigm4"]
-HS_LAST = 512
+HS_LAST = S.FLAG_HS_LAST
 
 
 @pytest.mark.parametrize("seed", list(range(N_SEEDS)) + [s_ for s_ in MARGINAL_FWD if s_ >= N_SEEDS] + R3_SEEDS)
@@ -167,13 +155,8 @@ def test_random_forward_all_gates_dtypes_and_last_state(seed):
         x_used = xt.to(torch.float64).numpy()
     bm, bft, last = bool(flags & BATCH_MAJOR), bool(flags & X_BFT), bool(flags & HS_LAST)
     xi = xt.permute(1, 2, 0).contiguous() if bft else (xt.transpose(0, 1).contiguous() if bm else xt)
-    e = torch.empty(0)
-    P = {k: e for k in ("w", "u", "w1", "w2", "u1", "u2")}
-    P.update({k: _t(v) for k, v in p.items()})
-    hs = fastgrnn_cuda.forward_unroll(xi.to(DEV), P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], _t(h0), gcode,
-                                      P["w1"], P["w2"], P["u1"], P["u2"], want_gates=False, flags=flags)[0]
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, _, _ = O.unroll_forward(x_used, p64, h0.astype(np.float64), gate=gate)
+    hs = S.forward_unroll(xi.to(DEV), S.to_dev(h0), S.cell_tensors(p), gate, want_gates=False, flags=flags)[0]
+    hs_o, _, _ = S.oracle64_forward(x_used, p, h0, gate)
     hs_32, _, _ = O.unroll_forward(x_used.astype(np.float32), p, h0, gate=gate)
     got = hs.to(torch.float64).cpu().numpy()
     if last:

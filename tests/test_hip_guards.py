@@ -12,24 +12,20 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from kws_amd import FastGRNNCUDA, _lib, fastgrnn_cuda, utils as U
     from kws_amd.head import head_xent
-DEV = "cuda:0"
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _fwd(x, h0, p, gate, flags=0):
-    e = torch.empty(0)
-    return fastgrnn_cuda.forward_unroll(_t(x), _t(p["w"]), _t(p["u"]), _t(p["bias_gate"]), _t(p["bias_update"]),
-                                        _t(p["zeta"]), _t(p["nu"]), _t(h0), gate, e, e, e, e, want_gates=False,
-                                        flags=flags)[0].cpu().numpy()
+    """hs alone of the cell dict ``p`` on numpy inputs, as numpy"""
+    return S.forward_unroll(S.to_dev(x), S.to_dev(h0), S.cell_tensors(p), gate, want_gates=False,
+                            flags=flags)[0].cpu().numpy()
 
 
 def test_relu_gate_state_beyond_fp16_range_matches_oracle():
@@ -46,8 +42,7 @@ def test_relu_gate_state_beyond_fp16_range_matches_oracle():
     h0 = rng.standard_normal((B, H)).astype(np.float32)
     assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=1, direction=0) == 2
     hs = _fwd(x, h0, p, 1)
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, _, _ = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate="relu")
+    hs_o, _, _ = S.oracle64_forward(x, p, h0, "relu")
     assert np.abs(hs_o).max() > 1e5 and np.isfinite(hs).all()
     # Error relative to the largest state of the same utterance and frame (single elements pass through zero while
     # their neighbours are at 1e6: what a consumer of h_t -- a dot product -- sees is the error against the row's
@@ -70,15 +65,14 @@ def test_sigmoid_gate_with_a_large_user_h0_matches_oracle(scale, B):
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     h0 = (scale * rng.uniform(0.5, 1.0, (B, H)) * rng.choice([-1.0, 1.0], (B, H))).astype(np.float32)
     hs = _fwd(x, h0, p, 0)
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, _, _ = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64))
+    hs_o, _, _ = S.oracle64_forward(x, p, h0)
     assert np.isfinite(hs).all()
     assert (np.abs(hs - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
     # a mixed batch: one workgroup tile with a large h0, the others zero -- the choice is per workgroup
     if B == 48:
         h0m = h0.copy(); h0m[16:] = 0.0
         hs_m = _fwd(x, h0m, p, 0)
-        hs_om, _, _ = O.unroll_forward(x.astype(np.float64), p64, h0m.astype(np.float64))
+        hs_om, _, _ = S.oracle64_forward(x, p, h0m)
         assert (np.abs(hs_m - hs_om) / np.maximum(1.0, np.abs(hs_om))).max() <= 1e-5
 
 
@@ -91,9 +85,7 @@ def test_nan_in_h0_stays_nan_in_bf16_outputs():
     x = torch.from_numpy(rng.standard_normal((T, B, F)).astype(np.float32)).to(torch.bfloat16).to(DEV)
     h0 = np.zeros((B, H), np.float32)
     h0[3, :] = np.frombuffer(np.uint32(0x7F800001).tobytes(), np.float32)[0]     # a NaN the integer form turned into inf
-    e = torch.empty(0)
-    hs = fastgrnn_cuda.forward_unroll(x, _t(p["w"]), _t(p["u"]), _t(p["bias_gate"]), _t(p["bias_update"]), _t(p["zeta"]),
-                                      _t(p["nu"]), _t(h0), 0, e, e, e, e, want_gates=False)[0].float().cpu().numpy()
+    hs = S.forward_unroll(x, S.to_dev(h0), S.cell_tensors(p), "sigmoid", want_gates=False)[0].float().cpu().numpy()
     assert np.isnan(hs[:, 3, :]).all()
     assert np.isfinite(np.delete(hs, 3, axis=1)).all()
 
@@ -139,13 +131,13 @@ def test_hard_threshold_support_and_count_on_device_match_numpy():
             a = rng.standard_normal(shape).astype(np.float32)
             if a.size > 4:
                 a.ravel()[:3] = a.ravel()[3]              # ties with each other
-            t = _t(a.copy())
+            t = S.to_dev(a.copy())
             out = U.hardThreshold(t, s)
             assert out is t and t.is_cuda
             ref = _np_hard_threshold(a, s)
             np.testing.assert_array_equal(t.cpu().numpy().ravel(), ref, err_msg="%s s=%g" % (shape, s))
             assert U.countNNZ(t, True) == int(np.count_nonzero(ref)) and U.countNNZ(t, False) == a.size
-            fresh = _t(a.copy())
+            fresh = S.to_dev(a.copy())
             U.supportBasedThreshold(fresh, t)
             np.testing.assert_array_equal(fresh.cpu().numpy().ravel(), np.where(ref != 0, a.ravel(), 0.0))
 
@@ -201,43 +193,23 @@ def test_weights_whose_blocks_sit_in_different_binades(H, F, r):
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
-    e = torch.empty(0)
-    P = {k: e for k in ("w", "u", "w1", "w2", "u1", "u2")}
-    P.update({k: _t(v) for k, v in p.items()})
     fl = _lib.FLAG_SAVE_PREACT
     assert fastgrnn_cuda.kernel_path(T, B, F, H, r or 0, r or 0, 0, direction=1, flags=fl) == 2
-    outs = fastgrnn_cuda.forward_unroll(_t(x), P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], _t(h0), 0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=fl)
-    gr = fastgrnn_cuda.backward_unroll(_t(G), _t(x), outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[-1], _t(h0),
-                                       P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=fl,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, zs_o, cs_o = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64))
+    outs, gr = S.fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), S.cell_tensors(p), "sigmoid", flags=fl, biases=True)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     assert (np.abs(outs[0].cpu().numpy() - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
-    g_o = O.unroll_backward(G.astype(np.float64), x.astype(np.float64), hs_o, zs_o, cs_o, p64, h0.astype(np.float64),
-                            diagnostics=True)
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
-    g = {n: v.cpu().numpy() for n, v in zip(names, gr) if v.numel()}
-    for k, v in g_o.items():
-        if k.startswith("_"):
-            continue
-        err = float(np.abs(g[k].reshape(v.shape) - v).max())
-        lim = 2e-5 * max(1.0, float(np.abs(v).max()))
-        if k in ("d_zeta", "d_nu"):
-            lim = max(lim, 2e-7 * g_o["_abs_" + k[2:]])
-        assert err <= lim, (k, err, lim)
+    S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag=(H, r))
 
 
 def test_fallback_to_the_generic_scan_warns_once():
     """A shape without matrix-pipe kernels (H = 100) at a size where it matters: one RuntimeWarning per shape and
     direction, none for shapes that are covered or too small to matter."""
     import warnings
-    e = torch.empty(0)
+
     def fwd(T, B, F, H):
         p = O.make_params(F, H, dtype=np.float32, seed=1)
         x = torch.zeros(T, B, F, device=DEV); h0 = torch.zeros(B, H, device=DEV)
-        return fastgrnn_cuda.forward_unroll(x, _t(p["w"]), _t(p["u"]), _t(p["bias_gate"]), _t(p["bias_update"]), _t(p["zeta"]),
-                                            _t(p["nu"]), h0, 0, e, e, e, e, want_gates=False)
+        return S.forward_unroll(x, h0, S.cell_tensors(p), "sigmoid", want_gates=False)
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         fwd(64, 128, 20, 100); fwd(64, 128, 20, 100)            # path 0, T*B = 8192

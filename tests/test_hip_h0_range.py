@@ -35,7 +35,7 @@ import torch
 from kws_amd import FastGRNNCUDA, _lib, fastgrnn_cuda
 from oracle import fastgrnn_oracle as O
 from tests import h0_range_cases as HC
-from tests.test_hip_parity import _copy_params
+from tests import support as S
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -44,11 +44,6 @@ SP, BM, BFT, LAST, X3 = (_lib.FLAG_SAVE_PREACT, _lib.FLAG_BATCH_MAJOR, _lib.FLAG
                          _lib.FLAG_FWD_BF16X3)
 R = 61                    # rows of the frame pool of the windowed cases
 SENTINEL = -7777.0
-GRAD_NAMES = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u"]
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 # ---- operands, computed once and left unchanged ---------------------------------------------------------------------
@@ -57,7 +52,7 @@ def _cell(H, F, rw, ru):
     p = HC.cell_params(H, F, rw, ru)
     e = torch.empty(0)
     P = {k: e for k in ("w", "u", "w1", "w2", "u1", "u2")}
-    P.update({k: _t(v) for k, v in p.items()})
+    P.update({k: S.to_dev(v) for k, v in p.items()})
     return p, P
 
 
@@ -68,13 +63,13 @@ def _scales(H):
     block = np.repeat(np.array([(0.5, 1.0, 2.0, 0.75, 1.5, 1.0, 0.6, 1.25)[k % 8] for k in range(H // 16)]), 16)
     sg = (block * (1.0 + 0.1 * rng.standard_normal(H))).astype(np.float32)
     sc = (block[::-1] * (1.0 + 0.1 * rng.standard_normal(H))).astype(np.float32)
-    return sg, sc, _t(sg), _t(sc)
+    return sg, sc, S.to_dev(sg), S.to_dev(sc)
 
 
 @functools.lru_cache(maxsize=None)
 def _pool(F):
     pool = np.random.default_rng(1000 + F).standard_normal((R, F)).astype(np.float32)
-    return pool, _t(pool)
+    return pool, S.to_dev(pool)
 
 
 @functools.lru_cache(maxsize=None)
@@ -85,7 +80,7 @@ def _starts(T):
     s[3], s[20], s[36], s[7] = 0, R - T, s[1], min(s[6] + 1, R - T)
     s = s[rng.permutation(B)].astype(np.int32)
     assert s.min() == 0 and s.max() == R - T and (np.diff(s) < 0).any()
-    return s, _t(s)
+    return s, S.to_dev(s)
 
 
 @functools.lru_cache(maxsize=None)
@@ -154,15 +149,13 @@ def _forward(c, T, h0, flags, x_tm):
     _, P = _cell(c.H, c.F, c.rw, c.ru)
     layout = "bft" if flags & BFT else ("bm" if flags & BM else "tm")
     x = _laid_out(x_tm, layout)
-    gate, update = _lib.NONLINEARITY[c.gate], _lib.NONLINEARITY[c.update]
     if c.affine:
         _, _, sg, sc = _scales(c.H)
         outs = [fastgrnn_cuda.forward_unroll_affine(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"],
-                                                    sg, sc, _t(h0), gate, update, flags=flags)]
+                                                    sg, sc, S.to_dev(h0), _lib.NONLINEARITY[c.gate],
+                                                    _lib.NONLINEARITY[c.update], flags=flags)]
     else:
-        outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], _t(h0),
-                                            gate, P["w1"], P["w2"], P["u1"], P["u2"], update_non_linearity=update,
-                                            want_gates=c.contract == "gates", flags=flags)
+        outs = S.forward_unroll(x, S.to_dev(h0), P, c.gate, update=c.update, want_gates=c.contract == "gates", flags=flags)
     return [_by_utterance(o, flags) for o in outs]
 
 
@@ -174,15 +167,6 @@ def _output_names(c):
     return {"hs": ["hs"], "gates": ["hs", "z_s", "h_prime_s"], "preact": ["hs", "pre"], "last": ["h_T"]}[c.contract]
 
 
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
 def _windows(c, T, h0, flags):
     """one call of fastgrnn_hip_forward_windows into a caller-owned hs with a sentinel block behind it and a NaN tail
     behind the pool; the output with the utterance in front"""
@@ -190,7 +174,7 @@ def _windows(c, T, h0, flags):
     _, P = _cell(c.H, c.F, 0, 0)
     sg, sc = _scales(c.H)[2:] if c.affine else (None, None)
     pool = torch.cat([_pool(c.F)[1], torch.full((T, c.F), float("nan"), device=DEV)])
-    starts, h0 = _starts(T)[1], _t(h0)
+    starts, h0 = _starts(T)[1], S.to_dev(h0)
     d = _lib.Desc(T, B, c.F, c.H, 0, 0, _lib.NONLINEARITY[c.gate], _lib.NONLINEARITY[c.update], _lib.F32, flags)
     assert lib.fastgrnn_hip_windows_supported(C.byref(d)) == 1
     nbytes = int(lib.fastgrnn_hip_forward_windows_workspace_bytes(C.byref(d), R))
@@ -243,12 +227,12 @@ def _check_saved_preactivation(case, pre):
     hprev = np.concatenate([h0[None].astype(np.float64), hs_o[:-1]])
     w, u = p["w"].astype(np.float64), p["u"].astype(np.float64)
     pre64 = x.astype(np.float64) @ w.T + hprev @ u.T
-    S = np.abs(x).astype(np.float64) @ np.abs(w).T + np.abs(hprev) @ np.abs(u).T
+    mag = np.abs(x).astype(np.float64) @ np.abs(w).T + np.abs(hprev) @ np.abs(u).T
     pre32 = x @ p["w"].T + hprev.astype(np.float32) @ p["u"].T
     assert pre32.dtype == np.float32
-    e32 = float((np.abs(pre32 - pre64) / S).max())
+    e32 = float((np.abs(pre32 - pre64) / mag).max())
     got = pre.to(torch.float64).cpu().numpy().transpose(1, 0, 2)
-    e = float((np.abs(got - pre64) / S).max())
+    e = float((np.abs(got - pre64) / mag).max())
     print("%s: saved pre-activation e %.3g, numpy float32 %.3g" % (HC.case_id(case), e, e32))
     assert e <= 4.0 * e32, (HC.case_id(case), e, e32)
 
@@ -266,7 +250,7 @@ def test_forward_with_h0_outside_the_fp16_range(case):
         got = _windows(c, T, h0, flags)
     elif c.entry == "train_windows":
         hs, saved = fastgrnn_cuda.forward_windows_train(_pool(c.F)[1], _starts(T)[1], T, P["w"], P["u"], P["bias_gate"],
-                                                        P["bias_update"], P["zeta"], P["nu"], _t(h0),
+                                                        P["bias_update"], P["zeta"], P["nu"], S.to_dev(h0),
                                                         _lib.NONLINEARITY[c.gate], batch_major=bool(flags & BM))
         got = [_by_utterance(hs, flags), _by_utterance(saved, flags)]
     else:
@@ -298,18 +282,16 @@ def test_forward_with_h0_outside_the_fp16_range(case):
         small = _forward(c, T, h0_small, flags, x_tm)
         for n, g, a, b in zip(names, got, x3, small):
             # (a) the same arithmetic as the three-plane call, tile by tile
-            assert _same_bits(g[fallback & fine], a[fallback & fine]), (HC.case_id(case), n, "fallback tile differs from FWD_BF16X3",
-                                                                       int((_bits(g[fallback & fine]) != _bits(a[fallback & fine])).sum()))
+            S.assert_same_bits(g[fallback & fine], a[fallback & fine],
+                               "%s %s: fallback tile differs from FWD_BF16X3" % (HC.case_id(case), n))
             # (b) per workgroup: the other tiles are those of the call without the large rows
             rest = ~fallback & fine
-            assert _same_bits(g[rest], b[rest]), (HC.case_id(case), n, "a tile inside the range changed",
-                                                  int((_bits(g[rest]) != _bits(b[rest])).sum()))
+            S.assert_same_bits(g[rest], b[rest], "%s %s: a tile inside the range changed" % (HC.case_id(case), n))
     elif c.ref == "unroll":
         # the windowed scans change addresses, not arithmetic: the bits of the existing forward on the gathered windows
         want = _forward(c, T, h0, flags | (SP if c.entry == "train_windows" else 0), x_tm)
         for n, g, a in zip(names, got, want):
-            assert _same_bits(g, a), (HC.case_id(case), n, "differs from the forward on the gathered windows",
-                                      int((_bits(g) != _bits(a)).sum()))
+            S.assert_same_bits(g, a, "%s %s: differs from the forward on the gathered windows" % (HC.case_id(case), n))
 
     if c.gate == "sigmoid":
         _check_hs_against_oracle(case, got[0], rows if nonfinite else ())
@@ -326,14 +308,11 @@ def test_backward_on_hidden_states_of_order_1e5(case):
     h0 = HC.h0_pattern(case.pattern, c.H)[0]
     x = _x(c.F, T, False, False)[1]
     G = HC.output_gradient(c.H)
-    e = torch.empty(0)
-    outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], _t(h0), 0,
-                                        e, e, e, e, flags=SP)
+    outs = S.forward_unroll(x, S.to_dev(h0), P, "sigmoid", flags=SP)
     assert float(outs[0].abs().max()) > 1e4
     _check_hs_against_oracle(case, outs[0].transpose(0, 1))
-    gr = fastgrnn_cuda.backward_unroll(_t(G), x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[-1], _t(h0),
-                                       e, e, e, e, 0, flags=SP, bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-    _check_gradients(case, {n: v.cpu().numpy() for n, v in zip(GRAD_NAMES, gr)})
+    gr = S.backward_of(outs, S.to_dev(G), x, S.to_dev(h0), P, "sigmoid", flags=SP, biases=True)
+    _check_gradients(case, {n: v.cpu().numpy() for n, v in zip(S.GRAD_NAMES[:8], gr)})
 
 
 def _check_gradients(case, g):
@@ -355,12 +334,12 @@ def test_module_forward_and_backward_with_a_large_hidden_state():
     c, T = case.cfg, case.T
     p, _ = _cell(c.H, c.F, 0, 0)
     m = FastGRNNCUDA(c.F, c.H, device=DEV)
-    _copy_params(m, p)
+    S.copy_cell_params(m, p)
     x = _x(c.F, T, False, False)[1].clone().requires_grad_(True)
-    h0 = _t(HC.h0_pattern(case.pattern, c.H)[0]).requires_grad_(True)
+    h0 = S.to_dev(HC.h0_pattern(case.pattern, c.H)[0]).requires_grad_(True)
     G = HC.output_gradient(c.H)
     hs = m(x, h0)
-    loss = (hs * _t(G)).sum()
+    loss = (hs * S.to_dev(G)).sum()
     loss.backward()
     lim = _check_hs_against_oracle(case, hs.detach().transpose(0, 1))
     hs_o = _oracle_of(case)[0]

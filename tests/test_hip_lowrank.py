@@ -8,34 +8,25 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from kws_amd import FastGRNNCUDA, fastgrnn_cuda
-DEV = "cuda:0"
-SAVE_PREACT, BATCH_MAJOR, X_BFT, GRAD_LAST, HS_LAST = 4, 16, 128, 256, 512
+SAVE_PREACT, BATCH_MAJOR, X_BFT, GRAD_LAST, HS_LAST = (S.FLAG_SAVE_PREACT, S.FLAG_BATCH_MAJOR, S.FLAG_X_BFT,
+                                                       S.FLAG_GRAD_LAST, S.FLAG_HS_LAST)
 F, H = 32, 256
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _params(rw, ru, seed=4):
     p = O.make_params(F, H, rw, ru, dtype=np.float32, seed=seed, randomize_scalars=True)
-    e = torch.empty(0)
-    P = {k: e for k in ("w", "u", "w1", "w2", "u1", "u2")}
-    P.update({k: _t(v) for k, v in p.items()})
-    return p, P
+    return p, S.cell_tensors(p)
 
 
 def _run(P, x, G, h0, flags, gate=0):
-    outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, gate,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-    gr = fastgrnn_cuda.backward_unroll(G, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[2], h0,
-                                       P["w1"], P["w2"], P["u1"], P["u2"], gate, flags=flags,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+    outs, gr = S.fwd_bwd(x, h0, G, P, gate, flags=flags, biases=True)
     return list(outs), list(gr)
 
 
@@ -86,21 +77,17 @@ def test_grad_last_and_hs_last(B, bf16, batch_major):
     (G[:, -1] if batch_major else G[-1]).copy_(gl)
     assert fastgrnn_cuda.kernel_path(T, B, F, H, r, r, 0, dtype=dt, direction=1, flags=base | GRAD_LAST) == 2
     o, g_dense = _run(P, x, G, h0, base)
-    gr = fastgrnn_cuda.backward_unroll(gl, x, o[0], P["zeta"], P["nu"], P["w"], P["u"], o[1], o[2], h0,
-                                       P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=base | GRAD_LAST,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+    gr = S.backward_of(o, gl, x, h0, P, "sigmoid", flags=base | GRAD_LAST, biases=True)
     for k in (0, 1, 2, 3, 4, 5, 8, 9, 10, 11):
         assert torch.equal(g_dense[k], gr[k]), k
     fl = HS_LAST | (BATCH_MAJOR if batch_major else 0)
     assert fastgrnn_cuda.kernel_path(T, B, F, H, r, r, 0, dtype=dt, direction=0, flags=fl) == 2
-    hl = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, 0,
-                                      P["w1"], P["w2"], P["u1"], P["u2"], want_gates=False, flags=fl)[0]
+    hl = S.forward_unroll(x, h0, P, "sigmoid", want_gates=False, flags=fl)[0]
     last = o[0][:, -1] if batch_major else o[0][-1]
     assert hl.shape == (B, H) and hl.dtype == dt
     assert float((hl.float() - last.float()).abs().max()) <= (2.0 ** -7 if bf16 else 2e-6)
     with pytest.raises(RuntimeError):                  # HS_LAST saves nothing for a backward
-        fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, 0,
-                                     P["w1"], P["w2"], P["u1"], P["u2"], flags=fl | SAVE_PREACT)
+        S.forward_unroll(x, h0, P, "sigmoid", flags=fl | SAVE_PREACT)
 
 
 @pytest.mark.parametrize("B,rw,ru", [(64, 16, 16), (37, 16, 16), (48, 8, 8)])
@@ -115,7 +102,7 @@ def test_bf16_sequences_fp32_master_grads_lowrank(B, rw, ru):
     G_bf = bf(rng.standard_normal((T, B, H)).astype(np.float32))
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, 0, dtype=torch.bfloat16, direction=1, flags=SAVE_PREACT) == 2
-    o, gr = _run(P, x_bf.to(DEV), G_bf.to(DEV), _t(h0), SAVE_PREACT)
+    o, gr = _run(P, x_bf.to(DEV), G_bf.to(DEV), S.to_dev(h0), SAVE_PREACT)
     hs, pre = o[0], o[1]
     assert hs.dtype == torch.bfloat16 and pre.dtype == torch.float32 and gr[0].dtype == torch.bfloat16
     p64 = {k: v.astype(np.float64) for k, v in p.items()}
@@ -131,8 +118,7 @@ def test_bf16_sequences_fp32_master_grads_lowrank(B, rw, ru):
     # state before it was rounded for storage -- the exact value of the function that ran -- while the oracle above
     # sees the rounded hs everywhere.  Its bound is the distance between the oracle on rounded and on exact states.
     g_x = O.unroll_backward(G64, x64, hs_o, z_k, c_k, p64, h64)
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
-    g = {n: v for n, v in zip(names, gr) if v.numel()}
+    g = {n: v for n, v in zip(S.GRAD_NAMES, gr) if v.numel()}
     dx = g.pop("d_x").to(torch.float64).cpu().numpy()
     ref = g_o.pop("d_x")
     assert (np.abs(dx - ref) / np.maximum(1.0, np.abs(ref))).max() <= 2.0 ** -8 + 2e-5
@@ -142,7 +128,7 @@ def test_bf16_sequences_fp32_master_grads_lowrank(B, rw, ru):
         err = float(np.abs(g[k].cpu().numpy().reshape(v.shape) - v).max())
         lim = 2e-5 * max(1.0, float(np.abs(v).max()))
         if k in ("d_zeta", "d_nu"):
-            lim = max(lim, 2e-7 * g_o["_abs_" + k[2:]])
+            lim = max(lim, S.SCALAR_TERM_TOL * g_o["_abs_" + k[2:]])
         if k == "d_u2":
             lim += 1.5 * float(np.abs(g_x[k] - v).max())
         assert err <= lim, (k, err, lim)
@@ -191,9 +177,7 @@ def test_other_factorised_cells_run_on_the_dense_kernels(rw, ru, B, preact, bm):
     T = 11
     rng = np.random.default_rng(5 + B)
     p = O.make_params(F, H, rw, ru, dtype=np.float32, seed=29, randomize_scalars=True)
-    e = torch.empty(0)
-    P = {k: e for k in ("w", "u", "w1", "w2", "u1", "u2")}
-    P.update({k: _t(v) for k, v in p.items()})
+    P = S.cell_tensors(p)
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
@@ -201,31 +185,17 @@ def test_other_factorised_cells_run_on_the_dense_kernels(rw, ru, B, preact, bm):
     for direction in (0, 1):
         assert fastgrnn_cuda.kernel_path(T, B, F, H, rw or 0, ru or 0, 0, direction=direction, flags=fl) == 2
     lay = (lambda a: np.ascontiguousarray(a.transpose(1, 0, 2))) if bm else (lambda a: a)
-    outs = fastgrnn_cuda.forward_unroll(_t(lay(x)), P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], _t(h0), 0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=fl)
+    outs = S.forward_unroll(S.to_dev(lay(x)), S.to_dev(h0), P, "sigmoid", flags=fl)
     assert len(outs) == (2 if preact else 3)
-    gr = fastgrnn_cuda.backward_unroll(_t(lay(G)), _t(lay(x)), outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[-1], _t(h0),
-                                       P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=fl,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+    gr = S.backward_of(outs, S.to_dev(lay(G)), S.to_dev(lay(x)), S.to_dev(h0), P, "sigmoid", flags=fl, biases=True)
     if bm:
         outs = [o.transpose(0, 1) for o in outs]
         gr = [gr[0].transpose(0, 1)] + list(gr[1:])
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, zs_o, cs_o = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64))
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     assert (np.abs(outs[0].cpu().numpy() - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
-    g_o = O.unroll_backward(G.astype(np.float64), x.astype(np.float64), hs_o, zs_o, cs_o, p64, h0.astype(np.float64),
-                            diagnostics=True)
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
-    g = {n: v.cpu().numpy() for n, v in zip(names, gr) if v.numel()}
+    g = {n: v for n, v in zip(S.GRAD_NAMES, gr) if v.numel()}
     assert set(g) == {k for k in g_o if not k.startswith("_")}
-    for k, v in g_o.items():
-        if k.startswith("_"):
-            continue
-        err = float(np.abs(g[k].reshape(v.shape) - v).max())
-        lim = 2e-5 * max(1.0, float(np.abs(v).max()))
-        if k in ("d_zeta", "d_nu"):
-            lim = max(lim, 2e-7 * g_o["_abs_" + k[2:]])
-        assert err <= lim, (k, err, lim)
+    S.check_grads(g, g_o, tol=2e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag=(rw, ru, B, preact, bm))
 
 
 def test_module_with_rank_32_trains_on_the_matrix_pipe():
@@ -245,9 +215,7 @@ def test_factorised_cells_on_the_dense_h128_kernels(Fi, Hi, rw, ru, B, flags):
     T = 10
     rng = np.random.default_rng(7 + B)
     p = O.make_params(Fi, Hi, rw, ru, dtype=np.float32, seed=31, randomize_scalars=True)
-    e = torch.empty(0)
-    P = {k: e for k in ("w", "u", "w1", "w2", "u1", "u2")}
-    P.update({k: _t(v) for k, v in p.items()})
+    P = S.cell_tensors(p)
     x = rng.standard_normal((T, B, Fi)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, Hi))).astype(np.float32)
     G = rng.standard_normal((T, B, Hi)).astype(np.float32)
@@ -256,27 +224,12 @@ def test_factorised_cells_on_the_dense_h128_kernels(Fi, Hi, rw, ru, B, flags):
     unlay = (lambda t: t.transpose(0, 1)) if bm else (lambda t: t)
     for direction in (0, 1):
         assert fastgrnn_cuda.kernel_path(T, B, Fi, Hi, rw or 0, ru or 0, 0, direction=direction, flags=flags) == 2
-    outs = fastgrnn_cuda.forward_unroll(_t(lay(x)), P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], _t(h0), 0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-    gr = fastgrnn_cuda.backward_unroll(_t(lay(G)), _t(lay(x)), outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[-1], _t(h0),
-                                       P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, zs_o, cs_o = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64))
+    outs, gr = S.fwd_bwd(S.to_dev(lay(x)), S.to_dev(h0), S.to_dev(lay(G)), P, "sigmoid", flags=flags, biases=True)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     assert (np.abs(unlay(outs[0]).cpu().numpy() - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
-    g_o = O.unroll_backward(G.astype(np.float64), x.astype(np.float64), hs_o, zs_o, cs_o, p64, h0.astype(np.float64),
-                            diagnostics=True)
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
-    g = {n: v for n, v in zip(names, gr) if v.numel()}
+    g = {n: v for n, v in zip(S.GRAD_NAMES, gr) if v.numel()}
     g["d_x"] = unlay(g["d_x"])
-    for k, v in g_o.items():
-        if k.startswith("_"):
-            continue
-        err = float(np.abs(g[k].cpu().numpy().reshape(v.shape) - v).max())
-        lim = 2e-5 * max(1.0, float(np.abs(v).max()))
-        if k in ("d_zeta", "d_nu"):
-            lim = max(lim, 2e-7 * g_o["_abs_" + k[2:]])
-        assert err <= lim, (k, err, lim)
+    S.check_grads(g, g_o, tol=2e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag=(Fi, Hi, rw, ru, B, flags))
 
 
 @pytest.mark.parametrize("B,rw,ru,bf16", [(4096, 16, 16, False), (4096 + 5, 16, 16, False), (2048, 7, 13, False), (4096, 16, 16, True)])
@@ -311,9 +264,7 @@ def test_factor_gradients_contracted_inside_the_scan(B, rw, ru, bf16):
         cat = torch.cat([parts[0][k], parts[1][k]], dim=1 if k == 0 else 0)
         assert torch.equal(g1[k], cat), k
     if not bf16:
-        gr = fastgrnn_cuda.backward_unroll(-0.5 * G, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[2], h0,
-                                           P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=SAVE_PREACT,
-                                           bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+        gr = S.backward_of(outs, -0.5 * G, x, h0, P, "sigmoid", flags=SAVE_PREACT, biases=True)
         for k in (8, 9, 10, 11):
             assert float((gr[k] + 0.5 * g1[k]).abs().max()) <= 2e-6 * max(1.0, float(g1[k].abs().max())), k
 
@@ -324,6 +275,5 @@ def test_lowrank_backward_wants_both_saved_tensors():
     x = torch.randn(5, 16, F, device=DEV); G = torch.randn(5, 16, H, device=DEV); h0 = torch.zeros(16, H, device=DEV)
     outs, _ = _run(P, x, G, h0, SAVE_PREACT)
     with pytest.raises(RuntimeError):
-        fastgrnn_cuda.backward_unroll(G, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], torch.empty(0, device=DEV), outs[2], h0,
-                                      P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=SAVE_PREACT,
-                                      bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+        S.backward_unroll(G, x, outs[0], torch.empty(0, device=DEV), outs[2], h0, P, "sigmoid", flags=SAVE_PREACT,
+                          bias_gate=P["bias_gate"], bias_update=P["bias_update"])

@@ -15,15 +15,16 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import layer_cases as LC
+from tests import support as S
+from tests.support import DEV, GRAD_NAMES as NAMES
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
-    from kws_amd import FastGRNNCUDA, GraphedStep, _lib, fastgrnn_cuda
-DEV = "cuda:0"
-SP, BM, BFT, GL, ZE, NIG = 4, 16, 128, 256, 4096, 8192
-GATE = {"sigmoid": 0, "relu": 1, "tanh": 2, "quantTanh": 3, "quantSigm": 4, "quantSigm4": 5}
-NAMES = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
+    from kws_amd import FastGRNNCUDA, GraphedStep, fastgrnn_cuda
+SP, BM, BFT, GL, ZE, NIG = (S.FLAG_SAVE_PREACT, S.FLAG_BATCH_MAJOR, S.FLAG_X_BFT, S.FLAG_GRAD_LAST, S.FLAG_ZERO_EXTEND,
+                            S.FLAG_NO_INPUT_GRAD)
 
 
 def _cases():
@@ -57,39 +58,12 @@ def _id(c):
                                      "-gl" if gl else "", B)
 
 
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
-
-
-def _same_bits(a, b, what):
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    assert torch.equal(_bits(a), _bits(b)), (what, float((a.float() - b.float()).abs().max()))
-
-
 def _params(F, H, seed, relu=False):
     p = O.make_params(F, H, dtype=np.float32, seed=seed, randomize_scalars=True)
     if relu:                                    # an unbounded gate: z = relu(U h + ...) ~ |h| would square h per step
         p["bias_gate"] = (p["bias_gate"] - 1.5).astype(np.float32)
         p["u"] = (0.1 * p["u"]).astype(np.float32)
-    t = lambda k: torch.from_numpy(np.ascontiguousarray(p[k])).to(DEV)
-    e = torch.empty(0, device=DEV)
-    return dict(w=t("w"), u=t("u"), w1=e, w2=e, u1=e, u2=e, bias_gate=t("bias_gate"), bias_update=t("bias_update"),
-                zeta=t("zeta"), nu=t("nu"))
-
-
-def _forward(x, h0, P, gate, update, flags):
-    outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0,
-                                        GATE[gate], P["w1"], P["w2"], P["u1"], P["u2"], flags=flags,
-                                        update_non_linearity=GATE[update])
-    return outs[0], outs[1], (outs[2] if len(outs) > 2 else outs[1])
-
-
-def _backward(G, x, hs, z, aux, h0, P, gate, update, flags, need_dx):
-    g = fastgrnn_cuda.backward_unroll(G, x, hs, P["zeta"], P["nu"], P["w"], P["u"], z, aux, h0, P["w1"], P["w2"],
-                                      P["u1"], P["u2"], GATE[gate], flags=flags, update_non_linearity=GATE[update],
-                                      bias_gate=P["bias_gate"], bias_update=P["bias_update"], need_dx=need_dx)
-    return dict(zip(NAMES, g))
+    return S.cell_tensors(p)
 
 
 @pytest.mark.parametrize("case", CASES, ids=_id)
@@ -100,7 +74,8 @@ def test_no_input_grad_leaves_every_other_output_bitwise(case):
     dt = torch.bfloat16 if bf else torch.float32
     for direction in (0, 1):
         for f in (flags, flags | NIG):
-            assert fastgrnn_cuda.kernel_path(T, B, F, H, 0, 0, GATE[gate], GATE[update], dt, direction, f) == 2
+            assert fastgrnn_cuda.kernel_path(T, B, F, H, 0, 0, S.NONLINEARITY[gate], S.NONLINEARITY[update], dt, direction,
+                                             f) == 2
     P = _params(F, H, seed=11 + B % 7, relu=gate == "relu")
     gen = torch.Generator(device="cpu").manual_seed(5)
     xshape = {"tm": (T, B, F), "bm": (B, T, F), "bft": (B, F, T)}[layout]
@@ -108,17 +83,18 @@ def test_no_input_grad_leaves_every_other_output_bitwise(case):
     h0 = (0.5 * torch.randn(B, H, generator=gen)).to(DEV)
     gshape = (B, H) if gl else ((B, T, H) if layout == "bm" else (T, B, H))
     G = torch.randn(gshape, generator=gen).to(DEV).to(dt)
-    hs, z, aux = _forward(x, h0, P, gate, update, flags)
-    ref = _backward(G, x, hs, z, aux, h0, P, gate, update, flags, need_dx=True)
-    nodx = _backward(G, x, hs, z, aux, h0, P, gate, update, flags, need_dx=False)      # the shim adds NIG, d_x = NULL
-    given = _backward(G, x, hs, z, aux, h0, P, gate, update, flags | NIG, need_dx=True)  # the flag with d_x given
+    outs = S.forward_unroll(x, h0, P, gate, update=update, flags=flags)
+    bwd = lambda fl, need_dx: LC.named_backward(G, x, outs, h0, P, gate, fl, need_dx=need_dx, update=update)
+    ref = bwd(flags, True)
+    nodx = bwd(flags, False)                    # the shim adds NIG, d_x = NULL
+    given = bwd(flags | NIG, True)              # the flag with d_x given
     torch.cuda.synchronize()
     assert nodx["d_x"].numel() == 0 and ref["d_x"].shape == x.shape
     for k in NAMES:
         if ref[k].numel():
-            _same_bits(given[k], ref[k], "flag with d_x given: " + k)
+            S.assert_same_bits(given[k], ref[k], "flag with d_x given: " + k)
             if k != "d_x":
-                _same_bits(nodx[k], ref[k], k)
+                S.assert_same_bits(nodx[k], ref[k], k)
     for k in ("d_u", "d_w", "d_h0", "d_zeta"):
         assert torch.isfinite(ref[k]).all(), k
 
@@ -130,13 +106,13 @@ def test_no_input_grad_is_repeatable_at_the_headline_shape():
     x = torch.randn(T, B, F, generator=gen).to(DEV)
     h0 = torch.zeros(B, H, device=DEV)
     G = torch.randn(T, B, H, generator=gen).to(DEV)
-    hs, z, aux = _forward(x, h0, P, "sigmoid", "tanh", SP)
-    ref = _backward(G, x, hs, z, aux, h0, P, "sigmoid", "tanh", SP, need_dx=True)
-    runs = [_backward(G, x, hs, z, aux, h0, P, "sigmoid", "tanh", SP, need_dx=False) for _ in range(3)]
+    outs = S.forward_unroll(x, h0, P, "sigmoid", flags=SP)
+    ref = LC.named_backward(G, x, outs, h0, P, "sigmoid", SP, need_dx=True)
+    runs = [LC.named_backward(G, x, outs, h0, P, "sigmoid", SP, need_dx=False) for _ in range(3)]
     torch.cuda.synchronize()
     for r in runs:
         for k in NAMES[1:8]:
-            _same_bits(r[k], ref[k], k)
+            S.assert_same_bits(r[k], ref[k], k)
 
 
 def test_zero_extended_route_skips_the_input_gradient():
@@ -149,13 +125,13 @@ def test_zero_extended_route_skips_the_input_gradient():
     x = torch.randn(T, B, F, generator=gen).to(DEV)
     h0 = (0.5 * torch.randn(B, H, generator=gen)).to(DEV)
     G = torch.randn(T, B, H, generator=gen).to(DEV)
-    hs, z, aux = _forward(x, h0, P, "sigmoid", "tanh", SP | ZE)
-    ref = _backward(G, x, hs, z, aux, h0, P, "sigmoid", "tanh", SP | ZE, need_dx=True)
-    nodx = _backward(G, x, hs, z, aux, h0, P, "sigmoid", "tanh", SP | ZE, need_dx=False)
+    outs = S.forward_unroll(x, h0, P, "sigmoid", flags=SP | ZE)
+    ref = LC.named_backward(G, x, outs, h0, P, "sigmoid", SP | ZE, need_dx=True)
+    nodx = LC.named_backward(G, x, outs, h0, P, "sigmoid", SP | ZE, need_dx=False)
     torch.cuda.synchronize()
     assert nodx["d_x"].numel() == 0
     for k in NAMES[1:8]:
-        _same_bits(nodx[k], ref[k], k)
+        S.assert_same_bits(nodx[k], ref[k], k)
 
 
 def _module_grads(m, x, G, requires_grad):
@@ -179,9 +155,9 @@ def test_module_parameter_gradients_do_not_depend_on_requires_grad(H, batch_firs
     hs1, g1, dx1 = _module_grads(m, x, G, True)
     hs0, g0, dx0 = _module_grads(m, x, G, False)
     assert dx1 is not None and dx0 is None
-    _same_bits(hs0, hs1, "hs")
+    S.assert_same_bits(hs0, hs1, "hs")
     for (name, _), a, b in zip(m.named_parameters(), g0, g1):
-        _same_bits(a, b, name)
+        S.assert_same_bits(a, b, name)
 
 
 def test_graph_replay_without_the_input_gradient_matches_eager():
@@ -206,6 +182,6 @@ def test_graph_replay_without_the_input_gradient_matches_eager():
     for _ in range(2):
         hs_g = gs()
         torch.cuda.synchronize()
-        _same_bits(hs_g, hs_e, "graph hs")
+        S.assert_same_bits(hs_g, hs_e, "graph hs")
         for q, v in zip(params, ge):
-            _same_bits(q.grad, v, "graph grad")
+            S.assert_same_bits(q.grad, v, "graph grad")

@@ -9,6 +9,10 @@ Tolerances (north_star: 1e-5 fp32 against the reference's CPU path):
     T*B terms whose fp32 summation order differs from ATen's; the reference's own fp32
     CPU result differs from its fp64 result by the same order (checked below).
   * fp64: 1e-12 / 1e-10.
+  * d_zeta / d_nu in fp32: additionally 2e-7 of the sum of their terms' magnitudes (S.SCALAR_TERM_TOL).
+
+How a bound becomes a limit -- the one gradient checker, the scalar-term rule and its justification -- is in
+tests/support.py; each call below states its own bound.
 """
 import zlib
 
@@ -17,74 +21,26 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import layer_cases as LC
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
-    from kws_amd import FastGRNNCUDA, FastGRNNCUDACell, _lib, fastgrnn_cuda
-DEV = "cuda:0"
-
-GATE_CODE = {"sigmoid": 0, "relu": 1, "tanh": 2, "quantTanh": 3, "quantSigm": 4, "quantSigm4": 5}
-FORCE_GENERIC = 1
-FORCE_F32_MFMA = 2
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _param_tensors(p):
-    e = torch.empty(0)
-    g = lambda k: _t(p[k]) if k in p else e
-    return dict(w=g("w"), u=g("u"), w1=g("w1"), w2=g("w2"), u1=g("u1"), u2=g("u2"),
-                bias_gate=_t(p["bias_gate"]), bias_update=_t(p["bias_update"]), zeta=_t(p["zeta"]), nu=_t(p["nu"]))
+    from kws_amd import FastGRNNCUDA, FastGRNNCUDACell, fastgrnn_cuda
 
 
 def run_hip(x, h0, G, p, gate="sigmoid", update="tanh", flags=0):
     """forward_unroll + backward_unroll through the operator module; numpy in/out."""
-    P = _param_tensors(p)
-    xt, ht, Gt = _t(x), _t(h0), _t(G)
-    hs, zs, cs = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"],
-                                              P["nu"], ht, GATE_CODE[gate], P["w1"], P["w2"], P["u1"], P["u2"],
-                                              update_non_linearity=GATE_CODE[update], flags=flags)
-    outs = fastgrnn_cuda.backward_unroll(Gt, xt, hs, P["zeta"], P["nu"], P["w"], P["u"], zs, cs, ht,
-                                         P["w1"], P["w2"], P["u1"], P["u2"], GATE_CODE[gate],
-                                         update_non_linearity=GATE_CODE[update], flags=flags)
+    (hs, zs, cs), outs = S.fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), S.cell_tensors(p), gate, update=update,
+                                   flags=flags)
     torch.cuda.synchronize()
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
-    g = {n: o.cpu().numpy() for n, o in zip(names, outs) if o.numel()}
+    g = {n: o.cpu().numpy() for n, o in zip(S.GRAD_NAMES, outs) if o.numel()}
     return hs.cpu().numpy(), zs.cpu().numpy(), cs.cpu().numpy(), g
 
 
-# d_zeta / d_nu are ONE scalar each: sums of T*B*H terms of either sign that cancel to a result 1e2..1e4 times smaller
-# than the sum of their magnitudes, so an fp32 evaluation (the reference's own included) is bounded relative to THAT
-# sum: 2e-7 of it (every term good to about three fp32 roundings).  The oracle reports it (diagnostics=True ->
-# ref["_abs_zeta"], ref["_abs_nu"]).  The common relative limit applies on top, and the BASELINE configurations meet
-# it on its own at full size (tests/test_hip_fullsize.py).
-SCALAR_TERM_TOL = 2e-7
-
-
-def _scalar_abs_sums(G, x, p, h0, gate="sigmoid", update="tanh"):
-    """sum of |terms| of d_zeta / d_nu from the fp64 oracle (for fixtures that do not carry them)"""
-    p64 = {k: np.asarray(v, np.float64) for k, v in p.items()}
-    x64, h64 = np.asarray(x, np.float64), np.asarray(h0, np.float64)
-    hs, zs, cs = O.unroll_forward(x64, p64, h64, gate=gate, update=update)
-    d = O.unroll_backward(np.asarray(G, np.float64), x64, hs, zs, cs, p64, h64, gate=gate, update=update, diagnostics=True)
-    return {"_abs_zeta": d["_abs_zeta"], "_abs_nu": d["_abs_nu"]}
-
-
-def _check_grads(g, ref, tol, tag):
-    for k, v in ref.items():
-        if k.startswith("_"):
-            continue
-        abs_err = float(np.abs(g[k].reshape(v.shape) - v).max())
-        lim = tol * max(1.0, float(np.abs(v).max()))
-        if k in ("d_zeta", "d_nu") and g[k].dtype != np.float64 and ("_abs_" + k[2:]) in ref:
-            lim = max(lim, SCALAR_TERM_TOL * ref["_abs_" + k[2:]])
-        assert abs_err <= lim, (tag, k, abs_err / max(1.0, float(np.abs(v).max())))
-
-
-@pytest.mark.parametrize("flags", [0, FORCE_F32_MFMA, FORCE_GENERIC], ids=["dispatch", "f32mfma", "generic"])
+@pytest.mark.parametrize("flags", [0, S.FLAG_FORCE_F32_MFMA, S.FLAG_FORCE_GENERIC], ids=["dispatch", "f32mfma", "generic"])
 def test_golden_vectors(golden, flags):
     """HIP vs the reference CPU cell's own outputs (tests/golden/*.npz)."""
     f64 = golden["dtype"] == "f64"
@@ -92,9 +48,10 @@ def test_golden_vectors(golden, flags):
                             golden["gate"], golden["update"], flags)
     assert np.abs(hs - golden["hs"]).max() <= (1e-12 if f64 else 1e-5), golden["name"]
     ref = dict(golden["dparams"]); ref["d_x"] = golden["dx"]; ref["d_h0"] = golden["dh0"]
-    if not f64:
-        ref.update(_scalar_abs_sums(golden["G"], golden["x"], golden["params"], golden["h0"], golden["gate"], golden["update"]))
-    _check_grads(g, ref, 1e-10 if f64 else 2e-5, golden["name"])
+    if not f64:     # the sums of |terms| of d_zeta / d_nu, which the fixtures do not carry
+        g_o = S.oracle64(golden["x"], golden["G"], golden["params"], golden["h0"], golden["gate"], golden["update"])[3]
+        ref["_abs_zeta"], ref["_abs_nu"] = g_o["_abs_zeta"], g_o["_abs_nu"]
+    S.check_grads(g, ref, tol=1e-10 if f64 else 2e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag=golden["name"])
 
 
 CASES = [
@@ -117,24 +74,8 @@ CASES = [
 ]
 
 
-def _keep_relu_gates_off_the_kink(p, x, h0, margin=1e-4):
-    """Nudge bias_gate, unit by unit, until no relu-gate pre-activation a = pre + b_z of the whole sequence lies within
-    `margin` of zero (fp64 oracle; the recurrence moves with the bias, so a few rounds).  pre is recovered from the
-    update nonlinearity's output, c = tanh(pre + b_h)."""
-    p = {k: v.copy() for k, v in p.items()}
-    for _ in range(50):
-        p64 = {k: v.astype(np.float64) for k, v in p.items()}
-        _, _, cs = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate="relu")
-        a = np.arctanh(np.clip(cs, -1 + 1e-15, 1 - 1e-15)) - p64["bias_update"] + p64["bias_gate"]
-        close = np.abs(a).reshape(-1, a.shape[-1]).min(axis=0) < 2 * margin     # units with a value near the kink
-        if not close.any():
-            return p
-        p["bias_gate"][0, close] += np.float32(7 * margin)
-    raise AssertionError("could not move the relu gates off the kink")
-
-
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "T%dB%dF%dH%dr%d-%d%s" % c)
-@pytest.mark.parametrize("flags", [0, FORCE_F32_MFMA, FORCE_GENERIC], ids=["dispatch", "f32mfma", "generic"])
+@pytest.mark.parametrize("flags", [0, S.FLAG_FORCE_F32_MFMA, S.FLAG_FORCE_GENERIC], ids=["dispatch", "f32mfma", "generic"])
 def test_seeded_vs_oracle_fp32(case, flags):
     T, B, F, H, rw, ru, gate = case
     rng = np.random.default_rng(zlib.crc32(repr(case).encode()))
@@ -149,20 +90,17 @@ def test_seeded_vs_oracle_fp32(case, flags):
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
     if gate == "relu":
-        p = _keep_relu_gates_off_the_kink(p, x, h0)
+        p = S.keep_relu_gates_off_the_kink(p, x, h0)
     hs, zs, cs, g = run_hip(x, h0, G, p, gate, flags=flags)
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, zs_o, cs_o = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate=gate)
-    g_o = O.unroll_backward(G.astype(np.float64), x.astype(np.float64), hs_o, zs_o, cs_o, p64,
-                            h0.astype(np.float64), gate=gate, diagnostics=True)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0, gate)
     # 1e-5 absolute while |h| <= 1, relative beyond (a tanh/relu gate does not bound h)
     assert (np.abs(hs - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
     assert (np.abs(zs - zs_o) / np.maximum(1.0, np.abs(zs_o))).max() <= 1e-5 and np.abs(cs - cs_o).max() <= 1e-5
     # relu included: its derivative jumps at zero, but no gate pre-activation of these cases comes within 1e-4 of the
-    # kink (_keep_relu_gates_off_the_kink), 1e2 times what fp32 and fp64 can differ by there -- the masks agree, and the
+    # kink (S.keep_relu_gates_off_the_kink), 1e2 times what fp32 and fp64 can differ by there -- the masks agree, and the
     # comparison is the fp64 one of every other gate.  (Round 2 compared the relu cases with the oracle run in fp32 on
     # the kernel's OWN z: a same-mask self-consistency check.)
-    _check_grads(g, g_o, 2e-5, case)
+    S.check_grads(g, g_o, tol=2e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag=case)
 
 
 @pytest.mark.parametrize("lowrank", [False, True])
@@ -175,7 +113,7 @@ def test_seeded_vs_oracle_fp64(lowrank):
     hs_o, zs_o, cs_o = O.unroll_forward(x, p, h0)
     g_o = O.unroll_backward(G, x, hs_o, zs_o, cs_o, p, h0)
     assert np.abs(hs - hs_o).max() <= 1e-12
-    _check_grads(g, g_o, 1e-10, "fp64")
+    S.check_grads(g, g_o, tol=1e-10, scalar_term_tol=S.SCALAR_TERM_TOL, tag="fp64")
 
 
 @pytest.mark.parametrize("B", [64, 45, 1, 16])
@@ -189,25 +127,12 @@ def test_preact_mode_vs_oracle(B):
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
-    P = _param_tensors(p)
-    xt, ht, Gt = _t(x), _t(h0), _t(G)
-    SAVE_PREACT = 4
-    hs, pre = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], ht,
-                                           0, P["w1"], P["w2"], P["u1"], P["u2"], flags=SAVE_PREACT)
-    outs = fastgrnn_cuda.backward_unroll(Gt, xt, hs, P["zeta"], P["nu"], P["w"], P["u"], pre, pre, ht,
-                                         P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=SAVE_PREACT,
-                                         bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    x64, h64 = x.astype(np.float64), h0.astype(np.float64)
-    hs_o, zs_o, cs_o = O.unroll_forward(x64, p64, h64)
-    hprev = np.concatenate([h64[None], hs_o[:-1]], 0)
-    pre_o = x64 @ p64["w"].T + hprev @ p64["u"].T
+    (hs, pre), outs = S.fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), S.cell_tensors(p), "sigmoid",
+                                flags=S.FLAG_SAVE_PREACT, biases=True)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     assert np.abs(hs.cpu().numpy() - hs_o).max() <= 1e-5
-    assert np.abs(pre.cpu().numpy() - pre_o).max() <= 1e-5
-    g_o = O.unroll_backward(G.astype(np.float64), x64, hs_o, zs_o, cs_o, p64, h64, diagnostics=True)
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u"]
-    g = {n: o.cpu().numpy() for n, o in zip(names, outs[:8])}
-    _check_grads(g, g_o, 2e-5, "preact")
+    assert np.abs(pre.cpu().numpy() - S.dense_preactivation64(x, p, h0, hs_o)).max() <= 1e-5
+    S.check_grads(outs, g_o, tol=2e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag="preact")
 
 
 @pytest.mark.parametrize("T,B,gate,rw,ru", [(1, 16, 0, 16, 16), (6, 37, 0, 16, 16), (7, 64, 0, 16, 16), (9, 130, 0, 16, 16),
@@ -229,24 +154,17 @@ def test_lowrank_preact_contract_vs_oracle(T, B, gate, rw, ru):
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
-    P = _param_tensors(p)
-    xt, ht, Gt = _t(x), _t(h0), _t(G)
-    SAVE_PREACT = 4
-    assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, gate, direction=1, flags=SAVE_PREACT) == 2
+    assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, gate, direction=1, flags=S.FLAG_SAVE_PREACT) == 2
     assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, gate, direction=1) != 2
-    hs, pre, m = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"],
-                                              P["nu"], ht, gate, P["w1"], P["w2"], P["u1"], P["u2"],
-                                              flags=SAVE_PREACT)
+    (hs, pre, m), outs = S.fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), S.cell_tensors(p), gate,
+                                   flags=S.FLAG_SAVE_PREACT, biases=True)
     assert m.shape == (T * B, 32)                 # [U1.h | W1.x], each zero-extended to 16 columns, time-major
     m4 = m.cpu().numpy().reshape(T, B, 32)
     assert not m4[..., ru:16].any() and not m4[..., 16 + rw:].any()
     m_k = np.concatenate([m4[..., :ru], m4[..., 16:16 + rw]], -1)
-    outs = fastgrnn_cuda.backward_unroll(Gt, xt, hs, P["zeta"], P["nu"], P["w"], P["u"], pre, m, ht,
-                                         P["w1"], P["w2"], P["u1"], P["u2"], gate, flags=SAVE_PREACT,
-                                         bias_gate=P["bias_gate"], bias_update=P["bias_update"])
     p64 = {k: v.astype(np.float64) for k, v in p.items()}
     x64, h64 = x.astype(np.float64), h0.astype(np.float64)
-    hs_o, zs_o, cs_o = O.unroll_forward(x64, p64, h64, gate=GN[gate])
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0, GN[gate])
     hprev = np.concatenate([h64[None], hs_o[:-1]], 0)
     m_o = np.concatenate([hprev @ p64["u1"].T, x64 @ p64["w1"].T], -1)
     pre_o = m_o[..., ru:] @ p64["w2"].T + m_o[..., :ru] @ p64["u2"].T
@@ -254,7 +172,6 @@ def test_lowrank_preact_contract_vs_oracle(T, B, gate, rw, ru):
     assert rel(hs.cpu().numpy(), hs_o) <= 1e-5
     assert rel(m_k, m_o) <= 1e-5
     assert rel(pre.cpu().numpy(), pre_o) <= 1e-5
-    g_o = O.unroll_backward(G.astype(np.float64), x64, hs_o, zs_o, cs_o, p64, h64, gate=GN[gate], diagnostics=True)
     tol = 2e-5
     if gate == 1:      # same mask as the HIP path: the oracle in fp32 on the kernel's own states
         hsn = hs.cpu().numpy()
@@ -262,11 +179,8 @@ def test_lowrank_preact_contract_vs_oracle(T, B, gate, rw, ru):
         ck = np.tanh(pre.cpu().numpy() + p["bias_update"]).astype(np.float32)
         g_o = O.unroll_backward(G, x, hsn, zk, ck, p, h0, gate=GN[gate])
         tol = 5e-5
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u",
-             "d_w1", "d_w2", "d_u1", "d_u2"]
     assert outs[6].numel() == 0 and outs[7].numel() == 0
-    g = {n: o.cpu().numpy() for n, o in zip(names, outs) if o.numel()}
-    _check_grads(g, g_o, tol, "lowrank-preact")
+    S.check_grads(outs, g_o, tol=tol, scalar_term_tol=S.SCALAR_TERM_TOL, tag="lowrank-preact")
 
 
 def test_single_step_operators():
@@ -277,10 +191,10 @@ def test_single_step_operators():
     x = rng.standard_normal((B, F)).astype(np.float32)
     h = rng.standard_normal((B, H)).astype(np.float32)
     G = rng.standard_normal((B, H)).astype(np.float32)
-    P = _param_tensors(p)
-    new_h, z, c = fastgrnn_cuda.forward(_t(x), P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"],
-                                        _t(h), 0, P["w1"], P["w2"], P["u1"], P["u2"])
-    outs = fastgrnn_cuda.backward(_t(G), _t(x), _t(h), P["zeta"], P["nu"], P["w"], P["u"], z, c,
+    P = S.cell_tensors(p)
+    new_h, z, c = fastgrnn_cuda.forward(S.to_dev(x), P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"],
+                                        S.to_dev(h), 0, P["w1"], P["w2"], P["u1"], P["u2"])
+    outs = fastgrnn_cuda.backward(S.to_dev(G), S.to_dev(x), S.to_dev(h), P["zeta"], P["nu"], P["w"], P["u"], z, c,
                                   P["w1"], P["w2"], P["u1"], P["u2"], 0)
     assert len(outs) == 12 and outs[8].numel() == 0 and outs[6].shape == (H, F) and outs[0].shape == (B, F)
     p64 = {k: v.astype(np.float64) for k, v in p.items()}
@@ -290,14 +204,6 @@ def test_single_step_operators():
     assert np.abs(outs[0].cpu().numpy() - g_o["d_x"][0]).max() <= 2e-5
     assert np.abs(outs[5].cpu().numpy() - g_o["d_h0"]).max() <= 2e-5
     assert np.abs(outs[7].cpu().numpy() - g_o["d_u"]).max() <= 2e-5 * max(1, np.abs(g_o["d_u"]).max())
-
-
-def _copy_params(m, p):
-    with torch.no_grad():
-        for k, attr in (("w", "W"), ("u", "U"), ("w1", "W1"), ("w2", "W2"), ("u1", "U1"), ("u2", "U2"),
-                        ("bias_gate", "bias_gate"), ("bias_update", "bias_update"), ("zeta", "zeta"), ("nu", "nu")):
-            if k in p:
-                getattr(m, attr).copy_(torch.from_numpy(p[k]))
 
 
 @pytest.mark.parametrize("batch_first", [False, True])
@@ -315,8 +221,7 @@ def test_module_autograd_matches_cpu_port(batch_first, lowrank):
         F = 64 if lowrank == "dense256f64" else F    # H = 256 scans, [B,T,.] indexed in place under batch_first
         H, rw, ru, lowrank = 256, None, None, False
     if H == 256 and rw is None and batch_first:
-        from kws_amd import _lib as _l
-        assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=1, flags=_l.FLAG_SAVE_PREACT | _l.FLAG_BATCH_MAJOR) == 2
+        assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=1, flags=S.FLAG_SAVE_PREACT | S.FLAG_BATCH_MAJOR) == 2
     cell = FastGRNNCellPort(F, H, wRank=rw, uRank=ru)
     with torch.no_grad():
         cell.bias_gate.add_(0.3 * torch.randn_like(cell.bias_gate)); cell.zeta.fill_(0.4); cell.nu.fill_(-3.0)
@@ -377,7 +282,7 @@ def test_error_behaviour_mirrors_check_input():
     """fastgrnn_cuda.cpp:69-71: non-CUDA / non-contiguous operands raise RuntimeError."""
     F, H, T, B = 32, 128, 4, 6
     p = O.make_params(F, H)
-    P = _param_tensors(p)
+    P = S.cell_tensors(p)
     x = torch.randn(T, B, F, device=DEV)
     h0 = torch.zeros(B, H, device=DEV)
     args = lambda xx, hh: (xx, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], hh, 0,
@@ -398,11 +303,10 @@ def test_runs_on_current_stream_and_is_reentrant():
     SURVEY section 0.5): two side streams produce the same result as the default stream."""
     T, B, F, H = 20, 40, 32, 128
     p = O.make_params(F, H, seed=4)
-    P = _param_tensors(p)
+    P = S.cell_tensors(p)
     x = torch.randn(T, B, F, device=DEV)
     h0 = torch.zeros(B, H, device=DEV)
-    call = lambda: fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"],
-                                                P["nu"], h0, 0, P["w1"], P["w2"], P["u1"], P["u2"])[0]
+    call = lambda: S.forward_unroll(x, h0, P, "sigmoid")[0]
     base = call()
     torch.cuda.synchronize()
     outs = []
@@ -423,18 +327,16 @@ def _northstar(B, seed=0):
     x = torch.randn(T, B, F, generator=g).to(DEV)
     G = torch.randn(T, B, H, generator=g).to(DEV)
     p = O.make_params(F, H, seed=seed)
-    return x, G, p, _param_tensors(p)
+    return x, G, p, S.cell_tensors(p)
 
 
 def _fwd(x, P, h0=None, flags=0):
     h0 = torch.zeros(x.shape[1], P["u"].shape[0] if P["u"].numel() else P["u2"].shape[0], device=DEV) if h0 is None else h0
-    return fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, 0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
+    return S.forward_unroll(x, h0, P, "sigmoid", flags=flags)
 
 
 def _bwd(G, x, hs, zs, cs, P, h0, flags=0):
-    return fastgrnn_cuda.backward_unroll(G, x, hs, P["zeta"], P["nu"], P["w"], P["u"], zs, cs, h0,
-                                         P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags)
+    return S.backward_unroll(G, x, hs, zs, cs, h0, P, "sigmoid", flags=flags)
 
 
 def test_full_size_batch_independence_and_generic_agreement():
@@ -452,10 +354,9 @@ def test_full_size_batch_independence_and_generic_agreement():
     assert torch.equal(hs[:, lo:hi], hs_s)
     hs_r, _, _ = _fwd(x[:, lo:hi - 3].contiguous(), P)
     assert (hs[:, lo:hi - 3] - hs_r).abs().max() <= 2e-6
-    hs_g, zs_g, cs_g = _fwd(x, P, flags=FORCE_GENERIC)
+    hs_g, zs_g, cs_g = _fwd(x, P, flags=S.FLAG_FORCE_GENERIC)
     assert (hs - hs_g).abs().max() <= 1e-5
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, _, _ = O.unroll_forward(x[:, lo:hi].cpu().numpy().astype(np.float64), p64)
+    hs_o, _, _ = S.oracle64_forward(x[:, lo:hi].cpu().numpy(), p, None)
     assert np.abs(hs[:, lo:hi].cpu().numpy() - hs_o).max() <= 1e-5
 
 
@@ -485,27 +386,22 @@ def test_full_size_backward_linearity_and_shard_sum():
         assert (s - g1[i]).abs().max() <= 4e-5 * max(1.0, float(g1[i].abs().max())), i
     assert torch.allclose(torch.cat([parts[0][0], parts[1][0]], 1), g1[0], atol=1e-6, rtol=0)
     # the generic path AND the dispatched one against the fp64 oracle on the whole batch
-    gg = _bwd(G, x, hs, zs, cs, P, h0, flags=FORCE_GENERIC)
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    x64, G64 = x.cpu().numpy().astype(np.float64), G.cpu().numpy().astype(np.float64)
-    hs_o, zs_o, cs_o = O.unroll_forward(x64, p64)
-    g_o = O.unroll_backward(G64, x64, hs_o, zs_o, cs_o, p64, diagnostics=True)
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u"]
+    gg = _bwd(G, x, hs, zs, cs, P, h0, flags=S.FLAG_FORCE_GENERIC)
+    g_o = S.oracle64(x.cpu().numpy(), G.cpu().numpy(), p, None)[3]
     for tag, got in (("dispatch", g1), ("generic", gg)):
-        _check_grads({n: o.cpu().numpy() for n, o in zip(names, got[:8])}, g_o, 2e-5, tag)
+        S.check_grads(got, g_o, tol=2e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag=tag)
 
 
 def test_lowrank_config4_shape_vs_oracle_sample():
     """config (4): H=256, wRank=uRank=16, B=4096; sampled utterances vs fp64 oracle."""
     T, B, F, H, r = 99, 4096, 32, 256, 16
     p = O.make_params(F, H, r, r, seed=9)
-    P = _param_tensors(p)
+    P = S.cell_tensors(p)
     g = torch.Generator().manual_seed(5)
     x = torch.randn(T, B, F, generator=g).to(DEV)
     hs, zs, cs = _fwd(x, P)
     idx = [0, 17, 2048, 4095]
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, _, _ = O.unroll_forward(x[:, idx].cpu().numpy().astype(np.float64), p64)
+    hs_o, _, _ = S.oracle64_forward(x[:, idx].cpu().numpy(), p, None)
     assert np.abs(hs[:, idx].cpu().numpy() - hs_o).max() <= 1e-5
 
 
@@ -516,24 +412,20 @@ def test_run_to_run_bitwise_repeatability():
     backward)."""
     T = 99
     # (H, rank, B, flags, F): 8-wave kernels under both saved-tensor contracts, the low-rank pair, the 4-wave
-    # forward (8), the fp32-MFMA path (2), the headline batch, and the stack's layers (wide input; H = 256)
-    for (H, r, B, flags, F) in ((128, 0, 1024, 4, 32), (256, 16, 512, 4, 32), (128, 0, 1008, 0, 32), (128, 0, 1024, 4 | 8, 32),
-                                (128, 0, 512, 2, 32), (256, 16, 512, 0, 32), (128, 0, 4096, 4, 32), (128, 0, 1024, 4, 256),
-                                (256, 0, 1024, 4, 32), (256, 0, 1000, 0, 32)):
+    # forward, the fp32-MFMA path, the headline batch, and the stack's layers (wide input; H = 256)
+    SP, W4, F32 = S.FLAG_SAVE_PREACT, S.FLAG_FWD_4WAVE, S.FLAG_FORCE_F32_MFMA
+    for (H, r, B, flags, F) in ((128, 0, 1024, SP, 32), (256, 16, 512, SP, 32), (128, 0, 1008, 0, 32), (128, 0, 1024, SP | W4, 32),
+                                (128, 0, 512, F32, 32), (256, 16, 512, 0, 32), (128, 0, 4096, SP, 32), (128, 0, 1024, SP, 256),
+                                (256, 0, 1024, SP, 32), (256, 0, 1000, 0, 32)):
         p = O.make_params(F, H, r or None, r or None, seed=21)
-        P = _param_tensors(p)
+        P = S.cell_tensors(p)
         g = torch.Generator().manual_seed(3)
         x = torch.randn(T, B, F, generator=g).to(DEV)
         G = torch.randn(T, B, H, generator=g).to(DEV)
         h0 = torch.zeros(B, H, device=DEV)
         first = None
         for rep in range(12):
-            outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"],
-                                                h0, 0, P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-            aux2 = outs[2] if len(outs) > 2 else outs[1]
-            gr = fastgrnn_cuda.backward_unroll(G, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], aux2, h0,
-                                               P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags,
-                                               bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+            outs, gr = S.fwd_bwd(x, h0, G, P, "sigmoid", flags=flags, biases=True)
             allo = [o for o in list(outs) + list(gr) if o.numel()]
             if first is None:
                 first = [o.clone() for o in allo]
@@ -547,21 +439,17 @@ def test_batch_major_layout_equals_time_major(B, preact):
     """FLAG_BATCH_MAJOR (N1: the trainer's batch_first layout indexed in place, rnn.py:812-813,823-825):
     same arithmetic per utterance, so every output equals the time-major run bit for bit."""
     T, F, H = 23, 32, 128
-    BATCH_MAJOR, SAVE_PREACT = 16, 4
+    BATCH_MAJOR, SAVE_PREACT = S.FLAG_BATCH_MAJOR, S.FLAG_SAVE_PREACT
     p = O.make_params(F, H, seed=4, randomize_scalars=True)
-    P = _param_tensors(p)
+    P = S.cell_tensors(p)
     g = torch.Generator().manual_seed(9)
     x = torch.randn(T, B, F, generator=g).to(DEV)
     G = torch.randn(T, B, H, generator=g).to(DEV)
     h0 = (0.3 * torch.randn(B, H, generator=g)).to(DEV)
     base = SAVE_PREACT if preact else 0
-    kw = dict(bias_gate=P["bias_gate"], bias_update=P["bias_update"]) if preact else {}
 
     def run(xi, Gi, flags):
-        outs = fastgrnn_cuda.forward_unroll(xi, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"],
-                                            h0, 0, P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-        gr = fastgrnn_cuda.backward_unroll(Gi, xi, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[-1], h0,
-                                           P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags, **kw)
+        outs, gr = S.fwd_bwd(xi, h0, Gi, P, "sigmoid", flags=flags, biases=preact)
         return list(outs), list(gr)
 
     o_t, g_t = run(x, G, base)
@@ -574,9 +462,7 @@ def test_batch_major_layout_equals_time_major(B, preact):
     # not available off the split-precision path: the caller transposes instead
     assert fastgrnn_cuda.kernel_path(T, B, 20, 100, 0, 0, 0, direction=0, flags=base | BATCH_MAJOR) != 2
     with pytest.raises(RuntimeError):
-        fastgrnn_cuda.forward_unroll(x.transpose(0, 1).contiguous(), P["w"], P["u"], P["bias_gate"], P["bias_update"],
-                                     P["zeta"], P["nu"], h0, 0, P["w1"], P["w2"], P["u1"], P["u2"],
-                                     flags=BATCH_MAJOR | 1)
+        S.forward_unroll(x.transpose(0, 1).contiguous(), h0, P, "sigmoid", flags=BATCH_MAJOR | S.FLAG_FORCE_GENERIC)
 
 
 @pytest.mark.parametrize("F,H", [(32, 128), (32, 256), (64, 256), (256, 128), (64, 128)],
@@ -588,61 +474,7 @@ def test_bf16_sequences_fp32_master_grads(B, batch_major, F, H):
     saved pre-activation and every parameter gradient are fp32.  Checked against the fp64 oracle run
     on the SAME rounded tensors: hs and d_x to bf16 rounding (2^-8 relative), the fp32 outputs to the
     fp32 tolerances of the other tests."""
-    bf16_master_grads_case(31, B, batch_major, F, H)   # (H = 256: the first layer of the default stack, round 3)
-
-
-def bf16_master_grads_case(T, B, batch_major, F, H):
-    """the reference and the bounds of test_bf16_sequences_fp32_master_grads at any (T, B)
-    (tests/test_hip_partition_seams.py runs them where the weight-gradient GEMMs cut long chunks)"""
-    SAVE_PREACT, BATCH_MAJOR = 4, 16
-    rng = np.random.default_rng(77 + B)
-    p = O.make_params(F, H, dtype=np.float32, seed=23, randomize_scalars=True)
-    P = _param_tensors(p)
-    bf = lambda a: torch.from_numpy(a).to(torch.bfloat16)
-    x_bf = bf(rng.standard_normal((T, B, F)).astype(np.float32))
-    G_bf = bf(rng.standard_normal((T, B, H)).astype(np.float32))
-    h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
-    flags = SAVE_PREACT | (BATCH_MAJOR if batch_major else 0)
-    lay = (lambda t: t.transpose(0, 1).contiguous()) if batch_major else (lambda t: t)
-    unlay = (lambda t: t.transpose(0, 1)) if batch_major else (lambda t: t)
-    xt, Gt, ht = lay(x_bf).to(DEV), lay(G_bf).to(DEV), _t(h0)
-    bwd_fast = not (H == 256 and batch_major)   # (the H = 256 backward takes bf16 sequences time-major only; the module transposes)
-    assert fastgrnn_cuda.kernel_path(T, B, F, H, dtype=torch.bfloat16, direction=0, flags=flags) == 2
-    assert (fastgrnn_cuda.kernel_path(T, B, F, H, dtype=torch.bfloat16, direction=1, flags=flags) == 2) == bwd_fast
-    hs, pre = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], ht,
-                                           0, P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-    assert hs.dtype == torch.bfloat16 and pre.dtype == torch.float32
-    if bwd_fast:
-        outs = fastgrnn_cuda.backward_unroll(Gt, xt, hs, P["zeta"], P["nu"], P["w"], P["u"], pre, pre, ht,
-                                             P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags,
-                                             bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-        assert outs[0].dtype == torch.bfloat16 and outs[6].dtype == torch.float32
-    # ---- forward against the oracle on the rounded x: fp32 state inside, bf16 only when stored
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    x64 = x_bf.to(torch.float64).numpy(); G64 = G_bf.to(torch.float64).numpy(); h64 = h0.astype(np.float64)
-    hs_o, zs_o, cs_o = O.unroll_forward(x64, p64, h64)
-    hs_k = unlay(hs).to(torch.float64).cpu().numpy()
-    assert (np.abs(hs_k - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 2.0 ** -8 + 1e-5   # one bf16 rounding (RNE: 2^-9 relative)
-    hprev = np.concatenate([h64[None], hs_o[:-1]], 0)
-    assert np.abs(unlay(pre).cpu().numpy() - (x64 @ p64["w"].T + hprev @ p64["u"].T)).max() <= 1e-5
-    if not bwd_fast:
-        return
-    # ---- backward: the kernel sees the ROUNDED hs as h_prev (what autograd with bf16 activations does):
-    #      oracle on the same tensors, gates from the exact pre-activation
-    hs_r = hs_k.copy()
-    pre_k = unlay(pre).cpu().numpy().astype(np.float64)
-    z_k = 1.0 / (1.0 + np.exp(-(pre_k + p64["bias_gate"]))); c_k = np.tanh(pre_k + p64["bias_update"])
-    g_o = O.unroll_backward(G64, x64, hs_r, z_k, c_k, p64, h64, diagnostics=True)
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u"]
-    g = {n: o for n, o in zip(names, outs[:8])}
-    dx = unlay(g.pop("d_x")).to(torch.float64).cpu().numpy()
-    ref = g_o.pop("d_x")
-    assert (np.abs(dx - ref) / np.maximum(1.0, np.abs(ref))).max() <= 2.0 ** -8 + 2e-5
-    _check_grads({k: v.cpu().numpy() for k, v in g.items()}, g_o, 2e-5, "bf16-io")
-    # the reference's (z_s, h_prime_s) contract is not offered for bf16 sequences
-    with pytest.raises(RuntimeError):
-        fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], ht,
-                                     0, P["w1"], P["w2"], P["u1"], P["u2"], flags=flags & ~SAVE_PREACT)
+    LC.bf16_master_grads_case(31, B, batch_major, F, H)   # (H = 256: the first layer of the default stack, round 3)
 
 
 @pytest.mark.parametrize("F,H,batch_first", [(32, 128, False), (32, 256, False), (64, 256, False), (32, 256, True),
@@ -659,7 +491,7 @@ def test_module_bf16_sequences_autograd(F, H, batch_first):
     if batch_first:
         x, G = x.transpose(0, 1).contiguous(), G.transpose(0, 1).contiguous()
     else:
-        assert fastgrnn_cuda.kernel_path(T, B, F, H, dtype=torch.bfloat16, direction=1, flags=4) == 2
+        assert fastgrnn_cuda.kernel_path(T, B, F, H, dtype=torch.bfloat16, direction=1, flags=S.FLAG_SAVE_PREACT) == 2
     xb = x.to(DEV).requires_grad_(True)
     hb = m(xb)
     assert hb.dtype == torch.bfloat16
@@ -726,26 +558,21 @@ def test_quantised_gates_on_the_matrix_pipe(gate):
     kernels (one-saved-tensor contract).  Piecewise-linear gates have derivative jumps, so -- as for relu --
     the backward is compared with the oracle evaluated on the kernel's own gate values (same mask)."""
     T, B, F, H = 12, 37, 32, 128
-    SAVE_PREACT = 4
-    code = GATE_CODE[gate]
+    SAVE_PREACT = S.FLAG_SAVE_PREACT
+    code = S.NONLINEARITY[gate]
     rng = np.random.default_rng(code)
     p = O.make_params(F, H, dtype=np.float32, seed=31, randomize_scalars=True)
     p["bias_gate"] = (0.3 * p["bias_gate"]).astype(np.float32)   # pre-activations on both sides of the clamps
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
-    P = _param_tensors(p)
-    xt, ht, Gt = _t(x), _t(h0), _t(G)
+    P = S.cell_tensors(p)
+    xt, ht, Gt = S.to_dev(x), S.to_dev(h0), S.to_dev(G)
     assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=code, direction=0, flags=SAVE_PREACT) == 2
     assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=code, direction=1, flags=SAVE_PREACT) == 2
     assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=code, direction=1) != 2     # reference contract: generic scan
-    hs, pre = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], ht,
-                                           code, P["w1"], P["w2"], P["u1"], P["u2"], flags=SAVE_PREACT)
-    outs = fastgrnn_cuda.backward_unroll(Gt, xt, hs, P["zeta"], P["nu"], P["w"], P["u"], pre, pre, ht,
-                                         P["w1"], P["w2"], P["u1"], P["u2"], code, flags=SAVE_PREACT,
-                                         bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, zs_o, cs_o = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate=gate)
+    (hs, pre), outs = S.fwd_bwd(xt, ht, Gt, P, gate, flags=SAVE_PREACT, biases=True)
+    hs_o, zs_o, cs_o = S.oracle64_forward(x, p, h0, gate)
     assert (np.abs(hs.cpu().numpy() - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
     # a fair share of the gate values is strictly inside (0,1) / (-1,1): the test exercises both branches
     inside = (zs_o > (-1 if gate == "quantTanh" else 0)) & (zs_o < 1)
@@ -756,9 +583,7 @@ def test_quantised_gates_on_the_matrix_pipe(gate):
           "quantSigm4": np.clip((a + 2) / 4, 0, 1)}[gate].astype(np.float32)
     ck = np.tanh(pre_k + p["bias_update"]).astype(np.float32)
     g_o = O.unroll_backward(G, x, hs.cpu().numpy(), zk, ck, p, h0, gate=gate)
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u"]
-    g = {n: o.cpu().numpy() for n, o in zip(names, outs[:8])}
-    _check_grads(g, g_o, 5e-5, gate)
+    S.check_grads(outs, g_o, tol=5e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag=gate)
 
 
 @pytest.mark.parametrize("gate,B", [("sigmoid", 64), ("quantSigm", 37), ("sigmoid", 4096)])
@@ -767,31 +592,24 @@ def test_quant_tanh_update_on_the_matrix_pipe(gate, B):
     8-wave split-precision kernels: c = clip(pre + b_h, -1, 1), dc/da = 1 inside (-1,1), 0 outside.  Forward against
     the fp64 oracle; backward against the oracle on the kernel's own z, c (the clamp's derivative jumps)."""
     T, F, H = (12, 32, 128) if B < 4096 else (99, 32, 128)
-    SAVE_PREACT, QT = 4, GATE_CODE["quantTanh"]
-    code = GATE_CODE[gate]
+    SAVE_PREACT, QT = S.FLAG_SAVE_PREACT, S.NONLINEARITY["quantTanh"]
+    code = S.NONLINEARITY[gate]
     rng = np.random.default_rng(B)
     p = O.make_params(F, H, dtype=np.float32, seed=17, randomize_scalars=True)
     p["w"] = (3.0 * p["w"]).astype(np.float32)                  # update pre-activations on both sides of the clamp
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
-    P = _param_tensors(p)
-    xt, ht, Gt = _t(x), _t(h0), _t(G)
+    P = S.cell_tensors(p)
+    xt, ht, Gt = S.to_dev(x), S.to_dev(h0), S.to_dev(G)
     for direction, flags in ((0, 0), (0, SAVE_PREACT), (1, SAVE_PREACT)):
         assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=code, update_nl=QT, direction=direction, flags=flags) == 2
     assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=code, update_nl=QT, direction=1) != 2   # reference contract
-    hs, pre = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], ht,
-                                           code, P["w1"], P["w2"], P["u1"], P["u2"], update_non_linearity=QT,
-                                           flags=SAVE_PREACT)
-    hs_only = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], ht,
-                                           code, P["w1"], P["w2"], P["u1"], P["u2"], update_non_linearity=QT,
-                                           want_gates=False)[0]
+    hs, pre = S.forward_unroll(xt, ht, P, gate, update="quantTanh", flags=SAVE_PREACT)
+    hs_only = S.forward_unroll(xt, ht, P, gate, update="quantTanh", want_gates=False)[0]
     assert torch.equal(hs, hs_only)
-    outs = fastgrnn_cuda.backward_unroll(Gt, xt, hs, P["zeta"], P["nu"], P["w"], P["u"], pre, pre, ht,
-                                         P["w1"], P["w2"], P["u1"], P["u2"], code, update_non_linearity=QT,
-                                         flags=SAVE_PREACT, bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, zs_o, cs_o = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate=gate, update="quantTanh")
+    outs = S.backward_of((hs, pre), Gt, xt, ht, P, gate, update="quantTanh", flags=SAVE_PREACT, biases=True)
+    hs_o, zs_o, cs_o = S.oracle64_forward(x, p, h0, gate, "quantTanh")
     assert (np.abs(hs.cpu().numpy() - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
     inside = (cs_o > -1) & (cs_o < 1)
     assert 0.2 < inside.mean() < 0.98, inside.mean()
@@ -800,9 +618,7 @@ def test_quant_tanh_update_on_the_matrix_pipe(gate, B):
     zk = (1.0 / (1.0 + np.exp(-a.astype(np.float64))) if gate == "sigmoid" else np.clip((a + 1) / 2, 0, 1)).astype(np.float32)
     ck = np.clip(pre_k + p["bias_update"], -1, 1).astype(np.float32)
     g_o = O.unroll_backward(G, x, hs.cpu().numpy(), zk, ck, p, h0, gate=gate, update="quantTanh")
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u"]
-    g = {n: o.cpu().numpy() for n, o in zip(names, outs[:8])}
-    _check_grads(g, g_o, 5e-5, gate + "/quantTanh")
+    S.check_grads(outs, g_o, tol=5e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag=gate + "/quantTanh")
 
 
 @pytest.mark.parametrize("B,hs_batch_major,H", [(37, False, 128), (64, False, 128), (48, True, 128),
@@ -813,20 +629,16 @@ def test_trainer_bft_input_layout_in_place(B, hs_batch_major, H):
     run bit for bit.  H=128 (in place) and the reference's first layer H=256 (trainingConfig.py:12-15), which
     transposes the frames into its workspace in both calls."""
     T, F = 23, 32
-    SAVE_PREACT, BATCH_MAJOR, X_BFT = 4, 16, 128
+    SAVE_PREACT, BATCH_MAJOR, X_BFT = S.FLAG_SAVE_PREACT, S.FLAG_BATCH_MAJOR, S.FLAG_X_BFT
     p = O.make_params(F, H, seed=6, randomize_scalars=True)
-    P = _param_tensors(p)
+    P = S.cell_tensors(p)
     g = torch.Generator().manual_seed(10)
     x = torch.randn(T, B, F, generator=g).to(DEV)
     G = torch.randn(T, B, H, generator=g).to(DEV)
     h0 = (0.3 * torch.randn(B, H, generator=g)).to(DEV)
-    kw = dict(bias_gate=P["bias_gate"], bias_update=P["bias_update"])
 
     def run(xi, Gi, flags):
-        outs = fastgrnn_cuda.forward_unroll(xi, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"],
-                                            h0, 0, P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-        gr = fastgrnn_cuda.backward_unroll(Gi, xi, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[1], h0,
-                                           P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags, **kw)
+        outs, gr = S.fwd_bwd(xi, h0, Gi, P, "sigmoid", flags=flags, biases=True)
         return list(outs), list(gr)
 
     o_t, g_t = run(x, G, SAVE_PREACT)
@@ -874,20 +686,16 @@ def test_ab_kernel_variants_agree_with_the_default(B):
     three-bf16-plane forward state product (64).  They must agree with the default kernels to fp32 rounding
     (they differ in summation order and, for 64, in the operand split)."""
     T, F, H = 40, 32, 128
-    SAVE_PREACT, FWD_4WAVE, FWD_BF16X3 = 4, 8, 64
+    SAVE_PREACT, FWD_4WAVE, FWD_BF16X3 = S.FLAG_SAVE_PREACT, S.FLAG_FWD_4WAVE, S.FLAG_FWD_BF16X3
     p = O.make_params(F, H, seed=12, randomize_scalars=True)
-    P = _param_tensors(p)
+    P = S.cell_tensors(p)
     g = torch.Generator().manual_seed(14)
     x = torch.randn(T, B, F, generator=g).to(DEV)
     G = torch.randn(T, B, H, generator=g).to(DEV)
     h0 = (0.3 * torch.randn(B, H, generator=g)).to(DEV)
-    kw = dict(bias_gate=P["bias_gate"], bias_update=P["bias_update"])
 
     def run(flags):
-        outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"],
-                                            h0, 0, P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-        gr = fastgrnn_cuda.backward_unroll(G, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[1], h0,
-                                           P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags, **kw)
+        outs, gr = S.fwd_bwd(x, h0, G, P, "sigmoid", flags=flags, biases=True)
         return list(outs) + list(gr[:8])
 
     ref = run(SAVE_PREACT)
@@ -900,7 +708,7 @@ def test_ab_kernel_variants_agree_with_the_default(B):
 
 
 # ---- the classifier's view of the last layer (model.py:227 reads hs[T-1] alone) ---------------
-GRAD_LAST, HS_LAST = 256, 512
+GRAD_LAST, HS_LAST = S.FLAG_GRAD_LAST, S.FLAG_HS_LAST
 
 
 @pytest.mark.parametrize("B,preact,bf16,batch_major", [(64, True, False, False), (37, True, False, False),
@@ -911,24 +719,19 @@ def test_grad_last_equals_the_dense_zero_padded_gradient(B, preact, bf16, batch_
     other step is exact, so all twelve outputs equal the dense run's bit for bit."""
     T, F, H = 21, 32, 128
     p = O.make_params(F, H, seed=31, randomize_scalars=True)
-    P = _param_tensors(p)
+    P = S.cell_tensors(p)
     g = torch.Generator().manual_seed(32)
     dt = torch.bfloat16 if bf16 else torch.float32
     lead = (B, T) if batch_major else (T, B)
     x = torch.randn(*lead, F, generator=g).to(DEV).to(dt)
     gl = torch.randn(B, H, generator=g).to(DEV).to(dt)
     h0 = (0.3 * torch.randn(B, H, generator=g)).to(DEV)
-    flags = (4 if preact else 0) | (16 if batch_major else 0)
-    outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, 0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-    aux2 = outs[2] if len(outs) > 2 else outs[1]
-    kw = dict(bias_gate=P["bias_gate"], bias_update=P["bias_update"]) if preact else {}
+    flags = (S.FLAG_SAVE_PREACT if preact else 0) | (S.FLAG_BATCH_MAJOR if batch_major else 0)
+    outs = S.forward_unroll(x, h0, P, "sigmoid", flags=flags)
     dense = torch.zeros(*lead, H, device=DEV, dtype=dt)
     (dense[:, -1] if batch_major else dense[-1]).copy_(gl)
-    ref = fastgrnn_cuda.backward_unroll(dense, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], aux2, h0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags, **kw)
-    got = fastgrnn_cuda.backward_unroll(gl, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], aux2, h0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags | GRAD_LAST, **kw)
+    ref = S.backward_of(outs, dense, x, h0, P, "sigmoid", flags=flags, biases=preact)
+    got = S.backward_of(outs, gl, x, h0, P, "sigmoid", flags=flags | GRAD_LAST, biases=preact)
     for k, (a, b) in enumerate(zip(ref, got)):
         assert a.shape == b.shape and torch.equal(a, b), k
     # and against the oracle (fp32, time-major case only)
@@ -936,8 +739,7 @@ def test_grad_last_equals_the_dense_zero_padded_gradient(B, preact, bf16, batch_
         hs_o, zs_o, cs_o = O.unroll_forward(x.cpu().numpy(), p, h0.cpu().numpy())
         G = np.zeros((T, B, H), np.float32); G[-1] = gl.cpu().numpy()
         ref_o = O.unroll_backward(G, x.cpu().numpy(), hs_o, zs_o, cs_o, p, h0.cpu().numpy())
-        _check_grads({n: o.cpu().numpy() for n, o in zip(["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0",
-                                                           "d_w", "d_u"], got)}, ref_o, 1e-5, "grad_last")
+        S.check_grads(got, ref_o, tol=1e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag="grad_last")
 
 
 @pytest.mark.parametrize("B,bf16,batch_major", [(64, False, False), (37, False, False), (48, True, False), (37, False, True)])
@@ -946,24 +748,24 @@ def test_hs_last_forward_writes_only_the_final_state(B, bf16, batch_major):
     saved tensors requested the combination is refused."""
     T, F, H = 17, 32, 128
     p = O.make_params(F, H, seed=33, randomize_scalars=True)
-    P = _param_tensors(p)
+    P = S.cell_tensors(p)
     g = torch.Generator().manual_seed(34)
     dt = torch.bfloat16 if bf16 else torch.float32
     lead = (B, T) if batch_major else (T, B)
     x = torch.randn(*lead, F, generator=g).to(DEV).to(dt)
     h0 = (0.3 * torch.randn(B, H, generator=g)).to(DEV)
-    flags = 16 if batch_major else 0
-    args = (x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, 0, P["w1"], P["w2"], P["u1"], P["u2"])
-    full = fastgrnn_cuda.forward_unroll(*args, want_gates=False, flags=flags)[0]
-    last = fastgrnn_cuda.forward_unroll(*args, want_gates=False, flags=flags | HS_LAST)[0]
+    flags = S.FLAG_BATCH_MAJOR if batch_major else 0
+    fwd = lambda **kw: S.forward_unroll(x, h0, P, "sigmoid", **kw)
+    full = fwd(want_gates=False, flags=flags)[0]
+    last = fwd(want_gates=False, flags=flags | HS_LAST)[0]
     assert last.shape == (B, H)
     # a separately compiled variant of the same arithmetic (fma contraction may differ): fp32 rounding, not bits
     want = (full[:, -1] if batch_major else full[-1]).float()
     assert float((last.float() - want).abs().max()) <= (2.0 ** -7 if bf16 else 2e-6) * max(1.0, float(want.abs().max()))
     with pytest.raises(RuntimeError):
-        fastgrnn_cuda.forward_unroll(*args, want_gates=True, flags=flags | HS_LAST)
+        fwd(want_gates=True, flags=flags | HS_LAST)
     with pytest.raises(RuntimeError):                 # generic path: unsupported, loudly
-        fastgrnn_cuda.forward_unroll(*args, want_gates=False, flags=flags | HS_LAST | FORCE_GENERIC)
+        fwd(want_gates=False, flags=flags | HS_LAST | S.FLAG_FORCE_GENERIC)
 
 
 @pytest.mark.parametrize("kind", ["dense", "dense_batch_first", "lowrank", "dense_bf16"])

@@ -6,7 +6,8 @@ reductions of 128, 129, 130 and 257 workgroups.
 
 Every comparison is against the fp64 oracle (oracle/fastgrnn_oracle.py) or an fp64 product under the bounds the suite
 already holds these kernels to at full size, or exact (bit for bit) where the kernels promise it.  The helpers are those
-of test_hip_stack.py, test_hip_bft_wide.py, test_hip_parity.py, test_hip_fullsize.py and test_hip_bn_train.py.
+of tests/support.py; the cases shared with test_hip_stack.py, test_hip_bft_wide.py, test_hip_parity.py and
+test_hip_bn_train.py are in tests/layer_cases.py and tests/bn_train_golden.py.
 """
 import ctypes as C
 
@@ -15,18 +16,16 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import bn_train_golden as BN
+from tests import layer_cases as LC
 from tests import partition_cases as PC
-from tests import test_hip_bft_wide as W
-from tests import test_hip_bn_train as BN
-from tests import test_hip_fullsize as FS
-from tests import test_hip_parity as PAR
-from tests import test_hip_stack as S
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from kws_amd import _lib, fastgrnn_cuda
-DEV = "cuda:0"
 
 LAYERS = [(256, 32), (256, 64), (256, 128), (128, 64), (128, 128), (128, 256)]        # (H, F): GEMMs around the scan
 FRAME = [(128, 64), (128, 128), (128, 256), (256, 64), (256, 128)]                   # (H, F) of fastgrnn_hip_frame_gemm
@@ -62,7 +61,7 @@ def test_frame_gemm_rows_do_not_depend_on_the_cut(H, F, bf16):
     xt = torch.from_numpy(rng.standard_normal((Rmax, F)).astype(np.float32)).to(DEV)
     if bf16:
         xt = xt.to(torch.bfloat16)
-    wt = S._t(w)
+    wt = S.to_dev(w)
     dtype = _lib.BF16_IO if bf16 else _lib.F32
 
     def product(R):
@@ -110,7 +109,7 @@ def _scalar_tol(H, F):
 
 
 def _scalar_ratio(gr, g_o, H, F):
-    """error of d_zeta / d_nu over the bound S._check holds them to (reporting only)"""
+    """error of d_zeta / d_nu over the bound S.check_grads holds them to (reporting only)"""
     worst = 0.0
     for k, n in ((3, "zeta"), (4, "nu")):
         ref = float(np.asarray(g_o["d_" + n]).ravel()[0])
@@ -124,12 +123,6 @@ def _assert_path_2(T, B, F, H, flags, **kw):
         assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=direction, flags=flags, **kw) == 2, (T, B, F, H, direction)
 
 
-def _pre_oracle(x, h0, hs_o, p):
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hprev = np.concatenate([h0[None].astype(np.float64), hs_o[:-1]], 0)
-    return x.astype(np.float64) @ p64["w"].T + hprev @ p64["u"].T
-
-
 @pytest.mark.parametrize("T,B", PC.SHAPES, ids=_ids)
 @pytest.mark.parametrize("H,F", LAYERS, ids=_ids)
 def test_layer_forward_and_backward_vs_oracle(H, F, T, B):
@@ -141,13 +134,13 @@ def test_layer_forward_and_backward_vs_oracle(H, F, T, B):
     ratio is printed).  Against the plain 2e-5 of the result alone d_zeta of H=256 / F=32 at (99, 83) is at 1.38."""
     _assert_path_2(T, B, F, H, _lib.FLAG_SAVE_PREACT)
     p, x, h0, G = _draw(T, B, F, H)
-    outs, gr = S._run(S._t(x), S._t(h0), S._t(G), p, preact=True)
-    hs_o, zs_o, cs_o, g_o = S._oracle(x, G, p, h0)
+    outs, gr = LC.layer_fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), p, preact=True)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     e_hs = float(np.abs(outs[0].cpu().numpy() - hs_o).max())
-    e_pre = float(np.abs(outs[1].cpu().numpy() - _pre_oracle(x, h0, hs_o, p)).max())
+    e_pre = float(np.abs(outs[1].cpu().numpy() - S.dense_preactivation64(x, p, h0, hs_o)).max())
     print("layer H=%d F=%d T=%d B=%d: hs %.2e pre %.2e (of 1e-5)" % (H, F, T, B, e_hs, e_pre))
     assert e_hs <= 1e-5 and e_pre <= 1e-5, (e_hs, e_pre)
-    errs = S._check(gr, g_o, scalar_term_tol=_scalar_tol(H, F))
+    errs = S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=_scalar_tol(H, F), tag=(H, F, T, B))
     print("layer H=%d F=%d T=%d B=%d: worst gradient %.2e (of 2e-5) %s; scalars / their bound %.2f"
           % (H, F, T, B, max(errs.values()), {k: "%.1e" % v for k, v in errs.items()}, _scalar_ratio(gr, g_o, H, F)))
 
@@ -158,11 +151,11 @@ def test_layer_reference_contract_vs_oracle(T, B):
     H, F = 256, 64
     _assert_path_2(T, B, F, H, 0)
     p, x, h0, G = _draw(T, B, F, H)
-    outs, gr = S._run(S._t(x), S._t(h0), S._t(G), p, preact=False)
-    hs_o, zs_o, cs_o, g_o = S._oracle(x, G, p, h0)
+    outs, gr = LC.layer_fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), p, preact=False)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     assert np.abs(outs[0].cpu().numpy() - hs_o).max() <= 1e-5
     assert np.abs(outs[1].cpu().numpy() - zs_o).max() <= 1e-5 and np.abs(outs[2].cpu().numpy() - cs_o).max() <= 1e-5
-    S._check(gr, g_o, scalar_term_tol=_scalar_tol(H, F))
+    S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=_scalar_tol(H, F), tag=(T, B))
 
 
 # ---- (c) a sparse gradient on the seam rows ----------------------------------------------------------------------
@@ -177,13 +170,13 @@ def test_gradient_of_the_seam_utterances_alone(H, F, T, B):
     p, x, h0, _ = _draw(T, B, F, H)
     G = np.zeros((T, B, H), np.float32)
     G[:, bs] = np.random.default_rng(7 + B).standard_normal((T, len(bs), H)).astype(np.float32)
-    outs, gr = S._run(S._t(x), S._t(h0), S._t(G), p, preact=True)
+    outs, gr = LC.layer_fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), p, preact=True)
     rest = torch.ones(B, dtype=torch.bool, device=DEV)
     rest[bs] = False
     assert int((gr[0][:, rest] != 0).sum()) == 0 and int((gr[5][rest] != 0).sum()) == 0
-    _, _, _, g_o = S._oracle(np.ascontiguousarray(x[:, bs]), np.ascontiguousarray(G[:, bs]), p, np.ascontiguousarray(h0[bs]))
-    errs = S._check([gr[0][:, bs], gr[1], gr[2], gr[3], gr[4], gr[5][bs], gr[6], gr[7]], g_o,
-                    scalar_term_tol=_scalar_tol(H, F))
+    _, _, _, g_o = S.oracle64(np.ascontiguousarray(x[:, bs]), np.ascontiguousarray(G[:, bs]), p, np.ascontiguousarray(h0[bs]))
+    errs = S.check_grads([gr[0][:, bs], gr[1], gr[2], gr[3], gr[4], gr[5][bs], gr[6], gr[7]], g_o, tol=2e-5,
+                         scalar_term_tol=_scalar_tol(H, F), tag=(H, F, T, B))
     print("seams H=%d F=%d T=%d B=%d (%d utterances): worst gradient %.2e (of 2e-5)" % (H, F, T, B, len(bs),
                                                                                       max(errs.values())))
 
@@ -196,11 +189,11 @@ def test_bft_frames_bitwise_equal_to_the_time_major_call(H, F, T, B):
     workspace copy): the same bits as the time-major call, forward and backward"""
     SP, BFT = _lib.FLAG_SAVE_PREACT, _lib.FLAG_X_BFT
     _assert_path_2(T, B, F, H, SP | BFT)
-    x, xb, h0, G = W._data(T, B, F, H)
-    P = W._params(F, H, seed=11 + B % 7)
-    o_tm, o_bft = W._forward(x, h0, P, "sigmoid", SP), W._forward(xb, h0, P, "sigmoid", SP | BFT)
-    W._same_bits(o_bft[0], o_tm[0], "preact hs"); W._same_bits(o_bft[1], o_tm[1], "preact z")
-    W._compare_backward(G, x, xb, o_tm, o_bft, h0, P, "sigmoid", SP, "preact")
+    x, xb, h0, G = LC.bft_data(T, B, F, H)
+    P = LC.bft_params(F, H, seed=11 + B % 7)
+    o_tm, o_bft = S.forward_unroll(x, h0, P, "sigmoid", flags=SP), S.forward_unroll(xb, h0, P, "sigmoid", flags=SP | BFT)
+    S.assert_same_bits(o_bft[0], o_tm[0], "preact hs"); S.assert_same_bits(o_bft[1], o_tm[1], "preact z")
+    LC.compare_bft_backward(G, x, xb, o_tm, o_bft, h0, P, "sigmoid", SP, "preact")
 
 
 @pytest.mark.parametrize("T,B", [ODD_T, EVEN_B], ids=_ids)
@@ -212,15 +205,16 @@ def test_batch_major_takes_the_periodic_dU_gemm(T, B):
     BM = _lib.FLAG_BATCH_MAJOR
     _assert_path_2(T, B, F, H, _lib.FLAG_SAVE_PREACT | BM)
     p, x, h0, G = _draw(T, B, F, H)
-    xt, ht, Gt = S._t(x), S._t(h0), S._t(G)
-    outs, gr = S._run(xt, ht, Gt, p, preact=True)
-    outs_b, gr_b = S._run(xt.transpose(0, 1).contiguous(), ht, Gt.transpose(0, 1).contiguous(), p, flags=BM, preact=True)
+    xt, ht, Gt = S.to_dev(x), S.to_dev(h0), S.to_dev(G)
+    outs, gr = LC.layer_fwd_bwd(xt, ht, Gt, p, preact=True)
+    outs_b, gr_b = LC.layer_fwd_bwd(xt.transpose(0, 1).contiguous(), ht, Gt.transpose(0, 1).contiguous(), p, flags=BM, preact=True)
     assert torch.equal(outs_b[0].transpose(0, 1), outs[0]) and torch.equal(outs_b[1].transpose(0, 1), outs[1])
     assert torch.equal(gr_b[0].transpose(0, 1), gr[0])
     for k in (1, 2, 3, 4, 5):
-        assert torch.equal(gr[k], gr_b[k]), S.NAMES[k]
-    _, _, _, g_o = S._oracle(x, G, p, h0)
-    S._check([gr_b[0].transpose(0, 1)] + list(gr_b[1:8]), g_o, scalar_term_tol=_scalar_tol(H, F))
+        assert torch.equal(gr[k], gr_b[k]), S.GRAD_NAMES[k]
+    _, _, _, g_o = S.oracle64(x, G, p, h0)
+    S.check_grads([gr_b[0].transpose(0, 1)] + list(gr_b[1:8]), g_o, tol=2e-5, scalar_term_tol=_scalar_tol(H, F),
+                  tag=(T, B))
 
 
 @pytest.mark.parametrize("T,B", [(11, 1499), EVEN_B, (3, 1377)], ids=_ids)
@@ -235,7 +229,7 @@ def test_bf16_sequences_where_head_and_body_are_cut_differently(H, F, T, B):
         assert head > 0 and body != head, (body, head)
         if (T, B) == (3, 1377):
             assert body + head == PC.tn_slots(T * B, 2) + 1
-    PAR.bf16_master_grads_case(T, B, False, F, H)
+    LC.bf16_master_grads_case(T, B, False, F, H)
 
 
 # ---- (e) the slab reductions without a GEMM behind them ------------------------------------------------------------
@@ -254,21 +248,17 @@ def test_slab_reductions_across_their_rounds(H, rank, T, B):
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
-    P = FS._P(p)
-    xt, Gt, ht = FS._t(x), FS._t(G), FS._t(h0)
+    P = S.cell_tensors(p)
+    xt, Gt, ht = S.to_dev(x), S.to_dev(G), S.to_dev(h0)
     flags = _lib.FLAG_SAVE_PREACT
     r = rank or 0
     assert fastgrnn_cuda.kernel_path(T, B, F, H, r, r, direction=0, flags=flags) == 2
     assert fastgrnn_cuda.kernel_path(T, B, F, H, r, r, direction=1, flags=flags) == 2
-    outs = fastgrnn_cuda.forward_unroll(xt, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], ht, 0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=flags)
-    gr = fastgrnn_cuda.backward_unroll(Gt, xt, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[-1], ht,
-                                       P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=flags,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+    outs, gr = S.fwd_bwd(xt, ht, Gt, P, "sigmoid", flags=flags, biases=True)
     torch.cuda.synchronize()
-    hs_o, _, _, g_o = FS._oracle(x, G, p, h0)
+    hs_o, _, _, g_o = S.oracle64(x, G, p, h0)
     assert np.abs(outs[0].cpu().numpy() - hs_o).max() <= 1e-5
-    errs = FS._check_all(gr, g_o)
+    errs = S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=0.0, tag=(H, rank, T, B))
     print("slabs H=%d rank=%s T=%d B=%d: %s" % (H, rank, T, B, {k: "%.1e" % v for k, v in errs.items()}))
 
 

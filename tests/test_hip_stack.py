@@ -7,69 +7,14 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import layer_cases as LC
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from kws_amd import FastGRNNCUDA, RNNClassifierModel, _lib, fastgrnn_cuda
-DEV = "cuda:0"
-NAMES = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u"]
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _P(p):
-    return {k: _t(v) for k, v in p.items()}
-
-
-def _run(x, h0, G, p, gate=0, flags=0, preact=False):
-    """forward_unroll + backward_unroll; returns hs, aux list, grads (torch tensors on the device)."""
-    P = _P(p)
-    e = torch.empty(0)
-    if preact:
-        flags |= _lib.FLAG_SAVE_PREACT
-    outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0,
-                                        gate, e, e, e, e, flags=flags)
-    gr = fastgrnn_cuda.backward_unroll(G, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1],
-                                       outs[1] if preact else outs[2], h0, e, e, e, e, gate, flags=flags,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-    torch.cuda.synchronize()
-    return outs, gr
-
-
-def _oracle(x, G, p, h0, gate="sigmoid"):
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    x64, G64, h64 = x.astype(np.float64), G.astype(np.float64), h0.astype(np.float64)
-    hs, zs, cs = O.unroll_forward(x64, p64, h64, gate=gate)
-    return hs, zs, cs, O.unroll_backward(G64, x64, hs, zs, cs, p64, h64, gate=gate, diagnostics=True)
-
-
-# d_zeta / d_nu are ONE scalar each: sums of T*B*H terms of either sign that cancel to a result 1e2..1e4 times smaller
-# than the sum of their magnitudes.  scalar_term_tol > 0 bounds their error relative to that sum of magnitudes (which the
-# oracle reports) as well -- 2e-7 of it, i.e. every term good to about three fp32 roundings.  Round 2 applied that to
-# every layer shape, because the dense H=256 backward needed it (4-5.5e-5 of the result); since round 3 its chain carries
-# d_pre exactly and the default stack's first layer (F = 32, H = 256) is held to the plain 2e-5.  What still takes the
-# conditioning-aware bound are the layers with a wide input at full size (F = 256 / H = 128: d_nu 2.5e-5 of a result
-# that is 1e-4 of its terms' magnitudes; F = 64 / H = 256: 3.1e-5).
-SCALAR_TERM_TOL = 2e-7
-
-
-def _check(gr, g_o, tol=2e-5, scalar_term_tol=0.0):
-    errs = {}
-    bad = {}
-    for n, o in zip(NAMES, gr[:8]):
-        ref = g_o[n]
-        abs_err = float(np.abs(o.cpu().numpy().astype(np.float64).reshape(ref.shape) - ref).max())
-        errs[n] = abs_err / max(1.0, float(np.abs(ref).max()))
-        lim = tol * max(1.0, float(np.abs(ref).max()))
-        if scalar_term_tol and n in ("d_zeta", "d_nu") and ("_abs_" + n[2:]) in g_o:
-            lim = max(lim, scalar_term_tol * g_o["_abs_" + n[2:]])
-        if abs_err > lim:
-            bad[n] = errs[n]
-    assert not bad, (bad, errs)
-    return errs
 
 
 WIDE = [  # T, B, F, H, preact
@@ -93,17 +38,14 @@ def test_stack_layer_shapes_on_the_matrix_pipe_vs_oracle(case):
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
-    outs, gr = _run(_t(x), _t(h0), _t(G), p, preact=preact)
-    hs_o, zs_o, cs_o, g_o = _oracle(x, G, p, h0)
+    outs, gr = LC.layer_fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), p, preact=preact)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     assert np.abs(outs[0].cpu().numpy() - hs_o).max() <= 1e-5
     if preact:
-        p64 = {k: v.astype(np.float64) for k, v in p.items()}
-        hprev = np.concatenate([h0[None].astype(np.float64), hs_o[:-1]], 0)
-        pre_o = x.astype(np.float64) @ p64["w"].T + hprev @ p64["u"].T
-        assert np.abs(outs[1].cpu().numpy() - pre_o).max() <= 1e-5
+        assert np.abs(outs[1].cpu().numpy() - S.dense_preactivation64(x, p, h0, hs_o)).max() <= 1e-5
     else:
         assert np.abs(outs[1].cpu().numpy() - zs_o).max() <= 1e-5 and np.abs(outs[2].cpu().numpy() - cs_o).max() <= 1e-5
-    _check(gr, g_o)
+    S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=0.0, tag=case)
 
 
 @pytest.mark.parametrize("F,H", [(256, 128), (32, 256), (64, 256)])
@@ -120,17 +62,17 @@ def test_stack_layer_shapes_other_gates(F, H, gate):
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
     assert fastgrnn_cuda.kernel_path(T, B, F, H, gate_nl=code, direction=1, flags=_lib.FLAG_SAVE_PREACT) == 2
-    outs, gr = _run(_t(x), _t(h0), _t(G), p, gate=code, preact=True)
-    hs_o, zs_o, cs_o, g_o = _oracle(x, G, p, h0, gate=gate)
+    outs, gr = LC.layer_fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), p, gate=code, preact=True)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0, gate=gate)
     assert (np.abs(outs[0].cpu().numpy() - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
     if gate != "tanh":     # piecewise-linear gates: same mask as the kernel (the oracle in fp32 on the kernel's own states)
         pre = outs[1].cpu().numpy()
         zk = O.nonlinearity(pre + p["bias_gate"], gate).astype(np.float32)
         ck = np.tanh(pre + p["bias_update"]).astype(np.float32)
         g_o = O.unroll_backward(G, x, outs[0].cpu().numpy(), zk, ck, p, h0, gate=gate)
-        _check(gr, g_o, 5e-5)
+        S.check_grads(gr, g_o, tol=5e-5, scalar_term_tol=0.0, tag=gate)
     else:
-        _check(gr, g_o)
+        S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=0.0, tag=gate)
 
 
 @pytest.mark.parametrize("F,H", [(256, 128), (32, 256), (64, 256)])
@@ -140,18 +82,17 @@ def test_stack_layer_batch_major_and_last_state_contracts(F, H):
     T, B = 21, 37
     rng = np.random.default_rng(9)
     p = O.make_params(F, H, dtype=np.float32, seed=35, randomize_scalars=True)
-    P = _P(p)
-    e = torch.empty(0)
-    x = _t(rng.standard_normal((T, B, F)).astype(np.float32))
-    h0 = _t((0.5 * rng.standard_normal((B, H))).astype(np.float32))
-    G = _t(rng.standard_normal((T, B, H)).astype(np.float32))
-    outs, gr = _run(x, h0, G, p, preact=True)
+    P = S.cell_tensors(p)
+    x = S.to_dev(rng.standard_normal((T, B, F)).astype(np.float32))
+    h0 = S.to_dev((0.5 * rng.standard_normal((B, H))).astype(np.float32))
+    G = S.to_dev(rng.standard_normal((T, B, H)).astype(np.float32))
+    outs, gr = LC.layer_fwd_bwd(x, h0, G, p, preact=True)
     # (round 3: the H = 256 scans index [B,T,.] in place too -- two-stride rows, the d_pre workspace in the sequences'
     # row order, and a dU GEMM that takes every T-th row of H_prev from h0)
     xb, Gb = x.transpose(0, 1).contiguous(), G.transpose(0, 1).contiguous()
     assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=0, flags=_lib.FLAG_SAVE_PREACT | _lib.FLAG_BATCH_MAJOR) == 2
     assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=1, flags=_lib.FLAG_SAVE_PREACT | _lib.FLAG_BATCH_MAJOR) == 2
-    outs_b, gr_b = _run(xb, h0, Gb, p, flags=_lib.FLAG_BATCH_MAJOR, preact=True)
+    outs_b, gr_b = LC.layer_fwd_bwd(xb, h0, Gb, p, flags=_lib.FLAG_BATCH_MAJOR, preact=True)
     assert torch.equal(outs_b[0].transpose(0, 1), outs[0]) and torch.equal(outs_b[1].transpose(0, 1), outs[1])
     assert torch.equal(gr_b[0].transpose(0, 1), gr[0])
     for k, (a, b) in enumerate(zip(gr[1:8], gr_b[1:8])):
@@ -161,8 +102,8 @@ def test_stack_layer_batch_major_and_last_state_contracts(F, H):
             assert torch.equal(a, b), k
     if H == 256:
         # the reference operator's own contract (z_s and h_prime_s saved) in place as well, and the last-state pair
-        outs_z, gr_z = _run(x, h0, G, p)
-        outs_zb, gr_zb = _run(xb, h0, Gb, p, flags=_lib.FLAG_BATCH_MAJOR)
+        outs_z, gr_z = LC.layer_fwd_bwd(x, h0, G, p)
+        outs_zb, gr_zb = LC.layer_fwd_bwd(xb, h0, Gb, p, flags=_lib.FLAG_BATCH_MAJOR)
         for a, b in zip(outs_z, outs_zb):
             assert torch.equal(b.transpose(0, 1), a)
         assert torch.equal(gr_zb[0].transpose(0, 1), gr_z[0]) and torch.equal(gr_zb[5], gr_z[5])
@@ -170,31 +111,23 @@ def test_stack_layer_batch_major_and_last_state_contracts(F, H):
             assert float((gr_zb[k] - gr_z[k]).abs().max()) <= 2e-6 * max(1.0, float(gr_z[k].abs().max())), k
         fb = _lib.FLAG_SAVE_PREACT | _lib.FLAG_BATCH_MAJOR | _lib.FLAG_GRAD_LAST
         assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=1, flags=fb) == 2
-        got = fastgrnn_cuda.backward_unroll(G[-1].contiguous(), xb, outs_b[0], P["zeta"], P["nu"], P["w"], P["u"], outs_b[1],
-                                            outs_b[1], h0, e, e, e, e, 0, flags=fb, bias_gate=P["bias_gate"],
-                                            bias_update=P["bias_update"])
+        got = S.backward_of(outs_b, G[-1].contiguous(), xb, h0, P, "sigmoid", flags=fb, biases=True)
         Gl0 = torch.zeros_like(G); Gl0[-1] = G[-1]
-        want = fastgrnn_cuda.backward_unroll(Gl0, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[1], h0, e, e,
-                                             e, e, 0, flags=_lib.FLAG_SAVE_PREACT, bias_gate=P["bias_gate"],
-                                             bias_update=P["bias_update"])
+        want = S.backward_of(outs, Gl0, x, h0, P, "sigmoid", flags=_lib.FLAG_SAVE_PREACT, biases=True)
         assert torch.equal(got[0].transpose(0, 1), want[0]) and torch.equal(got[5], want[5])
         for k in (6, 7):
             assert float((got[k] - want[k]).abs().max()) <= 2e-6 * max(1.0, float(want[k].abs().max())), k
     # last-state gradient
     Gl = torch.zeros_like(G); Gl[-1] = G[-1]
     fl = _lib.FLAG_SAVE_PREACT
-    ref = fastgrnn_cuda.backward_unroll(Gl, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[1], h0, e, e, e, e,
-                                        0, flags=fl, bias_gate=P["bias_gate"], bias_update=P["bias_update"])
+    ref = S.backward_of(outs, Gl, x, h0, P, "sigmoid", flags=fl, biases=True)
     assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=1, flags=fl | _lib.FLAG_GRAD_LAST) == 2
-    got = fastgrnn_cuda.backward_unroll(G[-1].contiguous(), x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[1],
-                                        h0, e, e, e, e, 0, flags=fl | _lib.FLAG_GRAD_LAST, bias_gate=P["bias_gate"],
-                                        bias_update=P["bias_update"])
+    got = S.backward_of(outs, G[-1].contiguous(), x, h0, P, "sigmoid", flags=fl | _lib.FLAG_GRAD_LAST, biases=True)
     for a, b in zip(ref[:8], got[:8]):
         assert torch.equal(a, b)
     # inference: h_T only
     assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=0, flags=_lib.FLAG_HS_LAST) == 2
-    hT = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, 0,
-                                      e, e, e, e, want_gates=False, flags=_lib.FLAG_HS_LAST)[0]
+    hT = S.forward_unroll(x, h0, P, "sigmoid", want_gates=False, flags=_lib.FLAG_HS_LAST)[0]
     assert hT.shape == (B, H) and float((hT - outs[0][-1]).abs().max()) <= 2e-6
 
 
@@ -208,11 +141,12 @@ def test_stack_layer_full_batch_every_output_vs_fp64_oracle(F, H):
     G = rng.standard_normal((T, B, H)).astype(np.float32)
     h0 = np.zeros((B, H), np.float32)
     assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=1, flags=_lib.FLAG_SAVE_PREACT) == 2
-    outs, gr = _run(_t(x), _t(h0), _t(G), p, preact=True)
-    hs_o, zs_o, cs_o, g_o = _oracle(x, G, p, h0)
+    outs, gr = LC.layer_fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), p, preact=True)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     assert np.abs(outs[0].cpu().numpy() - hs_o).max() <= 1e-5
     # (the stack's first layer, F = 32 / H = 256: plain 2e-5; layers with a wide input: the conditioning-aware bound too)
-    errs = _check(gr, g_o, scalar_term_tol=0.0 if (F, H) == (32, 256) else SCALAR_TERM_TOL)
+    errs = S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=0.0 if (F, H) == (32, 256) else S.SCALAR_TERM_TOL,
+                         tag=(F, H))
     print("stack layer F=%d H=%d full-size errors: %s" % (F, H, {k: "%.2e" % v for k, v in errs.items()}))
 
 
@@ -223,11 +157,9 @@ def _build_model(g, dtype=torch.float32):
                            device=DEV)
     with torch.no_grad():
         for rnn, (p, _) in zip(m.rnn_list, g["layers"]):
-            rnn.W.copy_(_t(p["w"].astype(np.float32))); rnn.U.copy_(_t(p["u"].astype(np.float32)))
-            rnn.bias_gate.copy_(_t(p["bias_gate"].astype(np.float32))); rnn.bias_update.copy_(_t(p["bias_update"].astype(np.float32)))
-            rnn.zeta.copy_(_t(p["zeta"].astype(np.float32))); rnn.nu.copy_(_t(p["nu"].astype(np.float32)))
-        m.hidden2keyword.weight.copy_(_t(g["fc_w"].astype(np.float32)))
-        m.hidden2keyword.bias.copy_(_t(g["fc_b"].astype(np.float32)))
+            S.copy_cell_params(rnn, {k: v.astype(np.float32) for k, v in p.items()})
+        m.hidden2keyword.weight.copy_(S.to_dev(g["fc_w"].astype(np.float32)))
+        m.hidden2keyword.bias.copy_(S.to_dev(g["fc_b"].astype(np.float32)))
     return m
 
 
@@ -241,8 +173,8 @@ def test_two_layer_model_matches_the_reference_cells_chained(stack_golden, fused
         F_l = g["x"].shape[2] if l == 0 else g["hidden"][l - 1]
         assert fastgrnn_cuda.kernel_path(g["x"].shape[0], g["x"].shape[1], F_l, g["hidden"][l], direction=1,
                                          flags=_lib.FLAG_SAVE_PREACT) == 2
-    x = _t(g["x"].astype(np.float32)).requires_grad_(True)
-    y = _t(g["labels"])
+    x = S.to_dev(g["x"].astype(np.float32)).requires_grad_(True)
+    y = S.to_dev(g["labels"])
     m.init_hidden()
     if fused_head:
         loss = m.loss(x, y)
@@ -275,8 +207,8 @@ def test_two_layer_model_full_batch_vs_fp64_oracle_and_inference_path():
     y = rng.integers(0, C, (B,))
     g = {"hidden": hidden, "x": x, "fc_w": fc_w, "fc_b": fc_b, "layers": [(p, None) for p in layers]}
     m = _build_model(g)
-    xt = _t(x).requires_grad_(True)
-    loss = m.loss(xt, _t(y))
+    xt = S.to_dev(x).requires_grad_(True)
+    loss = m.loss(xt, S.to_dev(y))
     loss.backward()
     torch.cuda.synchronize()
     l64 = [{k: v.astype(np.float64) for k, v in p.items()} for p in layers]
@@ -294,7 +226,7 @@ def test_two_layer_model_full_batch_vs_fp64_oracle_and_inference_path():
             assert rel(par.grad, go[name]) <= 2e-5, (name, rel(par.grad, go[name]))
     with torch.no_grad():
         m.init_hidden()
-        scores = m(_t(x))
+        scores = m(S.to_dev(x))
     assert (np.abs(scores.cpu().numpy() - scores_o) / np.maximum(1.0, np.abs(scores_o))).max() <= 1e-5
 
 
@@ -310,8 +242,8 @@ def test_two_layer_model_with_bf16_sequences(stack_golden):
             assert fastgrnn_cuda.kernel_path(T, B, F_l, H_l, dtype=torch.bfloat16, direction=direction,
                                              flags=_lib.FLAG_SAVE_PREACT) == 2
     m = _build_model(g)
-    y = _t(g["labels"])
-    xb = _t(g["x"].astype(np.float32)).to(torch.bfloat16)
+    y = S.to_dev(g["labels"])
+    xb = S.to_dev(g["x"].astype(np.float32)).to(torch.bfloat16)
     res = []
     for x in (xb, xb.float()):
         for p_ in m.parameters():
@@ -339,8 +271,8 @@ def test_two_layer_model_reads_the_loaders_batch_in_place(stack_golden, want_dx)
     assert fastgrnn_cuda.kernel_path(T, B, F, g["hidden"][0], direction=1,
                                      flags=_lib.FLAG_SAVE_PREACT | _lib.FLAG_X_BFT) == 2
     m = _build_model(g)
-    y = _t(g["labels"])
-    audio = _t(np.ascontiguousarray(g["x"].astype(np.float32).transpose(1, 2, 0)))       # [B,F,T]
+    y = S.to_dev(g["labels"])
+    audio = S.to_dev(np.ascontiguousarray(g["x"].astype(np.float32).transpose(1, 2, 0)))       # [B,F,T]
     res = []
     for view in (True, False):
         a = audio.clone().requires_grad_(want_dx)
@@ -366,17 +298,13 @@ def test_input_gradient_is_optional_where_it_is_a_gemm_of_its_own(F, H):
     T, B = 9, 37
     rng = np.random.default_rng(3)
     p = O.make_params(F, H, dtype=np.float32, seed=37, randomize_scalars=True)
-    P = _P(p)
-    e = torch.empty(0)
-    x = _t(rng.standard_normal((T, B, F)).astype(np.float32))
-    h0 = _t((0.5 * rng.standard_normal((B, H))).astype(np.float32))
-    G = _t(rng.standard_normal((T, B, H)).astype(np.float32))
+    P = S.cell_tensors(p)
+    x = S.to_dev(rng.standard_normal((T, B, F)).astype(np.float32))
+    h0 = S.to_dev((0.5 * rng.standard_normal((B, H))).astype(np.float32))
+    G = S.to_dev(rng.standard_normal((T, B, H)).astype(np.float32))
     fl = _lib.FLAG_SAVE_PREACT
-    outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0, 0,
-                                        e, e, e, e, flags=fl)
-    run = lambda need: fastgrnn_cuda.backward_unroll(G, x, outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[1], h0,
-                                                     e, e, e, e, 0, flags=fl, bias_gate=P["bias_gate"],
-                                                     bias_update=P["bias_update"], need_dx=need)
+    outs = S.forward_unroll(x, h0, P, "sigmoid", flags=fl)
+    run = lambda need: S.backward_of(outs, G, x, h0, P, "sigmoid", flags=fl, biases=True, need_dx=need)
     full, lean = run(True), run(False)
     assert full[0].shape == x.shape and lean[0].numel() == 0
     for a, b in zip(full[1:8], lean[1:8]):
@@ -405,7 +333,7 @@ def test_h256_with_column_blocks_of_U_in_different_binades(B, preact):
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
-    outs, gr = _run(_t(x), _t(h0), _t(G), p, preact=preact)
-    hs_o, zs_o, cs_o, g_o = _oracle(x, G, p, h0)
+    outs, gr = LC.layer_fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), p, preact=preact)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     assert np.abs(outs[0].cpu().numpy() - hs_o).max() <= 1e-5
-    _check(gr, g_o)
+    S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=0.0, tag=(B, preact))

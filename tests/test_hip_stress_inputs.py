@@ -11,21 +11,17 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import support as S
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from kws_amd import _lib, fastgrnn_cuda
-DEV = "cuda:0"
 
 FAMILIES = {"dense128": (32, 128, None), "wide256": (256, 128, None), "h256": (32, 256, None), "lowrank16": (32, 256, 16),
             "rank32": (32, 256, 32), "lowrank_h128": (32, 128, 16)}
 SCENARIOS = ["big_weights", "tiny_weights", "saturated", "zeta_nu_extreme", "big_frames", "tiny_grad", "huge_grad",
              "zero_frames", "zero_grad", "two_steps", "sparse_weights"]
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 @pytest.mark.parametrize("scenario", SCENARIOS)
@@ -70,18 +66,10 @@ def test_unusual_inputs_against_the_oracle(family, scenario):
         x[:] = 0.0
     elif scenario == "zero_grad":
         G[:] = 0.0
-    e = torch.empty(0)
-    P = {k: e for k in ("w", "u", "w1", "w2", "u1", "u2")}
-    P.update({k: _t(v) for k, v in p.items()})
     fl = _lib.FLAG_SAVE_PREACT
     assert fastgrnn_cuda.kernel_path(T, B, F, H, r or 0, r or 0, 0, direction=1, flags=fl) == 2
-    outs = fastgrnn_cuda.forward_unroll(_t(x), P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], _t(h0), 0,
-                                        P["w1"], P["w2"], P["u1"], P["u2"], flags=fl)
-    gr = fastgrnn_cuda.backward_unroll(_t(G), _t(x), outs[0], P["zeta"], P["nu"], P["w"], P["u"], outs[1], outs[-1], _t(h0),
-                                       P["w1"], P["w2"], P["u1"], P["u2"], 0, flags=fl,
-                                       bias_gate=P["bias_gate"], bias_update=P["bias_update"])
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, zs_o, cs_o = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64))
+    outs, gr = S.fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), S.cell_tensors(p), "sigmoid", flags=fl, biases=True)
+    hs_o, zs_o, cs_o, g_o = S.oracle64(x, G, p, h0)
     hs = outs[0].cpu().numpy()
     assert np.isfinite(hs).all()
     # weights 8x the reference's scale make the recurrence expansive: ANY fp32 evaluation drifts from fp64 there, so
@@ -90,11 +78,8 @@ def test_unusual_inputs_against_the_oracle(family, scenario):
     hs_32, zs_32, cs_32 = O.unroll_forward(x, p, h0) if ill else (None, None, None)
     rel = lambda a: float((np.abs(a - hs_o) / np.maximum(1.0, np.abs(hs_o))).max())
     assert rel(hs) <= (max(1e-5, 3.0 * rel(hs_32)) if ill else 1e-5), (rel(hs), rel(hs_32) if ill else None)
-    g_o = O.unroll_backward(G.astype(np.float64), x.astype(np.float64), hs_o, zs_o, cs_o, p64, h0.astype(np.float64),
-                            diagnostics=True)
     g_32 = O.unroll_backward(G, x, hs_32, zs_32, cs_32, p, h0) if ill else None
-    names = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
-    g = {n: v.cpu().numpy() for n, v in zip(names, gr) if v.numel()}
+    g = {n: v.cpu().numpy() for n, v in zip(S.GRAD_NAMES, gr) if v.numel()}
     gscale = max(float(np.abs(G).max()), 0.0)
     for k, v in g_o.items():
         if k.startswith("_"):
@@ -107,7 +92,7 @@ def test_unusual_inputs_against_the_oracle(family, scenario):
         # fp32 rounding of their terms amounts to: the terms' magnitude sum for zeta / nu, the gradient scale otherwise
         lim = (6e-5 if ill else 3e-5) * ref_max
         if k in ("d_zeta", "d_nu"):
-            lim = max(lim, 2e-7 * g_o["_abs_" + k[2:]])
+            lim = max(lim, S.SCALAR_TERM_TOL * g_o["_abs_" + k[2:]])
         lim = max(lim, 1e-6 * gscale)
         if ill:
             # (three times what the same formulas evaluated in fp32 are off by.  The dense H=256 backward gets six: its

@@ -35,14 +35,13 @@ import torch
 
 from kws_amd import FastGRNNCUDA, RNNClassifierModel, _lib, fastgrnn_cuda
 from kws_amd.rnn import gather_windows
-from oracle import fastgrnn_oracle as O
-from tests.test_hip_parity import _check_grads, _keep_relu_gates_off_the_kink
-from tests.test_hip_windows import _plain_cell
+from tests import layer_cases as LC
+from tests import support as S
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 SP, BM, GL, NIG = _lib.FLAG_SAVE_PREACT, _lib.FLAG_BATCH_MAJOR, _lib.FLAG_GRAD_LAST, _lib.FLAG_NO_INPUT_GRAD
-GATES = {"sigmoid": 0, "relu": 1, "tanh": 2}
+GATES = ("sigmoid", "relu", "tanh")
 SHAPES = [(128, 32), (256, 32), (256, 64)]
 R, PAD = 300, 128
 SENTINEL = -7777.0
@@ -120,15 +119,11 @@ def _h0(B, H):
     return (0.5 * torch.randn(B, H, generator=g)).to(DEV)
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 @functools.lru_cache(maxsize=None)
 def _problem(H, F, gate, T, B, kind, gl):
     """Everything a case shares whatever its layout, computed once: parameters (numpy and device), the gathered
     windows [T,B,F], the gradient in time-major form, and the fp64 oracle's hs and gradients."""
-    p, _ = _plain_cell(H, F, gate)
+    p, _ = LC.plain_cell(H, F, gate)
     x = gather_windows(_pool(F), _starts(kind, B, T), T).transpose(0, 1).contiguous()
     h0 = _h0(B, H)
     xn, hn = x.cpu().numpy(), h0.cpu().numpy()
@@ -136,16 +131,13 @@ def _problem(H, F, gate, T, B, kind, gl):
         p = dict(p)
         p["u"] = (0.25 * p["u"]).astype(np.float32)
     if gate == "relu":
-        p = _keep_relu_gates_off_the_kink(p, xn, hn)
-    P = {k: _t(v) for k, v in p.items()}
+        p = S.keep_relu_gates_off_the_kink(p, xn, hn)
+    P = S.cell_tensors(p)
     g = torch.Generator().manual_seed(T * 1000 + B)
     G = torch.randn(T, B, H, generator=g)
     if gl:
         G[:-1] = 0.0
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    x64, h64 = xn.astype(np.float64), hn.astype(np.float64)
-    hs_o, zs_o, cs_o = O.unroll_forward(x64, p64, h64, gate=gate)
-    g_o = O.unroll_backward(G.numpy().astype(np.float64), x64, hs_o, zs_o, cs_o, p64, h64, gate=gate, diagnostics=True)
+    hs_o, _, _, g_o = S.oracle64(xn, G.numpy(), p, hn, gate)
     g_o.pop("d_x")
     return P, x, G.to(DEV), hs_o, g_o
 
@@ -167,7 +159,7 @@ def _with_tail(shape, dtype=torch.float32):
 
 def _raw_forward(H, F, gate, flags, pool, starts, T, h0, P, hs, saved):
     lib = _lib.load()
-    d = _lib.Desc(T, starts.numel(), F, H, 0, 0, GATES[gate], 2, _lib.F32, flags)
+    d = _lib.Desc(T, starts.numel(), F, H, 0, 0, S.NONLINEARITY[gate], 2, _lib.F32, flags)
     assert lib.fastgrnn_hip_train_windows_supported(C.byref(d)) == 1
     nbytes = int(lib.fastgrnn_hip_train_windows_forward_workspace_bytes(C.byref(d), R))
     ws = torch.full((nbytes + 256,), 0x5A, dtype=torch.uint8, device=DEV)
@@ -184,7 +176,7 @@ def _raw_backward(H, F, gate, flags, pool, starts, T, h0, P, G, hs, saved):
     """-> ({name: gradient}, their sentinel tails, the workspace, the bytes the library asked for)"""
     lib = _lib.load()
     B = starts.numel()
-    d = _lib.Desc(T, B, F, H, 0, 0, GATES[gate], 2, _lib.F32, flags)
+    d = _lib.Desc(T, B, F, H, 0, 0, S.NONLINEARITY[gate], 2, _lib.F32, flags)
     assert lib.fastgrnn_hip_train_windows_supported(C.byref(d)) == 1
     nbytes = int(lib.fastgrnn_hip_train_windows_backward_workspace_bytes(C.byref(d), R))
     ws = torch.full((nbytes + 256,), 0x5A, dtype=torch.uint8, device=DEV)
@@ -221,10 +213,8 @@ def test_train_windows_vs_existing_calls_oracle_and_sentinels(case):
     assert bool((hs_tail == SENTINEL).all()) and bool((saved_tail == SENTINEL).all()), "wrote beyond hs / saved"
     assert bool(torch.isfinite(hs).all()) and bool(torch.isfinite(saved).all()), "not finite: read beyond the pool?"
     # (a) the existing forward on the gathered windows: the same bits
-    e = torch.empty(0)
     x = lay(x_tm)
-    want_hs, want_pre = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"],
-                                                     P["nu"], h0, GATES[gate], e, e, e, e, flags=SP | layout)[:2]
+    want_hs, want_pre = S.forward_unroll(x, h0, P, gate, flags=SP | layout)[:2]
     assert torch.equal(hs, want_hs), "hs differs from forward_unroll on the gathered windows"
     assert torch.equal(saved, want_pre), "the saved pre-activation differs from forward_unroll's"
 
@@ -237,15 +227,14 @@ def test_train_windows_vs_existing_calls_oracle_and_sentinels(case):
     assert bool((ws[nbytes:] == 0x5A).all()), "wrote beyond the workspace (its end is the gathered copy of x)"
     # (d) the gathered copy alone: the last align256(T*B*F*4) bytes of the workspace
     copy_bytes = (T * B * F * 4 + 255) // 256 * 256
-    d0 = _lib.Desc(T, B, F, H, 0, 0, GATES[gate], 2, _lib.F32, layout | (GL if gl else 0))
+    d0 = _lib.Desc(T, B, F, H, 0, 0, S.NONLINEARITY[gate], 2, _lib.F32, layout | (GL if gl else 0))
     assert nbytes == int(_lib.load().fastgrnn_hip_backward_workspace_bytes(C.byref(d0))) + copy_bytes
     copy = ws[nbytes - copy_bytes:nbytes - copy_bytes + T * B * F * 4].view(torch.float32).view(x.shape)
     assert torch.equal(copy, x), "the gather kernel's copy differs from gather_windows"
     assert bool((ws[nbytes - copy_bytes + T * B * F * 4:nbytes] == 0x5A).all())
     # (b) the existing backward on the gathered windows without d_x: the same bits
-    ref = fastgrnn_cuda.backward_unroll(G, x, want_hs, P["zeta"], P["nu"], P["w"], P["u"], want_pre, want_pre, h0,
-                                        e, e, e, e, GATES[gate], flags=SP | layout | (GL if gl else 0),
-                                        bias_gate=P["bias_gate"], bias_update=P["bias_update"], need_dx=False)
+    ref = S.backward_of((want_hs, want_pre), G, x, h0, P, gate, flags=SP | layout | (GL if gl else 0), biases=True,
+                        need_dx=False)
     torch.cuda.synchronize()
     assert ref[0].numel() == 0
     for k, v in zip(GRADS, ref[1:8]):
@@ -262,7 +251,7 @@ def test_train_windows_vs_existing_calls_oracle_and_sentinels(case):
     print("%s: hs %.3g (bound 1e-5); gradients %s (bound 2e-5, d_zeta / d_nu also 2e-7 of their terms' magnitudes)"
           % (_id(case), err, " ".join("%s %.3g" % kv for kv in gerr.items())))
     assert err <= 1e-5
-    _check_grads({k: got[k].cpu().numpy() for k in GRADS}, g_o, 2e-5, _id(case))
+    S.check_grads({k: got[k] for k in GRADS}, g_o, tol=2e-5, scalar_term_tol=S.SCALAR_TERM_TOL, tag=_id(case))
 
 
 # ---- modules -----------------------------------------------------------------------------------------------------------

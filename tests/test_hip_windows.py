@@ -25,12 +25,12 @@ from kws_amd import FastGRNNCUDA, RNNClassifierModel, _lib, fastgrnn_cuda, fold_
 from kws_amd.rnn import gather_windows
 from oracle import fastgrnn_oracle as O
 from tests import batchnorm_golden as G
-from tests.test_hip_batchnorm import _fp32_scan, _fp64_scan, _random_bn
+from tests import layer_cases as LC
+from tests import support as S
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 A, BM, LAST = _lib.FLAG_PREACT_AFFINE, _lib.FLAG_BATCH_MAJOR, _lib.FLAG_HS_LAST
-GATES = {"sigmoid": 0, "relu": 1, "tanh": 2}
 SHAPES = [(128, 32), (256, 32), (256, 64)]
 T, R, B = 7, 61, 37
 SENTINEL = -7777.0
@@ -64,24 +64,9 @@ def _h0(H):
     return (0.5 * torch.randn(B, H, generator=g)).to(DEV)
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-@functools.lru_cache(maxsize=None)
-def _plain_cell(H, F, gate):
-    """Parameters as tests/test_hip_parity.py draws them (relu: scaled so that the state stays in range)."""
-    p = O.make_params(F, H, dtype=np.float32, seed=11, randomize_scalars=True)
-    if gate == "relu":
-        for k in ("w", "u"):
-            p[k] = (0.3 * p[k]).astype(np.float32)
-        p["bias_gate"] = (0.3 * p["bias_gate"] - 0.1).astype(np.float32)
-    return p, {k: _t(v) for k, v in p.items()}
-
-
 @functools.lru_cache(maxsize=None)
 def _affine_cell(H, F, gate):
-    m = _random_bn(F, H, gate, seed=H + F + len(gate))
+    m = G.random_bn(F, H, gate, seed=H + F + len(gate))
     return m, tuple(t.contiguous() for t in fold_batchnorm(m.cell))
 
 
@@ -92,13 +77,12 @@ def _reference(H, F, gate, affine, kind):
     h0 = _h0(H)
     if affine:
         m, _ = _affine_cell(H, F, gate)
-        ref = _fp64_scan(m, x, h0)
-        e32 = float((_fp32_scan(m, x, h0).double() - ref).abs().max())
+        ref = G.fp64_scan(m, x, h0)
+        e32 = float((G.fp32_scan(m, x, h0).double() - ref).abs().max())
         bound = 4 * e32 + 1e-5 * max(1.0, float(ref.abs().max()))
         return x, ref, lambda hs: (float((hs.double() - ref).abs().max()), bound)
-    p, _ = _plain_cell(H, F, gate)
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, _, _ = O.unroll_forward(x.cpu().numpy().astype(np.float64), p64, h0.cpu().numpy().astype(np.float64), gate=gate)
+    p, _ = LC.plain_cell(H, F, gate)
+    hs_o, _, _ = S.oracle64_forward(x.cpu().numpy(), p, h0.cpu().numpy(), gate)
     ref = torch.from_numpy(hs_o).to(DEV)
     return x, ref, lambda hs: (float(((hs.double() - ref).abs() / ref.abs().clamp(min=1.0)).max()), 1e-5)
 
@@ -107,7 +91,7 @@ def _operands(H, F, gate, affine):
     if affine:
         m, (w, u, bg, bu, sg, sc) = _affine_cell(H, F, gate)
         return w, u, bg, bu, m.cell.zeta, m.cell.nu, sg, sc
-    _, P = _plain_cell(H, F, gate)
+    _, P = LC.plain_cell(H, F, gate)
     return P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], None, None
 
 
@@ -115,7 +99,7 @@ def _raw_windows(H, F, gate, flags, pool_buf, rows, starts, h0, hs_buf, ops):
     """One call of the C entry point into caller-owned buffers."""
     lib = _lib.load()
     w, u, bg, bu, zeta, nu, sg, sc = ops
-    d = _lib.Desc(T, starts.numel(), F, H, 0, 0, GATES[gate], 2, _lib.F32, flags)
+    d = _lib.Desc(T, starts.numel(), F, H, 0, 0, S.NONLINEARITY[gate], 2, _lib.F32, flags)
     assert lib.fastgrnn_hip_windows_supported(C.byref(d)) == 1
     nbytes = int(lib.fastgrnn_hip_forward_windows_workspace_bytes(C.byref(d), rows))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV)
@@ -133,10 +117,9 @@ def _existing_forward(H, F, gate, flags, x_tm, h0, ops):
     w, u, bg, bu, zeta, nu, sg, sc = ops
     x = x_tm.transpose(0, 1).contiguous() if flags & BM else x_tm
     if sg is not None:
-        return fastgrnn_cuda.forward_unroll_affine(x, w, u, bg, bu, zeta, nu, sg, sc, h0, GATES[gate], flags=flags)
-    e = torch.empty(0)
-    return fastgrnn_cuda.forward_unroll(x, w, u, bg, bu, zeta, nu, h0, GATES[gate], e, e, e, e, want_gates=False,
-                                        flags=flags)[0]
+        return fastgrnn_cuda.forward_unroll_affine(x, w, u, bg, bu, zeta, nu, sg, sc, h0, S.NONLINEARITY[gate],
+                                                   flags=flags)
+    return S.forward_unroll(x, h0, LC.plain_cell(H, F, gate)[1], gate, want_gates=False, flags=flags)[0]
 
 
 @pytest.mark.parametrize("kind", ["hop1", "hop9", "perm"])
@@ -184,10 +167,8 @@ def _plain_model(F):
                            "sigmoid", "tanh", num_classes=12, device=DEV)
     with torch.no_grad():
         for rnn, p in zip(m.rnn_list, layers):
-            rnn.W.copy_(_t(p["w"])); rnn.U.copy_(_t(p["u"]))
-            rnn.bias_gate.copy_(_t(p["bias_gate"])); rnn.bias_update.copy_(_t(p["bias_update"]))
-            rnn.zeta.copy_(_t(p["zeta"])); rnn.nu.copy_(_t(p["nu"]))
-        m.hidden2keyword.weight.copy_(_t(fc_w)); m.hidden2keyword.bias.copy_(_t(fc_b))
+            S.copy_cell_params(rnn, p)
+        m.hidden2keyword.weight.copy_(S.to_dev(fc_w)); m.hidden2keyword.bias.copy_(S.to_dev(fc_b))
     return m, layers, fc_w, fc_b
 
 
@@ -278,7 +259,7 @@ def test_range_check_is_on_the_host():
         m.forward_windows(pool, neg, T)
     with pytest.raises(ValueError):
         m.forward_windows(pool, _starts("hop1"), R + 1)
-    P = _plain_cell(128, 32, "sigmoid")[1]
+    P = LC.plain_cell(128, 32, "sigmoid")[1]
     with pytest.raises(ValueError):
         fastgrnn_cuda.forward_windows(pool, bad, T, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"],
                                       P["nu"], _h0(128), 0)

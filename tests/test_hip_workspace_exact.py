@@ -15,6 +15,7 @@ import torch
 
 from kws_amd import _lib, fastgrnn_cuda
 from kws_amd import batchnorm_train
+from tests import support as S
 
 SP, BFT, ZE = _lib.FLAG_SAVE_PREACT, _lib.FLAG_X_BFT, _lib.FLAG_ZERO_EXTEND
 MARGIN = 4096
@@ -77,13 +78,13 @@ def _named(prefix, tensors):
 
 def _unrolled(dev, F, H, T, B, flags, rw=0, ru=0, dtype=torch.float32):
     r = _rand(1000 * H + 10 * F + B + T, dev)
-    w, u, bg, bu, zeta, nu, w1, w2, u1, u2 = _cell(r, F, H, rw, ru)
+    P = dict(zip(("w", "u", "bias_gate", "bias_update", "zeta", "nu", "w1", "w2", "u1", "u2"), _cell(r, F, H, rw, ru)))
     x = r(*((B, F, T) if flags & BFT else (T, B, F)), dtype=dtype)
     h0, G = r(B, H, k=0.5), r(T, B, H, dtype=dtype)
-    fwd = fastgrnn_cuda.forward_unroll(x, w, u, bg, bu, zeta, nu, h0, 0, w1, w2, u1, u2, flags=flags)
-    hs, z, h_prime = fwd[0], fwd[1], (fwd[2] if len(fwd) > 2 else NONE)
-    bwd = fastgrnn_cuda.backward_unroll(G, x, hs, zeta, nu, w, u, z, h_prime, h0, w1, w2, u1, u2, 0, flags=flags,
-                                        bias_gate=bg, bias_update=bu)
+    fwd = S.forward_unroll(x, h0, P, "sigmoid", flags=flags)
+    hs, z, h_prime = fwd[0], fwd[1], (fwd[2] if len(fwd) > 2 else NONE)      # (no third output: no h_prime is given)
+    bwd = S.backward_unroll(G, x, hs, z, h_prime, h0, P, "sigmoid", flags=flags, bias_gate=P["bias_gate"],
+                            bias_update=P["bias_update"])
     return {**_named("fwd", fwd), **_named("bwd", bwd)}
 
 

@@ -12,28 +12,15 @@ import pytest
 import torch
 
 from oracle import fastgrnn_oracle as O
+from tests import support as S
+from tests.support import DEV
 
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
-    from kws_amd import FastGRNNCUDA, GraphedStep, RNNClassifierModel, _lib, fastgrnn_cuda
+    from kws_amd import FastGRNNCUDA, GraphedStep, RNNClassifierModel, fastgrnn_cuda
     from kws_amd import _route
-DEV = "cuda:0"
-SP, BM, GL, HL, ZE = 4, 16, 256, 512, 4096
-GATE = {"sigmoid": 0, "relu": 1, "tanh": 2, "quantTanh": 3, "quantSigm": 4, "quantSigm4": 5}
-NAMES = ["d_x", "d_bias_gate", "d_bias_update", "d_zeta", "d_nu", "d_h0", "d_w", "d_u", "d_w1", "d_w2", "d_u1", "d_u2"]
-SCALAR_TERM_TOL = 2e-7          # tests/test_hip_parity.py: d_zeta / d_nu against the sum of their terms' magnitudes
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _P(p):
-    e = torch.empty(0, device=DEV)
-    g = lambda k: _t(p[k]) if k in p else e
-    return dict(w=g("w"), u=g("u"), w1=g("w1"), w2=g("w2"), u1=g("u1"), u2=g("u2"),
-                bias_gate=_t(p["bias_gate"]), bias_update=_t(p["bias_update"]), zeta=_t(p["zeta"]), nu=_t(p["nu"]))
+SP, BM, GL, HL, ZE = S.FLAG_SAVE_PREACT, S.FLAG_BATCH_MAJOR, S.FLAG_GRAD_LAST, S.FLAG_HS_LAST, S.FLAG_ZERO_EXTEND
 
 
 def _pad(t, shape):
@@ -60,26 +47,9 @@ def _pad_params(P, H, F, Hp, Fp):
 
 
 def fwd_bwd(x, h0, G, P, gate, flags, update="tanh", need_dx=True):
-    """forward_unroll under SAVE_PREACT + backward_unroll; returns hs, the saved tensor(s), the 12 gradients"""
-    outs = fastgrnn_cuda.forward_unroll(x, P["w"], P["u"], P["bias_gate"], P["bias_update"], P["zeta"], P["nu"], h0,
-                                        GATE[gate], P["w1"], P["w2"], P["u1"], P["u2"], flags=flags,
-                                        update_non_linearity=GATE[update])
-    hs, pre = outs[0], outs[1]
-    aux = outs[2] if len(outs) > 2 else pre
-    g = fastgrnn_cuda.backward_unroll(G, x, hs, P["zeta"], P["nu"], P["w"], P["u"], pre, aux, h0, P["w1"], P["w2"],
-                                      P["u1"], P["u2"], GATE[gate], flags=flags, update_non_linearity=GATE[update],
-                                      bias_gate=P["bias_gate"], bias_update=P["bias_update"], need_dx=need_dx)
-    return hs, pre, dict(zip(NAMES, g))
-
-
-def _bits(t):
-    t = t.contiguous()
-    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
-
-
-def _same_bits(a, b, what):
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    assert torch.equal(_bits(a), _bits(b)), (what, float((a.float() - b.float()).abs().max()))
+    """forward_unroll under SAVE_PREACT + backward_unroll; returns hs, the saved tensor, the 12 gradients by name"""
+    outs, g = S.fwd_bwd(x, h0, G, P, gate, update=update, flags=flags, biases=True, need_dx=need_dx)
+    return outs[0], outs[1], dict(zip(S.GRAD_NAMES, g))
 
 
 # F, H, w_rank, u_rank, B, T, bf16, extra flags, gate
@@ -107,7 +77,7 @@ BITWISE = [
 def test_padded_route_equals_the_explicitly_padded_call_bitwise(case):
     F, H, rw, ru, B, T, bf, extra, gate = case
     dt = torch.bfloat16 if bf else torch.float32
-    plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, rw, ru, GATE[gate], dtype=dt, flags=SP | extra)
+    plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, rw, ru, S.NONLINEARITY[gate], dtype=dt, flags=SP | extra)
     assert plan["forward"] == 1 and plan["backward"] == 1, plan
     Hp, Fp = plan["Hp"], plan["Fp"]
     rng = np.random.default_rng(F * 1000 + H)
@@ -115,12 +85,12 @@ def test_padded_route_equals_the_explicitly_padded_call_bitwise(case):
     if gate == "relu":
         for k in ("w", "u"):
             p[k] = (0.3 * p[k]).astype(np.float32)
-    P = _P(p)
+    P = S.cell_tensors(p)
     lead = (B, T) if extra & BM else (T, B)
-    x = _t(rng.standard_normal(lead + (F,)).astype(np.float32)).to(dt)
-    h0 = _t((0.5 * rng.standard_normal((B, H))).astype(np.float32))
-    G = _t(rng.standard_normal(((B,) if extra & GL else lead) + (H,)).astype(np.float32)).to(dt)
-    assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, GATE[gate], dtype=dt, direction=1, flags=SP | extra) == 0
+    x = S.to_dev(rng.standard_normal(lead + (F,)).astype(np.float32)).to(dt)
+    h0 = S.to_dev((0.5 * rng.standard_normal((B, H))).astype(np.float32))
+    G = S.to_dev(rng.standard_normal(((B,) if extra & GL else lead) + (H,)).astype(np.float32)).to(dt)
+    assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, S.NONLINEARITY[gate], dtype=dt, direction=1, flags=SP | extra) == 0
     hs, saved, g = fwd_bwd(x, h0, G, P, gate, SP | extra | ZE)
     assert saved.dtype == torch.uint8 and saved.numel() == plan["saved_bytes"]
     assert hs.shape == lead + (H,) and hs.dtype == dt
@@ -129,21 +99,21 @@ def test_padded_route_equals_the_explicitly_padded_call_bitwise(case):
     hs_n, _, g_n = fwd_bwd(_pad(x, lead + (Fp,)), _pad(h0, (B, Hp)), _pad(G, G.shape[:-1] + (Hp,)), Q, gate,
                            SP | extra)
     torch.cuda.synchronize()
-    _same_bits(hs, hs_n[..., :H], "hs")
-    _same_bits(g["d_x"], g_n["d_x"][..., :F], "d_x")
-    _same_bits(g["d_h0"], g_n["d_h0"][:, :H], "d_h0")
+    S.assert_same_bits(hs, hs_n[..., :H], "hs")
+    S.assert_same_bits(g["d_x"], g_n["d_x"][..., :F], "d_x")
+    S.assert_same_bits(g["d_h0"], g_n["d_h0"][:, :H], "d_h0")
     for k in ("d_bias_gate", "d_bias_update"):
-        _same_bits(g[k], g_n[k][:, :H], k)
+        S.assert_same_bits(g[k], g_n[k][:, :H], k)
     for k in ("d_zeta", "d_nu"):
-        _same_bits(g[k], g_n[k], k)
+        S.assert_same_bits(g[k], g_n[k], k)
     if rw:
-        _same_bits(g["d_w1"], g_n["d_w1"][:, :F], "d_w1"); _same_bits(g["d_w2"], g_n["d_w2"][:H], "d_w2")
+        S.assert_same_bits(g["d_w1"], g_n["d_w1"][:, :F], "d_w1"); S.assert_same_bits(g["d_w2"], g_n["d_w2"][:H], "d_w2")
     else:
-        _same_bits(g["d_w"], g_n["d_w"][:H, :F], "d_w")
+        S.assert_same_bits(g["d_w"], g_n["d_w"][:H, :F], "d_w")
     if ru:
-        _same_bits(g["d_u1"], g_n["d_u1"][:, :H], "d_u1"); _same_bits(g["d_u2"], g_n["d_u2"][:H], "d_u2")
+        S.assert_same_bits(g["d_u1"], g_n["d_u1"][:, :H], "d_u1"); S.assert_same_bits(g["d_u2"], g_n["d_u2"][:H], "d_u2")
     else:
-        _same_bits(g["d_u"], g_n["d_u"][:H, :H], "d_u")
+        S.assert_same_bits(g["d_u"], g_n["d_u"][:H, :H], "d_u")
     # the padded units' gradients are exact zeros (nothing leaks into the slices above)
     assert not g_n["d_h0"][:, H:].any() and not g_n["d_bias_gate"][:, H:].any()
 
@@ -155,11 +125,11 @@ def test_inference_forwards_bitwise(F, H, bf, bm):
     T, B = 9, 37
     dt = torch.bfloat16 if bf else torch.float32
     p = O.make_params(F, H, dtype=np.float32, seed=5, randomize_scalars=True)
-    P = _P(p)
+    P = S.cell_tensors(p)
     rng = np.random.default_rng(H)
     lead = (B, T) if bm else (T, B)
-    x = _t(rng.standard_normal(lead + (F,)).astype(np.float32)).to(dt)
-    h0 = _t((0.5 * rng.standard_normal((B, H))).astype(np.float32))
+    x = S.to_dev(rng.standard_normal(lead + (F,)).astype(np.float32)).to(dt)
+    h0 = S.to_dev((0.5 * rng.standard_normal((B, H))).astype(np.float32))
     plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, dtype=dt, flags=BM if bm else 0)
     Hp, Fp = plan["Hp"], plan["Fp"]
     Q = _pad_params(P, H, F, Hp, Fp)
@@ -168,12 +138,10 @@ def test_inference_forwards_bitwise(F, H, bf, bm):
             continue
         fl = (BM if bm else 0) | (HL if last else 0)
         assert fastgrnn_cuda.kernel_path(T, B, F, H, dtype=dt, flags=fl | ZE) == 2
-        run = lambda xx, hh, PP, f: fastgrnn_cuda.forward_unroll(
-            xx, PP["w"], PP["u"], PP["bias_gate"], PP["bias_update"], PP["zeta"], PP["nu"], hh, 0, PP["w1"], PP["w2"],
-            PP["u1"], PP["u2"], want_gates=False, flags=f)[0]
+        run = lambda xx, hh, PP, f: S.forward_unroll(xx, hh, PP, "sigmoid", want_gates=False, flags=f)[0]
         hs = run(x, h0, P, fl | ZE)
         hs_n = run(_pad(x, lead + (Fp,)), _pad(h0, (B, Hp)), Q, fl)
-        _same_bits(hs, hs_n[..., :H], "hs last=%s" % last)
+        S.assert_same_bits(hs, hs_n[..., :H], "hs last=%s" % last)
 
 
 def test_need_dx_false_skips_the_input_gradient():
@@ -181,27 +149,18 @@ def test_need_dx_false_skips_the_input_gradient():
     T, B, F, H = 6, 37, 100, 100
     assert fastgrnn_cuda.zero_extend_plan(T, B, F, H, flags=SP)["dx_optional"] == 1
     p = O.make_params(F, H, dtype=np.float32, seed=2, randomize_scalars=True)
-    P = _P(p)
+    P = S.cell_tensors(p)
     rng = np.random.default_rng(0)
-    x = _t(rng.standard_normal((T, B, F)).astype(np.float32)); h0 = _t(np.zeros((B, H), np.float32))
-    G = _t(rng.standard_normal((T, B, H)).astype(np.float32))
+    x = S.to_dev(rng.standard_normal((T, B, F)).astype(np.float32)); h0 = S.to_dev(np.zeros((B, H), np.float32))
+    G = S.to_dev(rng.standard_normal((T, B, H)).astype(np.float32))
     _, _, g0 = fwd_bwd(x, h0, G, P, "sigmoid", SP | ZE)
     _, _, g1 = fwd_bwd(x, h0, G, P, "sigmoid", SP | ZE, need_dx=False)
     assert g1["d_x"].numel() == 0
     for k in ("d_w", "d_u", "d_h0", "d_zeta"):
-        _same_bits(g0[k], g1[k], k)
+        S.assert_same_bits(g0[k], g1[k], k)
 
 
 # ---- against the reference's fixtures and the fp64 oracle ------------------------------------------------------------
-
-def _oracle(x, h0, G, p, gate="sigmoid", update="tanh"):
-    p64 = {k: np.asarray(v, np.float64) for k, v in p.items()}
-    x64, h64 = np.asarray(x, np.float64), np.asarray(h0, np.float64)
-    hs, zs, cs = O.unroll_forward(x64, p64, h64, gate=gate, update=update)
-    g = O.unroll_backward(np.asarray(G, np.float64), x64, hs, zs, cs, p64, h64, gate=gate, update=update,
-                          diagnostics=True)
-    return hs, g
-
 
 def _check(hs, g, hs_o, g_o, tol, tag, hs_tol=1e-5, ill=None):
     """ill = (hs_32, g_32, fac): an expansive recurrence (weights 8x the reference scale), judged beside the oracle
@@ -218,7 +177,7 @@ def _check(hs, g, hs_o, g_o, tol, tag, hs_tol=1e-5, ill=None):
         err = float(np.abs(a - v).max())
         lim = tol * max(1.0, float(np.abs(v).max()))
         if k in ("d_zeta", "d_nu"):
-            lim = max(lim, SCALAR_TERM_TOL * g_o["_abs_" + k[2:]])
+            lim = max(lim, S.SCALAR_TERM_TOL * g_o["_abs_" + k[2:]])
         if ill is not None:
             lim = max(lim, ill[2] * float(np.abs(ill[1][k].reshape(v.shape) - v).max()))
         assert err <= lim, (tag, k, err, lim)
@@ -236,15 +195,15 @@ def test_reference_fixtures_on_the_padded_route(name):
     H = h0.shape[1]
     rw = p["w1"].shape[0] if "w1" in p else 0
     ru = p["u1"].shape[0] if "u1" in p else 0
-    assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, GATE[gd["gate"]], direction=1, flags=SP | ZE) == 2
-    hs, _, g = fwd_bwd(_t(x), _t(h0), _t(G), _P(p), gd["gate"], SP | ZE)
+    assert fastgrnn_cuda.kernel_path(T, B, F, H, rw, ru, S.NONLINEARITY[gd["gate"]], direction=1, flags=SP | ZE) == 2
+    hs, _, g = fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), S.cell_tensors(p), gd["gate"], SP | ZE)
     if name.endswith("_f32"):        # the reference's own fp32 outputs
         ref = dict(gd["dparams"]); ref["d_x"] = gd["dx"]; ref["d_h0"] = gd["dh0"]
-        _, g_o = _oracle(x, h0, G, p, gd["gate"])
+        g_o = S.oracle64(x, G, p, h0, gd["gate"])[3]
         ref["_abs_zeta"], ref["_abs_nu"] = g_o["_abs_zeta"], g_o["_abs_nu"]
         _check(hs, g, gd["hs"], ref, 2e-5, name)
     else:                            # fp64 fixtures: the oracle on the fp32-rounded inputs (and the fixture itself)
-        hs_o, g_o = _oracle(x, h0, G, p, gd["gate"])
+        hs_o, _, _, g_o = S.oracle64(x, G, p, h0, gd["gate"])
         assert np.abs(hs_o - gd["hs"]).max() < 1e-6
         _check(hs, g, hs_o, g_o, 2e-5, name)
 
@@ -260,13 +219,11 @@ def test_quantised_fixture_with_the_kernels_own_gates():
     x, h0, G = f32(gd["x"]), f32(gd["h0"]), f32(gd["G"])
     T, B, F = x.shape
     H = h0.shape[1]
-    plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, gate_nl=GATE["quantSigm"], update_nl=GATE["quantTanh"],
+    plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, gate_nl=S.NONLINEARITY["quantSigm"], update_nl=S.NONLINEARITY["quantTanh"],
                                           flags=SP)
     assert plan["backward"] == 1
-    hs, saved, g = fwd_bwd(_t(x), _t(h0), _t(G), _P(p), "quantSigm", SP | ZE, update="quantTanh")
-    p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    hs_o, _, _ = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate="quantSigm",
-                                  update="quantTanh")
+    hs, saved, g = fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), S.cell_tensors(p), "quantSigm", SP | ZE, update="quantTanh")
+    hs_o, _, _ = S.oracle64_forward(x, p, h0, "quantSigm", "quantTanh")
     assert (np.abs(hs.cpu().numpy() - hs_o) / np.maximum(1.0, np.abs(hs_o))).max() <= 1e-5
     pre = saved[:T * B * plan["Hp"] * 4].view(torch.float32).view(T, B, plan["Hp"])[..., :H].cpu().numpy()
     zk = np.clip((pre + p["bias_gate"] + 1) / 2, 0, 1).astype(np.float32)
@@ -274,19 +231,6 @@ def test_quantised_fixture_with_the_kernels_own_gates():
     g_o = O.unroll_backward(G, x, hs.cpu().numpy(), zk, ck, p, h0, gate="quantSigm", update="quantTanh",
                             diagnostics=True)
     _check(hs, g, hs_o, g_o, 5e-5, "g7_quant")
-
-
-def _relu_off_kink(p, x, h0, margin=1e-4):
-    p = {k: v.copy() for k, v in p.items()}
-    for _ in range(50):
-        p64 = {k: v.astype(np.float64) for k, v in p.items()}
-        _, _, cs = O.unroll_forward(x.astype(np.float64), p64, h0.astype(np.float64), gate="relu")
-        a = np.arctanh(np.clip(cs, -1 + 1e-15, 1 - 1e-15)) - p64["bias_update"] + p64["bias_gate"]
-        close = np.abs(a).reshape(-1, a.shape[-1]).min(axis=0) < 2 * margin
-        if not close.any():
-            return p
-        p["bias_gate"][0, close] += np.float32(7 * margin)
-    raise AssertionError("could not move the relu gates off the kink")
 
 
 @pytest.mark.parametrize("H", [1, 16, 33, 100, 127, 129, 200, 255])
@@ -309,13 +253,13 @@ def test_odd_sizes_vs_the_fp64_oracle(F, H):
             h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
             G = rng.standard_normal((T, B, H)).astype(np.float32)
             if gate == "relu":
-                p = _relu_off_kink(p, x, h0)
+                p = S.keep_relu_gates_off_the_kink(p, x, h0)
             lay = (lambda a: np.ascontiguousarray(a.transpose(1, 0, 2))) if bm else (lambda a: a)
-            hs, _, g = fwd_bwd(_t(lay(x)), _t(h0), _t(lay(G)), _P(p), gate, SP | ZE | (BM if bm else 0))
+            hs, _, g = fwd_bwd(S.to_dev(lay(x)), S.to_dev(h0), S.to_dev(lay(G)), S.cell_tensors(p), gate, SP | ZE | (BM if bm else 0))
             if bm:
                 hs = hs.transpose(0, 1)
                 g["d_x"] = g["d_x"].transpose(0, 1)
-            hs_o, g_o = _oracle(x, h0, G, p, gate)
+            hs_o, _, _, g_o = S.oracle64(x, G, p, h0, gate)
             ill = None
             if scale > 1 or gate == "relu":      # (a relu gate is not contractive either: |z| is not < 1)
                 hs_32, zs_32, cs_32 = O.unroll_forward(x, p, h0, gate=gate)
@@ -337,7 +281,7 @@ def test_bf16_frames_vs_the_fp64_oracle(F, H):
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     plan = fastgrnn_cuda.zero_extend_plan(T, B, F, H, dtype=torch.bfloat16, flags=SP)
     assert plan["backward"] == 1
-    hs, saved, g = fwd_bwd(x_bf.to(DEV), _t(h0), G_bf.to(DEV), _P(p), "sigmoid", SP | ZE)
+    hs, saved, g = fwd_bwd(x_bf.to(DEV), S.to_dev(h0), G_bf.to(DEV), S.cell_tensors(p), "sigmoid", SP | ZE)
     assert hs.dtype == torch.bfloat16 and g["d_x"].dtype == torch.bfloat16 and g["d_u"].dtype == torch.float32
     p64 = {k: v.astype(np.float64) for k, v in p.items()}
     x64, G64, h64 = x_bf.double().numpy(), G_bf.double().numpy(), h0.astype(np.float64)
@@ -362,19 +306,12 @@ def test_full_size_training_step_vs_the_oracle():
     G = rng.standard_normal((T, B, H)).astype(np.float32)
     h0 = np.zeros((B, H), np.float32)
     assert fastgrnn_cuda.kernel_path(T, B, F, H, direction=1, flags=SP | ZE) == 2
-    hs, _, g = fwd_bwd(_t(x), _t(h0), _t(G), _P(p), "sigmoid", SP | ZE)
-    hs_o, g_o = _oracle(x, h0, G, p)
+    hs, _, g = fwd_bwd(S.to_dev(x), S.to_dev(h0), S.to_dev(G), S.cell_tensors(p), "sigmoid", SP | ZE)
+    hs_o, _, _, g_o = S.oracle64(x, G, p, h0)
     _check(hs, g, hs_o, g_o, 2e-5, "fullsize")
 
 
 # ---- modules --------------------------------------------------------------------------------------------------------
-
-def _copy(m, p):
-    with torch.no_grad():
-        for k, attr in (("w", "W"), ("u", "U"), ("bias_gate", "bias_gate"), ("bias_update", "bias_update"),
-                        ("zeta", "zeta"), ("nu", "nu")):
-            getattr(m, attr).copy_(torch.from_numpy(p[k]))
-
 
 @pytest.mark.parametrize("batch_first", [False, True])
 def test_module_h100_autograd_and_inference_vs_the_oracle(batch_first):
@@ -384,25 +321,25 @@ def test_module_h100_autograd_and_inference_vs_the_oracle(batch_first):
     x = rng.standard_normal((T, B, F)).astype(np.float32)
     G = rng.standard_normal((T, B, H)).astype(np.float32)
     m = FastGRNNCUDA(F, H, batch_first=batch_first, device=DEV)
-    _copy(m, p)
+    S.copy_cell_params(m, p)
     lay = (lambda a: np.ascontiguousarray(a.transpose(1, 0, 2))) if batch_first else (lambda a: a)
-    xt = _t(lay(x)).requires_grad_(True)
+    xt = S.to_dev(lay(x)).requires_grad_(True)
     out = m(xt)
-    (out * _t(lay(G))).sum().backward()
+    (out * S.to_dev(lay(G))).sum().backward()
     hs = out.detach().transpose(0, 1) if batch_first else out.detach()
     g = {"d_x": xt.grad.transpose(0, 1) if batch_first else xt.grad, "d_w": m.W.grad, "d_u": m.U.grad,
          "d_bias_gate": m.bias_gate.grad, "d_bias_update": m.bias_update.grad, "d_zeta": m.zeta.grad, "d_nu": m.nu.grad}
-    hs_o, g_o = _oracle(x, np.zeros((B, H), np.float32), G, p)
+    hs_o, _, _, g_o = S.oracle64(x, G, p, np.zeros((B, H), np.float32))
     _check(hs, g, hs_o, g_o, 2e-5, "module")
     with torch.no_grad():
-        hs_ng = m(_t(lay(x)))
-        last = m(_t(lay(x)), last_state=True)
+        hs_ng = m(S.to_dev(lay(x)))
+        last = m(S.to_dev(lay(x)), last_state=True)
     assert (hs_ng - out.detach()).abs().max() <= 1e-6         # (the hs-only scan variant)
     assert np.abs(last.cpu().numpy() - hs_o[-1]).max() <= 1e-5
     # bf16 frames through the module
     mb = FastGRNNCUDA(F, H, batch_first=batch_first, device=DEV)
-    _copy(mb, p)
-    xb = _t(lay(x)).to(torch.bfloat16).requires_grad_(True)
+    S.copy_cell_params(mb, p)
+    xb = S.to_dev(lay(x)).to(torch.bfloat16).requires_grad_(True)
     ob = mb(xb)
     assert ob.dtype == torch.bfloat16
     ob.float().square().mean().backward()
@@ -427,12 +364,12 @@ def test_classifier_100_100_all_gradients_vs_the_oracle_chain():
     model = RNNClassifierModel("FastGRNNCUDA", F, 2, [100, 100], [None, None], [None, None], [1.0, 1.0], [1.0, 1.0],
                                "sigmoid", "tanh", num_classes=C, device=DEV)
     for rnn, q in zip(model.rnn_list, layers):
-        _copy(rnn, q)
+        S.copy_cell_params(rnn, q)
     with torch.no_grad():
         model.hidden2keyword.weight.copy_(torch.from_numpy(fc_w)); model.hidden2keyword.bias.copy_(torch.from_numpy(fc_b))
     assert [fastgrnn_cuda.kernel_path(T, B, f, 100, direction=1, flags=SP | ZE) for f in (32, 100)] == [2, 2]
     assert [fastgrnn_cuda.zero_extend_plan(T, B, f, 100, flags=SP)["Fp"] for f in (32, 100)] == [32, 128]
-    loss = model.loss(_t(x), torch.from_numpy(y).to(DEV))
+    loss = model.loss(S.to_dev(x), torch.from_numpy(y).to(DEV))
     loss.backward()
     l64 = [{k: v.astype(np.float64) for k, v in q.items()} for q in layers]
     loss_o, _, _, _, grads_o, dw_o, _ = O.stack_forward_backward(x.astype(np.float64), l64, fc_w.astype(np.float64),
@@ -489,12 +426,12 @@ def test_graph_replay_and_repeatability_bitwise():
         return hs.detach().clone(), [q.grad.clone() for q in params]
 
     a, b = eager(), eager()
-    _same_bits(a[0], b[0], "hs twice")
+    S.assert_same_bits(a[0], b[0], "hs twice")
     for u, v in zip(a[1], b[1]):
-        _same_bits(u, v, "grad twice")
+        S.assert_same_bits(u, v, "grad twice")
     gs = GraphedStep(step)
     hs_g = gs()
     torch.cuda.synchronize()
-    _same_bits(hs_g, a[0], "graph hs")
+    S.assert_same_bits(hs_g, a[0], "graph hs")
     for q, v in zip(params, a[1]):
-        _same_bits(q.grad, v, "graph grad")
+        S.assert_same_bits(q.grad, v, "graph grad")

@@ -3,7 +3,6 @@ with and without the flag, that every path choice, workspace query and support p
 that the other entry points ignore it, and that the NODX scan variants pass both static assembly scanners.  No kernel
 is launched here: a call that passes the argument checks stops at the workspace check (status 5)."""
 import ctypes as C
-import itertools
 import os
 import re
 import subprocess
@@ -12,6 +11,8 @@ import sys
 import pytest
 
 from kws_amd import _lib
+from tests import plan_table_cases as PT
+from tests import support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
@@ -22,16 +23,7 @@ NULL = C.c_void_p(None)
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def _desc(**kw):
-    base = dict(T=99, B=4096, F=32, H=128, w_rank=0, u_rank=0, gate_nl=0, update_nl=2, dtype=0, flags=0)
-    base.update(kw)
-    return _lib.Desc(**base)
+    return S.built_library()
 
 
 def _backward_without_dx(lib, d):
@@ -53,10 +45,10 @@ PATH2 = [(gate, 2, 0, fl) for gate in range(3) for fl in (0, SP, _lib.FLAG_BATCH
 @pytest.mark.parametrize("gate,update,dtype,flags", PATH2)
 @pytest.mark.parametrize("B", [37, 4096])
 def test_null_dx_needs_the_flag_on_h128_f32(lib, gate, update, dtype, flags, B):
-    d = _desc(B=B, gate_nl=gate, update_nl=update, dtype=dtype, flags=flags)
+    d = PT.desc(B=B, gate_nl=gate, update_nl=update, dtype=dtype, flags=flags)
     assert lib.fastgrnn_hip_kernel_path(C.byref(d), 1) == 2
     assert _backward_without_dx(lib, d) == 1                    # as before: d_x is required without the flag
-    dn = _desc(B=B, gate_nl=gate, update_nl=update, dtype=dtype, flags=flags | NIG)
+    dn = PT.desc(B=B, gate_nl=gate, update_nl=update, dtype=dtype, flags=flags | NIG)
     assert _backward_without_dx(lib, dn) == 5                   # accepted: the next check is the workspace
 
 
@@ -64,14 +56,14 @@ def test_the_flag_changes_nothing_where_null_dx_was_accepted_or_refused(lib):
     # already optional: dense H = 256 and dense H = 128 with F > 32 (kernel path 2)
     for kw in (dict(H=256), dict(F=64), dict(F=256)):
         for fl in (SP, SP | NIG):
-            assert _backward_without_dx(lib, _desc(B=4, T=3, flags=fl, **kw)) == 5
+            assert _backward_without_dx(lib, PT.desc(B=4, T=3, flags=fl, **kw)) == 5
     # still required: other paths and factorised cells, whatever the flag says
     for kw in (dict(flags=_lib.FLAG_FORCE_GENERIC), dict(flags=_lib.FLAG_FORCE_F32_MFMA), dict(H=64),
                dict(H=100), dict(F=20), dict(w_rank=8, u_rank=8, flags=SP), dict(dtype=_lib.F64)):
         for extra in (0, NIG):
             k = dict(kw)
             k["flags"] = k.get("flags", 0) | extra
-            d = _desc(B=4, T=3, **k)
+            d = PT.desc(B=4, T=3, **k)
             if d.w_rank:
                 p = _lib.Params(NULL, NULL, *([ONE] * 8))
                 g = _lib.Grads(*([NULL] + [ONE] * 11))
@@ -86,14 +78,14 @@ def test_single_step_backward_ignores_the_flag(lib):
     p = _lib.Params(*([ONE] * 10))
     g = _lib.Grads(*([NULL] + [ONE] * 11))
     for fl in (0, NIG, SP | NIG):
-        d = _desc(T=1, B=4, flags=fl)
+        d = PT.desc(T=1, B=4, flags=fl)
         assert lib.fastgrnn_hip_backward(C.byref(d), C.byref(p), ONE, ONE, ONE, ONE, ONE, C.byref(g), NULL, 0,
                                          NULL) == 1
 
 
 def test_zero_extended_route_passes_null_dx_through_with_the_flag(lib):
     for fl, want in ((SP | ZE, 0), (SP | ZE | NIG, 1)):
-        d = _desc(H=100, flags=fl)
+        d = PT.desc(H=100, flags=fl)
         plan = _lib.ZextPlan()
         assert lib.fastgrnn_hip_zero_extend_plan(C.byref(d), C.byref(plan)) == 0
         assert (plan.backward, plan.Hp, plan.Fp, plan.dx_optional) == (1, 128, 32, want)
@@ -102,24 +94,8 @@ def test_zero_extended_route_passes_null_dx_through_with_the_flag(lib):
     for kw in (dict(H=200), dict(F=100, H=100)):
         for fl in (SP | ZE, SP | ZE | NIG):
             plan = _lib.ZextPlan()
-            assert lib.fastgrnn_hip_zero_extend_plan(C.byref(_desc(flags=fl, **kw)), C.byref(plan)) == 0
+            assert lib.fastgrnn_hip_zero_extend_plan(C.byref(PT.desc(flags=fl, **kw)), C.byref(plan)) == 0
             assert plan.dx_optional == 1, kw
-
-
-ALL_FLAGS = [_lib.FLAG_FORCE_GENERIC, _lib.FLAG_FORCE_F32_MFMA, SP, _lib.FLAG_FWD_4WAVE, _lib.FLAG_BATCH_MAJOR,
-             _lib.FLAG_FWD_BF16X3, _lib.FLAG_X_BFT, _lib.FLAG_GRAD_LAST, _lib.FLAG_HS_LAST, _lib.FLAG_PREACT_AFFINE,
-             _lib.FLAG_BN_TRAIN, ZE]
-
-
-def _grid():
-    shapes = [(32, 128, 0, 0), (64, 128, 0, 0), (256, 128, 0, 0), (32, 256, 0, 0), (128, 256, 0, 0), (32, 64, 0, 0),
-              (32, 100, 0, 0), (100, 100, 0, 0), (32, 256, 16, 16), (32, 128, 8, 8), (7, 20, 0, 0)]
-    flag_sets = [0] + ALL_FLAGS + [SP | f for f in ALL_FLAGS] + [SP | ZE | _lib.FLAG_BATCH_MAJOR,
-                                                                  _lib.FLAG_BN_TRAIN | _lib.FLAG_BATCH_MAJOR,
-                                                                  _lib.FLAG_PREACT_AFFINE | _lib.FLAG_HS_LAST]
-    for (F, H, rw, ru), fl, gate, update, dtype, B in itertools.product(shapes, flag_sets, (0, 2, 4), (2, 3),
-                                                                       (0, 1, 2), (37, 4096)):
-        yield _desc(B=B, F=F, H=H, w_rank=rw, u_rank=ru, gate_nl=gate, update_nl=update, dtype=dtype, flags=fl)
 
 
 def _answers(lib, d):
@@ -139,7 +115,7 @@ def _answers(lib, d):
 
 def test_every_query_and_predicate_answers_the_same_with_the_flag(lib):
     n = 0
-    for d in _grid():
+    for d in PT.grid():
         dn = _lib.Desc(d.T, d.B, d.F, d.H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, d.flags | NIG)
         assert _answers(lib, dn) == _answers(lib, d), (d.F, d.H, d.w_rank, d.gate_nl, d.update_nl, d.dtype, d.flags)
         n += 1
@@ -156,12 +132,12 @@ def test_forward_entry_points_ignore_the_flag(lib):
             for extra in (0, NIG):
                 k = dict(kw)
                 k["flags"] = k.get("flags", 0) | extra
-                d = _desc(B=4096, **k)
+                d = PT.desc(B=4096, **k)
                 res.append((lib.fastgrnn_hip_forward_unroll(C.byref(d), C.byref(p), ONE, ONE, ONE, ONE, NULL, ONE, ws,
                                                             NULL),
                             lib.fastgrnn_hip_forward_unroll_affine(C.byref(d), C.byref(p), ONE, ONE, ONE, ONE, ONE, ONE,
                                                                    ws, NULL)))
-                d1 = _desc(T=1, B=4096, **k)
+                d1 = PT.desc(T=1, B=4096, **k)
                 res[-1] += (lib.fastgrnn_hip_forward(C.byref(d1), C.byref(p), ONE, ONE, ONE, ONE, ONE, ONE, ws, NULL),)
             assert res[0] == res[1], (kw, ws, res)
             assert all(s != 0 for s in res[0])          # nothing was launched
@@ -175,7 +151,7 @@ def test_bn_train_entry_points_ignore_the_flag(lib):
         for extra in (0, NIG):
             k = dict(kw)
             k["flags"] = k.get("flags", 0) | extra
-            d = _desc(B=4096, **k)
+            d = PT.desc(B=4096, **k)
             res.append((lib.fastgrnn_hip_bn_train_supported(C.byref(d)),
                         lib.fastgrnn_hip_bn_train_forward(C.byref(d), C.byref(p), C.byref(bn), ONE, ONE, ONE, ONE, ONE,
                                                           NULL, 0, NULL)))

@@ -2,22 +2,19 @@
 TN GEMM's chunk rule agrees with the library: the backward workspace of the dense H=256 / F=32 layer holds the GEMM's
 partials, so its size follows the chunk count.  No kernel is launched here."""
 import ctypes as C
-import os
 
 import pytest
 
 from kws_amd import _lib
 from tests import partition_cases as PC
+from tests import support as S
 
 SLOT = 2 * 128 * 256 * 4          # one partial of dU = d_pre^T . H_prev at M = N = 256 (nblk = 2): 262 144 bytes
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
+    return S.built_library()
 
 
 def test_table_covers_every_class():

@@ -1,15 +1,15 @@
 """CPU-side checks of fastgrnn_hip_plan (include/fastgrnn_hip.h): over the descriptor grid of
-test_no_input_grad_cpu, with and without FASTGRNN_FLAG_NO_INPUT_GRAD, the plan agrees field by field with the older
+tests/plan_table_cases.py, with and without FASTGRNN_FLAG_NO_INPUT_GRAD, the plan agrees field by field with the older
 single-answer queries; dx_optional agrees with what backward_unroll itself accepts; forward_ws_optional and
 rank_space_cols hold exactly on the descriptors listed here.  No kernel is launched: a call that passes the argument
 checks stops at the workspace check (status 5)."""
 import ctypes as C
-import os
 
 import pytest
 
 from kws_amd import _lib
-from tests.test_no_input_grad_cpu import _desc, _grid
+from tests import plan_table_cases as PT
+from tests import support as S
 
 NIG, SP, ZE = _lib.FLAG_NO_INPUT_GRAD, _lib.FLAG_SAVE_PREACT, _lib.FLAG_ZERO_EXTEND
 BM, BFT = _lib.FLAG_BATCH_MAJOR, _lib.FLAG_X_BFT
@@ -20,22 +20,13 @@ ZEXT_FIELDS = ("forward", "backward", "Hp", "Fp", "dx_optional", "reserved", "sa
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
+    return S.built_library()
 
 
 def _plan(lib, d, status=0):
     p = _lib.Plan()
     assert lib.fastgrnn_hip_plan(C.byref(d), C.byref(p)) == status
     return p
-
-
-def _both_grids():
-    for d in _grid():
-        yield d
-        yield _lib.Desc(d.T, d.B, d.F, d.H, d.w_rank, d.u_rank, d.gate_nl, d.update_nl, d.dtype, d.flags | NIG)
 
 
 def _backward(lib, d, d_x):
@@ -48,7 +39,7 @@ def _backward(lib, d, d_x):
 
 def test_plan_agrees_with_every_older_query(lib):
     n = 0
-    for d in _both_grids():
+    for d in PT.both_grids():
         what = (d.F, d.H, d.w_rank, d.gate_nl, d.update_nl, d.dtype, d.flags)
         plan = _lib.Plan()
         zx = _lib.ZextPlan()
@@ -73,7 +64,7 @@ def test_dx_optional_is_what_backward_unroll_accepts(lib):
     workspace are asked, so nothing is ever launched.  A descriptor whose backward is refused as unsupported (7) with
     d_x given is refused the same way without it, and its plan must not call d_x optional."""
     asked = {0: 0, 1: 0}
-    for d in _both_grids():
+    for d in PT.both_grids():
         plan = _plan(lib, d)
         if plan.workspace_bytes[1] == 0:
             continue
@@ -104,14 +95,14 @@ WS_REQUIRED = [dict(), dict(flags=SP), dict(H=256), dict(H=256, F=64, flags=SP),
 def test_forward_ws_optional_on_the_listed_descriptors(lib):
     p = _lib.Params(*([ONE] * 10))
     for kw in WS_OPTIONAL:
-        d = _desc(**kw)
+        d = PT.desc(**kw)
         plan = _plan(lib, d)
         assert plan.path[0] == 2 and plan.zext.forward == 0 and plan.workspace_bytes[0] > 0, kw
         assert plan.forward_ws_optional == 1, kw
         # without z_s the workspace is required: the call stops there
         assert lib.fastgrnn_hip_forward_unroll(C.byref(d), C.byref(p), ONE, ONE, ONE, NULL, NULL, NULL, 0, NULL) == 5, kw
     for kw in WS_REQUIRED:
-        d = _desc(**kw)
+        d = PT.desc(**kw)
         plan = _plan(lib, d)
         assert plan.forward_ws_optional == 0, kw
         if plan.workspace_bytes[0] and not d.flags & (_lib.FLAG_PREACT_AFFINE | _lib.FLAG_BN_TRAIN):
@@ -138,23 +129,23 @@ NO_RANK_SPACE = [dict(H=256, w_rank=8, u_rank=8),                          # no 
 
 def test_rank_space_cols_on_the_listed_descriptors(lib):
     for kw in RANK_SPACE:
-        plan = _plan(lib, _desc(**kw))
+        plan = _plan(lib, PT.desc(**kw))
         assert plan.path[0] == 2 and plan.path[1] == 2 and plan.zext.forward == 0, kw
         assert plan.rank_space_cols == 32, kw
     for kw in NO_RANK_SPACE:
-        assert _plan(lib, _desc(**kw)).rank_space_cols == 0, kw
-    zx = _plan(lib, _desc(H=200, w_rank=8, u_rank=8, flags=SP | ZE)).zext
+        assert _plan(lib, PT.desc(**kw)).rank_space_cols == 0, kw
+    zx = _plan(lib, PT.desc(H=200, w_rank=8, u_rank=8, flags=SP | ZE)).zext
     assert (zx.forward, zx.backward, zx.Hp, zx.Fp) == (1, 1, 256, 32)
 
 
 def test_error_convention(lib):
     p = _lib.Plan()
     assert lib.fastgrnn_hip_plan(None, C.byref(p)) == 1
-    assert lib.fastgrnn_hip_plan(C.byref(_desc()), None) == 1
+    assert lib.fastgrnn_hip_plan(C.byref(PT.desc()), None) == 1
     for kw, st in ((dict(T=0, flags=ZE), 2), (dict(gate_nl=9), 3), (dict(dtype=5), 4)):
-        p = _plan(lib, _desc(F=64, flags=SP))
+        p = _plan(lib, PT.desc(F=64, flags=SP))
         assert p.path[0] == 2 and p.forward_ws_optional == 1
-        assert lib.fastgrnn_hip_plan(C.byref(_desc(**kw)), C.byref(p)) == st
+        assert lib.fastgrnn_hip_plan(C.byref(PT.desc(**kw)), C.byref(p)) == st
         assert bytes(p) == bytes(C.sizeof(_lib.Plan)), kw           # out zeroed
 
 

@@ -7,18 +7,15 @@ import os
 import numpy as np
 import pytest
 
-from kws_amd import _lib
 from tests.plan_table_cases import answers
+from tests import support as S
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan", "plan_table.npz")
 
 
 @pytest.fixture(scope="module")
 def tables():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return dict(np.load(GOLDEN)), answers(_lib.load())
+    return dict(np.load(GOLDEN)), answers(S.built_library())
 
 
 def test_the_table_asks_what_was_recorded(tables):

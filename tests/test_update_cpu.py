@@ -15,6 +15,7 @@ import torch
 
 from kws_amd import _lib, optim
 from tests import update_cases as U
+from tests import support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "kws_amd", "csrc", "kernels_update.hip")
@@ -24,10 +25,7 @@ OK, NULLP, SHAPE, UNSUP = 0, 1, 2, 7
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
+    return S.built_library()
 
 
 # ---- the oracles -------------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from kws_amd import _lib, fastgrnn_cuda
+from tests import support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
@@ -18,10 +19,7 @@ ZE, SP = _lib.FLAG_ZERO_EXTEND, _lib.FLAG_SAVE_PREACT
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
+    return S.built_library()
 
 
 def _desc(**kw):
