@@ -670,6 +670,69 @@ int fastgrnn_hip_augment_draw(int32_t B, uint64_t seed, const int64_t *step, con
                               const fastgrnn_augment_ranges *r, int32_t n_noise, int32_t noise_len_max,
                               const int32_t *noise_lengths, fastgrnn_mfcc_aug *aug, void *stream);
 
+/* train_schedule -- what a trainer iteration takes from outside the model, computed on the device from the step count:
+ * the batch (a shuffled epoch order without replacement, the reference loader's shuffle=True), the learning rate (the
+ * five schedules of the reference's configure_lr, trainClassifier.py:97-123, utils.py:116-143) and the IHT phase
+ * (trainClassifier.py:251-259).  With it a training run is so many replays of one captured graph with no host write in
+ * between.  One small launch on `stream`, no allocation, no workspace, no host decision on device data: capturable.
+ * step[1] (int64) is a DEVICE scalar that is only read; s = max(step[0], 0) is the 0-BASED number of the iteration about
+ * to run -- the fused optimizer's step_t as it stands BEFORE train_update's caller increments it, which is what
+ * augment_draw reads.  d is a HOST struct.  Outputs, all on the device:
+ *   index[B] int32     the batch's clip numbers, each in 0 .. N-1
+ *   lr[1] float        the learning rate (train_update's lr)
+ *   iht_mode[1] int32  0 / 1 / 2, train_update's codes; may be NULL while sparsify == 0 (otherwise 0 is written)
+ *   where[4] int64     epoch, i_batch, slot = min(s, log_len - 1), 0
+ * Position.  ticks = N / (B world) (integer division: drop_last), epoch = s / ticks, i_batch = s mod ticks,
+ *   index[b] = perm_epoch((i_batch world + rank) B + b):  within an epoch the ranks' batches are disjoint and no clip
+ * comes twice; N mod (B world) clips sit the epoch out, others in every epoch.
+ * Permutation, stateless: k = the smallest even integer >= 2 with 2^k >= N, half = k / 2, mask = 2^half - 1.  One pass
+ * maps x < 2^k to (L, R) = (x >> half, x & mask), runs four Feistel rounds r = 0 .. 3 of
+ *   (L, R) <- (R, L ^ (P(R, r) & mask)),   P(R, r) = word 0 of Philox4x32-10 (augment_draw's generator) with the key
+ *   (seed_lo, seed_hi) and the counter (R, epoch_lo, epoch_hi, 0x80000000 | r)
+ * and gives x = (L << half) | R; the pass is repeated while x >= N (cycle walking; it ends because the pass is a
+ * bijection of 0 .. 2^k-1, whose cycle through a start below N returns below N).  The top bit of the last counter word
+ * keeps these counters apart from augment_draw's under one seed.  index[b] depends on (seed, N, B, world, rank, s, b)
+ * alone, not on the launch geometry.
+ * IHT phase, with sparsify != 0 (integer comparisons that agree with the reference's float ones for every pair):
+ *   3 epoch < num_epochs: 0;   else 3 epoch < 2 num_epochs: 1 if i_batch mod trim_level == 0 else 2;   else 2.
+ * Learning rate at it = s + lr_lead, in double, rounded once to float.  The reference calls scheduler.step() BEFORE
+ * optimizer.step() (trainClassifier.py:244-249), so its iteration s runs at it = s + 1: lr_lead = 1; torch's documented
+ * order is lr_lead = 0.  By lr_kind:
+ *   FASTGRNN_LR_CONSTANT               lr_base
+ *   FASTGRNN_LR_TRIANGLE               c = floor(1 + it / (2 stepsize)),  x = |it / stepsize - 2 c + 1|,
+ *                                      lr_min + (lr_base - lr_min) gamma^(it / 3) x
+ *   FASTGRNN_LR_COSINE                 lr_min + (lr_base - lr_min) (1 + cos(pi it / t_max)) / 2   (the closed form;
+ *                                      torch's recursive form differs by rounding and divides by zero at some t_max)
+ *   FASTGRNN_LR_EXPONENTIAL            lr_base gamma^it
+ *   FASTGRNN_LR_STEP                   lr_base gamma^floor(it / step_size)
+ *   FASTGRNN_LR_EXPONENTIAL_RESETTING  e = it - reset if it > reset else it,  lr_base gamma^e
+ * Fields that a kind does not name are not read.
+ * Errors, all before any launch: FASTGRNN_ERR_NULL_POINTER (d, step, index, lr, where; iht_mode while sparsify != 0),
+ * FASTGRNN_ERR_BAD_SHAPE (B < 1; world < 1; rank outside 0 .. world-1; B world > 2^31 - 1 or N < B world; num_epochs,
+ * trim_level or log_len < 1; lr_lead other than 0, 1; lr_base or lr_min negative or not finite; gamma <= 0 or not
+ * finite on the kinds that read it; stepsize likewise on TRIANGLE, t_max on COSINE; step_size < 1 on STEP; reset < 0
+ * on EXPONENTIAL_RESETTING), FASTGRNN_ERR_UNSUPPORTED (an unknown lr_kind).  No value of step[0] moves a write outside
+ * index[0 .. B). */
+#define FASTGRNN_LR_CONSTANT 0
+#define FASTGRNN_LR_TRIANGLE 1
+#define FASTGRNN_LR_COSINE 2
+#define FASTGRNN_LR_EXPONENTIAL 3
+#define FASTGRNN_LR_STEP 4
+#define FASTGRNN_LR_EXPONENTIAL_RESETTING 5
+typedef struct fastgrnn_schedule_desc {
+  int32_t N, B, world, rank;          /* clips in the bank, clips per batch and rank, ranks, this rank */
+  uint64_t seed;
+  int32_t num_epochs, trim_level;     /* the IHT phases' thirds; a threshold every trim_level batches */
+  int32_t sparsify;                   /* 0: the phase is always 0 */
+  int32_t lr_kind, lr_lead, reserved;
+  int64_t log_len;                    /* >= 1: where[2] stays below it */
+  double lr_base, lr_min, gamma, stepsize, t_max;
+  int64_t step_size, reset;
+} fastgrnn_schedule_desc;
+
+int fastgrnn_hip_train_schedule(const fastgrnn_schedule_desc *d, const int64_t *step, int32_t *index, float *lr,
+                                int32_t *iht_mode, int64_t *where, void *stream);
+
 /* frame_gemm -- the one genuinely dense, non-recurrent contraction of a layer, as a call of its own:
  *   P[rows, H] = X[rows, F] . W^T,   W:[H,F]  (rows = T*B; the reference computes it per step, `mm` at .cu:356).
  * forward_unroll runs exactly this launch in front of the scan for layers whose input is wider than 32 (the scan of a

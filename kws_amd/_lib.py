@@ -51,7 +51,7 @@ EXPORTS = (
     "fastgrnn_hip_head_predict_workspace_bytes", "fastgrnn_hip_head_predict", "fastgrnn_hip_vote_windows",
     "fastgrnn_hip_train_update",
     "fastgrnn_hip_mfcc_tables_bytes", "fastgrnn_hip_mfcc_init_tables", "fastgrnn_hip_mfcc_workspace_bytes",
-    "fastgrnn_hip_mfcc", "fastgrnn_hip_mfcc_augment", "fastgrnn_hip_augment_draw",
+    "fastgrnn_hip_mfcc", "fastgrnn_hip_mfcc_augment", "fastgrnn_hip_augment_draw", "fastgrnn_hip_train_schedule",
 )
 
 
@@ -156,6 +156,20 @@ class AugmentRanges(C.Structure):
                 ("noise_gain_hi", C.c_float)]
 
 
+# fastgrnn_schedule_desc.lr_kind, by the reference's scheduler names (trainClassifier.py:107-122)
+LR_KINDS = {None: 0, "TriangleLR": 1, "CosineAnnealingLR": 2, "ExponentialLR": 3, "StepLR": 4,
+            "ExponentialResettingLR": 5}
+
+
+class ScheduleDesc(C.Structure):
+    """fastgrnn_schedule_desc."""
+    _fields_ = [("N", C.c_int32), ("B", C.c_int32), ("world", C.c_int32), ("rank", C.c_int32), ("seed", C.c_uint64),
+                ("num_epochs", C.c_int32), ("trim_level", C.c_int32), ("sparsify", C.c_int32), ("lr_kind", C.c_int32),
+                ("lr_lead", C.c_int32), ("reserved", C.c_int32), ("log_len", C.c_int64),
+                ("lr_base", C.c_double), ("lr_min", C.c_double), ("gamma", C.c_double), ("stepsize", C.c_double),
+                ("t_max", C.c_double), ("step_size", C.c_int64), ("reset", C.c_int64)]
+
+
 class FastGRNNLibraryError(RuntimeError):
     pass
 
@@ -225,6 +239,8 @@ def load():
     lib.fastgrnn_hip_augment_draw.restype = i32
     lib.fastgrnn_hip_augment_draw.argtypes = [C.c_int32, C.c_uint64, vp, vp, C.POINTER(AugmentRanges), C.c_int32,
                                               C.c_int32, vp, vp, vp]
+    lib.fastgrnn_hip_train_schedule.restype = i32
+    lib.fastgrnn_hip_train_schedule.argtypes = [C.POINTER(ScheduleDesc), vp, vp, vp, vp, vp, vp]
     lib.fastgrnn_hip_frame_gemm.restype = i32
     lib.fastgrnn_hip_frame_gemm.argtypes = [sz, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp]
     BP, BG = C.POINTER(BnParams), C.POINTER(BnGrads)

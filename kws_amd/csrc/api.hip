@@ -570,6 +570,29 @@ int fastgrnn_hip_augment_draw(int32_t B, uint64_t seed, const int64_t* step, con
                           reinterpret_cast<hipStream_t>(stream));
 }
 
+int fastgrnn_hip_train_schedule(const fastgrnn_schedule_desc* d, const int64_t* step, int32_t* index, float* lr,
+                                int32_t* iht_mode, int64_t* where, void* stream) {
+  if (!d) return FASTGRNN_ERR_NULL_POINTER;
+  if (d->B < 1 || d->world < 1 || d->rank < 0 || d->rank >= d->world) return FASTGRNN_ERR_BAD_SHAPE;
+  const int64_t per_tick = (int64_t)d->B * d->world;
+  if (per_tick > INT32_MAX || d->N < per_tick) return FASTGRNN_ERR_BAD_SHAPE;
+  if (d->num_epochs < 1 || d->trim_level < 1 || d->log_len < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  if (d->lr_lead != 0 && d->lr_lead != 1) return FASTGRNN_ERR_BAD_SHAPE;
+  if (d->lr_kind < FASTGRNN_LR_CONSTANT || d->lr_kind > FASTGRNN_LR_EXPONENTIAL_RESETTING) return FASTGRNN_ERR_UNSUPPORTED;
+  // (written so that a NaN fails every range check)
+  const double inf = __builtin_huge_val();
+  if (!(d->lr_base >= 0.0 && d->lr_base < inf) || !(d->lr_min >= 0.0 && d->lr_min < inf)) return FASTGRNN_ERR_BAD_SHAPE;
+  const int kind = d->lr_kind;
+  if (kind != FASTGRNN_LR_CONSTANT && kind != FASTGRNN_LR_COSINE && !(d->gamma > 0.0 && d->gamma < inf))
+    return FASTGRNN_ERR_BAD_SHAPE;
+  if (kind == FASTGRNN_LR_TRIANGLE && !(d->stepsize > 0.0 && d->stepsize < inf)) return FASTGRNN_ERR_BAD_SHAPE;
+  if (kind == FASTGRNN_LR_COSINE && !(d->t_max > 0.0 && d->t_max < inf)) return FASTGRNN_ERR_BAD_SHAPE;
+  if (kind == FASTGRNN_LR_STEP && d->step_size < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  if (kind == FASTGRNN_LR_EXPONENTIAL_RESETTING && d->reset < 0) return FASTGRNN_ERR_BAD_SHAPE;
+  if (!step || !index || !lr || !where || (d->sparsify && !iht_mode)) return FASTGRNN_ERR_NULL_POINTER;
+  return train_schedule_run(*d, step, index, lr, iht_mode, where, reinterpret_cast<hipStream_t>(stream));
+}
+
 int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void* x, const void* w, void* p, int32_t dtype,
                             void* stream) {
   if (!x || !w || !p) return FASTGRNN_ERR_NULL_POINTER;

@@ -212,6 +212,11 @@ int mfcc_augment_run(const fastgrnn_mfcc_desc& d, const fastgrnn_mfcc_bank& bank
 int augment_draw_run(int B, uint64_t seed, const int64_t* step, const int32_t* index, const fastgrnn_augment_ranges& r,
                      int n_noise, int noise_len_max, const int32_t* noise_lengths, fastgrnn_mfcc_aug* aug, hipStream_t s);
 
+// the batch, the learning rate and the IHT phase of an iteration from the step count (kernels_schedule.hip);
+// arguments already checked
+int train_schedule_run(const fastgrnn_schedule_desc& d, const int64_t* step, int32_t* index, float* lr,
+                       int32_t* iht_mode, int64_t* where, hipStream_t s);
+
 // training-mode BatchNorm cell (kernels_bn_train.hip): FASTGRNN_FLAG_BN_TRAIN
 bool bn_train_supported(const fastgrnn_desc& d);
 size_t bn_train_forward_ws(const fastgrnn_desc& d);

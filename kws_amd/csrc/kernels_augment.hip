@@ -6,6 +6,7 @@
 //                and is never written to memory.  Stages b-e, LDS and the rules of DESIGN.md 4.0 are mfcc_k's.
 //   aug_draw_k   the records of a batch from Philox4x32-10 on (seed, step, clip): one thread per clip, two blocks each.
 #include "mfcc_body.h"
+#include "philox.h"
 
 namespace fastgrnn {
 namespace {
@@ -16,20 +17,7 @@ __global__ __launch_bounds__(MF_THREADS) void mfcc_aug_k(mfcc_aug_args a) {
 }
 
 // ---- the draw ----------------------------------------------------------------------------------------------------------
-struct u32x4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c.x), l0 = 0xD2511F53u * c.x;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c.z), l1 = 0xCD9E8D57u * c.z;
-    c = u32x4{h1 ^ c.y ^ k0, l1, h0 ^ c.w ^ k1, l0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
+// (Philox4x32-10 itself: philox.h, shared with kernels_schedule.hip)
 __device__ __forceinline__ float unit_of(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }     // exact
 __device__ __forceinline__ int below(uint32_t x, uint32_t n) { return (int)__umulhi(x, n); }
 __device__ __forceinline__ float between(float lo, float hi, float u) {

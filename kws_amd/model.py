@@ -26,6 +26,9 @@ Same constructor arguments, attribute and parameter names as the reference (``rn
 * ``predict`` / ``batch_accuracy`` / ``evaluate`` (trainClassifier.py:54-65, 286-316) and ``detect_stream``
   (inferencetry.py:213-227) end in the fused inference head and the majority vote: scores, argmax, the count of
   correct rows and the detector's vote stay on the device;
+* ``fit_audio`` is the non-rolling loop of ``fit`` (trainClassifier.py:196-272) from an audio bank on the device, its
+  batches, learning rates and IHT phases computed there by a ``kws_amd.TrainSchedule``: one captured graph replayed for
+  the whole run, ``evaluate()`` after every epoch;
 * the shadow ``rnn_list_`` / ``tracking`` ONNX-export path (model.py:72-84,187-195) is not built (export is
   disabled in the reference, trainClassifier.py:42-52), nor are the rolling hidden-state bags
   (model.py:135-148: data-loader bookkeeping, no arithmetic).
@@ -40,6 +43,7 @@ from .batchnorm import FastGRNNBatchNorm
 from .batchnorm_train import FastGRNNBatchNormCUDA
 from .head import head_predict, keyword_loss, vote_windows
 from .fastgrnn_cuda import check_starts_range
+from .graph import GraphedStep
 from .optim import _FusedOptimizer
 from .rnn import FastGRNNCUDA, gather_windows
 
@@ -354,6 +358,77 @@ class RNNClassifierModel(nn.Module):
             bucket.all_reduce_()
         optimizer.step(iht)
         return loss.detach()
+
+    def fit_audio(self, audio, lengths, labels, frontend, augment, optimizer, schedule, *, graph=True, bucket=None,
+                  validation=None):
+        """A whole training run (trainClassifier.py:196-272, the non-rolling loop) from the audio bank, driven by a
+        ``kws_amd.TrainSchedule``: ``schedule.num_epochs * schedule.ticks`` iterations of
+
+            init_hidden()                    (trainClassifier.py:221: every batch starts from the zero state)
+            schedule.advance()               index, lr_t, iht_t and the position from optimizer.step_t
+            loss = train_step_audio(audio, lengths, labels, schedule.index, frontend, augment, optimizer, iht=None)
+            schedule.record(loss)
+
+        With ``graph=True`` that body is captured once in a ``GraphedStep`` and replayed; nothing is written from the
+        host between replays, and the run starts from the state the model and the optimizer were in (the capture's
+        warm-up iterations are undone: parameters, buffers, optimizer state, support masks, ``step_t`` and the logs).
+        ``graph=False`` runs the same body eagerly and gives the same bits.  The run begins at ``optimizer.step_t`` as it
+        stands (0 for a fresh optimizer; one sync, before the first iteration) and ends at iteration
+        ``num_epochs * ticks`` counted from 0.
+        ``validation``: an iterable of ``(input, labels)`` batches, or a callable returning one, handed to ``evaluate()``
+        after every epoch -- the only sync inside the run; the model is put back in training mode afterwards.  Returns
+        the reference's log: one ``{"epoch", "loss", "accuracy", "learning_rate"}`` per epoch, the epoch's last loss and
+        learning rate read from ``schedule.loss_log`` / ``lr_log`` at the end."""
+        if not isinstance(optimizer, _FusedOptimizer):
+            raise TypeError("fit_audio() needs a kws_amd.FusedAdam or kws_amd.FusedSGD (got %s)" % type(optimizer).__name__)
+        if getattr(schedule, "optimizer", None) is not optimizer:
+            raise ValueError("fit_audio(): the schedule was built for another optimizer (it writes that one's lr_t / iht_t)")
+        if labels.shape[0] != schedule.num_clips or audio.shape[0] != schedule.num_clips:
+            raise ValueError("fit_audio(): the schedule shuffles %d clips, the bank holds %d with %d labels"
+                             % (schedule.num_clips, audio.shape[0], labels.shape[0]))
+
+        def body():
+            self.init_hidden()
+            schedule.advance()
+            loss = self.train_step_audio(audio, lengths, labels, schedule.index, frontend, augment, optimizer, iht=None,
+                                         bucket=bucket)
+            schedule.record(loss)
+            return loss
+
+        self.train()
+        step = body
+        if graph:
+            keep = self._run_state(optimizer, schedule)
+            step = GraphedStep(body)
+            self._restore_run_state(optimizer, keep)
+        first = int(optimizer.step_t.item())
+        accuracies = [None] * schedule.num_epochs
+        for s in range(first, schedule.total_iterations):
+            step()
+            if (s + 1) % schedule.ticks == 0 and validation is not None:
+                accuracies[s // schedule.ticks] = self.evaluate(validation() if callable(validation) else validation)
+                self.train()
+        return schedule.epoch_log(accuracies)
+
+    def _run_state(self, optimizer, schedule):
+        """Copies of everything an iteration writes, keyed by the tensor that holds it: parameters, buffers, optimizer
+        state, support masks, the step count and the schedule's logs."""
+        held = list(self.parameters()) + list(self.buffers()) + [optimizer.step_t, schedule.loss_log, schedule.lr_log]
+        held += [mask for _, mask in optimizer._iht.values()]
+        for p in optimizer.param_groups[0]["params"]:
+            held += [t for t in optimizer.state.get(p, {}).values() if isinstance(t, torch.Tensor)]
+        return [(t, t.detach().clone()) for t in held]
+
+    def _restore_run_state(self, optimizer, keep):
+        with torch.no_grad():
+            known = {id(t) for t, _ in keep}
+            for t, value in keep:
+                t.copy_(value)
+            for p in optimizer.param_groups[0]["params"]:     # moments created by the warm-up: back to their zeros
+                for t in optimizer.state.get(p, {}).values():
+                    if isinstance(t, torch.Tensor) and id(t) not in known:
+                        t.zero_()
+        self.init_hidden()
 
     def loss_windows(self, pool, starts, labels, window=99):
         """``loss()`` on the batch whose utterance ``b`` is the ``window`` consecutive rows of ``pool:[R,F]`` from row

@@ -5,7 +5,8 @@ keys and ``state_dict`` layout whose ``step()`` hands EVERY parameter of the mod
 kernel launch per 32 parameter tensors applies the update and, on the W/U matrices registered with ``register_iht``,
 the hard threshold (``utils.hardThreshold``) or the support mask (``utils.supportBasedThreshold``).  The learning rate,
 the step count and the IHT phase are read from device scalars (``lr_t``, ``step_t``, ``iht_t``), so a step captured in a
-HIP graph serves a whole training run: the caller rewrites the scalars between replays.
+HIP graph serves a whole training run: the caller rewrites the scalars between replays, or a ``kws_amd.TrainSchedule``
+computes the learning rate (the reference's five schedules) and the phase on the device from ``step_t``, inside the graph.
 
 Limits, each refused with a message that names it: one param group; float32, dense, contiguous parameters on one
 device; ``amsgrad``, ``maximize``, ``differentiable`` and decoupled weight decay (AdamW) off; at most 2^22 elements per

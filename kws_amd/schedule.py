@@ -1,0 +1,154 @@
+"""The batch, the learning rate and the IHT phase of every trainer iteration, computed on the device from the step count.
+
+A trainer iteration already runs on the device and captures in one graph (``RNNClassifierModel.train_step_audio``); what
+the host still supplied between two replays were the batch's clip indices, the learning rate and the IHT phase.  All
+three are functions of the iteration number, which lives in the fused optimizer's ``step_t``:
+
+* ``TrainSchedule.advance()`` is one library call (``fastgrnn_hip_train_schedule``, include/fastgrnn_hip.h) that reads
+  ``step_t`` and writes ``index:[B]`` (the batch of a shuffled epoch order without replacement: a keyed permutation of the
+  clip numbers, new in every epoch, sharded over ``world`` ranks), ``optimizer.lr_t`` (one of the reference's five
+  schedules, trainClassifier.py:97-123 and utils.py:116-143, or the constant rate), ``optimizer.iht_t``
+  (trainClassifier.py:251-259, ``kws_amd.iht_phase``) and ``where = (epoch, i_batch, slot, 0)``;
+* ``TrainSchedule.record(loss)`` files the loss and the learning rate under ``slot`` in two device logs;
+* ``RNNClassifierModel.fit_audio`` captures ``advance`` + ``train_step_audio`` + ``record`` once and replays the graph
+  ``num_epochs * ticks`` times: no host-to-device write, no loader thread, reproducible from ``seed``.
+
+Two deliberate differences from the reference: an epoch has ``ticks = num_clips // (batch_size * world)`` whole batches
+(drop_last; the reference's loader ends an epoch on a short batch, which a captured graph's fixed shapes cannot take, and
+its ``ticks`` is the fraction ``num_clips / batch_size``), and ``"CosineAnnealingLR"`` is torch's CLOSED form (the
+recursive one the reference steps differs from it by rounding and divides by zero at some non-integer ``T_max``).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib
+from .fastgrnn_cuda import _call
+from .optim import _FusedOptimizer
+
+LR_SCHEDULERS = tuple(_lib.LR_KINDS)
+
+
+def _whole(v, name, lo):
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+        raise ValueError("%s must be an integer >= %d (got %r)" % (name, lo, v))
+    return v
+
+
+def _positive(v, name):
+    v = float(v)
+    if not (v > 0.0 and v != math.inf):
+        raise ValueError("%s must be a finite positive number (got %r)" % (name, v))
+    return v
+
+
+class TrainSchedule:
+    """``TrainSchedule(optimizer, num_clips, batch_size, num_epochs, seed=...)``: the run's position, batch, learning rate
+    and IHT phase as functions of ``optimizer.step_t``.
+
+    ``optimizer``: a ``FusedAdam`` / ``FusedSGD`` built with ``capturable=True`` (its ``lr_t`` then belongs to the caller,
+    here to ``advance``); its ``lr`` is the schedules' base (peak) rate.  ``lr_scheduler``: ``None`` or one of the
+    reference's names, with ``configure_lr``'s constants (``ticks`` as above): ``steps = 2 lr_peaks + 1``, ``stepsize =
+    num_epochs / steps * ticks`` (TriangleLR), ``t_max = ticks * num_epochs / steps`` (CosineAnnealingLR), ``reset =
+    int(num_epochs * ticks / 3)`` (ExponentialResettingLR), ``lr_min`` falling back to the base rate.  ``lr_lead = 1``
+    is the reference's order -- ``scheduler.step()`` before ``optimizer.step()``, so iteration ``s`` runs at the
+    schedule's ``s + 1`` --, ``lr_lead = 0`` torch's documented one.  ``sparsify`` turns the IHT phases on (``trim_level``:
+    a threshold every so many batches of the middle third; the reference's default is 15).  ``world`` / ``rank``: each
+    rank builds its own schedule and gets a disjoint share of every epoch.  ``log_len``: entries of ``loss_log`` /
+    ``lr_log`` (default: one per iteration); iterations past it share the last entry.
+
+    Construction needs no GPU (the tensors live on the optimizer's device); ``advance`` does."""
+
+    def __init__(self, optimizer, num_clips, batch_size, num_epochs, *, seed, lr_scheduler=None, lr_min=None, lr_peaks=1,
+                 gamma=1.0, lr_step_size=1, lr_lead=1, sparsify=False, trim_level=15, world=1, rank=0, log_len=None):
+        if not isinstance(optimizer, _FusedOptimizer):
+            raise TypeError("TrainSchedule needs a kws_amd.FusedAdam or kws_amd.FusedSGD (got %s): it writes the "
+                            "optimizer's device scalars lr_t and iht_t" % type(optimizer).__name__)
+        if not optimizer.param_groups[0].get("capturable"):
+            raise ValueError("TrainSchedule needs an optimizer built with capturable=True: otherwise %s.step() overwrites "
+                             "lr_t from param_groups" % type(optimizer).__name__)
+        self.optimizer = optimizer
+        self.num_clips = _whole(num_clips, "num_clips", 1)
+        self.batch_size = _whole(batch_size, "batch_size", 1)
+        self.num_epochs = _whole(num_epochs, "num_epochs", 1)
+        self.world = _whole(world, "world", 1)
+        self.rank = _whole(rank, "rank", 0)
+        if self.rank >= self.world:
+            raise ValueError("rank must be in 0..world-1 (got rank %d of %d)" % (self.rank, self.world))
+        if self.batch_size * self.world > 2 ** 31 - 1 or self.num_clips > 2 ** 31 - 1:
+            raise ValueError("num_clips and batch_size * world must fit int32")
+        if self.num_clips < self.batch_size * self.world:
+            raise ValueError("num_clips = %d holds no batch of %d clips on each of %d ranks (drop_last)"
+                             % (self.num_clips, self.batch_size, self.world))
+        self.seed = _whole(seed, "seed", 0)
+        if self.seed >= 1 << 64:
+            raise ValueError("seed must fit 64 bits (got %d)" % self.seed)
+        if lr_scheduler not in _lib.LR_KINDS:
+            raise ValueError("lr_scheduler must be one of %s (got %r)" % (", ".join(map(repr, LR_SCHEDULERS)), lr_scheduler))
+        if lr_lead not in (0, 1):
+            raise ValueError("lr_lead must be 0 or 1 (got %r)" % (lr_lead,))
+        self.lr_scheduler, self.lr_lead = lr_scheduler, int(lr_lead)
+        self.sparsify = bool(sparsify)
+        self.trim_level = _whole(trim_level, "trim_level", 1)
+        self.lr_base = float(optimizer.param_groups[0]["lr"])
+        self.lr_min = self.lr_base if not lr_min else float(lr_min)          # configure_lr: `if not lr_min`
+        if not (0.0 <= self.lr_min < math.inf and 0.0 <= self.lr_base < math.inf):
+            raise ValueError("the learning rates must be finite and >= 0 (got lr %r, lr_min %r)" % (self.lr_base, lr_min))
+        self.gamma = _positive(gamma, "gamma")
+        self.lr_step_size = _whole(lr_step_size, "lr_step_size", 1)
+        lr_peaks = lr_peaks if isinstance(lr_peaks, int) else float(lr_peaks)      # (the reference's --lr_peaks is a float)
+        _positive(lr_peaks, "lr_peaks")
+        # configure_lr's constants, in its order of operations
+        self.ticks = self.num_clips // (self.batch_size * self.world)
+        self.total_iterations = self.num_epochs * self.ticks
+        self.steps = lr_peaks * 2 + 1
+        self.stepsize = self.num_epochs / self.steps * self.ticks
+        self.t_max = self.ticks * self.num_epochs / self.steps
+        self.reset = int(self.num_epochs * self.ticks / 3)
+        self.log_len = self.total_iterations if log_len is None else _whole(log_len, "log_len", 1)
+        dev = optimizer._device
+        self.device = dev
+        self.index = torch.zeros(self.batch_size, dtype=torch.int32, device=dev)
+        self.where = torch.zeros(4, dtype=torch.int64, device=dev)
+        self.loss_log = torch.zeros(self.log_len, dtype=torch.float32, device=dev)
+        self.lr_log = torch.zeros(self.log_len, dtype=torch.float32, device=dev)
+        self.desc = _lib.ScheduleDesc(self.num_clips, self.batch_size, self.world, self.rank, self.seed, self.num_epochs,
+                                      self.trim_level, int(self.sparsify), _lib.LR_KINDS[lr_scheduler], self.lr_lead, 0,
+                                      self.log_len, self.lr_base, self.lr_min, self.gamma, self.stepsize, self.t_max,
+                                      self.lr_step_size, self.reset)
+
+    def advance(self):
+        """Fill ``index``, ``optimizer.lr_t``, ``optimizer.iht_t`` and ``where`` for the iteration that ``optimizer.step_t``
+        counts as done so far (0-based: the scalar as it stands before this iteration's ``step()``): one library call,
+        no host decision on device data, nothing synchronises.  Follow it with ``train_step_audio(..., self.index, ...,
+        iht=None)``, which leaves ``iht_t`` as written here."""
+        opt = self.optimizer
+        if self.device.type != "cuda":
+            raise RuntimeError("TrainSchedule.advance() runs on the GPU (the optimizer is on %s); kws_amd has no CPU "
+                               "fallback" % (self.device,))
+        with torch.cuda.device(self.device):
+            _call(_lib.load().fastgrnn_hip_train_schedule, "fastgrnn train_schedule", "train_schedule", self.device, None,
+                  C.byref(self.desc), opt.step_t.data_ptr(), self.index.data_ptr(), opt.lr_t.data_ptr(),
+                  opt.iht_t.data_ptr(), self.where.data_ptr())
+        return self.index
+
+    def record(self, loss):
+        """``loss_log[slot] = loss`` and ``lr_log[slot] = lr_t`` for the ``slot`` that ``advance`` wrote: two indexed
+        copies addressed by the device scalar, no sync, capturable."""
+        slot = self.where[2:3]
+        self.loss_log.index_copy_(0, slot, loss.detach().reshape(1).to(torch.float32))
+        self.lr_log.index_copy_(0, slot, self.optimizer.lr_t)
+
+    def epoch_log(self, accuracies=None):
+        """The reference's log (trainClassifier.py:272): one dict per epoch with the epoch's last loss, its last learning
+        rate and ``accuracies[epoch]`` (None without), read from the two logs -- one device-to-host copy each."""
+        loss, lr = self.loss_log.cpu().tolist(), self.lr_log.cpu().tolist()
+        out = []
+        for epoch in range(self.num_epochs):
+            slot = min((epoch + 1) * self.ticks - 1, self.log_len - 1)
+            out.append({"epoch": epoch, "loss": loss[slot], "accuracy": accuracies[epoch] if accuracies else None,
+                        "learning_rate": lr[slot]})
+        return out
