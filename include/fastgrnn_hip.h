@@ -545,6 +545,61 @@ int fastgrnn_hip_train_update(const fastgrnn_update_hyper *h, const fastgrnn_upd
                               int32_t n_segs, const float *lr, const int64_t *step, const int32_t *iht_mode,
                               void *stream);
 
+/* optim_update -- train_update for the other six optimizers of the trainer's configure_optimizer
+ * (trainClassifier.py:67-95), which keep up to three state tensors per parameter.  train_update's conventions hold
+ * throughout: one launch per FASTGRNN_UPDATE_MAX_SEGS segments, one workgroup per segment, the segment table in the
+ * kernel arguments; nothing allocated, nothing copied, never a synchronise, so the call may be captured in a graph;
+ * lr, step (the 1-based number of THIS step, incremented by the caller) and iht_mode are DEVICE scalars that are only
+ * read; segs is a HOST array; the IHT phase (mode 1: exact threshold + support; mode 2: support mask) follows the update
+ * with train_update's semantics and the state tensors are never masked; repeatable bit for bit.
+ * The rules are torch.optim's (torch 2.10, foreach=False, maximize=False, not differentiable): fp32 operands and
+ * arithmetic, what depends on the step count in double.  t = step[0]; g' = g + wd p in every rule but Rprop;
+ * lerp(a, b, w) = a + w (b - a), evaluated as torch does (b - (b - a)(1 - w) from w = 0.5 on).
+ *   algo 2, RMSprop.  h = alpha, eps, momentum; flags bit 0: centered.  state = square_avg v, momentum_buffer b (read
+ *     and written only with momentum > 0), grad_avg a (only when centered).
+ *     v' = alpha v + (1-alpha) g'^2;  centered: a' = lerp(a, g', 1-alpha), d = sqrt(v' - a'^2) + eps;  else
+ *     d = sqrt(v') + eps;  momentum > 0: b' = momentum b + g'/d, p' = p - lr b';  else p' = p - lr g'/d
+ *   algo 3, Adagrad.  h = lr_decay, eps.  state = sum s (the caller fills it with initial_accumulator_value).
+ *     clr = lr / (1 + (t-1) lr_decay);  s' = s + g'^2;  p' = p - clr g' / (sqrt(s') + eps)
+ *   algo 4, Adadelta.  h = rho, eps.  state = square_avg v, acc_delta a.
+ *     v' = rho v + (1-rho) g'^2;  D = sqrt(a + eps) / sqrt(v' + eps) g';  a' = rho a + (1-rho) D^2;  p' = p - lr D
+ *   algo 5, Adamax.  h = beta1, beta2, eps.  state = exp_avg m, exp_inf u.
+ *     m' = lerp(m, g', 1-beta1);  u' = max(beta2 u, |g'| + eps);  p' = p - (lr / (1 - beta1^t)) m' / u'
+ *   algo 6, ASGD.  h = lambd, alpha, t0.  state = ax.  eta and mu are what the previous step left (step 1: eta = lr,
+ *     mu = 1);  p' = p (1 - lambd eta) - eta g' (g' from the old p; 1 - lambd eta formed in double, rounded once);
+ *     ax' = p' if mu == 1 else ax + mu (p' - ax);  then eta <- lr / (1 + lambd lr t)^alpha, mu <- 1 / max(1, t - t0),
+ *     both rounded to fp32.  They live in scalars[4] (device, fp32), two pairs indexed by the step's parity: step t reads
+ *     scalars[2((t-1)&1) .. +1] (t > 1) and writes scalars[2(t&1) .. +1], so no workgroup reads what another has replaced.
+ *   algo 7, Rprop.  h = etaminus, etaplus, step_min, step_max.  state = prev, step_size (the caller fills it with the
+ *     learning rate).  s = sign(g prev), the product rounded to fp32;  step' = clamp(step (etaplus if s > 0, etaminus if
+ *     s < 0, else 1), step_min, step_max);  g'' = 0 where s < 0 else g;  p' = p - sign(g'') step';  prev' = g''.
+ *     lr[0] and step[0] are not used; weight_decay must be 0.
+ * Errors, all before any launch: FASTGRNN_ERR_NULL_POINTER (h, segs, lr, step; a segment's param, grad or a state
+ * tensor its rule needs; support on a segment with iht != 0, and iht_mode when there is such a segment; scalars under
+ * ASGD), FASTGRNN_ERR_UNSUPPORTED (algo outside 2..7: Adam and SGD are train_update's), FASTGRNN_ERR_BAD_SHAPE
+ * (n_segs < 1; n outside 1..2^22; keep_rank outside 0..n-1; weight_decay < 0; a hyper-parameter outside
+ * torch.optim's constructor range -- alpha, momentum, lr_decay < 0; rho outside [0,1]; beta1, beta2 outside [0,1) --;
+ * eps <= 0 under RMSprop, Adagrad, Adadelta, Adamax, where it divides; under Rprop weight_decay != 0, etaminus outside
+ * (0,1), etaplus <= 1, step_min > step_max; any of them NaN).  No workspace. */
+typedef struct fastgrnn_optim_seg {
+  void *param; const void *grad;      /* [n] fp32, device */
+  void *state[3];                     /* per rule, in the order listed above; those a rule does not use: NULL */
+  uint8_t *support;                   /* [n], required iff iht != 0 */
+  int64_t n, keep_rank;               /* as fastgrnn_update_seg */
+  int32_t iht, reserved;
+} fastgrnn_optim_seg;
+
+typedef struct fastgrnn_optim_hyper {
+  int32_t algo;                       /* 2 RMSprop, 3 Adagrad, 4 Adadelta, 5 Adamax, 6 ASGD, 7 Rprop */
+  int32_t flags;                      /* RMSprop: bit 0 centered */
+  double h[6];                        /* per rule, above; the rest ignored */
+  double weight_decay;
+} fastgrnn_optim_hyper;
+
+int fastgrnn_hip_optim_update(const fastgrnn_optim_hyper *h, const fastgrnn_optim_seg *segs /* HOST array */,
+                              int32_t n_segs, const float *lr, const int64_t *step, const int32_t *iht_mode,
+                              float *scalars /* ASGD only: device [4] */, void *stream);
+
 /* mfcc -- the reference's featuriser, librosa.feature.mfcc + librosa.feature.delta at librosa 0.10.2's defaults as
  * data_pipeline/mfccProcessor.py:43-58 calls them, then the pad / cut and the normalisation of preprocessing.py:79-88 and
  * inferencetry.py:165-200, from raw audio in one launch.  sr = 16000, n_fft = win_length = 400, hop = 160, n_mels = 128

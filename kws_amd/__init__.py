@@ -14,7 +14,8 @@ from .batchnorm_train import FastGRNNBatchNormCUDA  # noqa: F401
 from .model import RNNClassifierModel  # noqa: F401
 from .graph import GraphedStep  # noqa: F401
 from . import optim  # noqa: F401
-from .optim import FusedAdam, FusedSGD, iht_phase  # noqa: F401
+from .optim import (FusedAdadelta, FusedAdagrad, FusedAdam, FusedAdamax, FusedASGD, FusedRMSprop, FusedRprop,  # noqa: F401
+                    FusedSGD, configure_optimizer, iht_phase)
 from . import features  # noqa: F401
 from .features import MFCCFrontend, mfcc_features  # noqa: F401
 from . import augment  # noqa: F401
@@ -25,5 +26,6 @@ from .schedule import TrainSchedule  # noqa: F401
 __all__ = ["fastgrnn_cuda", "utils", "head", "FastGRNNCUDA", "FastGRNNCUDACell", "FastGRNNFunction",
            "FastGRNNUnrollFunction", "KeywordHead", "keyword_loss", "head_predict", "vote_windows", "RNNClassifierModel", "GraphedStep",
            "FastGRNNBatchNorm", "FastGRNNBatchNormCell", "fold_batchnorm", "FastGRNNBatchNormCUDA",
-           "optim", "FusedAdam", "FusedSGD", "iht_phase", "features", "MFCCFrontend", "mfcc_features",
+           "optim", "FusedAdam", "FusedSGD", "FusedRMSprop", "FusedAdagrad", "FusedAdadelta", "FusedAdamax", "FusedASGD",
+           "FusedRprop", "configure_optimizer", "iht_phase", "features", "MFCCFrontend", "mfcc_features",
            "augment", "AudioAugment", "pack_augment", "unpack_augment", "schedule", "TrainSchedule"]

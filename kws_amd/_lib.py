@@ -49,7 +49,7 @@ EXPORTS = (
     "fastgrnn_hip_train_windows_backward_workspace_bytes", "fastgrnn_hip_forward_windows_train",
     "fastgrnn_hip_backward_windows",
     "fastgrnn_hip_head_predict_workspace_bytes", "fastgrnn_hip_head_predict", "fastgrnn_hip_vote_windows",
-    "fastgrnn_hip_train_update",
+    "fastgrnn_hip_train_update", "fastgrnn_hip_optim_update",
     "fastgrnn_hip_mfcc_tables_bytes", "fastgrnn_hip_mfcc_init_tables", "fastgrnn_hip_mfcc_workspace_bytes",
     "fastgrnn_hip_mfcc", "fastgrnn_hip_mfcc_augment", "fastgrnn_hip_augment_draw", "fastgrnn_hip_train_schedule",
 )
@@ -119,6 +119,21 @@ class UpdateHyper(C.Structure):
     """fastgrnn_update_hyper."""
     _fields_ = [("algo", C.c_int32), ("nesterov", C.c_int32), ("beta1_or_momentum", C.c_double),
                 ("beta2_or_dampening", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double)]
+
+
+RMSPROP, ADAGRAD, ADADELTA, ADAMAX, ASGD, RPROP = 2, 3, 4, 5, 6, 7     # fastgrnn_optim_hyper.algo
+RMSPROP_CENTERED = 1            # fastgrnn_optim_hyper.flags
+
+
+class OptimSeg(C.Structure):
+    """fastgrnn_optim_seg: one parameter tensor of fastgrnn_hip_optim_update."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state", C.c_void_p * 3), ("support", C.c_void_p),
+                ("n", C.c_int64), ("keep_rank", C.c_int64), ("iht", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimHyper(C.Structure):
+    """fastgrnn_optim_hyper."""
+    _fields_ = [("algo", C.c_int32), ("flags", C.c_int32), ("h", C.c_double * 6), ("weight_decay", C.c_double)]
 
 
 MFCC_PEAK_NORMALIZE = 1         # FASTGRNN_MFCC_PEAK_NORMALIZE
@@ -225,6 +240,8 @@ def load():
     lib.fastgrnn_hip_vote_windows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.fastgrnn_hip_train_update.restype = i32
     lib.fastgrnn_hip_train_update.argtypes = [C.POINTER(UpdateHyper), C.POINTER(UpdateSeg), C.c_int32, vp, vp, vp, vp]
+    lib.fastgrnn_hip_optim_update.restype = i32
+    lib.fastgrnn_hip_optim_update.argtypes = [C.POINTER(OptimHyper), C.POINTER(OptimSeg), C.c_int32, vp, vp, vp, vp, vp]
     MD = C.POINTER(MfccDesc)
     lib.fastgrnn_hip_mfcc_tables_bytes.restype = sz
     lib.fastgrnn_hip_mfcc_tables_bytes.argtypes = []

@@ -493,6 +493,53 @@ int fastgrnn_hip_train_update(const fastgrnn_update_hyper* h, const fastgrnn_upd
   return train_update(*h, segs, n_segs, lr, step, iht_mode, reinterpret_cast<hipStream_t>(stream));
 }
 
+int fastgrnn_hip_optim_update(const fastgrnn_optim_hyper* h, const fastgrnn_optim_seg* segs, int32_t n_segs,
+                              const float* lr, const int64_t* step, const int32_t* iht_mode, float* scalars,
+                              void* stream) {
+  if (!h || !segs || !lr || !step) return FASTGRNN_ERR_NULL_POINTER;
+  if (h->algo < 2 || h->algo > 7) return FASTGRNN_ERR_UNSUPPORTED;
+  if (n_segs < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  const double* v = h->h;
+  bool ok = false;                    // (every comparison written so that a NaN fails it)
+  int needs = 1;                      // which of state[0..2] the rule reads, as a bit mask
+  switch (h->algo) {
+    case 2:                           // RMSprop: alpha, eps, momentum
+      ok = v[0] >= 0.0 && v[1] > 0.0 && v[2] >= 0.0 && h->weight_decay >= 0.0;
+      needs = 1 | (v[2] > 0.0 ? 2 : 0) | ((h->flags & 1) ? 4 : 0);
+      break;
+    case 3:                           // Adagrad: lr_decay, eps
+      ok = v[0] >= 0.0 && v[1] > 0.0 && h->weight_decay >= 0.0;
+      break;
+    case 4:                           // Adadelta: rho, eps
+      ok = v[0] >= 0.0 && v[0] <= 1.0 && v[1] > 0.0 && h->weight_decay >= 0.0;
+      needs = 3;
+      break;
+    case 5:                           // Adamax: beta1, beta2, eps
+      ok = v[0] >= 0.0 && v[0] < 1.0 && v[1] >= 0.0 && v[1] < 1.0 && v[2] > 0.0 && h->weight_decay >= 0.0;
+      needs = 3;
+      break;
+    case 6:                           // ASGD: lambd, alpha, t0 (torch takes any value)
+      ok = v[0] == v[0] && v[1] == v[1] && v[2] == v[2] && h->weight_decay >= 0.0;
+      if (!scalars) return FASTGRNN_ERR_NULL_POINTER;
+      break;
+    default:                          // Rprop: etaminus, etaplus, step_min, step_max
+      ok = v[0] > 0.0 && v[0] < 1.0 && v[1] > 1.0 && v[2] <= v[3] && h->weight_decay == 0.0;
+      needs = 3;
+      break;
+  }
+  if (!ok) return FASTGRNN_ERR_BAD_SHAPE;
+  for (int32_t k = 0; k < n_segs; ++k) {
+    const fastgrnn_optim_seg& sg = segs[k];
+    if (!sg.param || !sg.grad) return FASTGRNN_ERR_NULL_POINTER;
+    for (int j = 0; j < 3; ++j)
+      if ((needs >> j & 1) && !sg.state[j]) return FASTGRNN_ERR_NULL_POINTER;
+    if (sg.iht && (!sg.support || !iht_mode)) return FASTGRNN_ERR_NULL_POINTER;
+    if (sg.n < 1 || sg.n > FASTGRNN_UPDATE_MAX_N || sg.keep_rank < 0 || sg.keep_rank >= sg.n)
+      return FASTGRNN_ERR_BAD_SHAPE;
+  }
+  return optim_update(*h, segs, n_segs, lr, step, iht_mode, scalars, reinterpret_cast<hipStream_t>(stream));
+}
+
 // FASTGRNN_OK or the refusal of a featuriser descriptor (include/fastgrnn_hip.h lists the supported range)
 static int check_mfcc_desc(const fastgrnn_mfcc_desc* d) {
   if (!d) return FASTGRNN_ERR_NULL_POINTER;

@@ -303,7 +303,8 @@ class RNNClassifierModel(nn.Module):
         nor writes a layer's ``oldmats``, and ``sparsify()`` / ``sparsifyWithSupport()`` stay as they are.  The two
         mechanisms are not meant to be mixed within one run."""
         if not isinstance(optimizer, _FusedOptimizer):
-            raise TypeError("train_step() needs a kws_amd.FusedAdam or kws_amd.FusedSGD (got %s): a torch optimizer's "
+            raise TypeError("train_step() needs a kws_amd.FusedAdam or kws_amd.FusedSGD, or another fused optimizer of "
+                            "kws_amd.optim (got %s): a torch optimizer's "
                             "step() has no IHT phase -- call loss(), backward(), optimizer.step() and sparsify() yourself"
                             % type(optimizer).__name__)
         for p in self.parameters():
@@ -329,7 +330,8 @@ class RNNClassifierModel(nn.Module):
         the host first), so the step captures in a ``GraphedStep``: ``index`` is a captured input that the caller
         overwrites between replays, and every replay draws new augmentations as ``step_t`` advances."""
         if not isinstance(optimizer, _FusedOptimizer):
-            raise TypeError("train_step_audio() needs a kws_amd.FusedAdam or kws_amd.FusedSGD (got %s)"
+            raise TypeError("train_step_audio() needs a kws_amd.FusedAdam or kws_amd.FusedSGD, or another fused "
+                            "optimizer of kws_amd.optim (got %s)"
                             % type(optimizer).__name__)
         if self.rnn_name == "FastGRNNBatchNorm":
             raise NotImplementedError("loss() trains FastGRNNCUDA models; FastGRNNBatchNorm runs in eval mode only")
@@ -380,7 +382,8 @@ class RNNClassifierModel(nn.Module):
         the reference's log: one ``{"epoch", "loss", "accuracy", "learning_rate"}`` per epoch, the epoch's last loss and
         learning rate read from ``schedule.loss_log`` / ``lr_log`` at the end."""
         if not isinstance(optimizer, _FusedOptimizer):
-            raise TypeError("fit_audio() needs a kws_amd.FusedAdam or kws_amd.FusedSGD (got %s)" % type(optimizer).__name__)
+            raise TypeError("fit_audio() needs a kws_amd.FusedAdam or kws_amd.FusedSGD, or another fused optimizer of "
+                            "kws_amd.optim (got %s)" % type(optimizer).__name__)
         if getattr(schedule, "optimizer", None) is not optimizer:
             raise ValueError("fit_audio(): the schedule was built for another optimizer (it writes that one's lr_t / iht_t)")
         if labels.shape[0] != schedule.num_clips or audio.shape[0] != schedule.num_clips:

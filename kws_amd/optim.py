@@ -1,7 +1,10 @@
 """``optimizer.step()`` and the IHT phase of a trainer iteration (trainClassifier.py:249-259) in one library call.
 
-``FusedAdam`` / ``FusedSGD`` are ``torch.optim.Optimizer`` subclasses with torch's constructor arguments, ``param_groups``
-keys and ``state_dict`` layout whose ``step()`` hands EVERY parameter of the model to ``fastgrnn_hip_train_update``: one
+``FusedAdam`` / ``FusedSGD`` (on ``fastgrnn_hip_train_update``) and ``FusedRMSprop`` / ``FusedAdagrad`` / ``FusedAdadelta`` /
+``FusedAdamax`` / ``FusedASGD`` / ``FusedRprop`` (on ``fastgrnn_hip_optim_update``) -- the eight optimizers of the
+reference's ``configure_optimizer``, which ``configure_optimizer(params, options)`` here maps to them -- are
+``torch.optim.Optimizer`` subclasses with torch's constructor arguments, ``param_groups``
+keys and ``state_dict`` layout whose ``step()`` hands EVERY parameter of the model to the library: one
 kernel launch per 32 parameter tensors applies the update and, on the W/U matrices registered with ``register_iht``,
 the hard threshold (``utils.hardThreshold``) or the support mask (``utils.supportBasedThreshold``).  The learning rate,
 the step count and the IHT phase are read from device scalars (``lr_t``, ``step_t``, ``iht_t``), so a step captured in a
@@ -10,8 +13,9 @@ computes the learning rate (the reference's five schedules) and the phase on the
 
 Limits, each refused with a message that names it: one param group; float32, dense, contiguous parameters on one
 device; ``amsgrad``, ``maximize``, ``differentiable`` and decoupled weight decay (AdamW) off; at most 2^22 elements per
-tensor.  Constructing an optimizer and moving its state need no GPU -- ``step()`` does.  The other eight optimizers of the
-reference's ``configure_optimizer`` stay with ``torch.optim``.
+tensor.  Constructing an optimizer and moving its state need no GPU -- ``step()`` does.  ``capturable`` is accepted by
+every class, also where ``torch.optim``'s has no such argument.  ``FusedRprop`` adapts a step size per element and never
+reads the learning rate after its state exists: ``lr_t`` -- and a ``TrainSchedule`` that writes it -- is ignored there.
 
 The library writes parameters, moments and masks through raw pointers; ``step()`` then bumps the parameters' torch
 versions, so a step between a forward and its backward, or a cache keyed on ``_version``, sees it.  The segment table
@@ -54,7 +58,10 @@ def iht_phase(epoch, num_epochs, i_batch, trim_level):
 
 class _FusedOptimizer(torch.optim.Optimizer):
     _ALGO = None
-    _STATE_KEYS = ()                                  # the tensors of a parameter's state, in state0, state1 order
+    _STATE_KEYS = ()                                  # the tensors of a parameter's state, in the segment's slot order
+    _SEG = _lib.UpdateSeg                             # the library's segment structure and ...
+    _ENTRY = "fastgrnn_hip_train_update"              # ... the call that takes it
+    _ALL_STATE_KEYS = ()                              # where _slots() depends on the settings: every key it can name
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
@@ -90,6 +97,20 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def _hyper(self, group):
         raise NotImplementedError
 
+    def _slots(self, group):
+        """(slot, key) of every state tensor the group's settings use; the other slots of a segment stay NULL"""
+        return tuple(enumerate(self._STATE_KEYS))
+
+    def _new_state(self, p, key, group):
+        return torch.zeros_like(p, memory_format=torch.contiguous_format)
+
+    def _set_states(self, sg, ptrs):
+        sg.state0, sg.state1 = ptrs.get(0), ptrs.get(1)
+
+    def _extra_args(self):
+        """what the library call takes between ``iht_mode`` and the stream"""
+        return ()
+
     # ---- IHT --------------------------------------------------------------------------------------------------------
     def register_iht(self, model_or_layer):
         """Mark the W/U matrices (or their factors) of a layer, or of every layer in a model's ``rnn_list``, for the IHT
@@ -124,9 +145,10 @@ class _FusedOptimizer(torch.optim.Optimizer):
     # ---- the step ---------------------------------------------------------------------------------------------------
     def _init_state(self, p):
         st = self.state[p]
-        for k in self._STATE_KEYS:
+        group = self.param_groups[0]
+        for _, k in self._slots(group):
             if st.get(k) is None:
-                st[k] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st[k] = self._new_state(p, k, group)
         return st
 
     def _segments(self):
@@ -134,24 +156,24 @@ class _FusedOptimizer(torch.optim.Optimizer):
         a parameter's or gradient's address, or the identity of a state tensor or a mask (the table keeps those tensors
         referenced, so an identity is never recycled while the table lives).  Gradients are checked on every call."""
         ps = [p for p in self.param_groups[0]["params"] if p.grad is not None]
+        slots = self._slots(self.param_groups[0])
         key = []
         for p in ps:
             g, st = p.grad, self.state.get(p) or self._init_state(p)
             if g.dtype is not torch.float32 or g.is_sparse or g.device != p.device or not g.is_contiguous():
                 raise RuntimeError("%s: gradients must be dense contiguous float32 tensors on the parameter's device"
                                    % type(self).__name__)
-            key.append((p.data_ptr(), g.data_ptr()) + tuple(id(st.get(k)) for k in self._STATE_KEYS)
+            key.append((p.data_ptr(), g.data_ptr()) + tuple(id(st.get(k)) for _, k in slots)
                        + (id(self._iht[p][1]) if p in self._iht else 0,))
         if self._table is not None and self._table[0] == key:
             return self._table[1], self._table[2]
-        segs = (_lib.UpdateSeg * max(1, len(ps)))()
+        segs = (self._SEG * max(1, len(ps)))()
         held = []
         for sg, p in zip(segs, ps):
             st = self._init_state(p)
             sg.param, sg.grad, sg.n = p.data_ptr(), p.grad.data_ptr(), p.numel()
-            sg.state0 = st[self._STATE_KEYS[0]].data_ptr()
-            sg.state1 = st[self._STATE_KEYS[1]].data_ptr() if len(self._STATE_KEYS) > 1 else None
-            held.extend(st[k] for k in self._STATE_KEYS)
+            self._set_states(sg, {slot: st[k].data_ptr() for slot, k in slots})
+            held.extend(st[k] for _, k in slots)
             if p in self._iht:
                 sg.keep_rank, mask = self._iht[p]
                 sg.support, sg.iht = mask.data_ptr(), 1
@@ -202,8 +224,9 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self.step_t.add_(1)
         hy = self._hyper(group)
         with torch.cuda.device(self._device):
-            _call(_lib.load().fastgrnn_hip_train_update, "fastgrnn train_update", None, self._device, None,
-                  C.byref(hy), segs, n, self.lr_t.data_ptr(), self.step_t.data_ptr(), self.iht_t.data_ptr())
+            _call(getattr(_lib.load(), self._ENTRY), self._ENTRY.replace("fastgrnn_hip_", "fastgrnn "), None,
+                  self._device, None, C.byref(hy), segs, n, self.lr_t.data_ptr(), self.step_t.data_ptr(),
+                  self.iht_t.data_ptr(), *self._extra_args())
         # the library wrote through raw pointers: tell torch, so that whatever is keyed on a tensor's version (autograd's
         # saved-tensor check, the eval-mode BatchNorm fold cache) sees the step
         torch.autograd.graph.increment_version(self._table[4])
@@ -232,7 +255,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         for p in self.param_groups[0]["params"]:
             st = self.state.get(p)
             if st:
-                for k in self._STATE_KEYS:
+                for k in self._ALL_STATE_KEYS or self._STATE_KEYS:
                     if st.get(k) is not None:
                         st[k] = st[k].to(device=p.device, dtype=torch.float32).contiguous()
         self.step_t.fill_(self._import_step(state_dict))
@@ -327,3 +350,239 @@ class FusedSGD(_FusedOptimizer):
         if any(have) and not all(have):
             raise ValueError("FusedSGD keeps one step count for all parameters (some have a momentum buffer, some none)")
         return 1 if any(have) else 0
+
+
+class _FusedOptim(_FusedOptimizer):
+    """What the six rules of ``fastgrnn_hip_optim_update`` share: its segment structure, the refusals, torch's
+    per-parameter ``step`` in checkpoints."""
+    _SEG = _lib.OptimSeg
+    _ENTRY = "fastgrnn_hip_optim_update"
+
+    def _set_states(self, sg, ptrs):
+        for slot, ptr in ptrs.items():
+            sg.state[slot] = ptr
+
+    def _extra_args(self):
+        return (None,)                                       # scalars: ASGD's alone
+
+    def _ranges(self, g):
+        """-> (ok, what the message says must hold, the values it shows)"""
+        raise NotImplementedError
+
+    def _check_group(self):
+        g, name = self.param_groups[0], type(self).__name__
+        g.setdefault("capturable", False)
+        for k in ("maximize", "differentiable"):
+            if g.get(k):
+                raise ValueError("%s does not implement %s=True" % (name, k))
+        if isinstance(g["lr"], torch.Tensor):
+            raise ValueError("%s takes a float lr (the device scalar is lr_t)" % name)
+        ok, rule, got = self._ranges(g)
+        if not (float(g["lr"]) >= 0.0 and ok):
+            raise ValueError("%s: lr >= 0, %s (got %r, %s)" % (name, rule, g["lr"], ", ".join("%r" % (v,) for v in got)))
+
+    def _export_step(self, t):
+        for p in self.param_groups[0]["params"]:
+            if p in self.state and self.state[p]:
+                self.state[p]["step"] = torch.tensor(float(t))          # torch's: a float32 scalar on the host
+
+    def _import_step(self, sd):
+        steps = {int(float(st["step"])) for st in self.state.values() if st and "step" in st}
+        if len(steps) > 1:
+            raise ValueError("%s keeps one step count for all parameters (the checkpoint has %s)"
+                             % (type(self).__name__, sorted(steps)))
+        return steps.pop() if steps else 0
+
+
+class FusedRMSprop(_FusedOptim):
+    """``torch.optim.RMSprop`` (momentum, centered, L2 weight decay) on ``fastgrnn_hip_optim_update``."""
+    _ALGO = _lib.RMSPROP
+    _ALL_STATE_KEYS = ("square_avg", "momentum_buffer", "grad_avg")
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False,
+                 capturable=False, foreach=None, maximize=False, differentiable=False):
+        super().__init__(params, dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=centered,
+                                      weight_decay=weight_decay, capturable=capturable, foreach=foreach,
+                                      maximize=maximize, differentiable=differentiable))
+
+    def _ranges(self, g):
+        g.setdefault("momentum", 0)
+        g.setdefault("centered", False)
+        return (g["alpha"] >= 0.0 and g["eps"] > 0.0 and g["momentum"] >= 0.0 and g["weight_decay"] >= 0.0,
+                "alpha >= 0, eps > 0, momentum >= 0, weight_decay >= 0",
+                (g["alpha"], g["eps"], g["momentum"], g["weight_decay"]))
+
+    def _slots(self, g):                                     # torch creates the two optional buffers only where used
+        return ((0, "square_avg"),) + (((1, "momentum_buffer"),) if g["momentum"] > 0 else ()) \
+            + (((2, "grad_avg"),) if g["centered"] else ())
+
+    def _hyper(self, g):
+        return _lib.OptimHyper(_lib.RMSPROP, _lib.RMSPROP_CENTERED if g["centered"] else 0,
+                               (float(g["alpha"]), float(g["eps"]), float(g["momentum"])), float(g["weight_decay"]))
+
+
+class FusedAdagrad(_FusedOptim):
+    """``torch.optim.Adagrad`` (lr_decay, L2 weight decay, dense gradients) on ``fastgrnn_hip_optim_update``.  As
+    torch's, it creates its state -- ``sum``, filled with ``initial_accumulator_value`` -- when it is constructed."""
+    _ALGO = _lib.ADAGRAD
+    _STATE_KEYS = ("sum",)
+
+    def __init__(self, params, lr=1e-2, lr_decay=0, weight_decay=0, initial_accumulator_value=0, eps=1e-10,
+                 foreach=None, *, maximize=False, differentiable=False, fused=None, capturable=False):
+        super().__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay,
+                                      initial_accumulator_value=initial_accumulator_value, foreach=foreach,
+                                      maximize=maximize, differentiable=differentiable, fused=fused,
+                                      capturable=capturable))
+        for p in self.param_groups[0]["params"]:
+            self._init_state(p)
+            self.state[p]["step"] = torch.tensor(0.0)
+
+    def _ranges(self, g):
+        return (g["lr_decay"] >= 0.0 and g["eps"] > 0.0 and g["weight_decay"] >= 0.0
+                and g["initial_accumulator_value"] >= 0.0,
+                "lr_decay >= 0, eps > 0, weight_decay >= 0, initial_accumulator_value >= 0",
+                (g["lr_decay"], g["eps"], g["weight_decay"], g["initial_accumulator_value"]))
+
+    def _new_state(self, p, key, g):
+        return torch.full_like(p, float(g["initial_accumulator_value"]), memory_format=torch.contiguous_format)
+
+    def _hyper(self, g):
+        return _lib.OptimHyper(_lib.ADAGRAD, 0, (float(g["lr_decay"]), float(g["eps"])), float(g["weight_decay"]))
+
+
+class FusedAdadelta(_FusedOptim):
+    """``torch.optim.Adadelta`` (L2 weight decay) on ``fastgrnn_hip_optim_update``."""
+    _ALGO = _lib.ADADELTA
+    _STATE_KEYS = ("square_avg", "acc_delta")
+
+    def __init__(self, params, lr=1.0, rho=0.9, eps=1e-6, weight_decay=0, foreach=None, *, capturable=False,
+                 maximize=False, differentiable=False):
+        super().__init__(params, dict(lr=lr, rho=rho, eps=eps, weight_decay=weight_decay, maximize=maximize,
+                                      capturable=capturable, foreach=foreach, differentiable=differentiable))
+
+    def _ranges(self, g):
+        return (0.0 <= g["rho"] <= 1.0 and g["eps"] > 0.0 and g["weight_decay"] >= 0.0,
+                "rho in [0,1], eps > 0, weight_decay >= 0", (g["rho"], g["eps"], g["weight_decay"]))
+
+    def _hyper(self, g):
+        return _lib.OptimHyper(_lib.ADADELTA, 0, (float(g["rho"]), float(g["eps"])), float(g["weight_decay"]))
+
+
+class FusedAdamax(_FusedOptim):
+    """``torch.optim.Adamax`` (L2 weight decay) on ``fastgrnn_hip_optim_update``."""
+    _ALGO = _lib.ADAMAX
+    _STATE_KEYS = ("exp_avg", "exp_inf")
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, foreach=None, *, maximize=False,
+                 differentiable=False, capturable=False):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, foreach=foreach,
+                                      maximize=maximize, differentiable=differentiable, capturable=capturable))
+
+    def _ranges(self, g):
+        b1, b2 = g["betas"]
+        return (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and g["eps"] > 0.0 and g["weight_decay"] >= 0.0,
+                "betas in [0,1), eps > 0, weight_decay >= 0", (g["betas"], g["eps"], g["weight_decay"]))
+
+    def _hyper(self, g):
+        return _lib.OptimHyper(_lib.ADAMAX, 0, (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])),
+                               float(g["weight_decay"]))
+
+
+class FusedASGD(_FusedOptim):
+    """``torch.optim.ASGD`` on ``fastgrnn_hip_optim_update``.  ``eta`` and ``mu``, which torch keeps per parameter (all
+    equal), live in ``scalars``: float32 ``[4]`` on the parameters' device, the pair ``scalars[2 (t & 1):][:2]`` being what
+    step ``t`` left for step ``t + 1`` (the library's double buffer); ``state_dict()`` exports them under torch's keys."""
+    _ALGO = _lib.ASGD
+    _STATE_KEYS = ("ax",)
+
+    def __init__(self, params, lr=1e-2, lambd=1e-4, alpha=0.75, t0=1e6, weight_decay=0, foreach=None, maximize=False,
+                 differentiable=False, capturable=False):
+        super().__init__(params, dict(lr=lr, lambd=lambd, alpha=alpha, t0=t0, weight_decay=weight_decay,
+                                      foreach=foreach, maximize=maximize, differentiable=differentiable,
+                                      capturable=capturable))
+        self.scalars = torch.tensor([float(lr), 1.0] * 2, dtype=torch.float32, device=self._device)
+
+    def _ranges(self, g):
+        finite = all(math.isfinite(float(g[k])) for k in ("lambd", "alpha", "t0"))
+        return (finite and g["weight_decay"] >= 0.0, "finite lambd, alpha and t0, weight_decay >= 0",
+                (g["lambd"], g["alpha"], g["t0"], g["weight_decay"]))
+
+    def _extra_args(self):
+        return (self.scalars.data_ptr(),)
+
+    def _hyper(self, g):
+        return _lib.OptimHyper(_lib.ASGD, 0, (float(g["lambd"]), float(g["alpha"]), float(g["t0"])),
+                               float(g["weight_decay"]))
+
+    def _export_step(self, t):
+        super()._export_step(t)
+        # (before the first step the kernel reads neither: eta = lr_t, mu = 1, which is what torch starts from)
+        eta, mu = self.scalars[2 * (t & 1):][:2].tolist() if t >= 1 else (float(self.lr_t), 1.0)
+        for p in self.param_groups[0]["params"]:
+            if p in self.state and self.state[p]:
+                self.state[p]["eta"], self.state[p]["mu"] = torch.tensor(eta), torch.tensor(mu)
+
+    def _import_step(self, sd):
+        t = super()._import_step(sd)
+        pairs = {(float(st["eta"]), float(st["mu"])) for st in self.state.values() if st and "eta" in st and "mu" in st}
+        if len(pairs) > 1:
+            raise ValueError("FusedASGD keeps one eta and mu for all parameters (the checkpoint has %s)" % sorted(pairs))
+        eta, mu = pairs.pop() if pairs else (float(self.param_groups[0]["lr"]), 1.0)
+        self.scalars.copy_(torch.tensor([eta, mu] * 2, dtype=torch.float32))
+        return t
+
+
+class FusedRprop(_FusedOptim):
+    """``torch.optim.Rprop`` on ``fastgrnn_hip_optim_update``.  Every element has a step size of its own, which starts
+    at ``lr`` when the state is created (the first step, or a checkpoint) and is adapted from the gradient's sign: the
+    learning rate is not read again, so ``lr_t``, schedulers and a ``TrainSchedule`` have no effect on this rule."""
+    _ALGO = _lib.RPROP
+    _STATE_KEYS = ("prev", "step_size")
+
+    def __init__(self, params, lr=1e-2, etas=(0.5, 1.2), step_sizes=(1e-6, 50), *, capturable=False, foreach=None,
+                 maximize=False, differentiable=False):
+        super().__init__(params, dict(lr=lr, etas=etas, step_sizes=step_sizes, foreach=foreach, maximize=maximize,
+                                      capturable=capturable, differentiable=differentiable))
+
+    def _ranges(self, g):
+        (em, ep), (lo, hi) = g["etas"], g["step_sizes"]
+        return (0.0 < em < 1.0 < ep and lo <= hi and not g.get("weight_decay"),
+                "0 < etaminus < 1 < etaplus, step_min <= step_max, no weight_decay", (g["etas"], g["step_sizes"]))
+
+    def _new_state(self, p, key, g):
+        if key == "step_size":
+            return torch.full_like(p, float(g["lr"]), memory_format=torch.contiguous_format)
+        return torch.zeros_like(p, memory_format=torch.contiguous_format)
+
+    def _hyper(self, g):
+        return _lib.OptimHyper(_lib.RPROP, 0, tuple(float(v) for v in tuple(g["etas"]) + tuple(g["step_sizes"])), 0.0)
+
+
+def configure_optimizer(params, options, capturable=False):
+    """The reference's ``configure_optimizer`` (trainClassifier.py:67-95) on the fused classes: ``options`` is a
+    ``TrainingOptions``-shaped object -- ``optimizer`` (one of the eight names), ``learning_rate`` and
+    ``optimizer_options`` (``OptimizerOptions``: trainingConfig.py:43-58) -- and every rule takes from it exactly what
+    the reference passes to ``torch.optim``."""
+    lr, oo = options.learning_rate, options.optimizer_options
+    name = options.optimizer
+    if name == "Adadelta":
+        return FusedAdadelta(params, lr=lr, weight_decay=oo.weight_decay, rho=oo.rho, eps=oo.eps, capturable=capturable)
+    if name == "Adagrad":
+        return FusedAdagrad(params, lr=lr, weight_decay=oo.weight_decay, lr_decay=oo.lr_decay, capturable=capturable)
+    if name == "Adam":
+        return FusedAdam(params, lr=lr, weight_decay=oo.weight_decay, betas=oo.betas, eps=oo.eps, capturable=capturable)
+    if name == "Adamax":
+        return FusedAdamax(params, lr=lr, weight_decay=oo.weight_decay, betas=oo.betas, eps=oo.eps, capturable=capturable)
+    if name == "ASGD":
+        return FusedASGD(params, lr=lr, weight_decay=oo.weight_decay, lambd=oo.lambd, alpha=oo.alpha, t0=oo.t0,
+                         capturable=capturable)
+    if name == "RMSprop":
+        return FusedRMSprop(params, lr=lr, weight_decay=oo.weight_decay, eps=oo.eps, alpha=oo.alpha,
+                            momentum=oo.momentum, centered=oo.centered, capturable=capturable)
+    if name == "Rprop":
+        return FusedRprop(params, lr=lr, etas=oo.etas, step_sizes=oo.step_sizes, capturable=capturable)
+    if name == "SGD":
+        return FusedSGD(params, lr=lr, weight_decay=oo.weight_decay, momentum=oo.momentum, dampening=oo.dampening,
+                        nesterov=oo.nesterov, capturable=capturable)
+    raise ValueError("configure_optimizer: %r is none of Adadelta, Adagrad, Adam, Adamax, ASGD, RMSprop, Rprop, SGD"
+                     % (name,))

@@ -49,8 +49,10 @@ class TrainSchedule:
     """``TrainSchedule(optimizer, num_clips, batch_size, num_epochs, seed=...)``: the run's position, batch, learning rate
     and IHT phase as functions of ``optimizer.step_t``.
 
-    ``optimizer``: a ``FusedAdam`` / ``FusedSGD`` built with ``capturable=True`` (its ``lr_t`` then belongs to the caller,
-    here to ``advance``); its ``lr`` is the schedules' base (peak) rate.  ``lr_scheduler``: ``None`` or one of the
+    ``optimizer``: a ``FusedAdam`` / ``FusedSGD``, or any other fused optimizer of ``kws_amd.optim``, built with
+    ``capturable=True`` (its ``lr_t`` then belongs to the caller, here to ``advance``); its ``lr`` is the schedules'
+    base (peak) rate.  Under ``FusedRprop`` ``lr_t`` is written and ignored: that rule keeps a step size per element and
+    reads no learning rate.  ``lr_scheduler``: ``None`` or one of the
     reference's names, with ``configure_lr``'s constants (``ticks`` as above): ``steps = 2 lr_peaks + 1``, ``stepsize =
     num_epochs / steps * ticks`` (TriangleLR), ``t_max = ticks * num_epochs / steps`` (CosineAnnealingLR), ``reset =
     int(num_epochs * ticks / 3)`` (ExponentialResettingLR), ``lr_min`` falling back to the base rate.  ``lr_lead = 1``
@@ -65,7 +67,8 @@ class TrainSchedule:
     def __init__(self, optimizer, num_clips, batch_size, num_epochs, *, seed, lr_scheduler=None, lr_min=None, lr_peaks=1,
                  gamma=1.0, lr_step_size=1, lr_lead=1, sparsify=False, trim_level=15, world=1, rank=0, log_len=None):
         if not isinstance(optimizer, _FusedOptimizer):
-            raise TypeError("TrainSchedule needs a kws_amd.FusedAdam or kws_amd.FusedSGD (got %s): it writes the "
+            raise TypeError("TrainSchedule needs a kws_amd.FusedAdam or kws_amd.FusedSGD, or another fused optimizer of "
+                            "kws_amd.optim (got %s): it writes the "
                             "optimizer's device scalars lr_t and iht_t" % type(optimizer).__name__)
         if not optimizer.param_groups[0].get("capturable"):
             raise ValueError("TrainSchedule needs an optimizer built with capturable=True: otherwise %s.step() overwrites "
