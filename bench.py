@@ -2,13 +2,20 @@
 """Headline benchmark: utterances/sec, FastGRNN forward+backward, T=99 feat=32
 hidden=128, bs=4096 per GPU (BASELINE.json `metric`), fp32, synthetic MFCC frames.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver with torch.distributed.run (one rank per GPU, RCCL);
 batch shards data-parallel (weak scaling: 4096 utterances per GPU) and the parameter
 gradients are all-reduced in one flattened bucket per step.  Rank 0 prints ONE JSON line.
 A "step" = zero grads, forward over the whole [T,B,F] batch, backward with a dense
 grad_hs ~ N(0,1), and (N > 1) the gradient all-reduce; inputs are resident in HBM.
+
+A plain run does what the headline needs and no more: set up, spin up, W warmup steps, the K timed steps, the
+--dump-outputs arrays, the result line (with the kernel durations sampled INSIDE the timed region and the rooflines
+computed from them, which cost no step of their own).  Everything that takes runs of its own is behind --full: the
+median over ten further K-step blocks, the graph-replay leg, the other BASELINE configurations with the frame GEMM
+(`configs`), the CPU baseline (`cpu_baseline`, `speedup_vs_cpu`) and, with --graph, the eager steps that sample the
+kernel durations.  The timed region is the same in both.
 """
 import argparse
 import json
@@ -236,7 +243,8 @@ def agree_on_count(n, world, device):
     return int(ns.item())
 
 
-def main():
+def make_parser():
+    """The command line, as a function so that a test can hold it to its defaults without a GPU."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -245,7 +253,11 @@ def main():
                     help="untimed device spin-up before the W warmup steps (same step, every rank): a fresh GPU is "
                          "still raising its clock during the first tens of milliseconds of load")
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="utterances per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg: the median over ten further blocks of K steps, "
+                         "the graph-replay leg, the other BASELINE configurations, the CPU baseline (half a minute in "
+                         "place of seconds; the timed region and the headline fields are the same either way)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--graph", action="store_true",
                     help="N=1 only: capture the step in a HIP graph (kws_amd.GraphedStep) and time replays -- the same "
                          "kernels with ~10 us of host work per step instead of 130-270 us; reported as host: hip_graph")
@@ -254,10 +266,16 @@ def main():
                          "with fp32 state, parameters and parameter gradients (BASELINE config 'bf16 with fp32 master grads')")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the other BASELINE configurations (fwd-only, bf16, low-rank, 2-layer stack) at N=1")
+                    help="with --full: skip the other BASELINE configurations (fwd-only, bf16, low-rank, 2-layer "
+                         "stack) at N=1")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, "
                          "fp32: hs_sample [T, 768, H] (a fixed, seeded sample of the batch) and grad_<parameter>")
+    return ap
+
+
+def main():
+    ap = make_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -343,7 +361,9 @@ def main():
     dt = time.perf_counter() - t0
     timing, fastgrnn_cuda._timing = samples, None
     outputs = snapshot_outputs(kept["hs"], model) if dump else None
-    if args.graph:                  # events cannot be recorded inside a replay: sample the kernel durations on eager steps
+    # events cannot be recorded inside a replay: --full samples the kernel durations on eager steps of their own (a plain
+    # --graph run reports no per-kernel figures)
+    if args.graph and args.full:
         torch.cuda.synchronize()
         for i in range(8):
             fastgrnn_cuda._timing = samples
@@ -352,22 +372,24 @@ def main():
         timing, fastgrnn_cuda._timing = samples, None
     # (beside the contract's single timed region: the median over 10 further blocks of the same K steps, so that a
     # 10-20 ms sample is not the only number -- reported as ms_per_step_median_of_blocks, never as `value`)
-    blocks = []
-    for _ in range(10):
-        torch.cuda.synchronize()
-        tb = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        blocks.append((time.perf_counter() - tb) / args.steps)
-    blocks.sort()
-    ms_median_blocks = 1e3 * blocks[len(blocks) // 2]
-    # second headline leg (N = 1, default run): the SAME step captured once in a HIP graph (kws_amd.GraphedStep) and
+    ms_median_blocks = None
+    if args.full:
+        blocks = []
+        for _ in range(10):
+            torch.cuda.synchronize()
+            tb = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            blocks.append((time.perf_counter() - tb) / args.steps)
+        blocks.sort()
+        ms_median_blocks = 1e3 * blocks[len(blocks) // 2]
+    # second headline leg (N = 1, --full): the SAME step captured once in a HIP graph (kws_amd.GraphedStep) and
     # replayed -- the same kernels with ~10 us of host work per step instead of the eager path's 120-270, i.e. what the
     # GPU side alone allows.  Same protocol: W warmup replays, K timed replays between synchronises, and the median
     # of ten further K-step blocks.
     graph_leg = None
-    if world == 1 and not args.graph:
+    if args.full and world == 1 and not args.graph:
         try:
             from kws_amd import GraphedStep
             gstep = GraphedStep(eager_step)
@@ -415,8 +437,9 @@ def main():
     if rank == 0:
         ms_f = [a.elapsed_time(b) for tag, a, b in timing if tag == "forward"]
         ms_b = [a.elapsed_time(b) for tag, a, b in timing if tag == "backward"]
-        avg_f = sum(ms_f) / len(ms_f)
-        avg_b = sum(ms_b) / len(ms_b)
+        sampled = bool(ms_f and ms_b)              # a plain --graph run has no per-kernel samples
+        avg_f = sum(ms_f) / len(ms_f) if sampled else float("nan")
+        avg_b = sum(ms_b) / len(ms_b) if sampled else float("nan")
         value = world * B * args.steps / dt
         path_f = fastgrnn_cuda.kernel_path(T, B, F, H, direction=0)
         path_b = fastgrnn_cuda.kernel_path(T, B, F, H, direction=1)
@@ -433,7 +456,7 @@ def main():
         out = {
             "metric": "utterances/sec fwd+bwd, T=99 feat=32 hidden=128, bs=4096 at 1/2/4/8 GPUs",
             "value": value, "unit": "utterances/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "spinup_ms": args.spinup_ms,
+            "spinup_ms": args.spinup_ms, "full": args.full,
             "ms_per_step": 1e3 * dt / args.steps, "ms_per_step_median_of_blocks": ms_median_blocks,
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None,
@@ -473,12 +496,14 @@ def main():
             "forward_kernel": {"avg_launch_ms": avg_f, "tflops": tf_f, "frac_f32_peak": tf_f / PEAK_F32_TFLOPS,
                                "hbm_gbs": B * BYTES_FWD / (avg_f * 1e-3) / 1e9},
         }
-        if world == 1 and not args.no_extra_configs:
+        if not sampled:
+            out["roofline"] = out["roofline_mfma"] = out["forward_kernel"] = None
+        if args.full and world == 1 and not args.no_extra_configs:
             print("[bench] headline done: %.0f utt/s; timing the other BASELINE configurations ..." % value,
                   file=sys.stderr, flush=True)
             del x, G
             out["configs"] = extra_configs(dev, B)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle.fastgrnn_torch_port import time_fwd_bwd
             # the GPU box gives one GPU's job a 16-core CPU share; more threads than that
             # only oversubscribes

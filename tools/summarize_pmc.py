@@ -19,7 +19,7 @@ def short(name):
 
 
 def main(root):
-    print("# rocprofv3 summary of `bench.py --steps 10 --warmup 3` (%s)\n" % os.path.basename(root.rstrip("/")))
+    print("# rocprofv3 summary of `bench.py --steps 10 --warmup 3 --full` (%s)\n" % os.path.basename(root.rstrip("/")))
     for f in glob.glob(os.path.join(root, "stats", "**", "*kernel_stats.csv"), recursive=True):
         print("## kernel-trace --stats\n\n| kernel | calls | avg us | total % |\n|---|---|---|---|")
         for r in csv.DictReader(open(f)):
