@@ -87,6 +87,10 @@ typedef enum fastgrnn_nonlinearity {
  * row tiles per wave) instead of the default 8-wave one.  Same results to fp32 rounding.  Ignored by the other
  * shapes of kernel path 2. */
 #define FASTGRNN_FLAG_FWD_4WAVE 8u
+/* A/B only: run the dense H=128/F=32 backward without input gradient (FASTGRNN_FLAG_NO_INPUT_GRAD, d_x == NULL) in
+ * its older 8-wave shape instead of the default 12-wave one (a helper wave per SIMD for the weight gradients; fp32
+ * sequences, sigmoid / relu / tanh gate, tanh update).  The same bits in every output.  Ignored by every other call. */
+#define FASTGRNN_FLAG_BWD_8WAVE 32u
 /* Batch-major sequences (the trainer's batch_first layout, rnn.py:812-813,823-825): x, hs, z_s, c_s,
  * grad_hs and d_x are [B,T,.] instead of [T,B,.]; h0/d_h0 stay [B,H].  Kernel path 2 (dense H=128, dense H=256
  * with the limits of its table entry -- no bf16 backward -- and the low-rank H=256 scans) -- anything else answers

@@ -29,6 +29,9 @@ FLAG_PREACT_AFFINE = 1024     # fastgrnn_hip_forward_unroll_affine: per-unit pre
 FLAG_BN_TRAIN = 2048          # fastgrnn_hip_bn_train_*: the training-mode BatchNorm cell
 FLAG_ZERO_EXTEND = 4096       # odd H <= 256 / F on kernel path 2 by zero-padding to a path-2 shape (a permission)
 FLAG_NO_INPUT_GRAD = 8192     # backward_unroll: d_x may be NULL on dense H=128/F=32 too (a permission)
+# FASTGRNN_FLAG_BWD_8WAVE (A/B: the 8-wave shape of the H=128/F=32 backward without input gradient).  Not a FLAG_*
+# name: those are the set tests/support.py re-exports, one by one.
+AB_BWD_8WAVE = 32
 
 # include/fastgrnn_hip.h: fastgrnn_nonlinearity.  0..2 are the reference's table
 # (rnn.py:478,751); 3..5 the CPU cell's quantised family (rnn.py:53-60).

@@ -565,8 +565,13 @@ constexpr bool bwd_w8_built(int gate, bool preact, bool bf, bool nox, bool uq, b
   if (bf) return preact;
   return true;
 }
-template <int GATE, bool PREACT, bool RAGGED, bool BF = false, bool NOX = false, bool UQ = false, bool NODX = false>
-__global__ __launch_bounds__(512) void bwd_scan_split_w8(
+// s_setprio of waves 0-7 in the 12-wave kernel, set once in front of the loop; the helper waves stay at 0.  (0 = no
+// s_setprio at all, same-run A/B: the backward 0.8 % slower in the median, inside the spread -- profiles/r13.)
+constexpr int W12_RECURRENCE_PRIO = 1;
+// The body of both backward kernels.  HW (helper waves; F = 32 NODX only): bwd_scan_split_w12 below -- waves 0-7 keep
+// the recurrence alone, waves 8-11 do nothing but the weight gradients.  Without it: bwd_scan_split_w8.
+template <int GATE, bool PREACT, bool RAGGED, bool BF, bool NOX, bool UQ, bool NODX, bool HW>
+__device__ __forceinline__ void bwd_scan_split_body(
     int Tn, int B, int rsT, int rsB, int mode, const float* __restrict__ ghs, const float* __restrict__ x,
     const float* __restrict__ hs, const float* __restrict__ aux0, const float* __restrict__ aux1,
     const float* __restrict__ h0, const float* __restrict__ w, const float* __restrict__ u,
@@ -574,6 +579,8 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
     const float* __restrict__ zeta, const float* __restrict__ nu,
     float* __restrict__ d_x, float* __restrict__ d_h0, float* __restrict__ part) {
   constexpr int H = 128, F = 32, KS = 4, NFT = NOX ? 0 : 2, NC = NOX ? 4 : 5;   // NC column tiles per column half
+  constexpr int NT = HW ? 768 : 512;               // threads of the workgroup
+  static_assert(!HW || (NODX && !NOX), "helper waves: the F = 32 scans without d_x");
   // F = 32: whose turn the weight gradients are is decided per unrolled copy of iter(), and the gradient is replaced by
   // zeros where it is used, not behind its request (see iter() and load_ew).  The wide-input scans (NOX) keep the
   // run-time test and the select at the request: with both changed their results changed (the recorded digests of
@@ -601,22 +608,25 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
   const float sz = fsigmoid(zeta[0]), sn = fsigmoid(nu[0]);
   // Odd T: step T-1 has no partner; it is paired with a virtual step T whose images are zero.
   if (Tn & 1) {
-    for (int idx = tid; idx < IMG / 4; idx += 512) reinterpret_cast<unsigned*>(&S.img[Tn & 3][0])[idx] = 0u;
+    for (int idx = tid; idx < IMG / 4; idx += NT) reinterpret_cast<unsigned*>(&S.img[Tn & 3][0])[idx] = 0u;
   }
+  const bool helper = HW && wv >= 8;               // wave-uniform: a weight-gradient wave, no part in the recurrence
   if (PREACT && tid < 256) S.bias[tid >> 7][tid & 127] = (tid < 128 ? bz : bh)[tid & 127];
 
   // ---- resident A operands ------------------------------------------------------------------
   // chain: d_h[k][b] = sum_n U[n][k] d_pre[b][n]; A row i is k = 16w + i, K in natural unit order
   Frag3 UTf[KS];
+  if (!helper) {                                   // (a helper wave has no row tile of U: wv * 16 is beyond its columns)
 #pragma unroll
-  for (int s2 = 0; s2 < KS; ++s2) {
-    f32x4 lo, hi;
+    for (int s2 = 0; s2 < KS; ++s2) {
+      f32x4 lo, hi;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      lo[j] = u[(size_t)(32 * s2 + 8 * g + j) * H + wv * 16 + i];
-      hi[j] = u[(size_t)(32 * s2 + 8 * g + 4 + j) * H + wv * 16 + i];
+      for (int j = 0; j < 4; ++j) {
+        lo[j] = u[(size_t)(32 * s2 + 8 * g + j) * H + wv * 16 + i];
+        hi[j] = u[(size_t)(32 * s2 + 8 * g + 4 + j) * H + wv * 16 + i];
+      }
+      UTf[s2] = split3(lo, hi);
     }
-    UTf[s2] = split3(lo, hi);
   }
   // d_x[f][b] = sum_n W[n][f] d_pre[b][n]: feature tile xf2, K-step xks
   const int xf2 = wv & 1, xks = wv >> 1;
@@ -632,15 +642,30 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
   }
   f32x4 sbz = f32x4{0.f, 0.f, 0.f, 0.f}, sbh = sbz, dh = sbz;
   float pz = 0.f, pn = 0.f, pz_c = 0.f, pn_c = 0.f;     // d_zeta / d_nu partial sums, compensated
+  // The lane's coordinates for the flush behind the loop.  12 waves (168 registers per lane): derived again there from
+  // a copy of tid the compiler cannot trace back, not kept in registers across the loop; 8 waves: the values above.
+  struct LaneId { int i, n0, b; bool valid; };
+  auto lane_again = [&]() __attribute__((always_inline)) {
+    int t2 = tid;
+    if constexpr (HW) asm volatile("" : "+v"(t2));
+    const int i2 = t2 & 15, b2 = blockIdx.x * 16 + i2;
+    return LaneId{i2, __builtin_amdgcn_readfirstlane(t2 >> 6) * 16 + ((t2 & 63) >> 4) * 4, b2, !RAGGED || b2 < B};
+  };
   auto role_body = [&](auto role_tag) __attribute__((always_inline)) {
   // dW / dU accumulators: row tiles 2rp + a, column tiles 5ch + c  (column tile 0,1 = dW, 2..9 = dU)
+  // Roles 0, 1 (8 waves): recurrence + the weight gradients of column half ch = wv >> 2, a compile-time constant per
+  // code path.  With helper waves: role 2 = recurrence alone (waves 0-7), role 3 = a helper, both column halves of
+  // row-tile pair wv - 8 (it runs on SIMD wv & 3, beside recurrence waves wv - 8 and wv - 4).
   const int rp = wv & 3;
-  constexpr int ch = decltype(role_tag)::value;   // column half = wv >> 2, a compile-time constant per code path
-  f32x4 acc[2][NC];
+  constexpr int role = decltype(role_tag)::value;
+  constexpr bool HELPER = role == 3, WG = role != 2;
+  constexpr int ch = role & 1;
+  constexpr int NA = HELPER ? 2 * NC : NC;        // accumulators per row tile
+  f32x4 acc[2][NA];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int c = 0; c < NC; ++c) acc[a][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < NA; ++c) acc[a][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // lane-constant LDS byte offsets (within one step's image block)
   const unsigned lds_img = (unsigned)(size_t)&S.img[0][0];
@@ -670,11 +695,18 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
   const unsigned dp_off = !NOX ? 0u : (valid ? ((unsigned)b * (unsigned)rsB * H + n0) * 4u
                                              : (((unsigned)Tn * (unsigned)B + i) * H + n0) * 4u);
   const unsigned lane_x = NOX ? 0u : (xbft ? ((unsigned)xbc * F + xf) * (unsigned)Tn : (unsigned)xbc * (unsigned)rsB * F + xf);
-  auto ldg4 = [](const void* base, unsigned byte_off) __attribute__((always_inline)) {
-    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off);
+  // 12 waves (168 registers per lane): the lane offset reaches each load as a 32-bit value the compiler cannot trace
+  // back, so the load keeps the scalar-base + 32-bit-offset form.  Left alone it widens the loop-invariant offsets to
+  // 64-bit pairs in front of the loop: a register more per stream, which this shape does not have.
+  auto off32 = [](unsigned byte_off) __attribute__((always_inline)) {
+    if constexpr (HW) asm volatile("" : "+v"(byte_off));
+    return byte_off;
   };
-  auto ldg2 = [](const void* base, unsigned byte_off) __attribute__((always_inline)) {
-    return *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(base) + byte_off);
+  auto ldg4 = [&](const void* base, unsigned byte_off) __attribute__((always_inline)) {
+    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + off32(byte_off));
+  };
+  auto ldg2 = [&](const void* base, unsigned byte_off) __attribute__((always_inline)) {
+    return *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(base) + off32(byte_off));
   };
   auto load_ew = [&](int t, EwOps& e) __attribute__((always_inline)) {
     const size_t step_h = (size_t)t * rsT * H;       // uniform: element offset of step t's rows
@@ -701,15 +733,17 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
       // h_prev of step 0 is the fp32 h0: requested HERE, with the step's other operands (load_ew runs behind a
       // completion read), not in unpack_ew, which sits between the chain's MFMAs and the first read of their result
       if (t == 0) e.h = ldg4(h0, lane_bh * 4u);
-      if (!NOX) e.xraw = *reinterpret_cast<const unsigned short*>(xbase + lane_x * ESZ);
+      if (!NOX) e.xraw = *reinterpret_cast<const unsigned short*>(xbase + off32(lane_x * ESZ));
     } else {
       e.g = ldg4(gbase, goff);
       if constexpr (!SELECT_AT_USE) {
         e.g = g_zero ? f32x4{0.f, 0.f, 0.f, 0.f} : e.g;
         if (RAGGED && !valid) e.g = f32x4{0.f, 0.f, 0.f, 0.f};
       }
-      e.h = (t == 0) ? ldg4(h0, lane_bh * 4u) : ldg4(hbase, lane_e * 4u);
-      if (!NOX) e.xv = *reinterpret_cast<const float*>(xbase + lane_x * 4u);
+      // (12 waves: base and offset are selected and ONE load is written -- off32 in both arms would make them a branch)
+      if constexpr (HW) e.h = ldg4((t == 0) ? reinterpret_cast<const char*>(h0) : hbase, ((t == 0) ? lane_bh : lane_e) * 4u);
+      else e.h = (t == 0) ? ldg4(h0, lane_bh * 4u) : ldg4(hbase, lane_e * 4u);
+      if (!NOX) e.xv = *reinterpret_cast<const float*>(xbase + off32(lane_x * 4u));
     }
   };
   auto unpack4 = [](const uint2 v) __attribute__((always_inline)) {
@@ -827,8 +861,10 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
   // are zero: three of mfma6's six terms, in its order (the same bits).  The pair (1, 0) reads the fp32 h0 and keeps six.
   // (Decided per call site, not by a branch on sU: a wave-uniform branch between the MFMAs of a scan step brought back
   // intermittent wrong d_x rows -- 2 of 12 test processes -- that the static scans do not see: DESIGN.md 4.0.)
-  auto weight_grads = [&](auto pure_tag, int sU) __attribute__((always_inline)) {
+  // half_tag: the column half (ch; a helper wave runs both, each into accumulators of its own)
+  auto weight_grads = [&](auto pure_tag, auto half_tag, int sU) __attribute__((always_inline)) {
     constexpr bool PURE3 = decltype(pure_tag)::value;
+    constexpr int CH = decltype(half_tag)::value, A0 = HELPER ? NC * CH : 0;   // column half, its first accumulator
     const unsigned im = lds_img + (unsigned)(((g < 2) ? sU : sU - 1) & 3) * IMG;
     const unsigned trA = im + trA_off, trH = im + trH_off, trX = im + trX_off;
     Frag3 Af[2];
@@ -837,7 +873,7 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) Af[a2].p[pl] = tr_frag(trA + pl * PLANE_H + a2 * 32, ROW_H);
     auto load_b = [&](int c, Frag3& bf) __attribute__((always_inline)) {
-      const int ct = NC * ch + c;                      // wave-uniform
+      const int ct = NC * CH + c;                      // wave-uniform
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
         bf.p[pl] = (ct < NFT) ? tr_frag(trX + pl * PLANE_X + ct * 32, ROW_X)
@@ -860,20 +896,20 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
         for (int c = 0; c < NB; ++c)
 #pragma unroll
           for (int a2 = 0; a2 < 2; ++a2) {
-            f32x4 v = mfma_bf16(Af[a2].p[2], Bf[c].p[0], acc[a2][C0 + c]);
+            f32x4 v = mfma_bf16(Af[a2].p[2], Bf[c].p[0], acc[a2][A0 + C0 + c]);
             v = mfma_bf16(Af[a2].p[1], Bf[c].p[0], v);
-            acc[a2][C0 + c] = mfma_bf16(Af[a2].p[0], Bf[c].p[0], v);
+            acc[a2][A0 + C0 + c] = mfma_bf16(Af[a2].p[0], Bf[c].p[0], v);
           }
       } else {
 #pragma unroll
         for (int c = 0; c < NB; ++c)
 #pragma unroll
-          for (int a2 = 0; a2 < 2; ++a2) acc[a2][C0 + c] = mfma6(Af[a2], Bf[c], acc[a2][C0 + c]);
+          for (int a2 = 0; a2 < 2; ++a2) acc[a2][A0 + C0 + c] = mfma6(Af[a2], Bf[c], acc[a2][A0 + C0 + c]);
       }
       __builtin_amdgcn_sched_barrier(0);       // (the scheduler otherwise sinks MFMAs below the read)
       float touch = 0.f;                       // one element of every accumulator of the batch: all have retired
 #pragma unroll
-      for (int c = 0; c < NB; ++c) touch += acc[0][C0 + c][0] + acc[1][C0 + c][0];
+      for (int c = 0; c < NB; ++c) touch += acc[0][A0 + C0 + c][0] + acc[1][A0 + C0 + c][0];
       completion_read(touch);
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -901,7 +937,7 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
     // contract (t + 2 > top) is the peeled one in front of the loop (even Tn), which has a tag of its own -- no
     // run-time condition around the phase in the steady state.
     constexpr bool MY_TURN = EVEN ? (ch == 0) : (ch == 1);
-    constexpr bool HEAVY = MY_TURN && !PEELED;
+    constexpr bool HEAVY = WG && MY_TURN && !PEELED;          // (never with helper waves: the phase is theirs)
     // (tried: s_setprio 1 / 3 from here to the weight gradients, 0 there -- no change in three interleaved runs)
     const unsigned char* im = &S.img[t & 3][0];
     Frag3 dB[KS];
@@ -962,15 +998,39 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
     SPLIT_STAMP(3)
     // this wave's share of a step pair's dW / dU: 60 independent MFMAs and no VALU work
     if constexpr (STATIC_TURNS) {
-      if constexpr (HEAVY) weight_grads(std::bool_constant<BF && !LAST>{}, EVEN ? t + 1 : t + 2);
+      if constexpr (HEAVY) weight_grads(std::bool_constant<BF && !LAST>{}, role_tag, EVEN ? t + 1 : t + 2);
     } else {
-      if (MY_TURN && (EVEN || t + 2 <= top)) weight_grads(std::bool_constant<BF && !LAST>{}, EVEN ? t + 1 : t + 2);
+      if (MY_TURN && (EVEN || t + 2 <= top)) weight_grads(std::bool_constant<BF && !LAST>{}, role_tag, EVEN ? t + 1 : t + 2);
     }
     SPLIT_STAMP(4)
     lds_barrier();
     SPLIT_STAMP(5)
   };
 
+  if constexpr (HELPER) {
+    // A helper wave: the batches the heavy wave of its SIMD runs in the 8-wave kernel, iteration by iteration -- the
+    // same step pair, column half, batch sizes, PURE3 choice and term order per unrolled copy, so every accumulator
+    // receives the same addends in the same order -- and every barrier of the loop.
+    // Image lifetime: iteration t publishes the images of step t-1 (buffer (t-1) & 3) and the images of every step
+    // >= t are complete when it starts.  The pair (t+1, t) is read in iterations t (column half 0) and t-1 (column
+    // half 1) only; its older buffer (t+1) & 3 is written again by iteration t-2 (step t-3), which starts behind the
+    // barrier that ends iteration t-1.  No run-time branch between the MFMAs of a step: the loop's back edge alone.
+    __syncthreads();                                // (the two barriers of the recurrence waves' prologue)
+    __syncthreads();
+    constexpr std::integral_constant<int, 0> h0_tag{};
+    constexpr std::integral_constant<int, 1> h1_tag{};
+    int t = Tn - 1;
+    if (t & 1) { lds_barrier(); --t; }              // peeled (even Tn): no pair to contract yet
+    for (; t >= 2; t -= 2) {
+      weight_grads(std::bool_constant<BF>{}, h0_tag, t + 1);
+      lds_barrier();
+      weight_grads(std::bool_constant<BF>{}, h1_tag, t + 1);
+      lds_barrier();
+    }
+    weight_grads(std::false_type{}, h0_tag, 1);     // iteration 0, then the tail: pair (1, 0) reads the fp32 h0's planes
+    lds_barrier();
+    weight_grads(std::false_type{}, h1_tag, 1);
+  } else {
   EwOps E;
   __syncthreads();                                  // bias staged, virtual-step images zeroed
   {
@@ -981,6 +1041,8 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
     if (Tn >= 2) load_ew(Tn - 2, E);
   }
   __syncthreads();
+  // the recurrence is the critical path: its waves go ahead of their SIMD's helper wave (which stays at 0)
+  if constexpr (HW && W12_RECURRENCE_PRIO > 0) __builtin_amdgcn_s_setprio(W12_RECURRENCE_PRIO);
   {
     int t = Tn - 1;
     if (t & 1) { iter(std::false_type{}, std::false_type{}, std::true_type{}, t, E); --t; }   // peeled: even Tn
@@ -993,11 +1055,15 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
 #ifdef FASTGRNN_DIAG_STAMPS
   if (blockIdx.x == 7 && l == 0) { for (int k2 = 0; k2 < 8; ++k2) g_sdiag[wv][k2] = dsum[k2]; }
 #endif
-  if constexpr (ch == 1) weight_grads(std::false_type{}, 1);   // pair (1, 0), column tiles NC..2NC-1
+  if constexpr (WG && ch == 1) weight_grads(std::false_type{}, role_tag, 1);   // pair (1, 0), column tiles NC..2NC-1
   finish_dx(0);
   // ---- flush ---------------------------------------------------------------------------------
-  if (valid) st4(d_h0 + (size_t)b * H + n0, dh);
   {
+    const LaneId q = lane_again();
+    if (q.valid) st4(d_h0 + (size_t)q.b * H + q.n0, dh);
+  }
+  }
+  if constexpr (WG) {
     float* pu = part + (size_t)blockIdx.x * SLAB;
     float* pw = pu + H * H;
 #pragma unroll
@@ -1006,29 +1072,36 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
       for (int r = 0; r < 4; ++r) {
         const int n = rp * 32 + a * 16 + 4 * g + r;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const int ct = NC * ch + c;                // wave-uniform
+        for (int c = 0; c < NA; ++c) {
+          const int ct = HELPER ? c : NC * ch + c;   // wave-uniform
           if (ct < NFT) pw[(size_t)n * F + ct * 16 + i] = acc[a][c][r];
           else pu[(size_t)n * H + (ct - NFT) * 16 + i] = acc[a][c][r];
         }
       }
   }
   };
-  if (wv < 4) role_body(std::integral_constant<int, 0>{}); else role_body(std::integral_constant<int, 1>{});
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float a = sbz[r], c = sbh[r];
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) { a += __shfl_xor(a, m); c += __shfl_xor(c, m); }
-    if (i == 0) {
-      float* pb = part + (size_t)blockIdx.x * SLAB + H * H + H * F;
-      pb[n0 + r] = a;
-      pb[H + n0 + r] = c;
-    }
+  if constexpr (HW) {
+    if (helper) role_body(std::integral_constant<int, 3>{}); else role_body(std::integral_constant<int, 2>{});
+  } else {
+    if (wv < 4) role_body(std::integral_constant<int, 0>{}); else role_body(std::integral_constant<int, 1>{});
   }
+  if (!helper) {                                   // the recurrence waves' sums
+    const LaneId q = lane_again();
 #pragma unroll
-  for (int m = 1; m < 64; m <<= 1) { pz += __shfl_xor(pz, m); pn += __shfl_xor(pn, m); }
-  if (l == 0) { S.red[wv] = pz; S.red[8 + wv] = pn; }
+    for (int r = 0; r < 4; ++r) {
+      float a = sbz[r], c = sbh[r];
+#pragma unroll
+      for (int m = 1; m < 16; m <<= 1) { a += __shfl_xor(a, m); c += __shfl_xor(c, m); }
+      if (q.i == 0) {
+        float* pb = part + (size_t)blockIdx.x * SLAB + H * H + H * F;
+        pb[q.n0 + r] = a;
+        pb[H + q.n0 + r] = c;
+      }
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) { pz += __shfl_xor(pz, m); pn += __shfl_xor(pn, m); }
+    if (l == 0) { S.red[wv] = pz; S.red[8 + wv] = pn; }
+  }
   __syncthreads();
   if (tid == 0) {
     float* pzn = part + (size_t)blockIdx.x * SLAB + H * H + H * F + 2 * H;
@@ -1038,6 +1111,42 @@ __global__ __launch_bounds__(512) void bwd_scan_split_w8(
     pzn[0] = a; pzn[1] = c;
   }
 }
+
+#define BWD_SCAN_ARGS                                                                                             \
+  int Tn, int B, int rsT, int rsB, int mode, const float* __restrict__ ghs, const float* __restrict__ x,           \
+      const float* __restrict__ hs, const float* __restrict__ aux0, const float* __restrict__ aux1,                \
+      const float* __restrict__ h0, const float* __restrict__ w, const float* __restrict__ u,                      \
+      const float* __restrict__ bz, const float* __restrict__ bh, const float* __restrict__ zeta,                  \
+      const float* __restrict__ nu, float* __restrict__ d_x, float* __restrict__ d_h0, float* __restrict__ part
+#define BWD_SCAN_PASS Tn, B, rsT, rsB, mode, ghs, x, hs, aux0, aux1, h0, w, u, bz, bh, zeta, nu, d_x, d_h0, part
+
+template <int GATE, bool PREACT, bool RAGGED, bool BF = false, bool NOX = false, bool UQ = false, bool NODX = false>
+__global__ __launch_bounds__(512) void bwd_scan_split_w8(BWD_SCAN_ARGS) {
+  bwd_scan_split_body<GATE, PREACT, RAGGED, BF, NOX, UQ, NODX, false>(BWD_SCAN_PASS);
+}
+
+// ------------------------------------------------------------------------------------------
+// backward, 12 waves  (H = 128, F = 32, no d_x)
+// ------------------------------------------------------------------------------------------
+// The 8-wave scan with the weight gradients moved off the recurrence's path.  There, one wave of each SIMD runs its
+// 60 weight-gradient MFMAs between publishing d_pre and the step's barrier while its partner waits at that barrier,
+// although nothing in the recurrence needs their result.  Here waves 0-7 are the same recurrence code without that
+// phase and a third wave per SIMD (waves 8-11) does nothing else: helper h owns row-tile pair h and both column
+// halves, runs the batches the heavy wave of its SIMD would have run in each iteration and takes every barrier of the
+// loop.  Every output has the bits of the 8-wave kernel's (the recurrence is unchanged; each dW / dU accumulator gets
+// the same addends in the same order).  Three waves per SIMD: at most 168 registers per lane.
+// Built for the NODX arms of the reference's cell on fp32 sequences (its three gates, tanh update, both saved-tensor
+// contracts): those fit 168 registers without scratch.  The bf16, quantTanh-update and quantSigm4 arms need two or
+// three registers more (8-12 bytes of scratch per lane) and stay on 8 waves, as do the scans that produce d_x.
+constexpr bool bwd_w12_built(int gate, bool preact, bool bf, bool nox, bool uq, bool nodx) {
+  return nodx && !nox && !bf && !uq && gate <= FASTGRNN_NL_TANH && bwd_w8_built(gate, preact, bf, nox, uq, nodx);
+}
+template <int GATE, bool PREACT, bool RAGGED, bool BF = false, bool UQ = false>
+__global__ __launch_bounds__(768) void bwd_scan_split_w12(BWD_SCAN_ARGS) {
+  bwd_scan_split_body<GATE, PREACT, RAGGED, BF, false, UQ, true, true>(BWD_SCAN_PASS);
+}
+#undef BWD_SCAN_ARGS
+#undef BWD_SCAN_PASS
 
 // Deterministic reduction of the per-workgroup slabs in ONE launch (same scheme as kernels_mfma.hip).
 __global__ __launch_bounds__(1024) void reduce_slabs_split(int nwg, const float* __restrict__ part,
@@ -1116,8 +1225,8 @@ GatherWs gather_ws(const fastgrnn_desc& d, size_t inner_bytes, void* base) {
   return {inner, xg, c.off};
 }
 
-// run-time values of bwd_scan_split_w8's template parameters
-struct BwdW8 { int gate; bool preact, ragged, bf, nox, uq, nodx; };
+// run-time values of bwd_scan_split_w8's template parameters; w12: bwd_scan_split_w12 in its place
+struct BwdW8 { int gate; bool preact, ragged, bf, nox, uq, nodx, w12; };
 
 // FASTGRNN_ERR_UNSUPPORTED: the library holds no kernel for this call (bwd_w8_built), nothing was launched
 int launch_bwd_w8(const fastgrnn_desc& d, const fastgrnn_params& p, const void* ghs, const void* x, const void* hs,
@@ -1127,8 +1236,8 @@ int launch_bwd_w8(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
   const bool wide = dense_wide_shape(d);
   const DpreBwdWs L = w8_bwd_ws(d, ws);
   float* const part = L.part, * const dpre = L.dpre;
-  auto go8 = [&](auto kern) __attribute__((always_inline)) {     // 8-wave kernels also take the x layout
-    hipLaunchKernelGGL(kern, grid, dim3(512), 0, s, d.T, d.B, row_stride_t(d), row_stride_b(d),
+  auto go8 = [&](auto kern, int waves) __attribute__((always_inline)) {     // 8-wave kernels also take the x layout
+    hipLaunchKernelGGL(kern, grid, dim3(64 * waves), 0, s, d.T, d.B, row_stride_t(d), row_stride_b(d),
                        ((d.flags & FASTGRNN_FLAG_X_BFT) ? 1 : 0) | ((d.flags & FASTGRNN_FLAG_GRAD_LAST) ? 2 : 0), (const float*)ghs,
                        (const float*)x, (const float*)hs,
                        (const float*)a0, (const float*)a1, (const float*)h0, (const float*)p.w, (const float*)p.u,
@@ -1138,8 +1247,11 @@ int launch_bwd_w8(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
   // NOX: a wide layer, W and x leave the scan.  NODX: F = 32 and no input gradient (d_x == NULL:
   // FASTGRNN_FLAG_NO_INPUT_GRAD, which the entry points admit on this shape only).  The variant is chosen here, once
   // per launch, never inside a step.
-  const BwdW8 v{d.gate_nl, (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0, (d.B % 16) != 0, d.dtype == FASTGRNN_BF16_IO,
-                wide, d.update_nl == FASTGRNN_NL_QUANT_TANH, !wide && g.d_x == nullptr};
+  // w12: the arms that have a kernel with helper waves (bwd_w12_built) run it unless FASTGRNN_FLAG_BWD_8WAVE asks for
+  // the older shape.
+  BwdW8 v{d.gate_nl, (d.flags & FASTGRNN_FLAG_SAVE_PREACT) != 0, (d.B % 16) != 0, d.dtype == FASTGRNN_BF16_IO,
+          wide, d.update_nl == FASTGRNN_NL_QUANT_TANH, !wide && g.d_x == nullptr, false};
+  v.w12 = !(d.flags & FASTGRNN_FLAG_BWD_8WAVE) && bwd_w12_built(v.gate, v.preact, v.bf, v.nox, v.uq, v.nodx);
   const bool launched =
       pick_int<0, 1, 2, 3, 4, 5>(v.gate, [&](auto G_) {
       return pick_bool(v.preact, [&](auto PA_) {
@@ -1147,13 +1259,18 @@ int launch_bwd_w8(const fastgrnn_desc& d, const fastgrnn_params& p, const void* 
       return pick_bool(v.nox, [&](auto NX_) {
       return pick_bool(v.uq, [&](auto UQ_) {
       return pick_bool(v.nodx, [&](auto ND_) {
+      return pick_bool(v.w12, [&](auto W12_) {
       return pick_bool(v.ragged, [&](auto RG_) {
         constexpr int G = decltype(G_)::value;
         constexpr bool PA = decltype(PA_)::value, BF = decltype(BF_)::value, NX = decltype(NX_)::value,
-                       UQ = decltype(UQ_)::value, ND = decltype(ND_)::value, RG = decltype(RG_)::value;
-        if constexpr (bwd_w8_built(G, PA, BF, NX, UQ, ND)) { go8(bwd_scan_split_w8<G, PA, RG, BF, NX, UQ, ND>); return true; }
+                       UQ = decltype(UQ_)::value, ND = decltype(ND_)::value, W12 = decltype(W12_)::value,
+                       RG = decltype(RG_)::value;
+        if constexpr (W12) {
+          if constexpr (bwd_w12_built(G, PA, BF, NX, UQ, ND)) { go8(bwd_scan_split_w12<G, PA, RG, BF, UQ>, 12); return true; }
+          else return false;
+        } else if constexpr (bwd_w8_built(G, PA, BF, NX, UQ, ND)) { go8(bwd_scan_split_w8<G, PA, RG, BF, NX, UQ, ND>, 8); return true; }
         else return false;
-      }); }); }); }); }); }); });
+      }); }); }); }); }); }); }); });
   if (!launched) return FASTGRNN_ERR_UNSUPPORTED;
   const int ntot = 128 * 128 + 128 * 32 + 2 * 128 + 2;
   hipLaunchKernelGGL(reduce_slabs_split, dim3((ntot + 63) / 64), dim3(1024), 0, s, nwg, part, (const float*)p.zeta,

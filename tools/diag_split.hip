@@ -16,8 +16,9 @@ static float* dev_rand(size_t n, float scale) {
   float* d; (void)hipMalloc(&d, n * 4); (void)hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice);
   return d;
 }
-// NODX: the headline step's backward (FASTGRNN_FLAG_NO_INPUT_GRAD: no d_x)
-template <bool PREACT, bool NODX>
+// NODX: the headline step's backward (FASTGRNN_FLAG_NO_INPUT_GRAD: no d_x); W12: bwd_scan_split_w12 (NODX only), whose
+// recurrence waves 0-7 carry the same stamps (stamp 4, the weight gradients, stays empty: the helper waves have them)
+template <bool PREACT, bool NODX, bool W12 = false>
 void run_bwd_w8(int T, int B) {
   constexpr int H = 128, F = 32;
   float *x = dev_rand((size_t)T * B * F, 1.f), *h0 = dev_rand((size_t)B * H, 0.f), *w = dev_rand(H * F, 0.17f);
@@ -30,15 +31,19 @@ void run_bwd_w8(int T, int B) {
   std::vector<float> ts;
   for (int rep = 0; rep < 10; ++rep) {
     (void)hipEventRecord(e0);
-    hipLaunchKernelGGL((bwd_scan_split_w8<0, PREACT, false, false, false, false, NODX>), dim3((B + 15) / 16), dim3(512), 0, 0, T, B, B, 1,
-                       0, ghs, x, hs, a0, a1, h0, w, u, bz, bh, zeta, nu, NODX ? (float*)nullptr : dx, dh0, part);
+    if constexpr (W12)
+      hipLaunchKernelGGL((bwd_scan_split_w12<0, PREACT, false>), dim3((B + 15) / 16), dim3(768), 0, 0, T, B, B, 1,
+                         0, ghs, x, hs, a0, a1, h0, w, u, bz, bh, zeta, nu, (float*)nullptr, dh0, part);
+    else
+      hipLaunchKernelGGL((bwd_scan_split_w8<0, PREACT, false, false, false, false, NODX>), dim3((B + 15) / 16), dim3(512), 0, 0, T, B, B, 1,
+                         0, ghs, x, hs, a0, a1, h0, w, u, bz, bh, zeta, nu, NODX ? (float*)nullptr : dx, dh0, part);
     (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
     float ms; (void)hipEventElapsedTime(&ms, e0, e1);
     if (rep >= 2) ts.push_back(ms);
   }
   std::sort(ts.begin(), ts.end());
-  printf("bwd_scan_split_w8 PREACT=%d NODX=%d: %.1f us (%.2f us/step)\n", (int)PREACT, (int)NODX, ts[ts.size() / 2] * 1e3,
-         ts[ts.size() / 2] * 1e3 / T);
+  printf("bwd_scan_split_%s PREACT=%d NODX=%d: %.1f us (%.2f us/step)\n", W12 ? "w12" : "w8", (int)PREACT, (int)NODX,
+         ts[ts.size() / 2] * 1e3, ts[ts.size() / 2] * 1e3 / T);
   unsigned long long h[8][8];
   (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_sdiag), sizeof(h));
   const char* names[6] = {"(glue)", "dB read issue + landing", "chain + ew_pre", "ew_post + publish + requests",
@@ -119,6 +124,7 @@ int main(int argc, char** argv) {
   run_fwd_w8<0>(99, B);
   run_fwd<1>(99, B);
   run_bwd_w8<true, true>(99, B);
+  run_bwd_w8<true, true, true>(99, B);
   run_bwd_w8<true, false>(99, B);
   run_bwd_w8<false, false>(99, B);
   return 0;
