@@ -192,6 +192,25 @@ bool pool_rows_ok(const fastgrnn_desc* d, size_t pool_rows) {
 bool bn_train_route(const fastgrnn_desc* d, route* r) {
   return resolve(d, r) == FASTGRNN_OK && (r->u.flags & FASTGRNN_FLAG_BN_TRAIN) && bn_train_supported(r->u);
 }
+
+const void* seg_state(const fastgrnn_update_seg& sg, int j) { return j == 0 ? sg.state0 : j == 1 ? sg.state1 : nullptr; }
+const void* seg_state(const fastgrnn_optim_seg& sg, int j) { return sg.state[j]; }
+
+// FASTGRNN_OK or the refusal of a segment array of either update call; needs: which of a segment's state slots 0..2
+// the rule reads, as a bit mask
+template <typename Seg>
+int check_update_segs(const Seg* segs, int32_t n_segs, int needs, const int32_t* iht_mode) {
+  for (int32_t k = 0; k < n_segs; ++k) {
+    const Seg& sg = segs[k];
+    if (!sg.param || !sg.grad) return FASTGRNN_ERR_NULL_POINTER;
+    for (int j = 0; j < 3; ++j)
+      if ((needs >> j & 1) && !seg_state(sg, j)) return FASTGRNN_ERR_NULL_POINTER;
+    if (sg.iht && (!sg.support || !iht_mode)) return FASTGRNN_ERR_NULL_POINTER;
+    if (sg.n < 1 || sg.n > FASTGRNN_UPDATE_MAX_N || sg.keep_rank < 0 || sg.keep_rank >= sg.n)
+      return FASTGRNN_ERR_BAD_SHAPE;
+  }
+  return FASTGRNN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -483,14 +502,8 @@ int fastgrnn_hip_train_update(const fastgrnn_update_hyper* h, const fastgrnn_upd
   if (adam && (!(b2 >= 0.0 && b2 < 1.0) || !(h->eps > 0.0))) return FASTGRNN_ERR_BAD_SHAPE;
   if (!adam && h->nesterov && (b1 <= 0.0 || b2 != 0.0)) return FASTGRNN_ERR_BAD_SHAPE;   // torch.optim.SGD's rule
   if (!adam && !(b2 == b2)) return FASTGRNN_ERR_BAD_SHAPE;
-  for (int32_t k = 0; k < n_segs; ++k) {
-    const fastgrnn_update_seg& sg = segs[k];
-    if (!sg.param || !sg.grad || !sg.state0 || (adam && !sg.state1)) return FASTGRNN_ERR_NULL_POINTER;
-    if (sg.iht && (!sg.support || !iht_mode)) return FASTGRNN_ERR_NULL_POINTER;
-    if (sg.n < 1 || sg.n > FASTGRNN_UPDATE_MAX_N || sg.keep_rank < 0 || sg.keep_rank >= sg.n)
-      return FASTGRNN_ERR_BAD_SHAPE;
-  }
-  return train_update(*h, segs, n_segs, lr, step, iht_mode, reinterpret_cast<hipStream_t>(stream));
+  if (const int st = check_update_segs(segs, n_segs, adam ? 3 : 1, iht_mode)) return st;
+  return update_step(*h, segs, n_segs, lr, step, iht_mode, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
 int fastgrnn_hip_optim_update(const fastgrnn_optim_hyper* h, const fastgrnn_optim_seg* segs, int32_t n_segs,
@@ -528,16 +541,8 @@ int fastgrnn_hip_optim_update(const fastgrnn_optim_hyper* h, const fastgrnn_opti
       break;
   }
   if (!ok) return FASTGRNN_ERR_BAD_SHAPE;
-  for (int32_t k = 0; k < n_segs; ++k) {
-    const fastgrnn_optim_seg& sg = segs[k];
-    if (!sg.param || !sg.grad) return FASTGRNN_ERR_NULL_POINTER;
-    for (int j = 0; j < 3; ++j)
-      if ((needs >> j & 1) && !sg.state[j]) return FASTGRNN_ERR_NULL_POINTER;
-    if (sg.iht && (!sg.support || !iht_mode)) return FASTGRNN_ERR_NULL_POINTER;
-    if (sg.n < 1 || sg.n > FASTGRNN_UPDATE_MAX_N || sg.keep_rank < 0 || sg.keep_rank >= sg.n)
-      return FASTGRNN_ERR_BAD_SHAPE;
-  }
-  return optim_update(*h, segs, n_segs, lr, step, iht_mode, scalars, reinterpret_cast<hipStream_t>(stream));
+  if (const int st = check_update_segs(segs, n_segs, needs, iht_mode)) return st;
+  return update_step(*h, segs, n_segs, lr, step, iht_mode, scalars, reinterpret_cast<hipStream_t>(stream));
 }
 
 // FASTGRNN_OK or the refusal of a featuriser descriptor (include/fastgrnn_hip.h lists the supported range)

@@ -196,12 +196,12 @@ int head_predict(int B, int H, int C, const void* h_last, const void* fc_w, cons
 bool vote_supported(int K);
 int vote_windows(int S, int Nw, int K, int M, const int32_t* pred, int32_t* majority, int32_t* event, hipStream_t s);
 
-// optimizer step + IHT phase for every parameter tensor (kernels_update.hip); arguments already checked, segs on the host
-int train_update(const fastgrnn_update_hyper& h, const fastgrnn_update_seg* segs, int n_segs, const float* lr,
-                 const int64_t* step, const int32_t* iht_mode, hipStream_t s);
-// the same for RMSprop, Adagrad, Adadelta, Adamax, ASGD and Rprop (kernels_optim.hip); arguments already checked
-int optim_update(const fastgrnn_optim_hyper& h, const fastgrnn_optim_seg* segs, int n_segs, const float* lr,
-                 const int64_t* step, const int32_t* iht_mode, float* scalars, hipStream_t s);
+// optimizer step + IHT phase for every parameter tensor (kernels_update.hip), for either public pair of structures:
+// fastgrnn_update_hyper / _seg (Adam, SGD) or fastgrnn_optim_hyper / _seg (the other six rules; scalars is ASGD's).
+// Arguments already checked, segs on the host
+template <typename Hyper, typename Seg>
+int update_step(const Hyper& h, const Seg* segs, int n_segs, const float* lr, const int64_t* step,
+                const int32_t* iht_mode, float* scalars, hipStream_t s);
 
 // MFCC + delta features from raw audio (kernels_mfcc.hip); arguments already checked
 size_t mfcc_tables_bytes();

@@ -62,6 +62,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
     _SEG = _lib.UpdateSeg                             # the library's segment structure and ...
     _ENTRY = "fastgrnn_hip_train_update"              # ... the call that takes it
     _ALL_STATE_KEYS = ()                              # where _slots() depends on the settings: every key it can name
+    _REFUSED = ("maximize", "differentiable")         # torch's options that must stay off
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
@@ -91,7 +92,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._table = None                            # (key, ctypes segment array, n): rebuilt when an address moves
 
     # ---- what the subclasses say ----------------------------------------------------------------------------------
-    def _check_group(self):
+    def _ranges(self, g):
+        """-> (ok, what the message says must hold, the values it shows)"""
         raise NotImplementedError
 
     def _hyper(self, group):
@@ -110,6 +112,18 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def _extra_args(self):
         """what the library call takes between ``iht_mode`` and the stream"""
         return ()
+
+    def _check_group(self):
+        g, name = self.param_groups[0], type(self).__name__
+        g.setdefault("capturable", False)
+        for k in self._REFUSED:
+            if g.get(k):
+                raise ValueError("%s does not implement %s=True" % (name, k))
+        if isinstance(g["lr"], torch.Tensor):
+            raise ValueError("%s takes a float lr (the device scalar is lr_t)" % name)
+        ok, rule, got = self._ranges(g)
+        if not (float(g["lr"]) >= 0.0 and ok):
+            raise ValueError("%s: lr >= 0, %s (got %r, %s)" % (name, rule, g["lr"], ", ".join("%r" % (v,) for v in got)))
 
     # ---- IHT --------------------------------------------------------------------------------------------------------
     def register_iht(self, model_or_layer):
@@ -234,10 +248,16 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     # ---- checkpoints: torch's layout, plus the masks under a key torch ignores ---------------------------------------
     def _export_step(self, t):
-        pass
+        for p in self.param_groups[0]["params"]:
+            if p in self.state and self.state[p]:
+                self.state[p]["step"] = torch.tensor(float(t))          # torch's: a float32 scalar on the host
 
     def _import_step(self, sd):
-        raise NotImplementedError
+        steps = {int(float(st["step"])) for st in self.state.values() if st and "step" in st}
+        if len(steps) > 1:
+            raise ValueError("%s keeps one step count for all parameters (the checkpoint has %s)"
+                             % (type(self).__name__, sorted(steps)))
+        return steps.pop() if steps else 0
 
     def state_dict(self):
         self._export_step(int(self.step_t.item()))
@@ -275,6 +295,7 @@ class FusedAdam(_FusedOptimizer):
     """``torch.optim.Adam`` (L2 weight decay, no amsgrad) on ``fastgrnn_hip_train_update``."""
     _ALGO = _lib.ADAM
     _STATE_KEYS = ("exp_avg", "exp_avg_sq")
+    _REFUSED = ("amsgrad", "maximize", "differentiable", "decoupled_weight_decay")
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
                  maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
@@ -283,34 +304,14 @@ class FusedAdam(_FusedOptimizer):
                                       differentiable=differentiable, fused=fused,
                                       decoupled_weight_decay=decoupled_weight_decay))
 
-    def _check_group(self):
-        g = self.param_groups[0]
-        g.setdefault("capturable", False)
-        for k in ("amsgrad", "maximize", "differentiable", "decoupled_weight_decay"):
-            if g.get(k):
-                raise ValueError("FusedAdam does not implement %s=True" % k)
-        if isinstance(g["lr"], torch.Tensor):
-            raise ValueError("FusedAdam takes a float lr (the device scalar is lr_t)")
+    def _ranges(self, g):
         b1, b2 = g["betas"]
-        if not (float(g["lr"]) >= 0.0 and 0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and g["eps"] > 0.0
-                and g["weight_decay"] >= 0.0):
-            raise ValueError("FusedAdam: lr >= 0, betas in [0,1), eps > 0, weight_decay >= 0 (got %r, %r, %r, %r)"
-                             % (g["lr"], g["betas"], g["eps"], g["weight_decay"]))
+        return (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and g["eps"] > 0.0 and g["weight_decay"] >= 0.0,
+                "betas in [0,1), eps > 0, weight_decay >= 0", (g["betas"], g["eps"], g["weight_decay"]))
 
     def _hyper(self, g):
         return _lib.UpdateHyper(_lib.ADAM, 0, float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                                 float(g["weight_decay"]))
-
-    def _export_step(self, t):
-        for p in self.param_groups[0]["params"]:
-            if p in self.state and self.state[p]:
-                self.state[p]["step"] = torch.tensor(float(t))          # torch's: a float32 scalar on the host
-
-    def _import_step(self, sd):
-        steps = {int(float(st["step"])) for st in self.state.values() if st and "step" in st}
-        if len(steps) > 1:
-            raise ValueError("FusedAdam keeps one step count for all parameters (the checkpoint has %s)" % sorted(steps))
-        return steps.pop() if steps else 0
 
 
 class FusedSGD(_FusedOptimizer):
@@ -324,17 +325,13 @@ class FusedSGD(_FusedOptimizer):
                                       nesterov=nesterov, maximize=maximize, foreach=foreach,
                                       differentiable=differentiable, fused=fused, capturable=capturable))
 
+    def _ranges(self, g):
+        return (0.0 <= g["momentum"] < 1.0 and g["weight_decay"] >= 0.0, "momentum in [0,1), weight_decay >= 0",
+                (g["momentum"], g["weight_decay"]))
+
     def _check_group(self):
+        super()._check_group()
         g = self.param_groups[0]
-        g.setdefault("capturable", False)
-        for k in ("maximize", "differentiable"):
-            if g.get(k):
-                raise ValueError("FusedSGD does not implement %s=True" % k)
-        if isinstance(g["lr"], torch.Tensor):
-            raise ValueError("FusedSGD takes a float lr (the device scalar is lr_t)")
-        if not (float(g["lr"]) >= 0.0 and 0.0 <= g["momentum"] < 1.0 and g["weight_decay"] >= 0.0):
-            raise ValueError("FusedSGD: lr >= 0, momentum in [0,1), weight_decay >= 0 (got %r, %r, %r)"
-                             % (g["lr"], g["momentum"], g["weight_decay"]))
         if g["nesterov"] and (g["momentum"] <= 0 or g["dampening"] != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")      # torch's own rule
 
@@ -342,7 +339,10 @@ class FusedSGD(_FusedOptimizer):
         return _lib.UpdateHyper(_lib.SGD, 1 if g["nesterov"] else 0, float(g["momentum"]), float(g["dampening"]), 0.0,
                                 float(g["weight_decay"]))
 
-    def _import_step(self, sd):
+    def _export_step(self, t):                               # torch.optim.SGD keeps no count ...
+        pass
+
+    def _import_step(self, sd):                              # ... so its checkpoints come without one
         if "fused_step" in sd:
             return int(sd["fused_step"])
         # torch.optim.SGD keeps no count: a buffer means the first step (b = g) is behind us
@@ -353,8 +353,7 @@ class FusedSGD(_FusedOptimizer):
 
 
 class _FusedOptim(_FusedOptimizer):
-    """What the six rules of ``fastgrnn_hip_optim_update`` share: its segment structure, the refusals, torch's
-    per-parameter ``step`` in checkpoints."""
+    """What the six rules of ``fastgrnn_hip_optim_update`` share: its segment structure and its ``scalars`` argument."""
     _SEG = _lib.OptimSeg
     _ENTRY = "fastgrnn_hip_optim_update"
 
@@ -364,34 +363,6 @@ class _FusedOptim(_FusedOptimizer):
 
     def _extra_args(self):
         return (None,)                                       # scalars: ASGD's alone
-
-    def _ranges(self, g):
-        """-> (ok, what the message says must hold, the values it shows)"""
-        raise NotImplementedError
-
-    def _check_group(self):
-        g, name = self.param_groups[0], type(self).__name__
-        g.setdefault("capturable", False)
-        for k in ("maximize", "differentiable"):
-            if g.get(k):
-                raise ValueError("%s does not implement %s=True" % (name, k))
-        if isinstance(g["lr"], torch.Tensor):
-            raise ValueError("%s takes a float lr (the device scalar is lr_t)" % name)
-        ok, rule, got = self._ranges(g)
-        if not (float(g["lr"]) >= 0.0 and ok):
-            raise ValueError("%s: lr >= 0, %s (got %r, %s)" % (name, rule, g["lr"], ", ".join("%r" % (v,) for v in got)))
-
-    def _export_step(self, t):
-        for p in self.param_groups[0]["params"]:
-            if p in self.state and self.state[p]:
-                self.state[p]["step"] = torch.tensor(float(t))          # torch's: a float32 scalar on the host
-
-    def _import_step(self, sd):
-        steps = {int(float(st["step"])) for st in self.state.values() if st and "step" in st}
-        if len(steps) > 1:
-            raise ValueError("%s keeps one step count for all parameters (the checkpoint has %s)"
-                             % (type(self).__name__, sorted(steps)))
-        return steps.pop() if steps else 0
 
 
 class FusedRMSprop(_FusedOptim):

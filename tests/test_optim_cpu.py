@@ -1,12 +1,11 @@
 """CPU-side checks of the six further fused optimizers (fastgrnn_hip_optim_update, kws_amd/optim.py): the fp64 oracles
 the GPU tests compare against, held to torch.optim in fp64; torch's own fp32 step inside the derived bounds on the GPU
 tests' operands; the entry point's argument checks without a launch; construction, limits and checkpoints to and from
-torch.optim on CPU tensors; configure_optimizer; and the static scans of the new kernel source."""
+torch.optim on CPU tensors; configure_optimizer; and that the radix select exists once (the static scans of the kernel
+source, which all eight rules share, are tests/test_update_cpu.py's)."""
 import copy
 import ctypes as C
 import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -18,7 +17,6 @@ from tests import optim_cases as OC
 from tests import support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "kws_amd", "csrc", "kernels_optim.hip")
 NULL, ONE = None, 256                                   # (a fake non-NULL pointer: nothing is launched)
 OK, NULLP, SHAPE, UNSUP = 0, 1, 2, 7
 FUSED = {"RMSprop": optim.FusedRMSprop, "Adagrad": optim.FusedAdagrad, "Adadelta": optim.FusedAdadelta,
@@ -392,48 +390,12 @@ def test_train_step_takes_the_new_classes_and_still_names_what_it_needs():
     assert TrainSchedule(opt, 64, 8, 3, seed=1).optimizer is opt                   # (the isinstance test lets every fused class in)
 
 
-# ---- static scans of the new kernel source ---------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def optim_asm(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("asm") / "kernels_optim.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                    "-o", out, SRC], check=True, cwd=os.path.dirname(SRC), capture_output=True)
-    return out
-
-
-def test_war_scan_clean(optim_asm):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "war_scan.py"), optim_asm],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "UNBOUNDED" not in r.stdout and "NOT SCANNED" not in r.stdout
-    assert r.stdout.strip().splitlines()[-1] == "total pairs: 0"
-
-
-@pytest.mark.parametrize("mode", ("--strict", "--narrow"))
-def test_no_lds_write_pending_at_a_branch_with_memory_instructions_behind_it(optim_asm, mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "lds_branch_vmem_scan.py"), optim_asm, mode],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.strip().splitlines()[-1] == "sites in loops: 0", r.stdout[-2000:]
-
-
-def test_the_kernels_use_no_scratch_and_one_workgroup_of_1024():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import resource_usage
-    finally:
-        sys.path.pop(0)
-    rows = resource_usage.usage(SRC)
-    assert len(rows) == 6 and all("optim_update_k" in r["pretty"] for r in rows)          # one kernel per rule
-    for r in rows:
-        assert r["scratch"] == 0 and r["lds"] <= 2048 and r["vgpr"] <= 64, r               # (1024 threads: 16 waves, 128 VGPRs at most)
-
-
+# ---- the static scans of kernels_update.hip, all eight rules, are tests/test_update_cpu.py's -------------------------
 def test_the_radix_select_exists_once():
-    """kernels_update.hip and kernels_optim.hip share the threshold phase through iht_select.h; neither has a copy"""
+    """kernels_update.hip holds the one radix select, and the one kernel template calls it once"""
     csrc = os.path.join(ROOT, "kws_amd", "csrc")
     holders = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")) and "atomicAdd(&hist[" in open(os.path.join(csrc, f)).read()]
-    assert holders == ["iht_select.h"]
-    for f in ("kernels_update.hip", "kernels_optim.hip"):
-        text = open(os.path.join(csrc, f)).read()
-        assert '#include "iht_select.h"' in text and "iht_threshold(" in text
+    assert holders == ["kernels_update.hip"]
+    text = open(os.path.join(csrc, "kernels_update.hip")).read()
+    assert text.count("atomicAdd(&hist[") == 1 and text.count("__global__") == 1
+    assert text.count("iht_threshold(") == 2                                   # the definition and the kernel's one call

@@ -1,8 +1,8 @@
 """CPU-side checks of the fused optimizer step (fastgrnn_hip_train_update, kws_amd/optim.py): the fp64 oracles the GPU
 tests compare against, held to torch.optim in fp64; the threshold rule against numpy's percentile on typed-out cases;
 iht_phase against the trainer's branch; the entry point's argument checks without a launch (as tests/test_abi_cpu.py
-does for the others); optimizer construction and checkpoints on CPU tensors; and the static scans of the new kernel
-source (the existing scanner tests list their sources by name)."""
+does for the others); optimizer construction and checkpoints on CPU tensors; and the static scans of the kernel source,
+kernels_update.hip, over the kernels of all eight rules (the other scanner tests list their sources by name)."""
 import copy
 import ctypes as C
 import os
@@ -341,7 +341,7 @@ def test_state_dict_round_trip_with_torch_sgd_and_the_masks():
     assert int(fresh.step_t) == 0                                          # no buffer yet: the next step is the first
 
 
-# ---- static scans of the new kernel source ---------------------------------------------------------------------------
+# ---- static scans of the kernel source, all eight rules --------------------------------------------------------------
 @pytest.fixture(scope="module")
 def update_asm(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("asm") / "kernels_update.s")
@@ -373,8 +373,9 @@ def test_the_kernel_uses_no_scratch_and_one_workgroup_of_1024():
     finally:
         sys.path.pop(0)
     rows = resource_usage.usage(SRC)
-    assert [r["pretty"] for r in rows] == ["train_update_k"]
-    assert rows[0]["scratch"] == 0 and rows[0]["lds"] <= 2048 and rows[0]["vgpr"] <= 64   # (1024 threads: 16 waves, 128 VGPRs at most)
+    assert sorted(r["pretty"] for r in rows) == ["void update_k<%d>" % a for a in range(8)]   # one kernel per rule
+    for r in rows:
+        assert r["scratch"] == 0 and r["lds"] <= 2048 and r["vgpr"] <= 64, r               # (1024 threads: 16 waves, 128 VGPRs at most)
 
 
 # ---- the segment table and the one-group limit, on CPU tensors (no launch) -------------------------------------------
