@@ -792,6 +792,64 @@ typedef struct fastgrnn_schedule_desc {
 int fastgrnn_hip_train_schedule(const fastgrnn_schedule_desc *d, const int64_t *step, int32_t *index, float *lr,
                                 int32_t *iht_mode, int64_t *where, void *stream);
 
+/* train_schedule_rolling, rolling_exchange -- the reference's rolling mode (options.rolling, trainClassifier.py:174-221,
+ * model.py:135-156), the only one in which a batch does not start from the zero state: each layer's final states are
+ * scattered into a "hidden bag" of M = B bag_count rows at shuffled positions, the next batch starts from bag rows
+ * 0 .. B-1, and the early epochs are cut short and start from cleared bags.  Position, shuffle and bag exchange are
+ * functions of the step count and the seed, so a rolling run too is so many replays of one captured graph.
+ * Both calls: one small launch on `stream`, no allocation, no workspace, no host decision on device data: capturable.
+ * d, r and the three pointer arrays are HOST data; step[1] is train_schedule's device scalar, s = max(step[0], 0).
+ * Constants, all integers:  ticks_full = N / (B world)  (drop_last),
+ *   max_roll = min(ticks_full, max_rolling_length + 2, num_epochs + 2),   n_short = max(0, max_roll - 2).
+ * Position.  Epoch e < n_short is a SHORT epoch of e + 2 iterations (the reference's rolling_length = e + 3, trained
+ * for i_batch = 0 .. e + 1 and left at the `break`); it starts at iteration e (e + 3) / 2.  The epochs after them have
+ * ticks_full iterations each, so a run has  n_short (n_short + 3) / 2 + (num_epochs - n_short) ticks_full  iterations
+ * (the reference's total_iterations wherever ticks_full >= 2; at ticks_full == 1 its count disagrees with its own
+ * loop, and both calls refuse that).  Iterations past the run's end continue in the full-epoch pattern.
+ *   fresh(s): the first iteration of every short epoch and of epoch n_short (s = 0 where there is no short epoch):
+ *             the batch starts from the zero state and nothing is scattered;
+ *   zero(s):  the first iteration of every short epoch: the bags are cleared (the reference's init_hidden_bag).
+ * train_schedule_rolling is train_schedule at that position -- index[b] = perm_epoch((i_batch world + rank) B + b), so
+ * a short epoch uses the first e + 2 batches of its order; the IHT rule on (epoch, i_batch); the learning rate at
+ * it = s + lr_lead from the descriptor's constants (the caller derives them from the reference's fractional
+ * ticks = total_iterations / num_epochs) -- with  where[4] = epoch, i_batch, slot, fresh | zero << 1.  Of r it reads
+ * max_rolling_length and bag_count alone.
+ * rolling_exchange, per layer l < layers (model.py:145-156 in one launch for all layers):
+ *   state[l]:[B,H_l] fp32  the previous iteration's final states (read)
+ *   bag[l]:[M,H_l] fp32    the hidden bag
+ *   h0[l]:[B,H_l] fp32     the states this iteration starts from (written; must not overlap state[l] or bag[l])
+ *   zero(s):   bag[l] becomes +0.0 everywhere;
+ *   fresh(s):  h0[l] becomes +0.0 everywhere and the bag is not touched otherwise (on the first iteration of epoch
+ *              n_short it keeps what the last short epoch left, as in the reference);
+ *   otherwise  bag[l][pi_s(j)] = state[l][j] for j < B, then h0[l][r] = bag[l][r] for r < B, reading the bag AFTER the
+ *              scatter.  Computed without any ordering inside the launch: h0[l][r] = state[l][pi_s^-1(r)] where
+ *              pi_s^-1(r) < B, else the old bag[l][r], which nothing writes in that case.  Rows are copied bit for bit.
+ * pi_s, the same for all layers (the reference draws one np.random.shuffle per iteration), is train_schedule's keyed
+ * permutation over 0 .. M-1: k = the smallest even integer >= 2 with 2^k >= M, four Feistel rounds per pass with
+ *   P(R, r) = word 0 of Philox4x32-10 with the key (seed_lo, seed_hi) and the counter (R, s_lo, s_hi, 0xC0000000 | r),
+ * cycle-walked while the result is >= M.  The two top bits of the last counter word keep these counters apart from
+ * augment_draw's (last word 0, 1) and the epoch order's (0x80000000 | r).  The inverse pass runs the rounds r = 3 .. 0
+ * as (L, R) <- (R ^ (P(L, r) & mask), L) and cycle-walks the same way.
+ * The exchange depends on (d, r, step[0], state, bag) alone: it recomputes the position and does not read `where`, so
+ * there is no ordering contract with the schedule call.  Rows move 16 bytes per lane where H_l mod 4 == 0 and the
+ * layer's three pointers are 16-byte aligned, one dword per lane otherwise.
+ * Errors, all before any launch: FASTGRNN_ERR_NULL_POINTER (d, r, step and every output of train_schedule; the three
+ * arrays and their first `layers` entries), train_schedule's refusals of d, FASTGRNN_ERR_BAD_SHAPE (ticks_full < 2;
+ * max_rolling_length < 0; bag_count < 1; B bag_count > 2^31 - 1; for rolling_exchange also layers outside 1 .. 3 or
+ * H[l] < 1 for an l < layers).  No value of step[0] moves a write outside index[0 .. B), bag[l] or h0[l]. */
+typedef struct fastgrnn_rolling_desc {
+  int32_t max_rolling_length;         /* >= 0; options.max_rolling_length */
+  int32_t bag_count;                  /* >= 1; rows of a bag = B * bag_count; the reference's 100 */
+  int32_t layers, reserved;           /* 1 .. 3 */
+  int32_t H[4];                       /* H[l] >= 1 for l < layers */
+} fastgrnn_rolling_desc;
+
+int fastgrnn_hip_train_schedule_rolling(const fastgrnn_schedule_desc *d, const fastgrnn_rolling_desc *r,
+                                        const int64_t *step, int32_t *index, float *lr, int32_t *iht_mode,
+                                        int64_t *where, void *stream);
+int fastgrnn_hip_rolling_exchange(const fastgrnn_schedule_desc *d, const fastgrnn_rolling_desc *r, const int64_t *step,
+                                  const float *const state[3], float *const bag[3], float *const h0[3], void *stream);
+
 /* frame_gemm -- the one genuinely dense, non-recurrent contraction of a layer, as a call of its own:
  *   P[rows, H] = X[rows, F] . W^T,   W:[H,F]  (rows = T*B; the reference computes it per step, `mm` at .cu:356).
  * forward_unroll runs exactly this launch in front of the scan for layers whose input is wider than 32 (the scan of a

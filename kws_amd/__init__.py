@@ -22,10 +22,13 @@ from . import augment  # noqa: F401
 from .augment import AudioAugment, pack_augment, unpack_augment  # noqa: F401
 from . import schedule  # noqa: F401
 from .schedule import TrainSchedule  # noqa: F401
+from . import rolling  # noqa: F401
+from .rolling import RollingBags  # noqa: F401
 
 __all__ = ["fastgrnn_cuda", "utils", "head", "FastGRNNCUDA", "FastGRNNCUDACell", "FastGRNNFunction",
            "FastGRNNUnrollFunction", "KeywordHead", "keyword_loss", "head_predict", "vote_windows", "RNNClassifierModel", "GraphedStep",
            "FastGRNNBatchNorm", "FastGRNNBatchNormCell", "fold_batchnorm", "FastGRNNBatchNormCUDA",
            "optim", "FusedAdam", "FusedSGD", "FusedRMSprop", "FusedAdagrad", "FusedAdadelta", "FusedAdamax", "FusedASGD",
            "FusedRprop", "configure_optimizer", "iht_phase", "features", "MFCCFrontend", "mfcc_features",
-           "augment", "AudioAugment", "pack_augment", "unpack_augment", "schedule", "TrainSchedule"]
+           "augment", "AudioAugment", "pack_augment", "unpack_augment", "schedule", "TrainSchedule",
+           "rolling", "RollingBags"]

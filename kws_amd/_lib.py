@@ -55,6 +55,7 @@ EXPORTS = (
     "fastgrnn_hip_train_update", "fastgrnn_hip_optim_update",
     "fastgrnn_hip_mfcc_tables_bytes", "fastgrnn_hip_mfcc_init_tables", "fastgrnn_hip_mfcc_workspace_bytes",
     "fastgrnn_hip_mfcc", "fastgrnn_hip_mfcc_augment", "fastgrnn_hip_augment_draw", "fastgrnn_hip_train_schedule",
+    "fastgrnn_hip_train_schedule_rolling", "fastgrnn_hip_rolling_exchange",
 )
 
 
@@ -188,6 +189,15 @@ class ScheduleDesc(C.Structure):
                 ("t_max", C.c_double), ("step_size", C.c_int64), ("reset", C.c_int64)]
 
 
+ROLLING_MAX_LAYERS = 3          # layers of one fastgrnn_hip_rolling_exchange launch
+
+
+class RollingDesc(C.Structure):
+    """fastgrnn_rolling_desc."""
+    _fields_ = [("max_rolling_length", C.c_int32), ("bag_count", C.c_int32), ("layers", C.c_int32),
+                ("reserved", C.c_int32), ("H", C.c_int32 * 4)]
+
+
 class FastGRNNLibraryError(RuntimeError):
     pass
 
@@ -261,6 +271,11 @@ def load():
                                               C.c_int32, vp, vp, vp]
     lib.fastgrnn_hip_train_schedule.restype = i32
     lib.fastgrnn_hip_train_schedule.argtypes = [C.POINTER(ScheduleDesc), vp, vp, vp, vp, vp, vp]
+    RD, P3 = C.POINTER(RollingDesc), C.POINTER(vp * 3)
+    lib.fastgrnn_hip_train_schedule_rolling.restype = i32
+    lib.fastgrnn_hip_train_schedule_rolling.argtypes = [C.POINTER(ScheduleDesc), RD, vp, vp, vp, vp, vp, vp]
+    lib.fastgrnn_hip_rolling_exchange.restype = i32
+    lib.fastgrnn_hip_rolling_exchange.argtypes = [C.POINTER(ScheduleDesc), RD, vp, P3, P3, P3, vp]
     lib.fastgrnn_hip_frame_gemm.restype = i32
     lib.fastgrnn_hip_frame_gemm.argtypes = [sz, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp]
     BP, BG = C.POINTER(BnParams), C.POINTER(BnGrads)

@@ -622,8 +622,8 @@ int fastgrnn_hip_augment_draw(int32_t B, uint64_t seed, const int64_t* step, con
                           reinterpret_cast<hipStream_t>(stream));
 }
 
-int fastgrnn_hip_train_schedule(const fastgrnn_schedule_desc* d, const int64_t* step, int32_t* index, float* lr,
-                                int32_t* iht_mode, int64_t* where, void* stream) {
+// the refusals of a schedule descriptor, in train_schedule's order
+static int check_schedule_desc(const fastgrnn_schedule_desc* d) {
   if (!d) return FASTGRNN_ERR_NULL_POINTER;
   if (d->B < 1 || d->world < 1 || d->rank < 0 || d->rank >= d->world) return FASTGRNN_ERR_BAD_SHAPE;
   const int64_t per_tick = (int64_t)d->B * d->world;
@@ -641,8 +641,47 @@ int fastgrnn_hip_train_schedule(const fastgrnn_schedule_desc* d, const int64_t* 
   if (kind == FASTGRNN_LR_COSINE && !(d->t_max > 0.0 && d->t_max < inf)) return FASTGRNN_ERR_BAD_SHAPE;
   if (kind == FASTGRNN_LR_STEP && d->step_size < 1) return FASTGRNN_ERR_BAD_SHAPE;
   if (kind == FASTGRNN_LR_EXPONENTIAL_RESETTING && d->reset < 0) return FASTGRNN_ERR_BAD_SHAPE;
+  return FASTGRNN_OK;
+}
+
+int fastgrnn_hip_train_schedule(const fastgrnn_schedule_desc* d, const int64_t* step, int32_t* index, float* lr,
+                                int32_t* iht_mode, int64_t* where, void* stream) {
+  const int st = check_schedule_desc(d);
+  if (st) return st;
   if (!step || !index || !lr || !where || (d->sparsify && !iht_mode)) return FASTGRNN_ERR_NULL_POINTER;
   return train_schedule_run(*d, step, index, lr, iht_mode, where, reinterpret_cast<hipStream_t>(stream));
+}
+
+// what both rolling calls refuse of the pair of descriptors (d has passed check_schedule_desc)
+static int check_rolling_desc(const fastgrnn_schedule_desc* d, const fastgrnn_rolling_desc* r) {
+  if (d->N / (d->B * d->world) < 2) return FASTGRNN_ERR_BAD_SHAPE;
+  if (r->max_rolling_length < 0 || r->bag_count < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  if ((int64_t)d->B * r->bag_count > INT32_MAX) return FASTGRNN_ERR_BAD_SHAPE;
+  return FASTGRNN_OK;
+}
+
+int fastgrnn_hip_train_schedule_rolling(const fastgrnn_schedule_desc* d, const fastgrnn_rolling_desc* r,
+                                        const int64_t* step, int32_t* index, float* lr, int32_t* iht_mode,
+                                        int64_t* where, void* stream) {
+  if (!d || !r) return FASTGRNN_ERR_NULL_POINTER;
+  int st = check_schedule_desc(d);
+  if (st || (st = check_rolling_desc(d, r))) return st;
+  if (!step || !index || !lr || !where || (d->sparsify && !iht_mode)) return FASTGRNN_ERR_NULL_POINTER;
+  return train_schedule_rolling_run(*d, *r, step, index, lr, iht_mode, where, reinterpret_cast<hipStream_t>(stream));
+}
+
+int fastgrnn_hip_rolling_exchange(const fastgrnn_schedule_desc* d, const fastgrnn_rolling_desc* r, const int64_t* step,
+                                  const float* const state[3], float* const bag[3], float* const h0[3], void* stream) {
+  if (!d || !r) return FASTGRNN_ERR_NULL_POINTER;
+  int st = check_schedule_desc(d);
+  if (st || (st = check_rolling_desc(d, r))) return st;
+  if (r->layers < 1 || r->layers > 3) return FASTGRNN_ERR_BAD_SHAPE;
+  for (int l = 0; l < r->layers; ++l)
+    if (r->H[l] < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  if (!step || !state || !bag || !h0) return FASTGRNN_ERR_NULL_POINTER;
+  for (int l = 0; l < r->layers; ++l)
+    if (!state[l] || !bag[l] || !h0[l]) return FASTGRNN_ERR_NULL_POINTER;
+  return rolling_exchange_run(*d, *r, step, state, bag, h0, reinterpret_cast<hipStream_t>(stream));
 }
 
 int fastgrnn_hip_frame_gemm(size_t rows, int32_t H, int32_t F, const void* x, const void* w, void* p, int32_t dtype,

@@ -220,6 +220,13 @@ int augment_draw_run(int B, uint64_t seed, const int64_t* step, const int32_t* i
 int train_schedule_run(const fastgrnn_schedule_desc& d, const int64_t* step, int32_t* index, float* lr,
                        int32_t* iht_mode, int64_t* where, hipStream_t s);
 
+// the same with the rolling position, and the hidden-state bags' scatter and gather of an iteration
+// (kernels_rolling.hip); arguments already checked
+int train_schedule_rolling_run(const fastgrnn_schedule_desc& d, const fastgrnn_rolling_desc& r, const int64_t* step,
+                               int32_t* index, float* lr, int32_t* iht_mode, int64_t* where, hipStream_t s);
+int rolling_exchange_run(const fastgrnn_schedule_desc& d, const fastgrnn_rolling_desc& r, const int64_t* step,
+                         const float* const state[3], float* const bag[3], float* const h0[3], hipStream_t s);
+
 // training-mode BatchNorm cell (kernels_bn_train.hip): FASTGRNN_FLAG_BN_TRAIN
 bool bn_train_supported(const fastgrnn_desc& d);
 size_t bn_train_forward_ws(const fastgrnn_desc& d);

@@ -26,12 +26,14 @@ Same constructor arguments, attribute and parameter names as the reference (``rn
 * ``predict`` / ``batch_accuracy`` / ``evaluate`` (trainClassifier.py:54-65, 286-316) and ``detect_stream``
   (inferencetry.py:213-227) end in the fused inference head and the majority vote: scores, argmax, the count of
   correct rows and the detector's vote stay on the device;
-* ``fit_audio`` is the non-rolling loop of ``fit`` (trainClassifier.py:196-272) from an audio bank on the device, its
-  batches, learning rates and IHT phases computed there by a ``kws_amd.TrainSchedule``: one captured graph replayed for
-  the whole run, ``evaluate()`` after every epoch;
+* ``fit_audio`` is the loop of ``fit`` (trainClassifier.py:174-272) from an audio bank on the device, its batches,
+  learning rates and IHT phases computed there by a ``kws_amd.TrainSchedule``: one captured graph replayed for the
+  whole run, ``evaluate()`` after every epoch.  On a schedule built with ``rolling=True`` it is the reference's rolling
+  mode: short early epochs, and every batch starting from the hidden-state bags of ``kws_amd.RollingBags``
+  (model.py:135-156) instead of the zero state, the bag exchange captured with the rest.  Unlike the reference's,
+  ``evaluate()`` there does not leak its last batch's states into the next training batch;
 * the shadow ``rnn_list_`` / ``tracking`` ONNX-export path (model.py:72-84,187-195) is not built (export is
-  disabled in the reference, trainClassifier.py:42-52), nor are the rolling hidden-state bags
-  (model.py:135-148: data-loader bookkeeping, no arithmetic).
+  disabled in the reference, trainClassifier.py:42-52).
 """
 from __future__ import annotations
 
@@ -46,6 +48,7 @@ from .fastgrnn_cuda import check_starts_range
 from .graph import GraphedStep
 from .optim import _FusedOptimizer
 from .rnn import FastGRNNCUDA, gather_windows
+from .rolling import RollingBags
 
 _RNN_CLASSES = {"FastGRNNCUDA": FastGRNNCUDA, "FastGRNNBatchNorm": FastGRNNBatchNorm,     # model.py:12-15
                 "FastGRNNBatchNormCUDA": FastGRNNBatchNormCUDA}
@@ -362,18 +365,30 @@ class RNNClassifierModel(nn.Module):
         return loss.detach()
 
     def fit_audio(self, audio, lengths, labels, frontend, augment, optimizer, schedule, *, graph=True, bucket=None,
-                  validation=None):
-        """A whole training run (trainClassifier.py:196-272, the non-rolling loop) from the audio bank, driven by a
-        ``kws_amd.TrainSchedule``: ``schedule.num_epochs * schedule.ticks`` iterations of
+                  validation=None, bags=None):
+        """A whole training run (trainClassifier.py:174-272) from the audio bank, driven by a
+        ``kws_amd.TrainSchedule``: ``schedule.total_iterations`` (``num_epochs * ticks``) iterations of
 
             init_hidden()                    (trainClassifier.py:221: every batch starts from the zero state)
             schedule.advance()               index, lr_t, iht_t and the position from optimizer.step_t
             loss = train_step_audio(audio, lengths, labels, schedule.index, frontend, augment, optimizer, iht=None)
             schedule.record(loss)
 
+        On a schedule built with ``rolling=True`` (the reference's ``--rolling``) the body is instead
+
+            schedule.advance()               ... at the rolling position: short early epochs
+            bags.exchange()                  the last states into the hidden bags, this batch's start out of them
+            loss = train_step_audio(...)
+            bags.commit()                    this batch's last states, for the next exchange
+            schedule.record(loss)
+
+        with ``bags`` a ``kws_amd.RollingBags(self, schedule)``, built here unless the caller passes its own to look
+        into.  The carried states live in ``bags``, so the validation passes between epochs cannot disturb them.
+
         With ``graph=True`` that body is captured once in a ``GraphedStep`` and replayed; nothing is written from the
         host between replays, and the run starts from the state the model and the optimizer were in (the capture's
-        warm-up iterations are undone: parameters, buffers, optimizer state, support masks, ``step_t`` and the logs).
+        warm-up iterations are undone: parameters, buffers, optimizer state, support masks, ``step_t``, the logs and the
+        bags).
         ``graph=False`` runs the same body eagerly and gives the same bits.  The run begins at ``optimizer.step_t`` as it
         stands (0 for a fresh optimizer; one sync, before the first iteration) and ends at iteration
         ``num_epochs * ticks`` counted from 0.
@@ -390,33 +405,47 @@ class RNNClassifierModel(nn.Module):
             raise ValueError("fit_audio(): the schedule shuffles %d clips, the bank holds %d with %d labels"
                              % (schedule.num_clips, audio.shape[0], labels.shape[0]))
 
+        rolling = bool(getattr(schedule, "rolling", False))
+        if rolling and bags is None:
+            bags = RollingBags(self, schedule)
+        if bags is not None and (not rolling or bags.schedule is not schedule or bags.model is not self):
+            raise ValueError("fit_audio(): bags go with a rolling schedule, and must have been built for this model and "
+                             "this schedule")
+
         def body():
-            self.init_hidden()
-            schedule.advance()
+            if rolling:
+                schedule.advance()
+                bags.exchange()
+            else:
+                self.init_hidden()
+                schedule.advance()
             loss = self.train_step_audio(audio, lengths, labels, schedule.index, frontend, augment, optimizer, iht=None,
                                          bucket=bucket)
+            if rolling:
+                bags.commit()
             schedule.record(loss)
             return loss
 
         self.train()
         step = body
         if graph:
-            keep = self._run_state(optimizer, schedule)
+            keep = self._run_state(optimizer, schedule, bags)
             step = GraphedStep(body)
             self._restore_run_state(optimizer, keep)
         first = int(optimizer.step_t.item())
         accuracies = [None] * schedule.num_epochs
         for s in range(first, schedule.total_iterations):
             step()
-            if (s + 1) % schedule.ticks == 0 and validation is not None:
-                accuracies[s // schedule.ticks] = self.evaluate(validation() if callable(validation) else validation)
+            if validation is not None and schedule.epoch_end(s):
+                accuracies[schedule.position(s)[0]] = self.evaluate(validation() if callable(validation) else validation)
                 self.train()
         return schedule.epoch_log(accuracies)
 
-    def _run_state(self, optimizer, schedule):
+    def _run_state(self, optimizer, schedule, bags=None):
         """Copies of everything an iteration writes, keyed by the tensor that holds it: parameters, buffers, optimizer
-        state, support masks, the step count and the schedule's logs."""
+        state, support masks, the step count, the schedule's logs and a rolling run's bags and states."""
         held = list(self.parameters()) + list(self.buffers()) + [optimizer.step_t, schedule.loss_log, schedule.lr_log]
+        held += bags.tensors() if bags is not None else []
         held += [mask for _, mask in optimizer._iht.values()]
         for p in optimizer.param_groups[0]["params"]:
             held += [t for t in optimizer.state.get(p, {}).values() if isinstance(t, torch.Tensor)]

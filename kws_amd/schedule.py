@@ -13,6 +13,11 @@ three are functions of the iteration number, which lives in the fused optimizer'
 * ``RNNClassifierModel.fit_audio`` captures ``advance`` + ``train_step_audio`` + ``record`` once and replays the graph
   ``num_epochs * ticks`` times: no host-to-device write, no loader thread, reproducible from ``seed``.
 
+* ``TrainSchedule(..., rolling=True)`` is the reference's ``--rolling`` mode (trainClassifier.py:174-221): ``n_short``
+  short epochs of 2, 3, .. iterations in front of the full ones, ``advance()`` through
+  ``fastgrnn_hip_train_schedule_rolling`` with ``where = (epoch, i_batch, slot, fresh | zero << 1)``; the hidden-state bags
+  that go with it are ``kws_amd.RollingBags``.
+
 Two deliberate differences from the reference: an epoch has ``ticks = num_clips // (batch_size * world)`` whole batches
 (drop_last; the reference's loader ends an epoch on a short batch, which a captured graph's fixed shapes cannot take, and
 its ``ticks`` is the fraction ``num_clips / batch_size``), and ``"CosineAnnealingLR"`` is torch's CLOSED form (the
@@ -62,10 +67,20 @@ class TrainSchedule:
     rank builds its own schedule and gets a disjoint share of every epoch.  ``log_len``: entries of ``loss_log`` /
     ``lr_log`` (default: one per iteration); iterations past it share the last entry.
 
+    ``rolling=True``: the reference's rolling mode.  ``full_ticks = num_clips // (batch_size * world)`` must be at least 2
+    (at 1 the reference's iteration count disagrees with its own loop), ``max_roll = min(full_ticks, max_rolling_length
+    + 2, num_epochs + 2)``, ``n_short = max(0, max_roll - 2)``: epoch ``e < n_short`` trains ``e + 2`` batches of its
+    order from cleared bags, the others ``full_ticks``, ``total_iterations = n_short (n_short + 3) / 2 + (num_epochs -
+    n_short) full_ticks``.  ``ticks`` is then the reference's fraction ``total_iterations / num_epochs``
+    (trainClassifier.py:187), from which ``configure_lr``'s constants are derived as there (``t_max =
+    total_iterations / steps``).  ``bag_count``: rows of a hidden bag per batch row (the reference's 100).  Without
+    ``rolling`` the two keywords are not read, ``full_ticks == ticks`` and ``n_short == 0``.
+
     Construction needs no GPU (the tensors live on the optimizer's device); ``advance`` does."""
 
     def __init__(self, optimizer, num_clips, batch_size, num_epochs, *, seed, lr_scheduler=None, lr_min=None, lr_peaks=1,
-                 gamma=1.0, lr_step_size=1, lr_lead=1, sparsify=False, trim_level=15, world=1, rank=0, log_len=None):
+                 gamma=1.0, lr_step_size=1, lr_lead=1, sparsify=False, trim_level=15, world=1, rank=0, log_len=None,
+                 rolling=False, max_rolling_length=100, bag_count=100):
         if not isinstance(optimizer, _FusedOptimizer):
             raise TypeError("TrainSchedule needs a kws_amd.FusedAdam or kws_amd.FusedSGD, or another fused optimizer of "
                             "kws_amd.optim (got %s): it writes the "
@@ -105,11 +120,31 @@ class TrainSchedule:
         lr_peaks = lr_peaks if isinstance(lr_peaks, int) else float(lr_peaks)      # (the reference's --lr_peaks is a float)
         _positive(lr_peaks, "lr_peaks")
         # configure_lr's constants, in its order of operations
-        self.ticks = self.num_clips // (self.batch_size * self.world)
-        self.total_iterations = self.num_epochs * self.ticks
+        self.full_ticks = self.num_clips // (self.batch_size * self.world)
+        self.rolling = bool(rolling)
         self.steps = lr_peaks * 2 + 1
+        if self.rolling:
+            self.max_rolling_length = _whole(max_rolling_length, "max_rolling_length", 0)
+            self.bag_count = _whole(bag_count, "bag_count", 1)
+            if self.max_rolling_length > 2 ** 31 - 1 or self.batch_size * self.bag_count > 2 ** 31 - 1:
+                raise ValueError("max_rolling_length and batch_size * bag_count must fit int32")
+            if self.full_ticks < 2:
+                raise ValueError("rolling training needs at least 2 batches per epoch and rank (num_clips = %d gives %d "
+                                 "of %d clips on each of %d ranks)"
+                                 % (self.num_clips, self.full_ticks, self.batch_size, self.world))
+            max_roll = min(self.full_ticks, self.max_rolling_length + 2, self.num_epochs + 2)
+            self.n_short = max(0, max_roll - 2)
+            self.total_iterations = (self.n_short * (self.n_short + 3) // 2
+                                     + (self.num_epochs - self.n_short) * self.full_ticks)
+            self.ticks = self.total_iterations / self.num_epochs             # trainClassifier.py:187: a float
+            self.t_max = self.total_iterations / self.steps                  # trainClassifier.py:114
+            self.rolling_desc = _lib.RollingDesc(self.max_rolling_length, self.bag_count, 0, 0)
+        else:
+            self.n_short = 0
+            self.ticks = self.full_ticks
+            self.total_iterations = self.num_epochs * self.ticks
+            self.t_max = self.ticks * self.num_epochs / self.steps
         self.stepsize = self.num_epochs / self.steps * self.ticks
-        self.t_max = self.ticks * self.num_epochs / self.steps
         self.reset = int(self.num_epochs * self.ticks / 3)
         self.log_len = self.total_iterations if log_len is None else _whole(log_len, "log_len", 1)
         dev = optimizer._device
@@ -132,11 +167,34 @@ class TrainSchedule:
         if self.device.type != "cuda":
             raise RuntimeError("TrainSchedule.advance() runs on the GPU (the optimizer is on %s); kws_amd has no CPU "
                                "fallback" % (self.device,))
+        outs = (opt.step_t.data_ptr(), self.index.data_ptr(), opt.lr_t.data_ptr(), opt.iht_t.data_ptr(),
+                self.where.data_ptr())
         with torch.cuda.device(self.device):
-            _call(_lib.load().fastgrnn_hip_train_schedule, "fastgrnn train_schedule", "train_schedule", self.device, None,
-                  C.byref(self.desc), opt.step_t.data_ptr(), self.index.data_ptr(), opt.lr_t.data_ptr(),
-                  opt.iht_t.data_ptr(), self.where.data_ptr())
+            if self.rolling:
+                _call(_lib.load().fastgrnn_hip_train_schedule_rolling, "fastgrnn train_schedule_rolling",
+                      "train_schedule_rolling", self.device, None, C.byref(self.desc), C.byref(self.rolling_desc), *outs)
+            else:
+                _call(_lib.load().fastgrnn_hip_train_schedule, "fastgrnn train_schedule", "train_schedule", self.device,
+                      None, C.byref(self.desc), *outs)
         return self.index
+
+    def epoch_start(self, epoch):
+        """The 0-based iteration at which ``epoch`` begins."""
+        short = min(epoch, self.n_short)
+        return short * (short + 3) // 2 + (epoch - short) * self.full_ticks
+
+    def position(self, s):
+        """``(epoch, i_batch)`` of the 0-based iteration ``s`` on the host: what ``advance`` writes to ``where[:2]``."""
+        s = max(int(s), 0)
+        first_full = self.epoch_start(self.n_short)
+        if s >= first_full:
+            return self.n_short + (s - first_full) // self.full_ticks, (s - first_full) % self.full_ticks
+        epoch = (math.isqrt(9 + 8 * s) - 3) // 2                     # the largest e with e (e + 3) / 2 <= s
+        return epoch, s - self.epoch_start(epoch)
+
+    def epoch_end(self, s):
+        """Whether the 0-based iteration ``s`` (a negative one counts as 0) is the last of its epoch."""
+        return self.position(max(int(s), 0) + 1)[1] == 0
 
     def record(self, loss):
         """``loss_log[slot] = loss`` and ``lr_log[slot] = lr_t`` for the ``slot`` that ``advance`` wrote: two indexed
@@ -151,7 +209,7 @@ class TrainSchedule:
         loss, lr = self.loss_log.cpu().tolist(), self.lr_log.cpu().tolist()
         out = []
         for epoch in range(self.num_epochs):
-            slot = min((epoch + 1) * self.ticks - 1, self.log_len - 1)
+            slot = min(self.epoch_start(epoch + 1) - 1, self.log_len - 1)
             out.append({"epoch": epoch, "loss": loss[slot], "accuracy": accuracies[epoch] if accuracies else None,
                         "learning_rate": lr[slot]})
         return out

@@ -21,6 +21,15 @@ out of time, and prints one JSON line with the rows that finished.  Rows, each a
                                 host scheduler cost at the least (the shuffle itself is prepared outside the timing)
              eager              the body of fit_audio(graph=False)
   advance  TrainSchedule.advance() alone.
+  rolling  the fit row's model on a TrainSchedule(rolling=True) (bag_count 100, every iteration in a full epoch: the
+           states go into the bags and come out of them), beside the non-rolling iteration in the same process:
+             device_fed_graph   the fit row's, for reference
+             rolling_graph      the captured rolling body of fit_audio: advance, RollingBags.exchange, the step, commit,
+                                record
+             host_exchange      the same graph without exchange(), and before every replay the exchange in torch index
+                                ops issued by the host, per layer bag[idx] = state and h0 = bag[:B] (the shuffles are
+                                prepared on the device outside the timing)
+             exchange           RollingBags.exchange() alone (timed by itself, with its own --run)
 
 Fails without a GPU."""
 import argparse
@@ -31,7 +40,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-ROWS = ("fit", "advance")
+ROWS = ("fit", "advance", "rolling")
 L, NUM_EPOCHS, TRIM = 16000, 300000, 2
 
 
@@ -71,7 +80,7 @@ def measure(routes, a):
     return dict({k: stats(v) for k, v in ts.items()}, run=run)
 
 
-def trainer(a, dev):
+def trainer(a, dev, **rolling):
     import torch
     from kws_amd import FusedAdam, RNNClassifierModel, TrainSchedule
     torch.manual_seed(0)
@@ -80,20 +89,17 @@ def trainer(a, dev):
     o = FusedAdam(m.parameters(), lr=1e-3, capturable=True)
     o.register_iht(m)
     s = TrainSchedule(o, 2 * a.batch, a.batch, NUM_EPOCHS, seed=1, lr_scheduler="StepLR", gamma=0.999, lr_step_size=1000,
-                      sparsify=True, trim_level=TRIM, log_len=4096)
+                      sparsify=True, trim_level=TRIM, log_len=4096, **rolling)
     return m, o, s
 
 
 def middle_third(o, s):
-    o.step_t.fill_((NUM_EPOCHS // 3 + 1) * s.ticks)
+    o.step_t.fill_((NUM_EPOCHS // 3 + 1) * s.full_ticks)
 
 
-def row_fit(a):
+def bank(a, dev, g):
     import torch
-    from kws_amd import AudioAugment, GraphedStep, MFCCFrontend, iht_phase
-    from kws_amd.optim import IHT_MODES
-    dev = torch.device("cuda:0")
-    g = torch.Generator().manual_seed(0)
+    from kws_amd import AudioAugment, MFCCFrontend
     n = 2 * a.batch
     pcm = (0.1 * torch.randn(n, L, generator=g) * 32767.0).round().clamp(-32768, 32767).to(torch.int16).to(dev)
     lengths = torch.full((n,), L, dtype=torch.int32, device=dev)
@@ -102,6 +108,17 @@ def row_fit(a):
     noises = [(0.1 * torch.randn(k, generator=g) * 32767.0).round().to(torch.int16) for k in (16000, 48000, 7000)]
     aug = AudioAugment(p_augment=0.25, max_shift=1600, gain=(0.8, 1.2), noise_gain=0.1, seed=1, noises=noises, device=dev)
     fe(pcm[:2])
+    return pcm, lengths, labels, fe, aug
+
+
+def row_fit(a):
+    import torch
+    from kws_amd import GraphedStep, iht_phase
+    from kws_amd.optim import IHT_MODES
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    n = 2 * a.batch
+    pcm, lengths, labels, fe, aug = bank(a, dev, g)
 
     def body(m, o, s, fed):
         m.init_hidden()
@@ -136,6 +153,64 @@ def row_fit(a):
     res["device_over_host_fed"] = round(res["device_fed_graph"]["median_us"] / res["host_fed_graph"]["median_us"], 4)
     res["device_over_eager"] = round(res["device_fed_graph"]["median_us"] / res["eager"]["median_us"], 4)
     res["model"] = "32->256->128, FusedAdam + IHT, int16 bank of %d clips, 16 MFCC + delta, T=99" % n
+    return res
+
+
+def row_rolling(a):
+    import torch
+    from kws_amd import GraphedStep, RollingBags
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    pcm, lengths, labels, fe, aug = bank(a, dev, g)
+    B, bag_count, shuffles = a.batch, 100, 64
+
+    def plain(m, o, s):
+        m.init_hidden()
+        s.advance()
+        loss = m.train_step_audio(pcm, lengths, labels, s.index, fe, aug, o, iht=None)
+        s.record(loss)
+        return loss
+
+    def rolling(m, o, s, bags, exchange):
+        s.advance()
+        if exchange:
+            bags.exchange()
+        else:
+            m.hidden_states = list(bags.h0)
+        loss = m.train_step_audio(pcm, lengths, labels, s.index, fe, aug, o, iht=None)
+        bags.commit()
+        s.record(loss)
+        return loss
+
+    m0, o0, s0 = trainer(a, dev)
+    (m1, o1, s1), (m2, o2, s2) = (trainer(a, dev, rolling=True, bag_count=bag_count) for _ in range(2))
+    bags1, bags2 = RollingBags(m1, s1), RollingBags(m2, s2)
+    plain_graph = GraphedStep(lambda: plain(m0, o0, s0))
+    rolling_graph = GraphedStep(lambda: rolling(m1, o1, s1, bags1, True))
+    host_graph = GraphedStep(lambda: rolling(m2, o2, s2, bags2, False))
+    idx = torch.stack([torch.randperm(B * bag_count, generator=g)[:B] for _ in range(shuffles)]).to(dev)
+    host = {"s": 0}
+
+    def host_exchange():
+        rows = idx[host["s"] % shuffles]
+        for state, bag, h0 in zip(bags2.state, bags2.bag, bags2.h0):
+            bag[rows] = state
+            h0.copy_(bag[:B])
+        host_graph()
+        host["s"] += 1
+
+    for o, s in ((o0, s0), (o1, s1), (o2, s2)):
+        middle_third(o, s)
+    res = measure({"device_fed_graph": plain_graph, "rolling_graph": rolling_graph, "host_exchange": host_exchange}, a)
+    res["exchange"] = measure({"exchange": bags1.exchange}, a)
+    torch.cuda.synchronize()
+    res["where_at_the_end"] = s1.where.tolist()
+    res["finite"] = bool(torch.isfinite(s1.loss_log).all() and torch.isfinite(s2.loss_log).all())
+    res["carried"] = bool(all(h.any() for h in bags1.h0))
+    res["rolling_over_plain"] = round(res["rolling_graph"]["median_us"] / res["device_fed_graph"]["median_us"], 4)
+    res["rolling_over_host_exchange"] = round(res["rolling_graph"]["median_us"] / res["host_exchange"]["median_us"], 4)
+    res["bytes_moved_per_exchange"] = 2 * B * sum(m1.hidden_units_list) * 4
+    res["model"] = "32->256->128, FusedAdam + IHT, bags of %d rows per layer" % (B * bag_count)
     return res
 
 
