@@ -42,6 +42,8 @@ template <typename T> __device__ __forceinline__ T dact(T y, int nl) {
 }
 
 static inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+// bytes per element of the sequences x / hs / grad_hs / d_x
+static inline size_t seq_esz(const fastgrnn_desc& d) { return d.dtype == FASTGRNN_BF16_IO ? 2 : 4; }
 
 // the status of a launcher that has enqueued its kernels
 static inline int launch_status() { return hipGetLastError() == hipSuccess ? FASTGRNN_OK : FASTGRNN_ERR_LAUNCH; }

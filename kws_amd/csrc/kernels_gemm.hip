@@ -681,35 +681,21 @@ __global__ __launch_bounds__(256) ONE_WAVE_PER_SIMD void tn_gemm_w4(size_t R, in
         pc[(size_t)((mq * 4 + a) * 16 + 4 * g + r) * N + (nh * NH + c) * 16 + (l & 15)] = acc[a][c][r];
 }
 
-// C[(mblk*128 + m) * ldc + n] = sum over row chunks of part[chunk][mblk][m][n], fixed order
+// C[(mblk*128 + m) * ldc + n] = sum over row chunks of part[chunk][mblk][m][n], fixed order (scan_common.h; 4 loads per
+// round)
 __global__ __launch_bounds__(1024) void tn_big_reduce(int nchunk, int nblk, int N, const float* __restrict__ part,
                                                       float* __restrict__ C, int ldc) {
-  __shared__ float sm[16][64];
-  const int o = threadIdx.x & 63, pid = threadIdx.x >> 6;
-  const int per_blk = 128 * N, total = nblk * per_blk;
-  const int idx = blockIdx.x * 64 + o;
-  float a = 0.f;
-  if (idx < total) {
-    const int blk = idx / per_blk, e = idx - blk * per_blk;
-    for (int c0 = pid; c0 < nchunk; c0 += 64) {
-      float v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = c0 + 16 * j;
-        v[j] = c < nchunk ? part[((size_t)c * nblk + blk) * per_blk + e] : 0.f;
-      }
-      a += (v[0] + v[1]) + (v[2] + v[3]);
-    }
-  }
-  sm[pid][o] = a;
-  __syncthreads();
-  if (pid == 0 && idx < total) {
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) t += sm[j][o];
-    const int blk = idx / per_blk, e = idx - blk * per_blk, m = e / N, n = e - m * N;
-    C[(size_t)(blk * 128 + m) * ldc + n] = t;
-  }
+  const int per_blk = 128 * N;
+  fixed_order_sum<4>(
+      nchunk, nblk * per_blk,
+      [&](int c, int idx) {
+        const int blk = idx / per_blk, e = idx - blk * per_blk;
+        return part + ((size_t)c * nblk + blk) * per_blk + e;
+      },
+      [&](int idx, float t) {
+        const int blk = idx / per_blk, e = idx - blk * per_blk, m = e / N, n = e - m * N;
+        C[(size_t)(blk * 128 + m) * ldc + n] = t;
+      });
 }
 
 // gather_windows_rows: the copy of x that the training calls over windows run the existing scans on -- every

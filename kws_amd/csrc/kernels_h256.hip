@@ -768,34 +768,19 @@ __global__ __launch_bounds__(512) void bwd_scan_h256(
   }
 }
 
-// bias / zeta / nu gradients: fixed-order sum over workgroups
+// bias / zeta / nu gradients: fixed-order sum over workgroups (scan_common.h; 4 loads per round)
 __global__ __launch_bounds__(1024) void reduce_h256_small(int nwg, const float* __restrict__ part,
                                                           const float* __restrict__ zeta, const float* __restrict__ nu,
                                                           float* __restrict__ d_bz, float* __restrict__ d_bh,
                                                           float* __restrict__ d_zeta, float* __restrict__ d_nu) {
-  __shared__ float sm[16][64];
-  const int o = threadIdx.x & 63, pid = threadIdx.x >> 6;
-  const int idx = blockIdx.x * 64 + o;               // 0 .. 2*256+1
-  float a = 0.f;
-  if (idx < 2 * H2 + 2) {
-    for (int wg0 = pid; wg0 < nwg; wg0 += 64) {
-      float v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { const int wg = wg0 + 16 * j; v[j] = wg < nwg ? part[(size_t)wg * SLAB2 + idx] : 0.f; }
-      a += (v[0] + v[1]) + (v[2] + v[3]);
-    }
-  }
-  sm[pid][o] = a;
-  __syncthreads();
-  if (pid == 0 && idx < 2 * H2 + 2) {
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) t += sm[j][o];
-    if (idx < H2) d_bz[idx] = t;
-    else if (idx < 2 * H2) d_bh[idx - H2] = t;
-    else if (idx == 2 * H2) { const float sz = 1.0f / (1.0f + expf(-zeta[0])); d_zeta[0] = t * sz * (1.0f - sz); }   // .cu:116,544
-    else { const float sn = 1.0f / (1.0f + expf(-nu[0])); d_nu[0] = t * sn * (1.0f - sn); }                          // .cu:117,545
-  }
+  fixed_order_sum<4>(
+      nwg, 2 * H2 + 2, [&](int wg, int idx) { return part + (size_t)wg * SLAB2 + idx; },
+      [&](int idx, float t) {
+        if (idx < H2) d_bz[idx] = t;
+        else if (idx < 2 * H2) d_bh[idx - H2] = t;
+        else if (idx == 2 * H2) d_zeta[0] = raw_scalar_grad(t, zeta);
+        else d_nu[0] = raw_scalar_grad(t, nu);
+      });
 }
 
 // The forward's workspace: one word per workgroup, "my rows of h0 are outside the fp16 path's range" (fwd_scan_h256

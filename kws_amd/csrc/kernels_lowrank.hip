@@ -683,9 +683,9 @@ __global__ __launch_bounds__(512) void bwd_scan_lowrank_split(
   }
 }
 
-// All gradients of the low-rank backward that are sums over workgroups: fixed-order sum of the slabs, written in the
-// operator's shapes (d_u2 [H,ru], d_w2 [H,rw], d_u1 [ru,H], d_w1 [rw,F]; rank padding dropped), raw-zeta / raw-nu
-// chain rule applied (.cu:116-117,544-545).
+// All gradients of the low-rank backward that are sums over workgroups: fixed-order sum of the slabs (scan_common.h; 4
+// loads per round), written in the operator's shapes (d_u2 [H,ru], d_w2 [H,rw], d_u1 [ru,H], d_w1 [rw,F]; rank padding
+// dropped), raw-zeta / raw-nu chain rule applied (.cu:116-117,544-545).
 __global__ __launch_bounds__(1024) void reduce_lowrank_slabs(int nwg, const float* __restrict__ part,
                                                              const float* __restrict__ zeta, const float* __restrict__ nu,
                                                              int ru, int rw, float* __restrict__ d_u1,
@@ -693,38 +693,23 @@ __global__ __launch_bounds__(1024) void reduce_lowrank_slabs(int nwg, const floa
                                                              float* __restrict__ d_w2, float* __restrict__ d_bz,
                                                              float* __restrict__ d_bh, float* __restrict__ d_zeta,
                                                              float* __restrict__ d_nu) {
-  __shared__ float sm[16][64];
-  const int o = threadIdx.x & 63, pid = threadIdx.x >> 6;
-  const int idx = blockIdx.x * 64 + o;               // 0 .. SL_ZN + 1
-  float a = 0.f;
-  if (idx < SL_ZN + 2) {
-    for (int wg0 = pid; wg0 < nwg; wg0 += 64) {
-      float v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { const int wg = wg0 + 16 * j; v[j] = wg < nwg ? part[(size_t)wg * SLAB_LR + idx] : 0.f; }
-      a += (v[0] + v[1]) + (v[2] + v[3]);
-    }
-  }
-  sm[pid][o] = a;
-  __syncthreads();
-  if (pid == 0 && idx < SL_ZN + 2) {
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) t += sm[j][o];
-    if (idx < SL_U1T) {
-      const int n = idx >> 5, j = idx & 31;
-      if (j < 16) { if (j < ru) d_u2[n * ru + j] = t; } else if (j - 16 < rw) d_w2[n * rw + (j - 16)] = t;
-    } else if (idx < SL_W1T) {
-      const int k = idx - SL_U1T, n = k >> 4, j = k & 15;
-      if (j < ru) d_u1[j * 256 + n] = t;
-    } else if (idx < SL_BZ) {
-      const int k = idx - SL_W1T, f = k >> 4, j = k & 15;
-      if (j < rw) d_w1[j * 32 + f] = t;
-    } else if (idx < SL_BZ + 256) d_bz[idx - SL_BZ] = t;
-    else if (idx < SL_ZN) d_bh[idx - SL_BZ - 256] = t;
-    else if (idx == SL_ZN) { const float sz = 1.0f / (1.0f + expf(-zeta[0])); d_zeta[0] = t * sz * (1.0f - sz); }   // .cu:116,544
-    else { const float sn = 1.0f / (1.0f + expf(-nu[0])); d_nu[0] = t * sn * (1.0f - sn); }                         // .cu:117,545
-  }
+  fixed_order_sum<4>(
+      nwg, SL_ZN + 2, [&](int wg, int idx) { return part + (size_t)wg * SLAB_LR + idx; },
+      [&](int idx, float t) {
+        if (idx < SL_U1T) {
+          const int n = idx >> 5, j = idx & 31;
+          if (j < 16) { if (j < ru) d_u2[n * ru + j] = t; } else if (j - 16 < rw) d_w2[n * rw + (j - 16)] = t;
+        } else if (idx < SL_W1T) {
+          const int k = idx - SL_U1T, n = k >> 4, j = k & 15;
+          if (j < ru) d_u1[j * 256 + n] = t;
+        } else if (idx < SL_BZ) {
+          const int k = idx - SL_W1T, f = k >> 4, j = k & 15;
+          if (j < rw) d_w1[j * 32 + f] = t;
+        } else if (idx < SL_BZ + 256) d_bz[idx - SL_BZ] = t;
+        else if (idx < SL_ZN) d_bh[idx - SL_BZ - 256] = t;
+        else if (idx == SL_ZN) d_zeta[0] = raw_scalar_grad(t, zeta);
+        else d_nu[0] = raw_scalar_grad(t, nu);
+      });
 }
 
 // x[B][F][T] (FASTGRNN_FLAG_X_BFT, the data loader's layout, trainClassifier.py:204) <-> time-major [T][B][F].  The
@@ -780,8 +765,6 @@ __global__ __launch_bounds__(256) void bft_transpose(int B, int T, const E* __re
   }
 }
 
-static inline size_t esz(const fastgrnn_desc& d) { return d.dtype == FASTGRNN_BF16_IO ? 2 : 4; }
-
 // the backward's slabs of partial sums (one per workgroup) and the d_x rows of the lanes beyond a ragged batch; under
 // FASTGRNN_FLAG_X_BFT the time-major copy of x and, for the backward, of d_x
 struct LowrankWs { float *part, *sink; char *xt, *dxt; size_t bytes; };
@@ -791,8 +774,8 @@ LowrankWs lowrank_ws(const fastgrnn_desc& d, bool backward, void* base) {
   LowrankWs L{};
   if (backward) { L.part = c.take<float>(nwg * SLAB_LR); L.sink = c.take<float>(16 * 32); }
   if (d.flags & FASTGRNN_FLAG_X_BFT) {
-    L.xt = c.take<char>(TB * 32 * esz(d));
-    if (backward) L.dxt = c.take<char>(TB * 32 * esz(d));
+    L.xt = c.take<char>(TB * 32 * seq_esz(d));
+    if (backward) L.dxt = c.take<char>(TB * 32 * seq_esz(d));
   }
   L.bytes = c.off;
   return L;
@@ -813,7 +796,7 @@ int lowrank_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
   int st;
   if (bft) {
     xs = L.xt; dxs = L.dxt;
-    if ((st = bft_transpose_run(d.B, d.T, 32, esz(d), x, L.xt, true, s))) return st;
+    if ((st = bft_transpose_run(d.B, d.T, 32, seq_esz(d), x, L.xt, true, s))) return st;
   }
   auto go = [&](auto kern) __attribute__((always_inline)) {
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), 0, s, d.T, d.B, rsT, rsB, xsT, xsB, d.w_rank, d.u_rank,
@@ -833,7 +816,7 @@ int lowrank_backward(const fastgrnn_desc& d, const fastgrnn_params& p, const voi
         else return false;
       }); }); });
   if (!launched) return FASTGRNN_ERR_UNSUPPORTED;
-  if (bft && (st = bft_transpose_run(d.B, d.T, 32, esz(d), L.dxt, g.d_x, false, s))) return st;
+  if (bft && (st = bft_transpose_run(d.B, d.T, 32, seq_esz(d), L.dxt, g.d_x, false, s))) return st;
   // every parameter gradient is a sum over the workgroups' slabs (.cu:544-555, factorised)
   hipLaunchKernelGGL(reduce_lowrank_slabs, dim3((SL_ZN + 2 + 63) / 64), dim3(1024), 0, s, nwg, L.part, (const float*)p.zeta,
                      (const float*)p.nu, d.u_rank, d.w_rank, (float*)g.d_u1, (float*)g.d_u2, (float*)g.d_w1,
@@ -858,7 +841,7 @@ int lowrank_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void
   const int xsT = bft ? d.B : rsT, xsB = bft ? 1 : rsB;
   if (bft) {
     const LowrankWs L = lowrank_ws(d, false, ws);
-    const int st = bft_transpose_run(d.B, d.T, 32, esz(d), x, L.xt, true, s);
+    const int st = bft_transpose_run(d.B, d.T, 32, seq_esz(d), x, L.xt, true, s);
     if (st) return st;
     x = L.xt;
   }

@@ -21,34 +21,11 @@
 // once; a tiny second kernel reduces the per-workgroup slabs deterministically.
 //
 // Reference semantics: forward .cu:42-60 + .cu:367-413; backward .cu:91-119 + .cu:473-545.
-#include "common.h"
+#include "scan_common.h"
 #include "variant_pick.h"
 
 namespace fastgrnn {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float LOG2E = 1.4426950408889634f;
-
-// v_exp_f32 / v_rcp_f32 are 1-ulp; absolute error of these forms is < 3e-7 (the parity
-// bar is 1e-5).  Saturation is exact: exp2(+inf) -> rcp(inf) = 0.
-__device__ __forceinline__ float fsigmoid(float a) {
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-LOG2E * a));
-}
-__device__ __forceinline__ float ftanh(float a) {
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((2.0f * LOG2E) * a));
-}
-template <int GATE> __device__ __forceinline__ float gate_act(float a) {
-  if (GATE == FASTGRNN_NL_SIGMOID) return fsigmoid(a);
-  if (GATE == FASTGRNN_NL_RELU) return a > 0.0f ? a : 0.0f;
-  return ftanh(a);
-}
-template <int GATE> __device__ __forceinline__ float gate_dact(float y) {
-  if (GATE == FASTGRNN_NL_SIGMOID) return (1.0f - y) * y;
-  if (GATE == FASTGRNN_NL_RELU) return y > 0.0f ? 1.0f : 0.0f;
-  return 1.0f - y * y;
-}
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -73,18 +50,6 @@ __device__ unsigned long long g_diag[4][16];
 #else
 #define SCHED_PIN(idx) if (!(DIAG & 32)) { __builtin_amdgcn_sched_barrier(0); }
 #endif
-
-// Workgroup barrier for LDS hand-offs only.  __syncthreads() would also emit
-// s_waitcnt vmcnt(0) and drain every in-flight global load/store each step; here only this
-// wave's LDS traffic is waited for, so prefetches and stores stay in flight across steps.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // ------------------------------------------------------------------------------------------
 // forward
@@ -655,45 +620,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 // Deterministic reduction of the per-workgroup slabs in ONE launch: out[i] = sum_wg part[wg][i]
-// for the whole gradient vector dU | dW | d_bz | d_bh | d_zeta | d_nu (.cu:542-545).  A block
-// owns 64 consecutive outputs; its 1024 threads split the workgroups 16 ways (all loads of a
-// thread in flight at once), then 64 threads add the 16 partials in a fixed order.
+// for the whole gradient vector dU | dW | d_bz | d_bh | d_zeta | d_nu (.cu:542-545), by
+// fixed_order_sum (scan_common.h) with 8 loads per round.
 __global__ __launch_bounds__(1024) void reduce_slabs(int nwg, int H, int F, int stride,
                                                      const float* __restrict__ part,
                                                      const float* __restrict__ zeta, const float* __restrict__ nu,
                                                      float* __restrict__ d_u, float* __restrict__ d_w,
                                                      float* __restrict__ d_bz, float* __restrict__ d_bh,
                                                      float* __restrict__ d_zeta, float* __restrict__ d_nu) {
-  __shared__ float sm[16][64];
-  const int o = threadIdx.x & 63, part_id = threadIdx.x >> 6;
-  const int idx = blockIdx.x * 64 + o;
-  const int ntot = H * H + H * F + 2 * H + 2;
-  float a = 0.f;
-  if (idx < ntot) {
-    float v[8];
-    for (int wg0 = part_id; wg0 < nwg; wg0 += 16 * 8) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int wg = wg0 + 16 * j;
-        v[j] = wg < nwg ? part[(size_t)wg * stride + idx] : 0.f;
-      }
-      a += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-  }
-  sm[part_id][o] = a;
-  __syncthreads();
-  if (part_id == 0 && idx < ntot) {
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) t += sm[j][o];
-    const int oW = H * H, oBz = oW + H * F, oBh = oBz + H, oZ = oBh + H;
-    if (idx < oW) d_u[idx] = t;
-    else if (idx < oBz) d_w[idx - oW] = t;
-    else if (idx < oBh) d_bz[idx - oBz] = t;
-    else if (idx < oZ) d_bh[idx - oBh] = t;
-    else if (idx == oZ) { const float sz = 1.0f / (1.0f + expf(-zeta[0])); d_zeta[0] = t * sz * (1.0f - sz); }   // .cu:116,544
-    else { const float sn = 1.0f / (1.0f + expf(-nu[0])); d_nu[0] = t * sn * (1.0f - sn); }                      // .cu:117,545
-  }
+  const int oW = H * H, oBz = oW + H * F, oBh = oBz + H, oZ = oBh + H;
+  fixed_order_sum<8>(
+      nwg, oZ + 2, [&](int wg, int idx) { return part + (size_t)wg * stride + idx; },
+      [&](int idx, float t) {
+        if (idx < oW) d_u[idx] = t;
+        else if (idx < oBz) d_w[idx - oW] = t;
+        else if (idx < oBh) d_bz[idx - oBz] = t;
+        else if (idx < oZ) d_bh[idx - oBh] = t;
+        else if (idx == oZ) d_zeta[0] = raw_scalar_grad(t, zeta);
+        else d_nu[0] = raw_scalar_grad(t, nu);
+      });
 }
 
 size_t bwd_ws_bytes(const fastgrnn_desc& d) {

@@ -1148,43 +1148,24 @@ __global__ __launch_bounds__(768) void bwd_scan_split_w12(BWD_SCAN_ARGS) {
 #undef BWD_SCAN_ARGS
 #undef BWD_SCAN_PASS
 
-// Deterministic reduction of the per-workgroup slabs in ONE launch (same scheme as kernels_mfma.hip).
+// Deterministic reduction of the per-workgroup slabs in ONE launch (fixed_order_sum, scan_common.h; 8 loads per round).
 __global__ __launch_bounds__(1024) void reduce_slabs_split(int nwg, const float* __restrict__ part,
                                                            const float* __restrict__ zeta, const float* __restrict__ nu,
                                                            float* __restrict__ d_u, float* __restrict__ d_w,
                                                            float* __restrict__ d_bz, float* __restrict__ d_bh,
                                                            float* __restrict__ d_zeta, float* __restrict__ d_nu) {
   constexpr int H = 128, F = 32;
-  __shared__ float sm[16][64];
-  const int o = threadIdx.x & 63, part_id = threadIdx.x >> 6;
-  const int idx = blockIdx.x * 64 + o;
-  const int ntot = H * H + H * F + 2 * H + 2;
-  float a = 0.f;
-  if (idx < ntot) {
-    float v[8];
-    for (int wg0 = part_id; wg0 < nwg; wg0 += 16 * 8) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int wg = wg0 + 16 * j;
-        v[j] = wg < nwg ? part[(size_t)wg * SLAB + idx] : 0.f;
-      }
-      a += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-  }
-  sm[part_id][o] = a;
-  __syncthreads();
-  if (part_id == 0 && idx < ntot) {
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) t += sm[j][o];
-    const int oW = H * H, oBz = oW + H * F, oBh = oBz + H, oZ = oBh + H;
-    if (idx < oW) d_u[idx] = t;
-    else if (idx < oBz) { if (d_w) d_w[idx - oW] = t; }     // (NOX scans leave dW to the TN GEMM: d_w == nullptr)
-    else if (idx < oBh) d_bz[idx - oBz] = t;
-    else if (idx < oZ) d_bh[idx - oBh] = t;
-    else if (idx == oZ) { const float sz = 1.0f / (1.0f + expf(-zeta[0])); d_zeta[0] = t * sz * (1.0f - sz); }   // .cu:116,544
-    else { const float sn = 1.0f / (1.0f + expf(-nu[0])); d_nu[0] = t * sn * (1.0f - sn); }                      // .cu:117,545
-  }
+  constexpr int oW = H * H, oBz = oW + H * F, oBh = oBz + H, oZ = oBh + H;
+  fixed_order_sum<8>(
+      nwg, oZ + 2, [&](int wg, int idx) { return part + (size_t)wg * SLAB + idx; },
+      [&](int idx, float t) {
+        if (idx < oW) d_u[idx] = t;
+        else if (idx < oBz) { if (d_w) d_w[idx - oW] = t; }     // (NOX scans leave dW to the TN GEMM: d_w == nullptr)
+        else if (idx < oBh) d_bz[idx - oBz] = t;
+        else if (idx < oZ) d_bh[idx - oBh] = t;
+        else if (idx == oZ) d_zeta[0] = raw_scalar_grad(t, zeta);
+        else d_nu[0] = raw_scalar_grad(t, nu);
+      });
 }
 
 // Dense H = 128 layers whose input is not 32 wide (F = 64 / 128 / 256: the reference's second layer, model.py:196-203):

@@ -80,8 +80,6 @@ struct Copies {
   }
 };
 
-size_t seq_esz(const fastgrnn_desc& d) { return d.dtype == FASTGRNN_BF16_IO ? 2 : 4; }
-
 // Offsets into the caller's workspace (NONE: not needed, the caller's tensor is used as it is).  The padded
 // parameters first, then the padded inputs, the padded outputs and the inner path-2 workspace.
 struct ZWs {

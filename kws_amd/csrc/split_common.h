@@ -2,9 +2,10 @@
 // row / TN GEMMs around them): exact three-bf16-plane and two-fp16-plane splits, the six- / three-term MFMA
 // products, the hardware-transposed LDS fragment read.  gfx950 only.  See kernels_split.hip's header for why
 // fp32 operands go to the bf16 matrix pipe this way, and DESIGN.md 4.0 for the operand rule the helpers'
-// users are written to.
+// users are written to.  What does not depend on the plane split -- the activations, ld4 / st4, lds_barrier, the
+// fixed-order reduction -- is in scan_common.h, which path 1 (kernels_mfma.hip) includes too.
 #pragma once
-#include "common.h"
+#include "scan_common.h"
 #include "variant_pick.h"
 #include <type_traits>
 #include <utility>
@@ -12,40 +13,11 @@
 namespace fastgrnn {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ float fsigmoid(float a) {
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-LOG2E * a));
-}
-__device__ __forceinline__ float ftanh(float a) {
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((2.0f * LOG2E) * a));
-}
-// gate nonlinearities: the reference's GPU table {sigmoid, relu, tanh} (rnn.py:478) and, on the 8-wave dense
-// kernels, the CPU cell's quantised family (rnn.py:53-60); derivatives through the output as in
-// common.h / .cu:27-40
-template <int GATE> __device__ __forceinline__ float gate_act(float a) {
-  if (GATE == FASTGRNN_NL_SIGMOID) return fsigmoid(a);
-  if (GATE == FASTGRNN_NL_RELU) return a > 0.0f ? a : 0.0f;
-  if (GATE == FASTGRNN_NL_QUANT_TANH) return fminf(fmaxf(a, -1.0f), 1.0f);
-  if (GATE == FASTGRNN_NL_QUANT_SIGM) return fminf(fmaxf((a + 1.0f) * 0.5f, 0.0f), 1.0f);
-  if (GATE == FASTGRNN_NL_QUANT_SIGM4) return fminf(fmaxf((a + 2.0f) * 0.25f, 0.0f), 1.0f);
-  return ftanh(a);
-}
-template <int GATE> __device__ __forceinline__ float gate_dact(float y) {
-  if (GATE == FASTGRNN_NL_SIGMOID) return (1.0f - y) * y;
-  if (GATE == FASTGRNN_NL_RELU) return y > 0.0f ? 1.0f : 0.0f;
-  if (GATE == FASTGRNN_NL_QUANT_TANH) return (y < 1.0f && y > -1.0f) ? 1.0f : 0.0f;
-  if (GATE == FASTGRNN_NL_QUANT_SIGM) return (y < 1.0f && y > 0.0f) ? 0.5f : 0.0f;
-  if (GATE == FASTGRNN_NL_QUANT_SIGM4) return (y < 1.0f && y > 0.0f) ? 0.25f : 0.0f;
-  return 1.0f - y * y;
-}
 
 // compensated (Kahan) running sum: s += y with the rounding error of every addition carried in c.  Used for the two
 // scalar gradients d_zeta / d_nu, whose per-lane sums run over T * (elements per lane) terms of either sign: a plain
@@ -56,9 +28,6 @@ __device__ __forceinline__ void kahan_add(float& s, float& c, float y) {
   c = (t - s) - yy;
   s = t;
 }
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // bf16 I/O variant (FASTGRNN_BF16_IO): sequences x / hs / grad_hs / d_x are bf16 in HBM, everything else fp32
 __device__ __forceinline__ float bf16_to_f32(unsigned short v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
@@ -78,12 +47,6 @@ __device__ __forceinline__ void st4_bf16(void* p, const f32x4 v) {
   const unsigned lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_cv{v[0], v[1]}, bf16x2_cv));
   const unsigned hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_cv{v[2], v[3]}, bf16x2_cv));
   *reinterpret_cast<uint2*>(p) = uint2{lo, hi};
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 #ifdef FASTGRNN_DIAG_STAMPS

@@ -14,10 +14,11 @@ the workspace the library asks for) and asserts that the table below covers ever
               spw = ceil(nstages / want); nch = ceil(nstages / spw); the grid is ceil(nch / 8) * 8 * nblk workgroups,
               those with chunk >= nch leave; tn_big_reduce sums nch partials (with bf16 sequences and 0 < shiftB < R the
               partials of the body over R - shiftB rows, then those of the fp32 head over shiftB rows).
-  slab sums   kws_amd/csrc/kernels_split.hip, reduce_slabs_split (and kernels_mfma.hip, reduce_slabs): 16 lanes x 8
-              workgroups per round, the outer loop strides by 128 workgroups;
-              kws_amd/csrc/kernels_h256.hip, reduce_h256_small (and kernels_lowrank.hip, reduce_lowrank_slabs): 16 x 4,
-              stride 64.  The last round is guarded workgroup by workgroup.
+  slab sums   kws_amd/csrc/scan_common.h, fixed_order_sum<W>: 16 groups x W partials per round, the outer loop strides
+              by 16 * W; the last round is guarded partial by partial.  Its callers fix W: 8 (stride 128 workgroups) in
+              reduce_slabs_split (kernels_split.hip) and reduce_slabs (kernels_mfma.hip), 4 (stride 64) in
+              reduce_h256_small (kernels_h256.hip), reduce_lowrank_slabs (kernels_lowrank.hip) and, over chunks,
+              tn_big_reduce (kernels_gemm.hip).
 """
 from collections import namedtuple
 

@@ -234,15 +234,28 @@ def test_bf16_sequences_where_head_and_body_are_cut_differently(H, F, T, B):
 
 # ---- (e) the slab reductions without a GEMM behind them ------------------------------------------------------------
 NWG_SHAPES = [(3, 2033), (4, 2049), EVEN_B, (2, 4097)]        # 128 workgroups (the last ragged), 129, 130, 257
+NWG_SHAPES_16 = [(3, 2048), (4, 2064), EVEN_B, (2, 4112)]     # the same counts in whole tiles (path 1's H=128 backward)
+# (id, H, rank, kernel path, shapes): path 2 under FLAG_SAVE_PREACT; path 1 as tests/test_hip_parity.py runs it
+SLAB_ROUTES = [("dense128", 128, None, 2, NWG_SHAPES), ("lowrank256", 256, 16, 2, NWG_SHAPES),
+               ("f32mfma128", 128, None, 1, NWG_SHAPES_16), ("f32mfma64", 64, None, 1, NWG_SHAPES)]
+SLAB_CASES = [pytest.param(H, rank, path, T, B, id="%s-%d-%d" % (name, T, B))
+              for name, H, rank, path, shapes in SLAB_ROUTES for T, B in shapes]
 
 
-@pytest.mark.parametrize("T,B", NWG_SHAPES, ids=_ids)
-@pytest.mark.parametrize("H,rank", [(128, None), (256, 16)], ids=["dense128", "lowrank256"])
-def test_slab_reductions_across_their_rounds(H, rank, T, B):
-    """dense H=128 / F=32 (reduce_slabs_split: rounds of 128 workgroups) and low-rank H=256 (reduce_lowrank_slabs:
-    rounds of 64): every weight gradient is a slab sum here.  Bounds of tests/test_hip_fullsize.py."""
+@pytest.mark.parametrize("H,rank,path,T,B", SLAB_CASES)
+def test_slab_reductions_across_their_rounds(H, rank, path, T, B):
+    """Every weight gradient is a slab sum here, by the one fixed_order_sum of kws_amd/csrc/scan_common.h: dense
+    H=128 / F=32 (reduce_slabs_split, 8 loads per round: rounds of 128 workgroups), low-rank H=256
+    (reduce_lowrank_slabs, 4 loads: rounds of 64) and path 1's reduce_slabs (8 loads) at H=128 and H=64 under
+    FLAG_FORCE_F32_MFMA with the reference's saved pair; one, two and three rounds, the last one guarded.  Path 1's
+    H=128 backward takes whole tiles only (mfma_supported), so it gets the same workgroup counts with B % 16 == 0.
+    Bounds of tests/test_hip_fullsize.py; path 1's scalar sums are not compensated, so d_zeta / d_nu get
+    SCALAR_TERM_TOL as in section (b)."""
     F = 32
-    assert [PC.slab_rounds(-(-b // 16), 128)[0] for _, b in NWG_SHAPES] == [1, 2, 2, 3]
+    for shapes in (NWG_SHAPES, NWG_SHAPES_16):
+        assert [-(-b // 16) for _, b in shapes] == [128, 129, 130, 257]
+        assert [PC.slab_rounds(-(-b // 16), 128)[0] for _, b in shapes] == [1, 2, 2, 3]
+    assert all(b % 16 == 0 for _, b in NWG_SHAPES_16)
     rng = np.random.default_rng(600 + B + H)
     p = O.make_params(F, H, rank, rank, np.float32, seed=61, randomize_scalars=True)
     x = rng.standard_normal((T, B, F)).astype(np.float32)
@@ -250,16 +263,17 @@ def test_slab_reductions_across_their_rounds(H, rank, T, B):
     h0 = (0.5 * rng.standard_normal((B, H))).astype(np.float32)
     P = S.cell_tensors(p)
     xt, Gt, ht = S.to_dev(x), S.to_dev(G), S.to_dev(h0)
-    flags = _lib.FLAG_SAVE_PREACT
+    flags = _lib.FLAG_SAVE_PREACT if path == 2 else _lib.FLAG_FORCE_F32_MFMA
     r = rank or 0
-    assert fastgrnn_cuda.kernel_path(T, B, F, H, r, r, direction=0, flags=flags) == 2
-    assert fastgrnn_cuda.kernel_path(T, B, F, H, r, r, direction=1, flags=flags) == 2
-    outs, gr = S.fwd_bwd(xt, ht, Gt, P, "sigmoid", flags=flags, biases=True)
+    assert fastgrnn_cuda.kernel_path(T, B, F, H, r, r, direction=0, flags=flags) == path
+    assert fastgrnn_cuda.kernel_path(T, B, F, H, r, r, direction=1, flags=flags) == path
+    outs, gr = S.fwd_bwd(xt, ht, Gt, P, "sigmoid", flags=flags, biases=path == 2)
     torch.cuda.synchronize()
     hs_o, _, _, g_o = S.oracle64(x, G, p, h0)
     assert np.abs(outs[0].cpu().numpy() - hs_o).max() <= 1e-5
-    errs = S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=0.0, tag=(H, rank, T, B))
-    print("slabs H=%d rank=%s T=%d B=%d: %s" % (H, rank, T, B, {k: "%.1e" % v for k, v in errs.items()}))
+    errs = S.check_grads(gr, g_o, tol=2e-5, scalar_term_tol=0.0 if path == 2 else S.SCALAR_TERM_TOL,
+                         tag=(H, rank, path, T, B))
+    print("slabs H=%d rank=%s path=%d T=%d B=%d: %s" % (H, rank, path, T, B, {k: "%.1e" % v for k, v in errs.items()}))
 
 
 # ---- (f) the BatchNorm trainer -------------------------------------------------------------------------------------

@@ -52,13 +52,16 @@ int main(int argc, char** argv) {
   unsigned* flags; (void)hipMalloc(&flags, (size_t)(B / 16 + 1) * 4);
   float* ghs = dev_rand((size_t)T * B * H, 1.f);
   const int nwg = (B + 15) / 16;
+  const unsigned hsT = (unsigned)B * H, hsB = H, xsT = (unsigned)B * F, xsB = F;   // time-major element strides
   const char* fn[6] = {"top", "W batch", "state batches", "epilogue", "publish", "barrier"};
-  timeit("fwd_scan_h256 fp16 path, AUX=2", T, nwg, 512, fn, 6, fwd_scan_h256<0, 2, false, 1>, T, B, (const float*)x, (const float*)h0,
-         (const float*)w, (const float*)u, (const float*)bz, (const float*)bh, (const float*)zeta, (const float*)nu, hs, zs, cs, flags);
-  timeit("fwd_scan_h256 bf16 path, AUX=2", T, nwg, 512, fn, 6, fwd_scan_h256<0, 2, false, 0>, T, B, (const float*)x, (const float*)h0,
-         (const float*)w, (const float*)u, (const float*)bz, (const float*)bh, (const float*)zeta, (const float*)nu, hs, zs, cs, flags);
+  timeit("fwd_scan_h256 fp16 path, AUX=2", T, nwg, 512, fn, 6, fwd_scan_h256<0, 2, false, 1>, T, B, hsT, hsB, xsT, xsB, (const float*)x,
+         (const float*)h0, (const float*)w, (const float*)u, (const float*)bz, (const float*)bh, (const float*)zeta, (const float*)nu, hs,
+         zs, cs, flags, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
+  timeit("fwd_scan_h256 bf16 path, AUX=2", T, nwg, 512, fn, 6, fwd_scan_h256<0, 2, false, 0>, T, B, hsT, hsB, xsT, xsB, (const float*)x,
+         (const float*)h0, (const float*)w, (const float*)u, (const float*)bz, (const float*)bh, (const float*)zeta, (const float*)nu, hs,
+         zs, cs, flags, (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
   const char* bn[6] = {"chain (prev step) + glue", "EW + scale", "barrier A", "split + publish", "barrier B", "tail"};
-  timeit("bwd_scan_h256 PREACT", T, nwg, 512, bn, 6, bwd_scan_h256<0, true, false>, T, B, 0, (const float*)ghs, (const float*)hs,
+  timeit("bwd_scan_h256 PREACT", T, nwg, 512, bn, 6, bwd_scan_h256<0, true, false>, T, B, 0, hsT, hsB, (const float*)ghs, (const float*)hs,
          (const float*)zs, (const float*)cs, (const float*)h0, (const float*)u, (const float*)bz, (const float*)bh, (const float*)zeta,
          (const float*)nu, dh0, dpre, part);
   return 0;
