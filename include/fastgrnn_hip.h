@@ -326,7 +326,12 @@ size_t fastgrnn_hip_backward_workspace_bytes(const fastgrnn_desc *d);
 /* forward_unroll -- replaces fastgrnn_unroll_forward (fastgrnn_cuda.cpp:147-180 ->
  * .cu:320-415).  x:[T,B,F], h0:[B,H] -> hs:[T,B,H]; z_s,c_s:[T,B,H] are the
  * reference's z_s / h_prime_s outputs and may be NULL when the caller does not
- * need them (forward-only use). */
+ * need them (forward-only use).
+ * The generic scan (path 0) holds its state tiles in up to 160 KiB of LDS: (16 H + 8 F + 8 w_rank + 8 u_rank) elements
+ * in forward_unroll, (18 H + 8 u_rank + 512) in backward_unroll.  A direction that does not fit -- on no other path
+ * either -- has fastgrnn_hip_kernel_path -1 and workspace 0, and its call returns FASTGRNN_ERR_UNSUPPORTED before the
+ * workspace check and before anything is launched.  The backward's limit is the lower one: ask the plan for both
+ * directions before training at such a size. */
 int fastgrnn_hip_forward_unroll(const fastgrnn_desc *d, const fastgrnn_params *p,
                                 const void *x, const void *h0,
                                 void *hs, void *z_s, void *c_s,

@@ -100,6 +100,7 @@ int resolve(const fastgrnn_desc* d, route* r) {
   const bool bn_train = (u.flags & FASTGRNN_FLAG_BN_TRAIN) != 0;         // fastgrnn_hip_bn_train_*
   for (int dir = 0; dir < 2; ++dir) {
     r->path[dir] = (bn_train || (affine && dir)) ? -1 : pick_path(&u, dir);
+    if (r->path[dir] == 0 && !generic_lds_fits(u, dir)) r->path[dir] = -1;      // the floor itself has a limit: its LDS
     r->need[dir] = path_ws(u, r->path[dir], dir);
   }
   // d_x may be NULL (the input's gradient is not wanted) where it is a GEMM of its own behind the scan, and under
@@ -280,6 +281,7 @@ int fastgrnn_hip_forward_unroll(const fastgrnn_desc* dz, const fastgrnn_params* 
   if (!x || !h0 || !hs) return FASTGRNN_ERR_NULL_POINTER;
   if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // fastgrnn_hip_forward_unroll_affine
   if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return FASTGRNN_ERR_UNSUPPORTED;        // fastgrnn_hip_bn_train_forward
+  if (r.path[0] < 0) return FASTGRNN_ERR_UNSUPPORTED;                            // no scan holds d in its LDS
   if (((d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_HS_LAST)) ||
        d->dtype == FASTGRNN_BF16_IO) && r.path[0] != 2)
     return FASTGRNN_ERR_UNSUPPORTED;
@@ -304,6 +306,7 @@ int fastgrnn_hip_forward_unroll_affine(const fastgrnn_desc* dz, const fastgrnn_p
   if (!(d->flags & FASTGRNN_FLAG_PREACT_AFFINE) || d->dtype == FASTGRNN_BF16_IO || d->w_rank || d->u_rank ||
       (d->flags & (FASTGRNN_FLAG_SAVE_PREACT | FASTGRNN_FLAG_GRAD_LAST | FASTGRNN_FLAG_BN_TRAIN)))
     return FASTGRNN_ERR_UNSUPPORTED;
+  if (r.path[0] < 0) return FASTGRNN_ERR_UNSUPPORTED;                            // no scan holds d in its LDS
   // (FASTGRNN_FLAG_X_BFT: path 2 takes it on the wide shapes -- affine_supported -- and nothing else does)
   if ((d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_HS_LAST | FASTGRNN_FLAG_X_BFT)) && r.path[0] != 2) return FASTGRNN_ERR_UNSUPPORTED;
   if ((st = check_ws(workspace, workspace_bytes, r.need[0]))) return st;
@@ -415,6 +418,7 @@ int fastgrnn_hip_backward_unroll(const fastgrnn_desc* dz, const fastgrnn_params*
   }
   if (d->flags & FASTGRNN_FLAG_PREACT_AFFINE) return FASTGRNN_ERR_UNSUPPORTED;   // inference only
   if (d->flags & FASTGRNN_FLAG_BN_TRAIN) return FASTGRNN_ERR_UNSUPPORTED;        // fastgrnn_hip_bn_train_backward
+  if (r.path[1] < 0) return FASTGRNN_ERR_UNSUPPORTED;                            // no scan holds d in its LDS
   const bool preact = (d->flags & FASTGRNN_FLAG_SAVE_PREACT) != 0;
   if ((preact || (d->flags & (FASTGRNN_FLAG_BATCH_MAJOR | FASTGRNN_FLAG_X_BFT | FASTGRNN_FLAG_GRAD_LAST)) || d->dtype == FASTGRNN_BF16_IO) && r.path[1] != 2)
     return FASTGRNN_ERR_UNSUPPORTED;

@@ -65,6 +65,9 @@ struct Carve {
 // ---- internal launchers (implemented in kernels_generic.hip / kernels_mfma.hip) ---------
 size_t generic_forward_ws(const fastgrnn_desc& d);
 size_t generic_backward_ws(const fastgrnn_desc& d);
+// the generic scan of d in that direction (0 forward, 1 backward) fits its dynamic LDS; where it does not, no kernel
+// runs d in that direction (kernel path -1) and the launcher refuses before it launches anything
+bool generic_lds_fits(const fastgrnn_desc& d, int direction);
 // sg, sc (FASTGRNN_FLAG_PREACT_AFFINE): [H] per-unit scales of the pre-activation in front of the gate and the
 // update nonlinearity, in the parameter dtype; NULL for the plain cell
 int generic_forward(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0,

@@ -347,7 +347,14 @@ BwdWs bwd_layout(const fastgrnn_desc& d) {
   size_t TB = (size_t)d.T * d.B;
   size_t nwg = (d.B + BT - 1) / BT;
   size_t nsplit = (TB + SPLITK_CHUNK - 1) / SPLITK_CHUNK;
-  size_t maxMN = (size_t)d.H * (d.H > d.F ? d.H : d.F);
+  // the split-K partials of the largest product generic_backward_t forms: H x F / H x H dense, H x rw and rw x F,
+  // H x ru and ru x H factorised (a rank may exceed H); never below H * max(H, F), what every descriptor asked for
+  // before ranks above H were counted
+  const size_t H = d.H, F = d.F, rw = d.w_rank, ru = d.u_rank;
+  size_t maxMN = H * (H > F ? H : F);
+  if (rw * F > maxMN) maxMN = rw * F;
+  if (rw * H > maxMN) maxMN = rw * H;
+  if (ru * H > maxMN) maxMN = ru * H;
   BwdWs w; size_t o = 0;
   w.dpre = o; o += align256(TB * d.H * es);
   w.part_bz = o; o += align256(nwg * d.H * es);
@@ -442,6 +449,27 @@ void launch_tn(size_t R, int M, int N, const T* A, const T* B0, const T* B1, siz
   launch_tn_ld<T>(R, M, N, A, M, B0, B1, shiftB, N, part, C, s);
 }
 
+// Dynamic LDS of the two scans, in bytes: the carve-up at the top of fwd_scan_generic / bwd_scan_generic.
+constexpr size_t GENERIC_LDS_MAX = 160 * 1024;     // one workgroup's share of a CU's LDS on gfx950
+
+size_t generic_lds_bytes(const fastgrnn_desc& d, int direction) {
+  const size_t es = d.dtype == FASTGRNN_F64 ? 8 : 4;
+  const size_t H = d.H, F = d.F, rw = d.w_rank, ru = d.u_rank;
+  if (direction) return (2 * BT * H + 2 * H + BT * ru + 2 * NTHREADS) * es;    // dh, dp | sbz, sbh | dmh | red
+  return (2 * BT * H + BT * F + BT * rw + BT * ru) * es;                       // hbuf[2] | xs | mx | mh
+}
+
+}  // namespace
+
+// The one host predicate per direction: the generic scan of d fits the LDS.  resolve() asks it (a direction that
+// does not fit has no kernel: path -1, no workspace, FASTGRNN_ERR_UNSUPPORTED before anything is launched) and the
+// launchers below assert it.
+bool generic_lds_fits(const fastgrnn_desc& d, int direction) {
+  return generic_lds_bytes(d, direction) <= GENERIC_LDS_MAX;
+}
+
+namespace {
+
 template <typename T>
 int generic_forward_t(const fastgrnn_desc& d, const fastgrnn_params& p, const void* x, const void* h0, void* hs,
                       void* zs, void* cs, void* ws, hipStream_t s, const void* sg, const void* sc) {
@@ -453,12 +481,18 @@ int generic_forward_t(const fastgrnn_desc& d, const fastgrnn_params& p, const vo
   // [out,in] -> [in,out] so that lanes (one per output unit) read contiguous weights
   const T* wsrc = reinterpret_cast<const T*>(rw ? p.w2 : p.w);
   const T* usrc = reinterpret_cast<const T*>(ru ? p.u2 : p.u);
+  if (!generic_lds_fits(d, 0)) return FASTGRNN_ERR_UNSUPPORTED;       // (resolve() has asked already: nothing is launched)
+  const size_t lds = generic_lds_bytes(d, 0);
+  const void* scan = sg ? reinterpret_cast<const void*>(&fwd_scan_generic<T, true>)
+                        : reinterpret_cast<const void*>(&fwd_scan_generic<T, false>);
+  if (hipFuncSetAttribute(scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return FASTGRNN_ERR_LAUNCH;
+  }
   hipLaunchKernelGGL(transpose_kernel<T>, dim3((unsigned)((wA_n + 255) / 256)), dim3(256), 0, s, wsrc, wA, H,
                      rw ? rw : F);
   hipLaunchKernelGGL(transpose_kernel<T>, dim3((unsigned)((uA_n + 255) / 256)), dim3(256), 0, s, usrc, uA, H,
                      ru ? ru : H);
-  size_t lds = ((size_t)2 * BT * H + (size_t)BT * F + (size_t)BT * rw + (size_t)BT * ru) * sizeof(T);
-  if (lds > 160 * 1024) return FASTGRNN_ERR_UNSUPPORTED;
   int nth = H >= NTHREADS ? NTHREADS : ((H + 63) / 64) * 64;
   unsigned nwg = (unsigned)((d.B + BT - 1) / BT);
   const T* bz = reinterpret_cast<const T*>(p.bias_gate);
@@ -472,7 +506,6 @@ int generic_forward_t(const fastgrnn_desc& d, const fastgrnn_params& p, const vo
     bz = pack; bh = pack + 2 * (size_t)H;
   }
   auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(nth), lds, s, d.T, d.B, F, H, rw, ru, d.gate_nl,
                        d.update_nl, reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(h0), wA,
                        reinterpret_cast<const T*>(p.w1), uA, reinterpret_cast<const T*>(p.u1), bz, bh,
@@ -504,10 +537,13 @@ int generic_backward_t(const fastgrnn_desc& d, const fastgrnn_params& p, const v
   const T* hs = reinterpret_cast<const T*>(hs_);
   const T* h0 = reinterpret_cast<const T*>(h0_);
   unsigned nwg = (unsigned)((d.B + BT - 1) / BT);
-  size_t lds = ((size_t)2 * BT * H + 2 * (size_t)H + (size_t)BT * ru + 2 * NTHREADS) * sizeof(T);
-  if (lds > 160 * 1024) return FASTGRNN_ERR_UNSUPPORTED;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_scan_generic<T>),
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (!generic_lds_fits(d, 1)) return FASTGRNN_ERR_UNSUPPORTED;       // (resolve() has asked already: nothing is launched)
+  const size_t lds = generic_lds_bytes(d, 1);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_scan_generic<T>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return FASTGRNN_ERR_LAUNCH;
+  }
   hipLaunchKernelGGL(bwd_scan_generic<T>, dim3(nwg), dim3(NTHREADS), lds, s, d.T, d.B, H, ru, d.gate_nl, d.update_nl,
                      reinterpret_cast<const T*>(ghs_), hs, reinterpret_cast<const T*>(zs),
                      reinterpret_cast<const T*>(cs), h0, reinterpret_cast<const T*>(p.u),

@@ -1,5 +1,6 @@
 """What the test files share: names of the ABI, operand builders, the only spelled-out calls of the unrolled
-operators, the bitwise comparison, the fp64 oracle preamble and the one gradient checker with its tolerance policy.
+operators, the bitwise comparison, the fp64 oracle preamble, the one gradient checker with its tolerance policy and the
+exact-workspace harness.
 
 A plain module (``from tests import support as S``): no conftest, nothing registered with pytest, importable without a
 GPU and without loading the library.  pytest does not rewrite the asserts of this module, so every one of them carries
@@ -207,6 +208,48 @@ def check_grads(got, ref, *, tol, scalar_term_tol, tag):
             bad[k] = "abs err %.6g > limit %.6g (rel %.6g)" % (abs_err, lim, errs[k])
     assert not bad, "%s: %s; relative errors of all: %s" % (tag, bad, errs)
     return errs
+
+
+# ---- exact workspaces ----------------------------------------------------------------------------------------------------
+
+WS_MARGIN = 4096
+
+
+class ExactWorkspace:
+    """fastgrnn_cuda._call with the cached workspace replaced, per call, by a 256-byte-aligned slice of exactly the
+    bytes the call asks for, cut from a buffer filled with 0xA5 with WS_MARGIN bytes on each side.  After the call
+    (and a synchronize) both margins must be untouched.  ``checked`` counts the calls that took a workspace; a call
+    without one goes through as it is.  Put in place of ``fastgrnn_cuda._call`` (monkeypatch)."""
+
+    def __init__(self, call):
+        self.call, self.checked = call, 0
+
+    def _buffer(self, nbytes, dev):
+        return torch.full((nbytes + 2 * WS_MARGIN,), 0xA5, dtype=torch.uint8, device=dev)
+
+    def __call__(self, fn, what, tag, dev, nbytes, *args):
+        if not nbytes:
+            return self.call(fn, what, tag, dev, nbytes, *args)
+        idx = dev.index
+        key = (idx, fastgrnn_cuda._get_raw_stream(torch.cuda.current_device() if idx is None else idx))
+        big = self._buffer(nbytes, dev)
+        ws = big[WS_MARGIN:WS_MARGIN + nbytes]
+        assert ws.data_ptr() % 256 == 0 and ws.numel() == nbytes
+        cache = fastgrnn_cuda._ws_cache
+        before = cache.get(key)
+        cache[key] = ws
+        try:
+            self.call(fn, what, tag, dev, nbytes, *args)
+            torch.cuda.synchronize(dev)
+            assert cache[key] is ws, what                     # the call took the seeded slice, not a larger buffer
+            assert bool((big[:WS_MARGIN] == 0xA5).all()), "%s wrote in front of its workspace" % what
+            assert bool((big[WS_MARGIN + nbytes:] == 0xA5).all()), "%s wrote past its %d workspace bytes" % (what, nbytes)
+        finally:
+            if before is None:
+                cache.pop(key, None)
+            else:
+                cache[key] = before
+        self.checked += 1
 
 
 # ---- the relu kink -----------------------------------------------------------------------------------------------------

@@ -1,11 +1,15 @@
-"""Every path-2 call stays inside a workspace of exactly the planned size and does not depend on what lies in it.
+"""Every path-2 call, and the path-0 and path-1 calls listed below, stay inside a workspace of exactly the planned size
+and do not depend on what lies in it.
 
 Each case runs a forward and a backward through the Python operators twice: the ordinary way, and with every call's
 workspace a 256-byte-aligned slice of exactly the bytes the call asks for, cut from a buffer filled with 0xA5 with
 4 KiB on each side.  The margins must come back untouched and every output must equal the ordinary run's bit for bit.
 A sha256 over every output of the case is compared with tests/golden/workspace_exact_digests.json, recorded on the GPU
 from the library before its host code was reorganised (FASTGRNN_WS_DIGESTS_OUT=<file> records instead of comparing): the reorganised
-launchers compute the same bits."""
+launchers compute the same bits.  The path-0 (generic scan) and path-1 (fp32-MFMA scan) entries were recorded later, from
+the build that first sized the generic backward's split-K partials by the largest product it forms: before it, the
+three path-0 cases with a rank above H wrote 1 KiB, 128 bytes and 1 KiB past their workspace (inside the margins
+here, with correct results).  The entries recorded first are unchanged."""
 import hashlib
 import json
 import os
@@ -18,43 +22,12 @@ from kws_amd import batchnorm_train
 from tests import support as S
 
 SP, BFT, ZE = _lib.FLAG_SAVE_PREACT, _lib.FLAG_X_BFT, _lib.FLAG_ZERO_EXTEND
-MARGIN = 4096
+GEN, F32M = _lib.FLAG_FORCE_GENERIC, _lib.FLAG_FORCE_F32_MFMA
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "workspace_exact_digests.json")
 RECORD = os.environ.get("FASTGRNN_WS_DIGESTS_OUT")
 # cases whose outputs differed between two recordings on the unchanged library: none
 UNSTABLE = frozenset()
 NONE = fastgrnn_cuda._NONE
-
-
-class _ExactWorkspace:
-    """fastgrnn_cuda._call with the cached workspace replaced, per call, by an exact slice between two margins"""
-
-    def __init__(self, call):
-        self.call, self.checked = call, 0
-
-    def __call__(self, fn, what, tag, dev, nbytes, *args):
-        if not nbytes:
-            return self.call(fn, what, tag, dev, nbytes, *args)
-        idx = dev.index
-        key = (idx, fastgrnn_cuda._get_raw_stream(torch.cuda.current_device() if idx is None else idx))
-        big = torch.full((nbytes + 2 * MARGIN,), 0xA5, dtype=torch.uint8, device=dev)
-        ws = big[MARGIN:MARGIN + nbytes]
-        assert ws.data_ptr() % 256 == 0 and ws.numel() == nbytes
-        cache = fastgrnn_cuda._ws_cache
-        before = cache.get(key)
-        cache[key] = ws
-        try:
-            self.call(fn, what, tag, dev, nbytes, *args)
-            torch.cuda.synchronize(dev)
-            assert cache[key] is ws, what                     # the call took the seeded slice, not a larger buffer
-            assert bool((big[:MARGIN] == 0xA5).all()), "%s wrote in front of its workspace" % what
-            assert bool((big[MARGIN + nbytes:] == 0xA5).all()), "%s wrote past its %d workspace bytes" % (what, nbytes)
-        finally:
-            if before is None:
-                cache.pop(key, None)
-            else:
-                cache[key] = before
-        self.checked += 1
 
 
 def _rand(seed, dev):
@@ -81,6 +54,8 @@ def _unrolled(dev, F, H, T, B, flags, rw=0, ru=0, dtype=torch.float32):
     P = dict(zip(("w", "u", "bias_gate", "bias_update", "zeta", "nu", "w1", "w2", "u1", "u2"), _cell(r, F, H, rw, ru)))
     x = r(*((B, F, T) if flags & BFT else (T, B, F)), dtype=dtype)
     h0, G = r(B, H, k=0.5), r(T, B, H, dtype=dtype)
+    if dtype == torch.float64:                   # fp64 cells: every operand in fp64 (the same draws, widened)
+        P, h0 = {k: v.double() for k, v in P.items()}, h0.double()
     fwd = S.forward_unroll(x, h0, P, "sigmoid", flags=flags)
     hs, z, h_prime = fwd[0], fwd[1], (fwd[2] if len(fwd) > 2 else NONE)      # (no third output: no h_prime is given)
     bwd = S.backward_unroll(G, x, hs, z, h_prime, h0, P, "sigmoid", flags=flags, bias_gate=P["bias_gate"],
@@ -131,7 +106,7 @@ def _both(name, fn, **kw):
 
 
 BF16 = torch.bfloat16
-CASES = (
+CASES_PATH_2 = (
     _both("h128_f32-sp-T3", _unrolled, F=32, H=128, T=3, flags=SP) +
     _both("h128_f64-sp", _unrolled, F=64, H=128, T=5, flags=SP) +
     _both("h128_f64-sp-bft", _unrolled, F=64, H=128, T=5, flags=SP | BFT) +
@@ -152,17 +127,42 @@ CASES = (
     _both("train_windows-h256_f64", _train_windows, F=64, H=256, T=5) +
     [("batchnorm-h128_f64-B6", _batchnorm, dict(F=64, H=128, T=3, B=6))]
 )
+# the generic scans: more than one trip of the unit loops; both ranks past the tiled GEMM's 64 columns, in fp64; a rank
+# above H, where a factor's product is the largest the split-K partials hold (tests/generic_cases.py)
+CASES_PATH_0 = [
+    ("generic-h300_f20", _unrolled, dict(F=20, H=300, T=3, B=9, flags=GEN)),
+    ("generic-h72_f80-r65-65-fp64", _unrolled, dict(F=80, H=72, T=3, B=9, flags=GEN, rw=65, ru=65, dtype=torch.float64)),
+    ("generic-h8_f32-rw16", _unrolled, dict(F=32, H=8, T=3, B=5, flags=GEN, rw=16)),
+    ("generic-h8_f13-ru20", _unrolled, dict(F=13, H=8, T=3, B=5, flags=GEN, ru=20)),
+    ("generic-h8_f32-rw16-ru20", _unrolled, dict(F=32, H=8, T=3, B=5, flags=GEN, rw=16, ru=20)),
+]
+CASES_PATH_1 = [
+    ("f32mfma-h128_f32-B48", _unrolled, dict(F=32, H=128, T=5, B=48, flags=F32M)),
+    ("f32mfma-h64_f32-B37", _unrolled, dict(F=32, H=64, T=5, B=37, flags=F32M)),
+    ("f32mfma-h128_f64-B16", _unrolled, dict(F=64, H=128, T=5, B=16, flags=F32M)),
+]
+CASES = CASES_PATH_2 + CASES_PATH_0 + CASES_PATH_1
 
 
-def test_every_unrolled_case_is_on_kernel_path_2():
-    for name, fn, kw in CASES:
+def _assert_on_path(cases, path):
+    for name, fn, kw in cases:
         if fn is _unrolled:
             k = dict(kw)
             dtype, flags = k.pop("dtype", torch.float32), k.pop("flags")
             rw, ru = k.pop("rw", 0), k.pop("ru", 0)
             for direction in (0, 1):
                 assert fastgrnn_cuda.kernel_path(k["T"], k["B"], k["F"], k["H"], rw, ru, dtype=dtype, direction=direction,
-                                                 flags=flags) == 2, (name, direction)
+                                                 flags=flags) == path, (name, direction)
+
+
+def test_every_unrolled_case_is_on_kernel_path_2():
+    _assert_on_path(CASES_PATH_2, 2)
+
+
+def test_the_generic_and_f32_mfma_cases_are_on_paths_0_and_1():
+    _assert_on_path(CASES_PATH_0, 0)
+    _assert_on_path(CASES_PATH_1, 1)
+    assert len(CASES_PATH_0) == 5 and len(CASES_PATH_1) == 3
 
 
 def _digest(t):
@@ -175,7 +175,7 @@ def test_exact_workspace_untouched_margins_same_bits(monkeypatch, name, fn, kw):
     dev = torch.device("cuda:0")
     ordinary = fn(dev, **kw)
     torch.cuda.synchronize(dev)
-    exact = _ExactWorkspace(fastgrnn_cuda._call)
+    exact = S.ExactWorkspace(fastgrnn_cuda._call)
     monkeypatch.setattr(fastgrnn_cuda, "_call", exact)
     monkeypatch.setattr(batchnorm_train, "_call", exact)
     again = fn(dev, **kw)

@@ -297,3 +297,54 @@ def test_relu_gates_end_up_off_the_kink():
     assert np.abs(S.relu_gate_preactivations(q, x, h0)).min() >= margin
     moved = [k for k in p if not np.array_equal(p[k], q[k])]
     assert moved == ["bias_gate"] and q["bias_gate"].dtype == np.float32
+
+
+# ---- the exact workspace -----------------------------------------------------------------------------------------------
+
+class _HostExactWorkspace(S.ExactWorkspace):
+    """the harness on host memory: the same buffer, cut so that the workspace slice is 256-byte aligned"""
+
+    def _buffer(self, nbytes, dev):
+        raw = torch.empty(nbytes + 2 * S.WS_MARGIN + 256, dtype=torch.uint8)
+        big = raw[(-(raw.data_ptr() + S.WS_MARGIN)) % 256:][:nbytes + 2 * S.WS_MARGIN]
+        big.fill_(0xA5)
+        return big
+
+
+def test_exact_workspace_hands_out_exact_slices_and_sees_writes_outside(monkeypatch):
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda dev=None: None)
+    monkeypatch.setattr(fastgrnn_cuda, "_get_raw_stream", lambda idx: 77)
+    monkeypatch.setattr(fastgrnn_cuda, "_ws_cache", {})
+    import ctypes as C
+    dev, cache, seen = torch.device("cpu"), fastgrnn_cuda._ws_cache, []
+
+    def call(fn, what, tag, dev, nbytes, *args):
+        ws = cache.get((None, 77))
+        seen.append((what, nbytes, None if ws is None else (ws.numel(), ws.data_ptr() % 256, int(ws[0]))))
+        if nbytes:
+            base = ws.data_ptr()
+            for off in fn(nbytes):              # fn: the byte offsets from the workspace's start that the "call" writes
+                C.memset(base + off, 0, 1)
+
+    exact = _HostExactWorkspace(call)
+    exact(lambda n: [], "no workspace", "t", dev, 0)
+    assert exact.checked == 0 and seen[-1] == ("no workspace", 0, None) and not cache
+    exact(lambda n: [0, n - 1], "inside", "t", dev, 1000)
+    assert exact.checked == 1 and seen[-1] == ("inside", 1000, (1000, 0, 0xA5)) and not cache
+    with pytest.raises(AssertionError, match="past its 1000 workspace bytes"):
+        exact(lambda n: [n], "one past", "t", dev, 1000)
+    with pytest.raises(AssertionError, match="past its 1000 workspace bytes"):
+        exact(lambda n: [n + S.WS_MARGIN - 1], "the margin's last byte", "t", dev, 1000)
+    with pytest.raises(AssertionError, match="in front of its workspace"):
+        exact(lambda n: [-1], "one in front", "t", dev, 1000)
+    assert exact.checked == 1 and not cache                  # a failed call is not counted and the cache is put back
+    held = cache[None, 77] = torch.zeros(8, dtype=torch.uint8)
+    exact(lambda n: [5], "with a cached buffer", "t", dev, 256)
+    assert cache[None, 77] is held and exact.checked == 2
+
+    def grows(fn, what, tag, dev, nbytes, *args):            # a call that replaces the seeded slice is caught
+        cache[None, 77] = torch.zeros(2 * nbytes, dtype=torch.uint8)
+    with pytest.raises(AssertionError, match="took more"):
+        _HostExactWorkspace(grows)(None, "took more", "t", dev, 256)
+    assert cache[None, 77] is held
