@@ -609,6 +609,59 @@ int fastgrnn_hip_optim_update(const fastgrnn_optim_hyper *h, const fastgrnn_opti
                               int32_t n_segs, const float *lr, const int64_t *step, const int32_t *iht_mode,
                               float *scalars /* ASGD only: device [4] */, void *stream);
 
+/* grad_guard -- the stage between backward and the update: the global gradient norm, the clipping coefficient of
+ * torch.nn.utils.clip_grad_norm_ and the rejection of a step whose gradient is not finite, decided on the device.  It
+ * runs on the gradient tensors ("segments") the update call is handed afterwards, with train_update's conventions: one
+ * launch per FASTGRNN_UPDATE_MAX_SEGS segments, one workgroup per segment, the segment table in the kernel arguments,
+ * then one single-workgroup launch; nothing allocated, nothing copied, never a synchronise, so the call may be
+ * captured in a graph.
+ *   S    = the sum over all elements of all segments of g^2, accumulated in double (the square of an fp32 value is
+ *          exact in double; finite gradients cannot overflow it, so S is non-finite iff some element is).  The order
+ *          of the additions is a function of n_segs and the n alone and no atomics are used: repeatable bit for bit.
+ *   norm = (float)sqrt(S)
+ *   skip = (flags & FASTGRNN_GUARD_SKIP_NONFINITE) && !isfinite(S)
+ *   coef = 0 when skip;  1 when max_norm is +inf;  else (float)min(1, max_norm / (sqrt(S) + 1e-6)), formed in double
+ *          and rounded once -- clip_grad_norm_'s rule with error_if_nonfinite=False, a NaN norm giving a NaN coef
+ *   applied += 1 when !skip, skipped += 1 when skip: each call increments exactly one of the two.
+ * state is DEVICE memory, zero-filled by the caller before the first step and otherwise only handed on to the guarded
+ * update calls; segs is a HOST array, read before the call returns; workspace: at least
+ * fastgrnn_hip_grad_guard_workspace_bytes(n_segs) bytes (one double per segment, rounded up to 256), 8-byte aligned.
+ *
+ * train_update_guarded / optim_update_guarded -- train_update / optim_update with `step` replaced by the state a
+ * grad_guard call on the same stream has just written.  The rule (all eight of them) is the unguarded one with two
+ * substitutions: g coef in place of g (one fp32 multiply before the weight-decay fmaf; Rprop: before the sign
+ * product), and t = guard->applied in place of step[0] wherever the rule uses the step count (Adam's and Adamax's
+ * bias corrections, Adagrad's decayed rate, SGD's first-step rule, ASGD's parity and its next eta / mu).  With
+ * guard->skip set the rule is the identity p' = p: the update writes no parameter, no state tensor and no ASGD
+ * scalar, and the IHT phase runs on p' with its usual meaning (mode 1 thresholds and records the support, mode 2
+ * masks).  With max_norm = +inf and finite gradients the call is bit-identical to the unguarded call at
+ * step[0] = applied (g 1.0f is exact).
+ * Errors, all before any launch.  grad_guard: FASTGRNN_ERR_NULL_POINTER (segs, state, workspace, a segment's grad),
+ * FASTGRNN_ERR_BAD_SHAPE (n_segs < 1; n outside 1..2^22; max_norm <= 0 or NaN), FASTGRNN_ERR_UNSUPPORTED (unknown
+ * flag bits), FASTGRNN_ERR_WORKSPACE (too small or not 8-byte aligned).  The guarded updates: guard NULL is
+ * FASTGRNN_ERR_NULL_POINTER; everything else as the unguarded call. */
+#define FASTGRNN_GUARD_SKIP_NONFINITE 1
+typedef struct fastgrnn_guard_seg {
+  const void *grad;                   /* [n] fp32, device */
+  int64_t n;                          /* 1 .. 2^22 */
+} fastgrnn_guard_seg;
+
+typedef struct fastgrnn_guard_state {   /* DEVICE, 32 bytes, zero-filled by the caller before the first step */
+  float norm, coef; int32_t skip, reserved; int64_t applied, skipped;
+} fastgrnn_guard_state;
+
+size_t fastgrnn_hip_grad_guard_workspace_bytes(int32_t n_segs);   /* 0 for n_segs < 1 */
+int fastgrnn_hip_grad_guard(const fastgrnn_guard_seg *segs /* HOST array */, int32_t n_segs, double max_norm,
+                            int32_t flags, fastgrnn_guard_state *state, void *workspace, size_t workspace_bytes,
+                            void *stream);
+int fastgrnn_hip_train_update_guarded(const fastgrnn_update_hyper *h, const fastgrnn_update_seg *segs /* HOST array */,
+                                      int32_t n_segs, const float *lr, const fastgrnn_guard_state *guard,
+                                      const int32_t *iht_mode, void *stream);
+int fastgrnn_hip_optim_update_guarded(const fastgrnn_optim_hyper *h, const fastgrnn_optim_seg *segs /* HOST array */,
+                                      int32_t n_segs, const float *lr, const fastgrnn_guard_state *guard,
+                                      const int32_t *iht_mode, float *scalars /* ASGD only: device [4] */,
+                                      void *stream);
+
 /* mfcc -- the reference's featuriser, librosa.feature.mfcc + librosa.feature.delta at librosa 0.10.2's defaults as
  * data_pipeline/mfccProcessor.py:43-58 calls them, then the pad / cut and the normalisation of preprocessing.py:79-88 and
  * inferencetry.py:165-200, from raw audio in one launch.  sr = 16000, n_fft = win_length = 400, hop = 160, n_mels = 128

@@ -56,6 +56,8 @@ EXPORTS = (
     "fastgrnn_hip_mfcc_tables_bytes", "fastgrnn_hip_mfcc_init_tables", "fastgrnn_hip_mfcc_workspace_bytes",
     "fastgrnn_hip_mfcc", "fastgrnn_hip_mfcc_augment", "fastgrnn_hip_augment_draw", "fastgrnn_hip_train_schedule",
     "fastgrnn_hip_train_schedule_rolling", "fastgrnn_hip_rolling_exchange",
+    "fastgrnn_hip_grad_guard_workspace_bytes", "fastgrnn_hip_grad_guard", "fastgrnn_hip_train_update_guarded",
+    "fastgrnn_hip_optim_update_guarded",
 )
 
 
@@ -138,6 +140,20 @@ class OptimSeg(C.Structure):
 class OptimHyper(C.Structure):
     """fastgrnn_optim_hyper."""
     _fields_ = [("algo", C.c_int32), ("flags", C.c_int32), ("h", C.c_double * 6), ("weight_decay", C.c_double)]
+
+
+GUARD_SKIP_NONFINITE = 1        # FASTGRNN_GUARD_SKIP_NONFINITE: fastgrnn_hip_grad_guard's flags
+
+
+class GuardSeg(C.Structure):
+    """fastgrnn_guard_seg: one gradient tensor of fastgrnn_hip_grad_guard."""
+    _fields_ = [("grad", C.c_void_p), ("n", C.c_int64)]
+
+
+class GuardState(C.Structure):
+    """fastgrnn_guard_state: the 32 bytes on the device that the guard writes and the guarded updates read."""
+    _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("skip", C.c_int32), ("reserved", C.c_int32),
+                ("applied", C.c_int64), ("skipped", C.c_int64)]
 
 
 MFCC_PEAK_NORMALIZE = 1         # FASTGRNN_MFCC_PEAK_NORMALIZE
@@ -255,6 +271,14 @@ def load():
     lib.fastgrnn_hip_train_update.argtypes = [C.POINTER(UpdateHyper), C.POINTER(UpdateSeg), C.c_int32, vp, vp, vp, vp]
     lib.fastgrnn_hip_optim_update.restype = i32
     lib.fastgrnn_hip_optim_update.argtypes = [C.POINTER(OptimHyper), C.POINTER(OptimSeg), C.c_int32, vp, vp, vp, vp, vp]
+    lib.fastgrnn_hip_grad_guard_workspace_bytes.restype = sz
+    lib.fastgrnn_hip_grad_guard_workspace_bytes.argtypes = [C.c_int32]
+    lib.fastgrnn_hip_grad_guard.restype = i32
+    lib.fastgrnn_hip_grad_guard.argtypes = [C.POINTER(GuardSeg), C.c_int32, C.c_double, C.c_int32, vp, vp, sz, vp]
+    lib.fastgrnn_hip_train_update_guarded.restype = i32
+    lib.fastgrnn_hip_train_update_guarded.argtypes = [C.POINTER(UpdateHyper), C.POINTER(UpdateSeg), C.c_int32, vp, vp, vp, vp]
+    lib.fastgrnn_hip_optim_update_guarded.restype = i32
+    lib.fastgrnn_hip_optim_update_guarded.argtypes = [C.POINTER(OptimHyper), C.POINTER(OptimSeg), C.c_int32, vp, vp, vp, vp, vp]
     MD = C.POINTER(MfccDesc)
     lib.fastgrnn_hip_mfcc_tables_bytes.restype = sz
     lib.fastgrnn_hip_mfcc_tables_bytes.argtypes = []

@@ -494,9 +494,10 @@ int fastgrnn_hip_vote_windows(int32_t S, int32_t Nw, int32_t num_windows, int32_
   return vote_windows(S, Nw, num_windows, majority, pred, majority_out, event_out, reinterpret_cast<hipStream_t>(stream));
 }
 
-int fastgrnn_hip_train_update(const fastgrnn_update_hyper* h, const fastgrnn_update_seg* segs, int32_t n_segs,
-                              const float* lr, const int64_t* step, const int32_t* iht_mode, void* stream) {
-  if (!h || !segs || !lr || !step) return FASTGRNN_ERR_NULL_POINTER;
+// FASTGRNN_OK or the refusal of train_update's arguments; count: the step scalar, or the guard state that replaces it
+static int check_train_update(const fastgrnn_update_hyper* h, const fastgrnn_update_seg* segs, int32_t n_segs,
+                              const float* lr, const void* count, const int32_t* iht_mode) {
+  if (!h || !segs || !lr || !count) return FASTGRNN_ERR_NULL_POINTER;
   if (h->algo != 0 && h->algo != 1) return FASTGRNN_ERR_UNSUPPORTED;
   if (n_segs < 1) return FASTGRNN_ERR_BAD_SHAPE;
   const bool adam = h->algo == 0;
@@ -506,14 +507,19 @@ int fastgrnn_hip_train_update(const fastgrnn_update_hyper* h, const fastgrnn_upd
   if (adam && (!(b2 >= 0.0 && b2 < 1.0) || !(h->eps > 0.0))) return FASTGRNN_ERR_BAD_SHAPE;
   if (!adam && h->nesterov && (b1 <= 0.0 || b2 != 0.0)) return FASTGRNN_ERR_BAD_SHAPE;   // torch.optim.SGD's rule
   if (!adam && !(b2 == b2)) return FASTGRNN_ERR_BAD_SHAPE;
-  if (const int st = check_update_segs(segs, n_segs, adam ? 3 : 1, iht_mode)) return st;
+  return check_update_segs(segs, n_segs, adam ? 3 : 1, iht_mode);
+}
+
+int fastgrnn_hip_train_update(const fastgrnn_update_hyper* h, const fastgrnn_update_seg* segs, int32_t n_segs,
+                              const float* lr, const int64_t* step, const int32_t* iht_mode, void* stream) {
+  if (const int st = check_train_update(h, segs, n_segs, lr, step, iht_mode)) return st;
   return update_step(*h, segs, n_segs, lr, step, iht_mode, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
-int fastgrnn_hip_optim_update(const fastgrnn_optim_hyper* h, const fastgrnn_optim_seg* segs, int32_t n_segs,
-                              const float* lr, const int64_t* step, const int32_t* iht_mode, float* scalars,
-                              void* stream) {
-  if (!h || !segs || !lr || !step) return FASTGRNN_ERR_NULL_POINTER;
+// ... and of optim_update's
+static int check_optim_update(const fastgrnn_optim_hyper* h, const fastgrnn_optim_seg* segs, int32_t n_segs,
+                              const float* lr, const void* count, const int32_t* iht_mode, const float* scalars) {
+  if (!h || !segs || !lr || !count) return FASTGRNN_ERR_NULL_POINTER;
   if (h->algo < 2 || h->algo > 7) return FASTGRNN_ERR_UNSUPPORTED;
   if (n_segs < 1) return FASTGRNN_ERR_BAD_SHAPE;
   const double* v = h->h;
@@ -545,8 +551,44 @@ int fastgrnn_hip_optim_update(const fastgrnn_optim_hyper* h, const fastgrnn_opti
       break;
   }
   if (!ok) return FASTGRNN_ERR_BAD_SHAPE;
-  if (const int st = check_update_segs(segs, n_segs, needs, iht_mode)) return st;
+  return check_update_segs(segs, n_segs, needs, iht_mode);
+}
+
+int fastgrnn_hip_optim_update(const fastgrnn_optim_hyper* h, const fastgrnn_optim_seg* segs, int32_t n_segs,
+                              const float* lr, const int64_t* step, const int32_t* iht_mode, float* scalars,
+                              void* stream) {
+  if (const int st = check_optim_update(h, segs, n_segs, lr, step, iht_mode, scalars)) return st;
   return update_step(*h, segs, n_segs, lr, step, iht_mode, scalars, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t fastgrnn_hip_grad_guard_workspace_bytes(int32_t n_segs) { return grad_guard_ws_bytes(n_segs); }
+
+int fastgrnn_hip_grad_guard(const fastgrnn_guard_seg* segs, int32_t n_segs, double max_norm, int32_t flags,
+                            fastgrnn_guard_state* state, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!segs || !state || !workspace) return FASTGRNN_ERR_NULL_POINTER;
+  if (n_segs < 1 || !(max_norm > 0.0)) return FASTGRNN_ERR_BAD_SHAPE;          // (a NaN max_norm fails the comparison)
+  if (flags & ~FASTGRNN_GUARD_SKIP_NONFINITE) return FASTGRNN_ERR_UNSUPPORTED;
+  for (int32_t k = 0; k < n_segs; ++k) {
+    if (!segs[k].grad) return FASTGRNN_ERR_NULL_POINTER;
+    if (segs[k].n < 1 || segs[k].n > FASTGRNN_UPDATE_MAX_N) return FASTGRNN_ERR_BAD_SHAPE;
+  }
+  if (workspace_bytes < grad_guard_ws_bytes(n_segs) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+    return FASTGRNN_ERR_WORKSPACE;
+  return grad_guard_run(segs, n_segs, max_norm, flags, state, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int fastgrnn_hip_train_update_guarded(const fastgrnn_update_hyper* h, const fastgrnn_update_seg* segs, int32_t n_segs,
+                                      const float* lr, const fastgrnn_guard_state* guard, const int32_t* iht_mode,
+                                      void* stream) {
+  if (const int st = check_train_update(h, segs, n_segs, lr, guard, iht_mode)) return st;
+  return update_step_guarded(*h, segs, n_segs, lr, guard, iht_mode, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int fastgrnn_hip_optim_update_guarded(const fastgrnn_optim_hyper* h, const fastgrnn_optim_seg* segs, int32_t n_segs,
+                                      const float* lr, const fastgrnn_guard_state* guard, const int32_t* iht_mode,
+                                      float* scalars, void* stream) {
+  if (const int st = check_optim_update(h, segs, n_segs, lr, guard, iht_mode, scalars)) return st;
+  return update_step_guarded(*h, segs, n_segs, lr, guard, iht_mode, scalars, reinterpret_cast<hipStream_t>(stream));
 }
 
 // FASTGRNN_OK or the refusal of a featuriser descriptor (include/fastgrnn_hip.h lists the supported range)

@@ -208,6 +208,16 @@ template <typename Hyper, typename Seg>
 int update_step(const Hyper& h, const Seg* segs, int n_segs, const float* lr, const int64_t* step,
                 const int32_t* iht_mode, float* scalars, hipStream_t s);
 
+// the gradient guard (kernels_guard.hip): the global norm, the clipping coefficient and the skip decision into *state,
+// and update_step under it -- the step count, the coefficient and the decision are read from *guard.  Arguments
+// already checked, segs on the host
+size_t grad_guard_ws_bytes(int n_segs);
+int grad_guard_run(const fastgrnn_guard_seg* segs, int n_segs, double max_norm, int flags, fastgrnn_guard_state* state,
+                   void* workspace, hipStream_t s);
+template <typename Hyper, typename Seg>
+int update_step_guarded(const Hyper& h, const Seg* segs, int n_segs, const float* lr, const fastgrnn_guard_state* guard,
+                        const int32_t* iht_mode, float* scalars, hipStream_t s);
+
 // MFCC + delta features from raw audio (kernels_mfcc.hip); arguments already checked
 size_t mfcc_tables_bytes();
 int mfcc_init_tables(void* tables, hipStream_t s);

@@ -24,9 +24,24 @@
 // writes the same two values into pair t & 1 with ordinary stores, so no workgroup can read what another has already
 // replaced.  Step 1 reads nothing: eta = lr, mu = 1, as torch initialises them.
 // One kernel per rule (a template argument), so that no rule carries another's registers.
+// kernels_guard.hip runs the same eight rules under the gradient guard and needs this file's kernel, its radix select,
+// its segment table and the host code that fills it.  It gets them by including THIS file with UPDATE_GUARD defined as
+// 1: the kernel template then comes out as guarded_update_k<ALGO>, which takes a fastgrnn_guard_state in place of the
+// step scalar, and the host entry point below is left out.  The switch is textual on purpose: compiled on its own
+// (UPDATE_GUARD 0) the kernel's body reaches the compiler as the text it was before the guard existed, and the eight
+// kernels come out with the same device code, digest for digest (profiles/r17_guard.md); the host side around it did
+// change (the table fill became update_launches, shared with the guarded entry).  The rules as an inlined device
+// function called by two wrappers came out with another schedule for two of the eight.
+// The three macros of the switch live from the kernel's signature to the end of its body and nowhere else.
 // Latency-bound byte work on at most 32 CUs (a model has 6-14 tensors of at most 256x256): what it saves is launches
 // and the host round trip, not bandwidth.
+#include <type_traits>
+
 #include "common.h"
+
+#ifndef UPDATE_GUARD
+#define UPDATE_GUARD 0
+#endif
 
 namespace fastgrnn {
 namespace {
@@ -132,10 +147,26 @@ __device__ __forceinline__ void iht_threshold(float* p, unsigned char* sup, cons
   }
 }
 
+// One workgroup's work: the rule ALGO on segment blockIdx.x of the table, then that segment's IHT phase.
+// UPDATE_GUARD 0: step_p is the caller's step count.
+// UPDATE_GUARD 1: the step count is guard->applied, every gradient element is multiplied by guard->coef (one fp32
+// multiply in front of the weight-decay fmaf), and with guard->skip set the rule is the identity: the update arm
+// stores nothing -- no parameter, no state tensor, no ASGD scalar -- and the IHT phase runs on the parameters as they
+// are.  All three come from loads at kernel entry, through a pointer that is uniform over the launch: the skip branch
+// is wave-uniform and is taken before the first LDS write.
+#if UPDATE_GUARD
+#define UPDATE_KERNEL guarded_update_k
+#define UPDATE_COUNT_ARG const fastgrnn_guard_state* __restrict__ guard
+#define UPDATE_GRAD(i) (g[i] * coef)
+#else
+#define UPDATE_KERNEL update_k
+#define UPDATE_COUNT_ARG const long long* __restrict__ step_p
+#define UPDATE_GRAD(i) g[i]
+#endif
 template <int ALGO>
-__global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper hy, const float* __restrict__ lr_p,
-                                                        const long long* __restrict__ step_p,
-                                                        const int* __restrict__ mode_p, float* scalars) {
+__global__ __launch_bounds__(UPD_THREADS) void UPDATE_KERNEL(upd_table tab, upd_hyper hy, const float* __restrict__ lr_p,
+                                                             UPDATE_COUNT_ARG, const int* __restrict__ mode_p,
+                                                             float* scalars) {
   __shared__ unsigned hist[256];
   // Adam: lr / (1 - beta1^t), sqrt(1 - beta2^t);  Adagrad: lr / (1 + (t-1) lr_decay);  Adamax: lr / (1 - beta1^t)
   __shared__ float s_sc[ALGO == ADAM ? 2 : 1];
@@ -146,7 +177,13 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
   float* p = sg.p;
   const float* g = sg.g;
   const float lr = lr_p[0];
+#if UPDATE_GUARD
+  const long long step = guard->applied;
+  const float coef = guard->coef;
+  const bool skip = guard->skip != 0;
+#else
   const long long step = step_p[0];
+#endif
   int mode = mode_p ? mode_p[0] : 0;
   if (!sg.iht || (mode != 1 && mode != 2)) mode = 0;         // (any other value on the device behaves as 0)
 
@@ -159,6 +196,13 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
     if (sup_now) sg.sup[i] = pn != 0.f ? 1 : 0;
   };
 
+#if UPDATE_GUARD
+  if (skip) {
+    // a rejected step: p' = p.  What rides along with the stores of p still happens, on the old values
+    if (mask_now || sup_now)
+      for (int i = tid; i < n; i += UPD_THREADS) store_p(i, p[i]);
+  } else
+#endif
   if constexpr (ALGO == ADAM) {
     // d0 = beta1, d1 = beta2; f0 = beta1, f1 = 1 - beta1, f2 = beta2, f3 = 1 - beta2
     if (tid == 0) {
@@ -172,7 +216,7 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
     float* v = sg.s1;
     for (int i = tid; i < n; i += UPD_THREADS) {
       const float pi = p[i];
-      const float gi = fmaf(hy.wd, pi, g[i]);
+      const float gi = fmaf(hy.wd, pi, UPDATE_GRAD(i));
       const float mi = fmaf(hy.f0, m[i], hy.f1 * gi);
       const float vi = fmaf(hy.f2, v[i], hy.f3 * gi * gi);
       const float denom = sqrtf(vi) / bc2_sqrt + hy.eps;
@@ -187,7 +231,7 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
     const bool first = step <= 1, has_mom = hy.f0 != 0.f;
     for (int i = tid; i < n; i += UPD_THREADS) {
       const float pi = p[i];
-      const float gi = fmaf(hy.wd, pi, g[i]);
+      const float gi = fmaf(hy.wd, pi, UPDATE_GRAD(i));
       float d = gi;
       if (has_mom) {                                           // (torch keeps no buffer, and ignores dampening, without momentum)
         const float bi = first ? gi : fmaf(hy.f0, b[i], hy.f1 * gi);
@@ -203,7 +247,7 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
     float* a = sg.s2;
     for (int i = tid; i < n; i += UPD_THREADS) {
       const float pi = p[i];
-      const float gi = fmaf(hy.wd, pi, g[i]);
+      const float gi = fmaf(hy.wd, pi, UPDATE_GRAD(i));
       const float v0 = v[i];
       const float a0 = hy.i0 ? a[i] : 0.f;
       const float b0 = hy.i1 ? b[i] : 0.f;
@@ -230,7 +274,7 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
     float* s = sg.s0;
     for (int i = tid; i < n; i += UPD_THREADS) {
       const float pi = p[i];
-      const float gi = fmaf(hy.wd, pi, g[i]);
+      const float gi = fmaf(hy.wd, pi, UPDATE_GRAD(i));
       const float si = fmaf(gi, gi, s[i]);
       s[i] = si;
       store_p(i, fmaf(-clr, gi / (sqrtf(si) + hy.eps), pi));
@@ -241,7 +285,7 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
     float* a = sg.s1;
     for (int i = tid; i < n; i += UPD_THREADS) {
       const float pi = p[i];
-      const float gi = fmaf(hy.wd, pi, g[i]);
+      const float gi = fmaf(hy.wd, pi, UPDATE_GRAD(i));
       const float ai = a[i];
       const float vi = fmaf(hy.f0, v[i], hy.f1 * gi * gi);
       v[i] = vi;
@@ -258,7 +302,7 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
     float* u = sg.s1;
     for (int i = tid; i < n; i += UPD_THREADS) {
       const float pi = p[i];
-      const float gi = fmaf(hy.wd, pi, g[i]);
+      const float gi = fmaf(hy.wd, pi, UPDATE_GRAD(i));
       const float mi = lerp_torch(m[i], gi, hy.f0, hy.f1);
       const float ui = fmaxf(hy.f2 * u[i], fabsf(gi) + hy.eps);
       m[i] = mi;
@@ -284,7 +328,7 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
     float* ax = sg.s0;
     for (int i = tid; i < n; i += UPD_THREADS) {
       const float pi = p[i];
-      const float gi = fmaf(hy.wd, pi, g[i]);
+      const float gi = fmaf(hy.wd, pi, UPDATE_GRAD(i));
       const float pn = fmaf(-eta, gi, pi * decay);
       const float axi = ax[i];
       ax[i] = copy ? pn : fmaf(mu, pn - axi, axi);             // (the average follows the unmasked step, as all state does)
@@ -295,7 +339,7 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
     float* prev = sg.s0;
     float* ss = sg.s1;
     for (int i = tid; i < n; i += UPD_THREADS) {
-      const float gi = g[i], pi = p[i], s0 = ss[i];
+      const float gi = UPDATE_GRAD(i), pi = p[i], s0 = ss[i];
       const float s = gi * prev[i];                            // (torch takes the sign of the rounded fp32 product)
       const float factor = s > 0.f ? hy.f1 : s < 0.f ? hy.f0 : 1.f;
       const float st = fminf(fmaxf(s0 * factor, hy.f2), hy.f3);
@@ -311,9 +355,12 @@ __global__ __launch_bounds__(UPD_THREADS) void update_k(upd_table tab, upd_hyper
   // ---- b. hard threshold: strictly below the magnitude of 0-based rank keep_rank goes, the support is recorded
   iht_threshold(p, sg.sup, n, sg.keep_rank, hist, s_sel);
 }
+#undef UPDATE_GRAD
+#undef UPDATE_COUNT_ARG
+#undef UPDATE_KERNEL
 
 // ---- the two public shapes of a call, brought to the kernel's: every float derives from the public doubles here
-upd_hyper to_hyper(const fastgrnn_update_hyper& h) {
+inline upd_hyper to_hyper(const fastgrnn_update_hyper& h) {
   upd_hyper hy = {};
   hy.d0 = h.beta1_or_momentum;
   hy.d1 = h.beta2_or_dampening;
@@ -327,7 +374,7 @@ upd_hyper to_hyper(const fastgrnn_update_hyper& h) {
   return hy;
 }
 
-upd_hyper to_hyper(const fastgrnn_optim_hyper& h) {
+inline upd_hyper to_hyper(const fastgrnn_optim_hyper& h) {
   upd_hyper hy = {};
   hy.wd = (float)h.weight_decay;
   switch (h.algo) {
@@ -372,29 +419,21 @@ upd_hyper to_hyper(const fastgrnn_optim_hyper& h) {
   return hy;
 }
 
-void set_states(upd_seg& d, const fastgrnn_update_seg& a) {
+inline void set_states(upd_seg& d, const fastgrnn_update_seg& a) {
   d.s0 = reinterpret_cast<float*>(a.state0);
   d.s1 = reinterpret_cast<float*>(a.state1);
 }
 
-void set_states(upd_seg& d, const fastgrnn_optim_seg& a) {
+inline void set_states(upd_seg& d, const fastgrnn_optim_seg& a) {
   d.s0 = reinterpret_cast<float*>(a.state[0]);
   d.s1 = reinterpret_cast<float*>(a.state[1]);
   d.s2 = reinterpret_cast<float*>(a.state[2]);
 }
 
-template <int ALGO>
-void launch(int cnt, const upd_table& tab, const upd_hyper& hy, const float* lr, const int64_t* step,
-            const int32_t* iht_mode, float* scalars, hipStream_t s) {
-  hipLaunchKernelGGL(update_k<ALGO>, dim3(cnt), dim3(UPD_THREADS), 0, s, tab, hy, lr, (const long long*)step,
-                     (const int*)iht_mode, scalars);
-}
-
-}  // namespace
-
-template <typename Hyper, typename Seg>
-int update_step(const Hyper& h, const Seg* segs, int n_segs, const float* lr, const int64_t* step,
-                const int32_t* iht_mode, float* scalars, hipStream_t s) {
+// The launches of a call: one per FASTGRNN_UPDATE_MAX_SEGS segments, the table filled from the public segments;
+// launch(std::integral_constant<int, ALGO>, cnt, tab, hy) starts the kernel of the call's rule.
+template <typename Hyper, typename Seg, typename Launch>
+void update_launches(const Hyper& h, const Seg* segs, int n_segs, Launch launch) {
   const upd_hyper hy = to_hyper(h);
   for (int s0 = 0; s0 < n_segs; s0 += FASTGRNN_UPDATE_MAX_SEGS) {
     const int cnt = n_segs - s0 < FASTGRNN_UPDATE_MAX_SEGS ? n_segs - s0 : FASTGRNN_UPDATE_MAX_SEGS;
@@ -411,16 +450,28 @@ int update_step(const Hyper& h, const Seg* segs, int n_segs, const float* lr, co
       d.iht = a.iht != 0;
     }
     switch (h.algo) {
-      case ADAM: launch<ADAM>(cnt, tab, hy, lr, step, iht_mode, scalars, s); break;
-      case SGD: launch<SGD>(cnt, tab, hy, lr, step, iht_mode, scalars, s); break;
-      case RMSPROP: launch<RMSPROP>(cnt, tab, hy, lr, step, iht_mode, scalars, s); break;
-      case ADAGRAD: launch<ADAGRAD>(cnt, tab, hy, lr, step, iht_mode, scalars, s); break;
-      case ADADELTA: launch<ADADELTA>(cnt, tab, hy, lr, step, iht_mode, scalars, s); break;
-      case ADAMAX: launch<ADAMAX>(cnt, tab, hy, lr, step, iht_mode, scalars, s); break;
-      case ASGD: launch<ASGD>(cnt, tab, hy, lr, step, iht_mode, scalars, s); break;
-      default: launch<RPROP>(cnt, tab, hy, lr, step, iht_mode, scalars, s); break;
+      case ADAM: launch(std::integral_constant<int, ADAM>{}, cnt, tab, hy); break;
+      case SGD: launch(std::integral_constant<int, SGD>{}, cnt, tab, hy); break;
+      case RMSPROP: launch(std::integral_constant<int, RMSPROP>{}, cnt, tab, hy); break;
+      case ADAGRAD: launch(std::integral_constant<int, ADAGRAD>{}, cnt, tab, hy); break;
+      case ADADELTA: launch(std::integral_constant<int, ADADELTA>{}, cnt, tab, hy); break;
+      case ADAMAX: launch(std::integral_constant<int, ADAMAX>{}, cnt, tab, hy); break;
+      case ASGD: launch(std::integral_constant<int, ASGD>{}, cnt, tab, hy); break;
+      default: launch(std::integral_constant<int, RPROP>{}, cnt, tab, hy); break;
     }
   }
+}
+
+}  // namespace
+
+#if !UPDATE_GUARD
+template <typename Hyper, typename Seg>
+int update_step(const Hyper& h, const Seg* segs, int n_segs, const float* lr, const int64_t* step,
+                const int32_t* iht_mode, float* scalars, hipStream_t s) {
+  update_launches(h, segs, n_segs, [&](auto algo, int cnt, const upd_table& tab, const upd_hyper& hy) {
+    hipLaunchKernelGGL(update_k<decltype(algo)::value>, dim3(cnt), dim3(UPD_THREADS), 0, s, tab, hy, lr,
+                       (const long long*)step, (const int*)iht_mode, scalars);
+  });
   return launch_status();
 }
 
@@ -428,5 +479,6 @@ template int update_step(const fastgrnn_update_hyper&, const fastgrnn_update_seg
                          const int32_t*, float*, hipStream_t);
 template int update_step(const fastgrnn_optim_hyper&, const fastgrnn_optim_seg*, int, const float*, const int64_t*,
                          const int32_t*, float*, hipStream_t);
+#endif
 
 }  // namespace fastgrnn

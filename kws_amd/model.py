@@ -443,10 +443,13 @@ class RNNClassifierModel(nn.Module):
 
     def _run_state(self, optimizer, schedule, bags=None):
         """Copies of everything an iteration writes, keyed by the tensor that holds it: parameters, buffers, optimizer
-        state, support masks, the step count, the schedule's logs and a rolling run's bags and states."""
+        state, support masks, the step count, a gradient guard's state, the schedule's logs and a rolling run's bags and
+        states."""
         held = list(self.parameters()) + list(self.buffers()) + [optimizer.step_t, schedule.loss_log, schedule.lr_log]
         held += bags.tensors() if bags is not None else []
         held += [mask for _, mask in optimizer._iht.values()]
+        if optimizer.guarded:                                 # the guard's device state (norm, counters) and its logs
+            held += [optimizer._guard[2]] + list(schedule._guard_logs())
         for p in optimizer.param_groups[0]["params"]:
             held += [t for t in optimizer.state.get(p, {}).values() if isinstance(t, torch.Tensor)]
         return [(t, t.detach().clone()) for t in held]

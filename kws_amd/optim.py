@@ -21,6 +21,12 @@ The library writes parameters, moments and masks through raw pointers; ``step()`
 versions, so a step between a forward and its backward, or a cache keyed on ``_version``, sees it.  The segment table
 handed to the library is cached and rebuilt when a parameter, gradient, state tensor or mask has been replaced.
 
+``guard(max_grad_norm=None, skip_nonfinite=True)`` puts the gradient guard in front of the update, on the device and
+inside the same graph: the global norm of all gradients (``fastgrnn_hip_grad_guard``: a fixed-order sum in double),
+``torch.nn.utils.clip_grad_norm_``'s coefficient, and the rejection of a step whose gradient holds a NaN or an
+infinity -- such a step leaves parameters and optimizer state as they are and is counted in ``skipped_t``; the rules
+then count the steps actually taken (``applied_t``), while ``step_t`` goes on counting iterations.
+
 The masks of the IHT phases belong to the optimizer (``support(param)``), not to the layers: ``sparsify()`` /
 ``sparsifyWithSupport()`` and their ``oldmats`` are untouched and independent.  Use one mechanism per run.
 """
@@ -90,6 +96,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._iht_filled = 0
         self._iht = {}                                # parameter -> (keep_rank, support mask)
         self._table = None                            # (key, ctypes segment array, n): rebuilt when an address moves
+        self._guard = None                            # guard(): (max_norm, flags, state, workspace)
 
     # ---- what the subclasses say ----------------------------------------------------------------------------------
     def _ranges(self, g):
@@ -124,6 +131,45 @@ class _FusedOptimizer(torch.optim.Optimizer):
         ok, rule, got = self._ranges(g)
         if not (float(g["lr"]) >= 0.0 and ok):
             raise ValueError("%s: lr >= 0, %s (got %r, %s)" % (name, rule, g["lr"], ", ".join("%r" % (v,) for v in got)))
+
+    # ---- the gradient guard -----------------------------------------------------------------------------------------
+    def guard(self, max_grad_norm=None, skip_nonfinite=True):
+        """Put the gradient guard in front of every ``step()``: with ``max_grad_norm`` the gradients are scaled by
+        ``min(1, max_grad_norm / (norm + 1e-6))`` (``clip_grad_norm_``'s rule, the 2-norm over all parameters; the
+        ``.grad`` tensors themselves are not written), with ``skip_nonfinite`` a step whose gradient holds a NaN or an
+        infinity is rejected: parameters, optimizer state and ``applied_t`` stay as they are, ``skipped_t`` counts it
+        and the IHT phase still runs.  Call it once, before the first ``step()``; returns ``self``.
+
+        Allocates the 32-byte device state and the workspace, and exposes the state as ``grad_norm_t``,
+        ``clip_coef_t`` (float32), ``skip_t`` (int32: the last step's decision), ``applied_t`` and ``skipped_t``
+        (int64) -- views, written by every step on the device.  Under a guard the rules take ``applied_t`` for their
+        step count (bias corrections and the like); ``step_t`` still counts iterations, which is what a
+        ``TrainSchedule`` reads."""
+        name = type(self).__name__
+        if self._guard is not None:
+            raise RuntimeError("%s.guard() may be called once" % name)
+        if int(self.step_t.item()) != 0:
+            raise RuntimeError("%s.guard() must come before the first step() (step_t is %d)"
+                               % (name, int(self.step_t.item())))
+        if max_grad_norm is None and not skip_nonfinite:
+            raise ValueError("%s.guard(): give max_grad_norm, or leave skip_nonfinite on -- with both off there is "
+                             "nothing to guard" % name)
+        max_norm = math.inf if max_grad_norm is None else float(max_grad_norm)
+        if not max_norm > 0.0:                               # (a NaN fails the comparison)
+            raise ValueError("%s.guard(): max_grad_norm must be > 0 (got %r)" % (name, max_grad_norm))
+        state = torch.zeros(4, dtype=torch.int64, device=self._device)          # fastgrnn_guard_state
+        n = len(self.param_groups[0]["params"])
+        ws = torch.zeros(((8 * n + 255) // 256 * 256) // 8, dtype=torch.float64, device=self._device)
+        self._guard = (max_norm, _lib.GUARD_SKIP_NONFINITE if skip_nonfinite else 0, state, ws)
+        f32, i32 = state.view(torch.float32), state.view(torch.int32)
+        self.grad_norm_t, self.clip_coef_t, self.skip_t = f32[0:1], f32[1:2], i32[2:3]
+        self.applied_t, self.skipped_t = state[2:3], state[3:4]
+        self._table = None
+        return self
+
+    @property
+    def guarded(self):
+        return self._guard is not None
 
     # ---- IHT --------------------------------------------------------------------------------------------------------
     def register_iht(self, model_or_layer):
@@ -192,8 +238,13 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 sg.keep_rank, mask = self._iht[p]
                 sg.support, sg.iht = mask.data_ptr(), 1
                 held.append(mask)
+        gsegs = None
+        if self._guard is not None:                           # the same gradients, as the guard call takes them
+            gsegs = (_lib.GuardSeg * max(1, len(ps)))()
+            for gs, p in zip(gsegs, ps):
+                gs.grad, gs.n = p.grad.data_ptr(), p.numel()
         # (a state tensor created just now changes the key the next call computes: one more rebuild, then hits)
-        self._table = (key, segs, len(ps), held, ps)
+        self._table = (key, segs, len(ps), held, ps, gsegs)
         return segs, len(ps)
 
     def add_param_group(self, param_group):
@@ -207,7 +258,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
         """One update of every parameter that has a gradient, then the IHT phase ``iht`` on the registered matrices:
         ``"none"``, ``"threshold"``, ``"support"``, or ``None`` to leave ``iht_t`` as the caller wrote it.  Copies
         ``param_groups[0]['lr']`` into ``lr_t`` (not with ``capturable=True``: the caller writes ``lr_t``), adds one to
-        ``step_t`` on the device and makes one library call."""
+        ``step_t`` on the device and makes one library call -- two after ``guard()``: the guard, then the update under
+        it."""
         if callable(iht):                                    # torch's positional step(closure)
             iht, closure = "none", iht
         loss = None
@@ -237,9 +289,15 @@ class _FusedOptimizer(torch.optim.Optimizer):
             return loss
         self.step_t.add_(1)
         hy = self._hyper(group)
+        entry, count = self._ENTRY, self.step_t
         with torch.cuda.device(self._device):
-            _call(getattr(_lib.load(), self._ENTRY), self._ENTRY.replace("fastgrnn_hip_", "fastgrnn "), None,
-                  self._device, None, C.byref(hy), segs, n, self.lr_t.data_ptr(), self.step_t.data_ptr(),
+            if self._guard is not None:
+                max_norm, flags, count, ws = self._guard
+                _call(_lib.load().fastgrnn_hip_grad_guard, "fastgrnn grad_guard", None, self._device, None,
+                      self._table[5], n, C.c_double(max_norm), flags, count.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+                entry += "_guarded"
+            _call(getattr(_lib.load(), entry), entry.replace("fastgrnn_hip_", "fastgrnn "), None,
+                  self._device, None, C.byref(hy), segs, n, self.lr_t.data_ptr(), count.data_ptr(),
                   self.iht_t.data_ptr(), *self._extra_args())
         # the library wrote through raw pointers: tell torch, so that whatever is keyed on a tensor's version (autograd's
         # saved-tensor check, the eval-mode BatchNorm fold cache) sees the step
@@ -259,12 +317,18 @@ class _FusedOptimizer(torch.optim.Optimizer):
                              % (type(self).__name__, sorted(steps)))
         return steps.pop() if steps else 0
 
+    def _rule_step(self):
+        """the step count the rules see: the steps taken under a guard, else the iterations"""
+        return int((self.applied_t if self._guard is not None else self.step_t).item())
+
     def state_dict(self):
-        self._export_step(int(self.step_t.item()))
+        self._export_step(self._rule_step())
         sd = super().state_dict()
         order = {p: i for i, p in enumerate(self.param_groups[0]["params"])}
         sd["iht_support"] = {order[p]: mask.clone() for p, (_, mask) in self._iht.items()}
         sd["fused_step"] = int(self.step_t.item())
+        if self._guard is not None:
+            sd["guard"] = {"applied": int(self.applied_t.item()), "skipped": int(self.skipped_t.item())}
         return sd
 
     def load_state_dict(self, state_dict):
@@ -278,7 +342,20 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 for k in self._ALL_STATE_KEYS or self._STATE_KEYS:
                     if st.get(k) is not None:
                         st[k] = st[k].to(device=p.device, dtype=torch.float32).contiguous()
-        self.step_t.fill_(self._import_step(state_dict))
+        t = self._import_step(state_dict)
+        if self._guard is None:
+            self.step_t.fill_(t)
+        else:
+            # the rules' count is `applied` (what the per-parameter `step` of a guarded checkpoint holds, and all a
+            # torch.optim checkpoint has); the iterations are a guarded checkpoint's fused_step
+            g = state_dict.get("guard") or {}
+            applied = int(g.get("applied", t))
+            skipped = int(g.get("skipped", 0))
+            self._guard[2].zero_()
+            self.applied_t.fill_(applied)
+            self.skipped_t.fill_(skipped)
+            self.step_t.fill_(int(state_dict["fused_step"]) if "guard" in state_dict and "fused_step" in state_dict
+                              else applied + skipped)
         ps = self.param_groups[0]["params"]
         for i, mask in (state_dict.get("iht_support") or {}).items():
             p = ps[int(i)]

@@ -153,6 +153,8 @@ class TrainSchedule:
         self.where = torch.zeros(4, dtype=torch.int64, device=dev)
         self.loss_log = torch.zeros(self.log_len, dtype=torch.float32, device=dev)
         self.lr_log = torch.zeros(self.log_len, dtype=torch.float32, device=dev)
+        self.norm_log = self.skip_log = None                                 # a guarded optimizer's: _guard_logs()
+        self._guard_logs()
         self.desc = _lib.ScheduleDesc(self.num_clips, self.batch_size, self.world, self.rank, self.seed, self.num_epochs,
                                       self.trim_level, int(self.sparsify), _lib.LR_KINDS[lr_scheduler], self.lr_lead, 0,
                                       self.log_len, self.lr_base, self.lr_min, self.gamma, self.stepsize, self.t_max,
@@ -196,20 +198,49 @@ class TrainSchedule:
         """Whether the 0-based iteration ``s`` (a negative one counts as 0) is the last of its epoch."""
         return self.position(max(int(s), 0) + 1)[1] == 0
 
+    def _guard_logs(self):
+        """``norm_log`` (float32) and ``skip_log`` (int32), ``[log_len]`` each, once the optimizer has a gradient guard;
+        ``(None, None)`` without one.  They are allocated when the schedule is built on a guarded optimizer, or, where
+        ``optimizer.guard()`` follows the schedule's construction, by the first call of this method -- ``record()``,
+        ``epoch_log()`` and ``fit_audio`` make it.  That first call must not fall inside a graph capture (the tensors
+        would belong to the capture's memory pool): it is refused there.  Call ``guard()`` before building the schedule,
+        or ``record()`` once eagerly, or this method, before capturing."""
+        if self.norm_log is None and getattr(self.optimizer, "guarded", False):
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TrainSchedule: the guard's logs would be allocated inside a graph capture -- call "
+                                   "optimizer.guard() before building the schedule, or schedule._guard_logs() before "
+                                   "the capture")
+            self.norm_log = torch.zeros(self.log_len, dtype=torch.float32, device=self.device)
+            self.skip_log = torch.zeros(self.log_len, dtype=torch.int32, device=self.device)
+        return self.norm_log, self.skip_log
+
     def record(self, loss):
         """``loss_log[slot] = loss`` and ``lr_log[slot] = lr_t`` for the ``slot`` that ``advance`` wrote: two indexed
-        copies addressed by the device scalar, no sync, capturable."""
+        copies addressed by the device scalar, no sync, capturable.  On a guarded optimizer also
+        ``norm_log[slot] = grad_norm_t`` and ``skip_log[slot] = skip_t``, the guard's verdict on this iteration."""
         slot = self.where[2:3]
         self.loss_log.index_copy_(0, slot, loss.detach().reshape(1).to(torch.float32))
         self.lr_log.index_copy_(0, slot, self.optimizer.lr_t)
+        norm_log, skip_log = self._guard_logs()
+        if norm_log is not None:
+            norm_log.index_copy_(0, slot, self.optimizer.grad_norm_t)
+            skip_log.index_copy_(0, slot, self.optimizer.skip_t)
 
     def epoch_log(self, accuracies=None):
         """The reference's log (trainClassifier.py:272): one dict per epoch with the epoch's last loss, its last learning
-        rate and ``accuracies[epoch]`` (None without), read from the two logs -- one device-to-host copy each."""
+        rate and ``accuracies[epoch]`` (None without), read from the two logs -- one device-to-host copy each.  On a
+        guarded optimizer every dict also carries ``"skipped"``, the number of the epoch's iterations the guard
+        rejected, and ``"grad_norm"``, the epoch's last gradient norm."""
         loss, lr = self.loss_log.cpu().tolist(), self.lr_log.cpu().tolist()
+        norm_log, skip_log = self._guard_logs()
+        if norm_log is not None:
+            norm, skip = norm_log.cpu().tolist(), skip_log.cpu().tolist()
         out = []
         for epoch in range(self.num_epochs):
             slot = min(self.epoch_start(epoch + 1) - 1, self.log_len - 1)
             out.append({"epoch": epoch, "loss": loss[slot], "accuracy": accuracies[epoch] if accuracies else None,
                         "learning_rate": lr[slot]})
+            if norm_log is not None:
+                out[-1]["skipped"] = sum(skip[min(self.epoch_start(epoch), self.log_len):slot + 1])
+                out[-1]["grad_norm"] = norm[slot]
         return out
