@@ -12,7 +12,7 @@ from .rnn import (FastGRNNCUDA, FastGRNNCUDACell, FastGRNNFunction,  # noqa: F40
 from .batchnorm import FastGRNNBatchNorm, FastGRNNBatchNormCell, fold_batchnorm  # noqa: F401
 from .batchnorm_train import FastGRNNBatchNormCUDA  # noqa: F401
 from .model import RNNClassifierModel  # noqa: F401
-from .graph import GraphedStep  # noqa: F401
+from .graph import GraphedStep, RunSnapshot  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import (FusedAdadelta, FusedAdagrad, FusedAdam, FusedAdamax, FusedASGD, FusedRMSprop, FusedRprop,  # noqa: F401
                     FusedSGD, configure_optimizer, iht_phase)
@@ -26,7 +26,7 @@ from . import rolling  # noqa: F401
 from .rolling import RollingBags  # noqa: F401
 
 __all__ = ["fastgrnn_cuda", "utils", "head", "FastGRNNCUDA", "FastGRNNCUDACell", "FastGRNNFunction",
-           "FastGRNNUnrollFunction", "KeywordHead", "keyword_loss", "head_predict", "vote_windows", "RNNClassifierModel", "GraphedStep",
+           "FastGRNNUnrollFunction", "KeywordHead", "keyword_loss", "head_predict", "vote_windows", "RNNClassifierModel", "GraphedStep", "RunSnapshot",
            "FastGRNNBatchNorm", "FastGRNNBatchNormCell", "fold_batchnorm", "FastGRNNBatchNormCUDA",
            "optim", "FusedAdam", "FusedSGD", "FusedRMSprop", "FusedAdagrad", "FusedAdadelta", "FusedAdamax", "FusedASGD",
            "FusedRprop", "configure_optimizer", "iht_phase", "features", "MFCCFrontend", "mfcc_features",

@@ -386,9 +386,12 @@ class RNNClassifierModel(nn.Module):
         into.  The carried states live in ``bags``, so the validation passes between epochs cannot disturb them.
 
         With ``graph=True`` that body is captured once in a ``GraphedStep`` and replayed; nothing is written from the
-        host between replays, and the run starts from the state the model and the optimizer were in (the capture's
-        warm-up iterations are undone: parameters, buffers, optimizer state, support masks, ``step_t``, the logs and the
-        bags).
+        host between replays, and the run starts from the state the model and the optimizer were in: the capture's
+        warm-up iterations are undone by ``GraphedStep(body, undo=[self, optimizer, schedule, bags])``, each of the four
+        listing in its ``run_tensors()`` what an iteration carries over to the next (parameters and buffers; ``step_t``,
+        support masks, guard state and the rule's state; the logs; the bags).  ``lr_t`` and ``iht_t`` are in no list,
+        ``advance()`` rewrites both every iteration; optimizer state that the warm-up created goes back to what the rule
+        creates it with (``run_reset``).
         ``graph=False`` runs the same body eagerly and gives the same bits.  The run begins at ``optimizer.step_t`` as it
         stands (0 for a fresh optimizer; one sync, before the first iteration) and ends at iteration
         ``num_epochs * ticks`` counted from 0.
@@ -429,9 +432,7 @@ class RNNClassifierModel(nn.Module):
         self.train()
         step = body
         if graph:
-            keep = self._run_state(optimizer, schedule, bags)
-            step = GraphedStep(body)
-            self._restore_run_state(optimizer, keep)
+            step = GraphedStep(body, undo=[self, optimizer, schedule] + ([bags] if bags is not None else []))
         first = int(optimizer.step_t.item())
         accuracies = [None] * schedule.num_epochs
         for s in range(first, schedule.total_iterations):
@@ -441,29 +442,12 @@ class RNNClassifierModel(nn.Module):
                 self.train()
         return schedule.epoch_log(accuracies)
 
-    def _run_state(self, optimizer, schedule, bags=None):
-        """Copies of everything an iteration writes, keyed by the tensor that holds it: parameters, buffers, optimizer
-        state, support masks, the step count, a gradient guard's state, the schedule's logs and a rolling run's bags and
-        states."""
-        held = list(self.parameters()) + list(self.buffers()) + [optimizer.step_t, schedule.loss_log, schedule.lr_log]
-        held += bags.tensors() if bags is not None else []
-        held += [mask for _, mask in optimizer._iht.values()]
-        if optimizer.guarded:                                 # the guard's device state (norm, counters) and its logs
-            held += [optimizer._guard[2]] + list(schedule._guard_logs())
-        for p in optimizer.param_groups[0]["params"]:
-            held += [t for t in optimizer.state.get(p, {}).values() if isinstance(t, torch.Tensor)]
-        return [(t, t.detach().clone()) for t in held]
+    def run_tensors(self):
+        """What a training step carries over to the next here (``kws_amd.graph.RunSnapshot``): parameters and buffers."""
+        return list(self.parameters()) + list(self.buffers())
 
-    def _restore_run_state(self, optimizer, keep):
-        with torch.no_grad():
-            known = {id(t) for t, _ in keep}
-            for t, value in keep:
-                t.copy_(value)
-            for p in optimizer.param_groups[0]["params"]:     # moments created by the warm-up: back to their zeros
-                for t in optimizer.state.get(p, {}).values():
-                    if isinstance(t, torch.Tensor) and id(t) not in known:
-                        t.zero_()
-        self.init_hidden()
+    def run_reset(self, held_ids):
+        self.init_hidden()                                    # (the carried states are results, not tensors kept here)
 
     def loss_windows(self, pool, starts, labels, window=99):
         """``loss()`` on the batch whose utterance ``b`` is the ``window`` consecutive rows of ``pool:[R,F]`` from row

@@ -32,6 +32,7 @@ The masks of the IHT phases belong to the optimizer (``support(param)``), not to
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -41,6 +42,12 @@ from . import _lib
 from .fastgrnn_cuda import _call
 
 IHT_MODES = {"none": _lib.IHT_NONE, "threshold": _lib.IHT_THRESHOLD, "support": _lib.IHT_SUPPORT}
+
+# guard(): the clipping norm, the flags, the 32-byte device state (fastgrnn_guard_state) and the reduction's workspace
+_Guard = collections.namedtuple("_Guard", "max_norm flags state workspace")
+# _segments(): the key it was built for, the ctypes segment array and its length, the tensors it points into (kept
+# alive), the parameters that had a gradient, and the guard call's view of the same gradients (None without a guard)
+_Table = collections.namedtuple("_Table", "key segs n held params guard_segs")
 
 
 def keep_rank(n, s):
@@ -95,8 +102,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._lr_filled = float(self.param_groups[0]["lr"])
         self._iht_filled = 0
         self._iht = {}                                # parameter -> (keep_rank, support mask)
-        self._table = None                            # (key, ctypes segment array, n): rebuilt when an address moves
-        self._guard = None                            # guard(): (max_norm, flags, state, workspace)
+        self._table = None                            # a _Table: rebuilt when an address moves
+        self._guard = None                            # guard(): a _Guard
 
     # ---- what the subclasses say ----------------------------------------------------------------------------------
     def _ranges(self, g):
@@ -160,7 +167,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         state = torch.zeros(4, dtype=torch.int64, device=self._device)          # fastgrnn_guard_state
         n = len(self.param_groups[0]["params"])
         ws = torch.zeros(((8 * n + 255) // 256 * 256) // 8, dtype=torch.float64, device=self._device)
-        self._guard = (max_norm, _lib.GUARD_SKIP_NONFINITE if skip_nonfinite else 0, state, ws)
+        self._guard = _Guard(max_norm, _lib.GUARD_SKIP_NONFINITE if skip_nonfinite else 0, state, ws)
         f32, i32 = state.view(torch.float32), state.view(torch.int32)
         self.grad_norm_t, self.clip_coef_t, self.skip_t = f32[0:1], f32[1:2], i32[2:3]
         self.applied_t, self.skipped_t = state[2:3], state[3:4]
@@ -202,6 +209,35 @@ class _FusedOptimizer(torch.optim.Optimizer):
         left a non-zero."""
         return self._iht[param][1].view(param.shape)
 
+    # ---- what a step carries over to the next (kws_amd.graph.RunSnapshot) ------------------------------------------
+    def _state_tensors(self):
+        """(parameter, key, tensor) of every state tensor the rule reads that exists so far"""
+        keys = [k for _, k in self._slots(self.param_groups[0])]
+        for p in self.param_groups[0]["params"]:
+            st = self.state.get(p) or {}
+            for k in keys:
+                if st.get(k) is not None:
+                    yield p, k, st[k]
+
+    def run_tensors(self):
+        """The tensors from which a step reads what an earlier step wrote: the step count, the support masks, the
+        guard's state and the rule's state tensors as far as they exist.  ``lr_t`` and ``iht_t`` are not among them:
+        ``step()`` keeps host mirrors of both (``_lr_filled``, ``_iht_filled``) that a copy into the device side
+        alone would leave stale, and whoever drives a captured step -- the caller, or a ``TrainSchedule`` -- rewrites
+        both before every step anyway.  (The ``step`` / ``eta`` / ``mu`` entries that ``state_dict()`` leaves in
+        ``state`` are exports for torch's layout; no step reads them.)"""
+        held = [self.step_t] + [mask for _, mask in self._iht.values()]
+        if self._guard is not None:
+            held.append(self._guard.state)
+        return held + [t for _, _, t in self._state_tensors()]
+
+    def run_reset(self, held_ids):
+        """State tensors that are not in the snapshot were created after it: back to what they are created with."""
+        group = self.param_groups[0]
+        for p, key, t in self._state_tensors():
+            if id(t) not in held_ids:
+                t.copy_(self._new_state(p, key, group))
+
     # ---- the step ---------------------------------------------------------------------------------------------------
     def _init_state(self, p):
         st = self.state[p]
@@ -225,8 +261,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
                                    % type(self).__name__)
             key.append((p.data_ptr(), g.data_ptr()) + tuple(id(st.get(k)) for _, k in slots)
                        + (id(self._iht[p][1]) if p in self._iht else 0,))
-        if self._table is not None and self._table[0] == key:
-            return self._table[1], self._table[2]
+        if self._table is not None and self._table.key == key:
+            return self._table.segs, self._table.n
         segs = (self._SEG * max(1, len(ps)))()
         held = []
         for sg, p in zip(segs, ps):
@@ -244,7 +280,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
             for gs, p in zip(gsegs, ps):
                 gs.grad, gs.n = p.grad.data_ptr(), p.numel()
         # (a state tensor created just now changes the key the next call computes: one more rebuild, then hits)
-        self._table = (key, segs, len(ps), held, ps, gsegs)
+        self._table = _Table(key, segs, len(ps), held, ps, gsegs)
         return segs, len(ps)
 
     def add_param_group(self, param_group):
@@ -292,16 +328,17 @@ class _FusedOptimizer(torch.optim.Optimizer):
         entry, count = self._ENTRY, self.step_t
         with torch.cuda.device(self._device):
             if self._guard is not None:
-                max_norm, flags, count, ws = self._guard
+                gd, count = self._guard, self._guard.state
                 _call(_lib.load().fastgrnn_hip_grad_guard, "fastgrnn grad_guard", None, self._device, None,
-                      self._table[5], n, C.c_double(max_norm), flags, count.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+                      self._table.guard_segs, n, C.c_double(gd.max_norm), gd.flags, count.data_ptr(),
+                      gd.workspace.data_ptr(), gd.workspace.numel() * 8)
                 entry += "_guarded"
             _call(getattr(_lib.load(), entry), entry.replace("fastgrnn_hip_", "fastgrnn "), None,
                   self._device, None, C.byref(hy), segs, n, self.lr_t.data_ptr(), count.data_ptr(),
                   self.iht_t.data_ptr(), *self._extra_args())
         # the library wrote through raw pointers: tell torch, so that whatever is keyed on a tensor's version (autograd's
         # saved-tensor check, the eval-mode BatchNorm fold cache) sees the step
-        torch.autograd.graph.increment_version(self._table[4])
+        torch.autograd.graph.increment_version(self._table.params)
         return loss
 
     # ---- checkpoints: torch's layout, plus the masks under a key torch ignores ---------------------------------------
@@ -351,7 +388,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
             g = state_dict.get("guard") or {}
             applied = int(g.get("applied", t))
             skipped = int(g.get("skipped", 0))
-            self._guard[2].zero_()
+            self._guard.state.zero_()
             self.applied_t.fill_(applied)
             self.skipped_t.fill_(skipped)
             self.step_t.fill_(int(state_dict["fused_step"]) if "guard" in state_dict and "fused_step" in state_dict
@@ -557,6 +594,9 @@ class FusedASGD(_FusedOptim):
 
     def _extra_args(self):
         return (self.scalars.data_ptr(),)
+
+    def run_tensors(self):                                   # step t + 1 reads the pair that step t wrote
+        return super().run_tensors() + [self.scalars]
 
     def _hyper(self, g):
         return _lib.OptimHyper(_lib.ASGD, 0, (float(g["lambd"]), float(g["alpha"]), float(g["t0"])),

@@ -59,6 +59,8 @@ class RollingBags:
         """Every tensor an iteration writes here (what a capture's warm-up has to put back)."""
         return self.state + self.bag + self.h0
 
+    run_tensors = tensors                                    # (kws_amd.graph.RunSnapshot's name for it)
+
     def exchange(self):
         """The bag exchange of the iteration that ``optimizer.step_t`` counts as done so far -- ``state`` into the bags at
         the iteration's shuffled rows, ``h0`` out of bag rows ``0 .. B-1``; zero states on an epoch's fresh start,

@@ -214,6 +214,12 @@ class TrainSchedule:
             self.skip_log = torch.zeros(self.log_len, dtype=torch.int32, device=self.device)
         return self.norm_log, self.skip_log
 
+    def run_tensors(self):
+        """The logs, whose slots hold what earlier iterations recorded (``kws_amd.graph.RunSnapshot``); asking for them
+        allocates a guarded optimizer's two, ahead of any capture.  ``index`` and ``where`` are not carried over:
+        ``advance()`` writes them before anything reads them."""
+        return [self.loss_log, self.lr_log] + [t for t in self._guard_logs() if t is not None]
+
     def record(self, loss):
         """``loss_log[slot] = loss`` and ``lr_log[slot] = lr_t`` for the ``slot`` that ``advance`` wrote: two indexed
         copies addressed by the device scalar, no sync, capturable.  On a guarded optimizer also

@@ -322,11 +322,12 @@ def test_run_state_holds_the_guards_tensors():
                                num_classes=12, device=torch.device("cpu"))
     opt = optim.FusedAdam(model.parameters(), capturable=True).guard(1.0)
     sched = TrainSchedule(opt, 64, 8, 3, seed=1)
-    held = {t.data_ptr() for t, _ in model._run_state(opt, sched)}
+    from kws_amd import RunSnapshot
+    held = {t.data_ptr() for t, _ in RunSnapshot([model, opt, sched]).held}
     assert {opt._guard[2].data_ptr(), sched.norm_log.data_ptr(), sched.skip_log.data_ptr()} <= held
     plain = optim.FusedAdam(model.parameters(), capturable=True)
-    n_plain = len(model._run_state(plain, TrainSchedule(plain, 64, 8, 3, seed=1)))
-    assert len(model._run_state(opt, sched)) == n_plain + 3
+    n_plain = len(RunSnapshot([model, plain, TrainSchedule(plain, 64, 8, 3, seed=1)]).held)
+    assert len(RunSnapshot([model, opt, sched]).held) == n_plain + 3
 
 
 # ---- static scans of kernels_guard.hip ---------------------------------------------------------------------------------

@@ -283,13 +283,7 @@ def test_train_step_audio_equals_train_step_on_the_materialised_audio():
         fused_step(model, opt)
     # three replays of one captured step equal the three eager steps
     g_opt = FusedAdam(third.parameters(), lr=0.01, capturable=True)
-    graphed = GraphedStep(lambda: fused_step(third, g_opt))
-    with torch.no_grad():                                                         # undo the warm-up steps
-        for p, p0 in zip(third.parameters(), start):
-            p.copy_(p0)
-            g_opt.state[p]["exp_avg"].zero_()
-            g_opt.state[p]["exp_avg_sq"].zero_()
-        g_opt.step_t.zero_()
+    graphed = GraphedStep(lambda: fused_step(third, g_opt), undo=(third, g_opt))
     for _ in range(3):
         graphed()
     torch.cuda.synchronize()

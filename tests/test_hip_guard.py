@@ -409,7 +409,6 @@ def batch(k):
 def test_one_captured_train_step_rejects_a_nan_batch_and_goes_on():
     model = small_model()
     eager = copy.deepcopy(model)
-    start = [p.detach().clone() for p in model.parameters()]
     opt = FusedAdam(model.parameters(), lr=0.01, weight_decay=1e-5, capturable=True).guard(max_grad_norm=5.0)
     e_opt = FusedAdam(eager.parameters(), lr=0.01, weight_decay=1e-5).guard(max_grad_norm=5.0)
     x, y = (t.clone() for t in batch(0))
@@ -418,14 +417,7 @@ def test_one_captured_train_step_rejects_a_nan_batch_and_goes_on():
         model.init_hidden()
         return model.train_step(x, y, opt, iht=None)
 
-    step = GraphedStep(fn)
-    with torch.no_grad():                                                  # undo the warm-up
-        for p, p0 in zip(model.parameters(), start):
-            p.copy_(p0)
-            opt.state[p]["exp_avg"].zero_()
-            opt.state[p]["exp_avg_sq"].zero_()
-        opt.step_t.zero_()
-        opt._guard[2].zero_()
+    step = GraphedStep(fn, undo=(model, opt))
     for k in range(1, 7):
         xb, yb = batch(k)
         x.copy_(xb)

@@ -9,6 +9,7 @@ exact.
 """
 import copy
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -354,15 +355,15 @@ def test_train_step_against_torch_optim_and_sparsify(rule):
 
 
 # ---- 5. one graph for the run -------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rule", ("rmsprop_centered_mom", "adagrad_decay", "asgd_avg"))
+@pytest.mark.parametrize("rule", ("rmsprop_centered_mom", "adagrad_decay", "asgd_avg", "rprop"))
 def test_one_captured_graph_serves_changing_lr_and_iht_phase(rule):
     """Adagrad's decayed rate follows step_t; ASGD's eta and mu are carried from replay to replay through both pairs of
-    the double buffer (four steps: both parities read and written, mu below one at the fourth)."""
+    the double buffer (four steps: both parities read and written, mu below one at the fourth); Rprop's step sizes
+    start at the constructor's lr, which is the plan's first, on both sides."""
     plan = [("none", 0.01), ("threshold", 0.004), ("support", 0.02), ("support", 0.007)]
     k, h = OC.kind(rule), OC.hyper(rule, 1e-5)
     model = default_model(5)
     eager = copy.deepcopy(model)
-    start = [p.detach().clone() for p in model.parameters()]
     x, y = batch(5)
 
     e_opt = fused_class(rule)(eager.parameters(), **h)
@@ -380,18 +381,9 @@ def test_one_captured_graph_serves_changing_lr_and_iht_phase(rule):
         model.init_hidden()
         return model.train_step(x, y, opt, iht=None)
 
-    step = GraphedStep(fn)
-    with torch.no_grad():
-        for p, p0 in zip(model.parameters(), start):
-            p.copy_(p0)
-            for key in OC.keys(rule):
-                opt.state[p][key].zero_()
-        for rnn in model.rnn_list:
-            opt.support(rnn.W).fill_(1)
-            opt.support(rnn.U).fill_(1)
-        opt.step_t.zero_()
-        if k == "ASGD":
-            opt.scalars.fill_(777.0)                                       # (step 1 reads neither pair)
+    step = GraphedStep(fn, undo=(model, opt))
+    if k == "ASGD":
+        opt.scalars.fill_(777.0)                                           # (step 1 reads neither pair)
     for iht, lr in plan:
         opt.lr_t.fill_(lr)
         opt.iht_t.fill_(optim.IHT_MODES[iht])
@@ -422,7 +414,9 @@ def test_one_captured_graph_serves_changing_lr_and_iht_phase(rule):
 N_CLIPS, L_MAX, BATCH, NUM_EPOCHS, TRIM, SEED = 16, 4000, 8, 3, 2, (0xC0FFEE << 32) | 0x1234
 
 
-def test_fit_audio_with_rmsprop_from_one_graph_equals_the_eager_loop():
+@functools.lru_cache(maxsize=None)
+def audio_run():
+    """the bank, the augmenter, the front end and the start model of the fit_audio tests: built once, only read"""
     rng = np.random.default_rng(11)
     lengths = rng.integers(1280, L_MAX + 1, N_CLIPS).astype(np.int32)
     lengths[:2] = (1280, L_MAX)
@@ -438,6 +432,11 @@ def test_fit_audio_with_rmsprop_from_one_graph_equals_the_eager_loop():
     torch.manual_seed(5)
     start = RNNClassifierModel("FastGRNNCUDA", 32, 1, [128], [None], [None], [0.5], [0.5], "sigmoid", "tanh",
                                num_classes=12, device=DEV)
+    return bank, lengths, labels, fe, aug, start
+
+
+def test_fit_audio_with_rmsprop_from_one_graph_equals_the_eager_loop():
+    bank, lengths, labels, fe, aug, start = audio_run()
 
     def trainer():
         model = copy.deepcopy(start)
@@ -464,6 +463,63 @@ def test_fit_audio_with_rmsprop_from_one_graph_equals_the_eager_loop():
         S.assert_same_bits(go.support(pa), eo.support(pb), "a support mask")
         kept = int((pa != 0).sum())                                        # the middle third thresholded, the last kept it
         assert kept <= int(go.support(pa).sum()) < pa.numel() and 0.45 * pa.numel() < kept < 0.55 * pa.numel()
+
+
+def fit_trainer(cls, **h):
+    model = copy.deepcopy(audio_run()[5])
+    opt = cls(model.parameters(), capturable=True, **h)
+    assert opt.register_iht(model) == 2
+    sched = TrainSchedule(opt, N_CLIPS, BATCH, NUM_EPOCHS, seed=SEED, lr_scheduler="StepLR", gamma=0.5, lr_step_size=2,
+                          sparsify=True, trim_level=TRIM)
+    assert (sched.ticks, sched.total_iterations) == (2, 6)
+    return model, opt, sched
+
+
+def assert_same_run(graphed, eager, keys):
+    (gm, go, gs), (em, eo, es) = graphed, eager
+    assert int(go.step_t) == int(eo.step_t) == 6
+    for (name, p), q in zip(gm.named_parameters(), em.parameters()):
+        S.assert_same_bits(p.detach(), q.detach(), name)
+        for key in keys:
+            S.assert_same_bits(go.state[p][key], eo.state[q][key], "%s of %s" % (key, name))
+    S.assert_same_bits(gs.loss_log, es.loss_log, "loss_log")
+    S.assert_same_bits(gs.lr_log, es.lr_log, "lr_log")
+    assert all(np.isfinite(gs.loss_log.tolist())) and len(set(gs.loss_log.tolist())) == 6
+    for pa, pb in ((gm.rnn_list[0].W, em.rnn_list[0].W), (gm.rnn_list[0].U, em.rnn_list[0].U)):
+        S.assert_same_bits(go.support(pa), eo.support(pb), "a support mask")
+
+
+def test_fit_audio_with_rprop_from_one_graph_equals_the_eager_loop():
+    """The warm-up creates Rprop's state; undone, step_size is the lr again (not zero) when the first replay reads it."""
+    bank, lengths, labels, fe, aug, _ = audio_run()
+    h = OC.hyper("rprop", 0.0)
+    graphed, eager = fit_trainer(optim.FusedRprop, **h), fit_trainer(optim.FusedRprop, **h)
+    graphed[0].fit_audio(bank, lengths, labels, fe, aug, graphed[1], graphed[2], graph=True)
+    eager[0].fit_audio(bank, lengths, labels, fe, aug, eager[1], eager[2], graph=False)
+    assert_same_run(graphed, eager, ("prev", "step_size"))
+    sizes = torch.cat([graphed[1].state[p]["step_size"].reshape(-1) for p in graphed[0].parameters()])
+    assert float(sizes.min()) < h["lr"] < float(sizes.max())                # (they adapted both ways from the lr)
+
+
+def test_fit_audio_with_asgd_resumed_at_step_three_from_one_graph_equals_the_eager_loop():
+    """A run that begins at step_t = 3: step 4 reads the pair of eta and mu that step 3 left, which the capture's
+    warm-up (steps 4, 5 and 6) overwrites at step 5 -- the undo has to put the double buffer back."""
+    bank, lengths, labels, fe, aug, _ = audio_run()
+    h = OC.hyper("asgd_avg", 1e-5)
+    graphed, eager = fit_trainer(optim.FusedASGD, **h), fit_trainer(optim.FusedASGD, **h)
+    eager[0].fit_audio(bank, lengths, labels, fe, aug, eager[1], eager[2], graph=False)
+    model, opt, sched = graphed
+    model.train()
+    for _ in range(3):
+        model.init_hidden()
+        sched.advance()
+        sched.record(model.train_step_audio(bank, lengths, labels, sched.index, fe, aug, opt, iht=None))
+    assert int(opt.step_t) == 3
+    model.fit_audio(bank, lengths, labels, fe, aug, opt, sched, graph=True)
+    assert_same_run(graphed, eager, ("ax",))
+    S.assert_same_bits(opt.scalars, eager[1].scalars, "scalars")
+    eta, mu = opt.scalars[:2].tolist()                                      # the pair of step 6
+    assert 0.0 < eta < OC.f32(h["lr"]) and mu == OC.f32(1 / 5)              # (both moved: t0 = 1)
 
 
 # ---- 7. versions --------------------------------------------------------------------------------------------------------

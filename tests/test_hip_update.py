@@ -393,7 +393,6 @@ def test_one_captured_graph_serves_changing_lr_and_iht_phase():
     plan = [("none", 0.01), ("threshold", 0.004), ("support", 0.02)]
     model = default_model(5)
     eager = copy.deepcopy(model)
-    start = [p.detach().clone() for p in model.parameters()]
     x, y = batch(5)
 
     # three eager steps
@@ -412,16 +411,7 @@ def test_one_captured_graph_serves_changing_lr_and_iht_phase():
         model.init_hidden()
         return model.train_step(x, y, opt, iht=None)
 
-    step = GraphedStep(fn)
-    with torch.no_grad():
-        for p, p0 in zip(model.parameters(), start):
-            p.copy_(p0)
-            opt.state[p]["exp_avg"].zero_()
-            opt.state[p]["exp_avg_sq"].zero_()
-        for rnn in model.rnn_list:
-            opt.support(rnn.W).fill_(1)
-            opt.support(rnn.U).fill_(1)
-        opt.step_t.zero_()
+    step = GraphedStep(fn, undo=(model, opt))
     for iht, lr in plan:
         opt.lr_t.fill_(lr)
         opt.iht_t.fill_(optim.IHT_MODES[iht])
