@@ -757,6 +757,51 @@ int fastgrnn_hip_mfcc_augment(const fastgrnn_mfcc_desc *d, const fastgrnn_mfcc_b
                               const fastgrnn_mfcc_aug *aug, const void *tables, const float *mean, const float *std,
                               void *feats, void *workspace, size_t workspace_bytes, void *stream);
 
+/* mfcc_stream -- mfcc for the detector's overlapping clips of ONE recording, with every frame of the recording taken
+ * through the DFT and the mel projection once instead of once per clip that contains it.  Clip b is samples
+ * b hop .. b hop + 15999 of the recording (audio: N elements, fp32 or int16, no alignment beyond the element's), and
+ * its features are DEFINED as fastgrnn_hip_mfcc's with L = 16000, no lengths and clip_stride = hop; there are
+ * (N - 16000) / hop + 1 clips.  hop is a multiple of 160, so clip b starts at frame kb = b hop / 160 of the recording:
+ * its frame r is the recording's frame g = kb + r, samples 160 g - 200 .. 160 g + 199.  Frames 2..98 lie wholly inside
+ * the clip -- their power spectrum and mel projection (steps 2-4) do not depend on the clip -- and frames 0, 1, 99, 100
+ * see the clip's zero padding.  Two calls share a workspace of fastgrnn_hip_mfcc_stream_workspace_bytes(d) bytes
+ * (a function of N alone; its layout is the library's business):
+ *   mfcc_stream_frames, once per recording: the mel power (step 4, 128 fp32, before the dB) of every frame
+ *     g = 0 .. N / 160 of the recording, zeros standing in for samples outside it, and the block maxima
+ *     max|y[160 j .. 160 j + 159]|.  It reads and checks N, hop and audio_dtype; clip0, B, the feature settings and
+ *     flags are ignored, so one call serves every mfcc_stream_clips on that recording.
+ *   mfcc_stream_clips: clips clip0 .. clip0 + B - 1 into feats [B, max_len, F] fp32, contiguous and fully written, a
+ *     frame pool exactly as mfcc leaves it: interior frames from the workspace, the four edge frames from the clip's own
+ *     zero-padded samples, then steps 5-10.  A long recording is scored in bounded memory: frames once, clips in chunks.
+ * Without FASTGRNN_MFCC_PEAK_NORMALIZE feats equals fastgrnn_hip_mfcc's BIT FOR BIT: every row of the three products is
+ * the same k-ordered chain on the same operands, whichever workgroup computes it.  With the flag: m = max|y| over the
+ * clip = the maximum of its 100 block maxima (exact, hence mfcc's m bit for bit); the edge frames are computed on
+ * y / m as in mfcc; an interior frame's mel power is the recording's M scaled to fl(fl(M s) s), s = fl(1 / m), before
+ * the 1e-10 floor of step 5; m == 0 leaves the clip unscaled.  The result differs from mfcc's by these fp32 roundings
+ * only.  A clip's rows depend on the clip's own samples only.  Both calls: one launch on `stream`, no allocation, no
+ * host decision on device data, no atomics -- capturable and repeatable bit for bit.
+ * Errors, all before any launch: FASTGRNN_ERR_NULL_POINTER: d, audio, tables, workspace (clips: feats, exactly one of
+ * mean / std);  FASTGRNN_ERR_BAD_SHAPE: N, hop, B, max_len or n_mfcc < 1, clip0 < 0, clip0 + B beyond the clip count,
+ * top_db NaN, size overflow;  FASTGRNN_ERR_BAD_DTYPE: audio_dtype;  FASTGRNN_ERR_UNSUPPORTED: hop not a multiple of
+ * 160, N < 16000 or N >= 2^31, n_mfcc / order / width / flags outside what mfcc takes;  FASTGRNN_ERR_WORKSPACE: fewer
+ * bytes than the query answers, or a pointer not 256-byte aligned. */
+typedef struct fastgrnn_mfcc_stream_desc {
+  int64_t N;            /* elements of the recording, 16000 <= N < 2^31 */
+  int32_t hop;          /* samples between clip starts: a multiple of 160, >= 160 */
+  int32_t audio_dtype;  /* FASTGRNN_MFCC_AUDIO_F32 / _I16 */
+  int32_t clip0, B;     /* this call featurises clips clip0 .. clip0+B-1 of (N-16000)/hop + 1 */
+  int32_t n_mfcc, order, width, max_len;
+  float top_db;
+  uint32_t flags;       /* 0 or FASTGRNN_MFCC_PEAK_NORMALIZE */
+} fastgrnn_mfcc_stream_desc;
+
+size_t fastgrnn_hip_mfcc_stream_workspace_bytes(const fastgrnn_mfcc_stream_desc *d);
+int fastgrnn_hip_mfcc_stream_frames(const fastgrnn_mfcc_stream_desc *d, const void *audio, const void *tables,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+int fastgrnn_hip_mfcc_stream_clips(const fastgrnn_mfcc_stream_desc *d, const void *audio, const void *tables,
+                                   void *workspace, size_t workspace_bytes, const float *mean, const float *std,
+                                   void *feats, void *stream);
+
 /* augment_draw -- the records of mfcc_augment from a counter-based generator, in one small launch: nothing is drawn on
  * the host, and a graph captured once draws new augmentations on every replay as step advances.  seed is a HOST value;
  * step[1] (int64) is a DEVICE scalar that is only read, like train_update's; index: [B] int32 on the device, copied to

@@ -17,7 +17,7 @@ from . import optim  # noqa: F401
 from .optim import (FusedAdadelta, FusedAdagrad, FusedAdam, FusedAdamax, FusedASGD, FusedRMSprop, FusedRprop,  # noqa: F401
                     FusedSGD, configure_optimizer, iht_phase)
 from . import features  # noqa: F401
-from .features import MFCCFrontend, mfcc_features  # noqa: F401
+from .features import MFCCFrontend, mfcc_features, mfcc_stream_features  # noqa: F401
 from . import augment  # noqa: F401
 from .augment import AudioAugment, pack_augment, unpack_augment  # noqa: F401
 from . import schedule  # noqa: F401
@@ -29,6 +29,6 @@ __all__ = ["fastgrnn_cuda", "utils", "head", "FastGRNNCUDA", "FastGRNNCUDACell",
            "FastGRNNUnrollFunction", "KeywordHead", "keyword_loss", "head_predict", "vote_windows", "RNNClassifierModel", "GraphedStep", "RunSnapshot",
            "FastGRNNBatchNorm", "FastGRNNBatchNormCell", "fold_batchnorm", "FastGRNNBatchNormCUDA",
            "optim", "FusedAdam", "FusedSGD", "FusedRMSprop", "FusedAdagrad", "FusedAdadelta", "FusedAdamax", "FusedASGD",
-           "FusedRprop", "configure_optimizer", "iht_phase", "features", "MFCCFrontend", "mfcc_features",
+           "FusedRprop", "configure_optimizer", "iht_phase", "features", "MFCCFrontend", "mfcc_features", "mfcc_stream_features",
            "augment", "AudioAugment", "pack_augment", "unpack_augment", "schedule", "TrainSchedule",
            "rolling", "RollingBags"]

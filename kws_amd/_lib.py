@@ -55,6 +55,7 @@ EXPORTS = (
     "fastgrnn_hip_train_update", "fastgrnn_hip_optim_update",
     "fastgrnn_hip_mfcc_tables_bytes", "fastgrnn_hip_mfcc_init_tables", "fastgrnn_hip_mfcc_workspace_bytes",
     "fastgrnn_hip_mfcc", "fastgrnn_hip_mfcc_augment", "fastgrnn_hip_augment_draw", "fastgrnn_hip_train_schedule",
+    "fastgrnn_hip_mfcc_stream_workspace_bytes", "fastgrnn_hip_mfcc_stream_frames", "fastgrnn_hip_mfcc_stream_clips",
     "fastgrnn_hip_train_schedule_rolling", "fastgrnn_hip_rolling_exchange",
     "fastgrnn_hip_grad_guard_workspace_bytes", "fastgrnn_hip_grad_guard", "fastgrnn_hip_train_update_guarded",
     "fastgrnn_hip_optim_update_guarded",
@@ -164,6 +165,16 @@ MFCC_MIN_SAMPLES, MFCC_MAX_SAMPLES = 1280, 16000     # the clip lengths fastgrnn
 class MfccDesc(C.Structure):
     """fastgrnn_mfcc_desc."""
     _fields_ = [("B", C.c_int32), ("L", C.c_int32), ("clip_stride", C.c_int64), ("audio_dtype", C.c_int32),
+                ("n_mfcc", C.c_int32), ("order", C.c_int32), ("width", C.c_int32), ("max_len", C.c_int32),
+                ("top_db", C.c_float), ("flags", C.c_uint32)]
+
+
+MFCC_STREAM_CLIP, MFCC_STREAM_HOP_UNIT = 16000, 160     # fastgrnn_hip_mfcc_stream_*: the clip length, what a hop is a multiple of
+
+
+class MfccStreamDesc(C.Structure):
+    """fastgrnn_mfcc_stream_desc."""
+    _fields_ = [("N", C.c_int64), ("hop", C.c_int32), ("audio_dtype", C.c_int32), ("clip0", C.c_int32), ("B", C.c_int32),
                 ("n_mfcc", C.c_int32), ("order", C.c_int32), ("width", C.c_int32), ("max_len", C.c_int32),
                 ("top_db", C.c_float), ("flags", C.c_uint32)]
 
@@ -290,6 +301,13 @@ def load():
     lib.fastgrnn_hip_mfcc.argtypes = [MD, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.fastgrnn_hip_mfcc_augment.restype = i32
     lib.fastgrnn_hip_mfcc_augment.argtypes = [MD, C.POINTER(MfccBank), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    SD = C.POINTER(MfccStreamDesc)
+    lib.fastgrnn_hip_mfcc_stream_workspace_bytes.restype = sz
+    lib.fastgrnn_hip_mfcc_stream_workspace_bytes.argtypes = [SD]
+    lib.fastgrnn_hip_mfcc_stream_frames.restype = i32
+    lib.fastgrnn_hip_mfcc_stream_frames.argtypes = [SD, vp, vp, vp, sz, vp]
+    lib.fastgrnn_hip_mfcc_stream_clips.restype = i32
+    lib.fastgrnn_hip_mfcc_stream_clips.argtypes = [SD, vp, vp, vp, sz, vp, vp, vp, vp]
     lib.fastgrnn_hip_augment_draw.restype = i32
     lib.fastgrnn_hip_augment_draw.argtypes = [C.c_int32, C.c_uint64, vp, vp, C.POINTER(AugmentRanges), C.c_int32,
                                               C.c_int32, vp, vp, vp]

@@ -628,6 +628,70 @@ int fastgrnn_hip_mfcc(const fastgrnn_mfcc_desc* d, const void* audio, const int3
   return mfcc_run(*d, audio, lengths, tables, mean, std, feats, reinterpret_cast<hipStream_t>(stream));
 }
 
+// FASTGRNN_OK or the refusal of what the streamed featuriser reads of the recording itself: all the frames call reads
+static int check_stream_recording(const fastgrnn_mfcc_stream_desc* d) {
+  if (!d) return FASTGRNN_ERR_NULL_POINTER;
+  if (d->N < 1 || d->hop < 1) return FASTGRNN_ERR_BAD_SHAPE;
+  if (d->audio_dtype != FASTGRNN_MFCC_AUDIO_F32 && d->audio_dtype != FASTGRNN_MFCC_AUDIO_I16) return FASTGRNN_ERR_BAD_DTYPE;
+  if (d->hop % 160 || d->N < 16000 || d->N >= 2147483648ll) return FASTGRNN_ERR_UNSUPPORTED;
+  return FASTGRNN_OK;
+}
+
+// ... and of the clips and the feature settings: a clip of the streamed call is a clip of fastgrnn_hip_mfcc with
+// L = 16000 and clip_stride = hop, so the settings go through that call's own check
+static int check_stream_clips(const fastgrnn_mfcc_stream_desc* d) {
+  if (!d) return FASTGRNN_ERR_NULL_POINTER;
+  if (d->N < 1 || d->hop < 1 || d->B < 1 || d->clip0 < 0) return FASTGRNN_ERR_BAD_SHAPE;
+  fastgrnn_mfcc_desc m;
+  m.B = d->B;
+  m.L = 16000;
+  m.clip_stride = d->hop;
+  m.audio_dtype = d->audio_dtype;
+  m.n_mfcc = d->n_mfcc;
+  m.order = d->order;
+  m.width = d->width;
+  m.max_len = d->max_len;
+  m.top_db = d->top_db;
+  m.flags = d->flags;
+  int st = check_mfcc_desc(&m);
+  if (st == FASTGRNN_ERR_BAD_SHAPE || st == FASTGRNN_ERR_BAD_DTYPE) return st;
+  const int rec = check_stream_recording(d);
+  if (rec) return rec;
+  if (st) return st;
+  if ((int64_t)d->clip0 + d->B > (d->N - 16000) / d->hop + 1) return FASTGRNN_ERR_BAD_SHAPE;
+  return FASTGRNN_OK;
+}
+
+size_t fastgrnn_hip_mfcc_stream_workspace_bytes(const fastgrnn_mfcc_stream_desc* d) {
+  return check_stream_recording(d) ? 0 : mfcc_stream_ws_bytes(*d);
+}
+
+// (a NULL workspace is refused before this as a missing operand: the two calls exist to share one)
+static int check_stream_ws(const fastgrnn_mfcc_stream_desc* d, void* workspace, size_t workspace_bytes) {
+  if (workspace_bytes < mfcc_stream_ws_bytes(*d) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+    return FASTGRNN_ERR_WORKSPACE;
+  return FASTGRNN_OK;
+}
+
+int fastgrnn_hip_mfcc_stream_frames(const fastgrnn_mfcc_stream_desc* d, const void* audio, const void* tables,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  int st = check_stream_recording(d);
+  if (st) return st;
+  if (!audio || !tables || !workspace) return FASTGRNN_ERR_NULL_POINTER;
+  if ((st = check_stream_ws(d, workspace, workspace_bytes))) return st;
+  return mfcc_stream_frames_run(*d, audio, tables, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int fastgrnn_hip_mfcc_stream_clips(const fastgrnn_mfcc_stream_desc* d, const void* audio, const void* tables,
+                                   void* workspace, size_t workspace_bytes, const float* mean, const float* std,
+                                   void* feats, void* stream) {
+  int st = check_stream_clips(d);
+  if (st) return st;
+  if (!audio || !tables || !workspace || !feats || (!mean != !std)) return FASTGRNN_ERR_NULL_POINTER;
+  if ((st = check_stream_ws(d, workspace, workspace_bytes))) return st;
+  return mfcc_stream_clips_run(*d, audio, tables, workspace, mean, std, feats, reinterpret_cast<hipStream_t>(stream));
+}
+
 // the noise bank's sizes, as both augmentation calls read them
 static int check_noise_bank(int32_t n_noise, int32_t noise_len_max, const int32_t* noise_lengths) {
   if (n_noise < 0) return FASTGRNN_ERR_BAD_SHAPE;

@@ -223,6 +223,12 @@ size_t mfcc_tables_bytes();
 int mfcc_init_tables(void* tables, hipStream_t s);
 int mfcc_run(const fastgrnn_mfcc_desc& d, const void* audio, const int32_t* lengths, const void* tables, const float* mean,
              const float* stdv, void* feats, hipStream_t s);
+// ... for the overlapping clips of one recording, its frames computed once (kernels_mfcc_stream.hip)
+size_t mfcc_stream_ws_bytes(const fastgrnn_mfcc_stream_desc& d);
+int mfcc_stream_frames_run(const fastgrnn_mfcc_stream_desc& d, const void* audio, const void* tables, void* ws,
+                           hipStream_t s);
+int mfcc_stream_clips_run(const fastgrnn_mfcc_stream_desc& d, const void* audio, const void* tables, void* ws,
+                          const float* mean, const float* stdv, void* feats, hipStream_t s);
 // ... reading an audio bank through augmentation records, and the records' draw (kernels_augment.hip)
 int mfcc_augment_run(const fastgrnn_mfcc_desc& d, const fastgrnn_mfcc_bank& bank, const void* audio, const int32_t* lengths,
                      const void* noise, const int32_t* noise_lengths, const fastgrnn_mfcc_aug* aug, const void* tables,

@@ -2,7 +2,8 @@
 // kernels_augment.hip (mfcc_aug_k: a clip of an audio bank read through an augmentation record).  One template with a
 // compile-time AUG switch around stage a; stages b-e are the same code for both.  The semantics are spelled out in
 // include/fastgrnn_hip.h (fastgrnn_hip_mfcc, fastgrnn_hip_mfcc_augment); the stages and the rules they keep are
-// described at the top of kernels_mfcc.hip.
+// described at the top of kernels_mfcc.hip.  Stages b-e are functions of their own: kernels_mfcc_stream.hip (a
+// recording's frames computed once for its overlapping clips) runs them on other row tiles around a stage a of its own.
 #pragma once
 #include "common.h"
 
@@ -79,6 +80,144 @@ __device__ __forceinline__ float add_rn(float a, float b) {
 }
 
 constexpr int MF_AUG_SHIFT_CAP = 1 << 20;        // |shift| >= 16 000 already empties a clip: the cap changes no sample
+
+// ---- stages b-e, shared by mfcc_body and the streamed kernels (kernels_mfcc_stream.hip).  Every output row of the
+// three products is a k-ordered chain of its own: which row tile, wave or workgroup computes a row does not change it.
+
+// b. power spectrum: [16 NRT rows] x [16 bins of this wave], cos and sin tiles side by side.  arow[rt]: the LDS word of
+// sample lk of the frame in row 16 rt + lr of the skewed audio image; the power goes to s_pow[16 rt + ..][MF_PS].
+template <int NRT>
+__device__ __forceinline__ void mfcc_power(const float* s_aud, float* s_pow, const float* tab, const int (&arow)[NRT],
+                                           int wave, int lr, int lk) {
+  f32x4 ac[NRT], as[NRT];
+#pragma unroll
+  for (int rt = 0; rt < NRT; ++rt) {
+    ac[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    as[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const float* bc = tab + TB_COS + (size_t)lk * MF_BINP + 16 * wave + lr;
+  const float* bs = tab + TB_SIN + (size_t)lk * MF_BINP + 16 * wave + lr;
+  for (int k0 = 0; k0 < MF_NFFT; k0 += 16) {
+    const int ks = k0 + (k0 >= MF_HOP ? MF_SKEW : 0) + (k0 >= 2 * MF_HOP ? MF_SKEW : 0);   // (a batch never straddles a hop)
+    float fa[4][NRT], fc[4], fs[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      fc[u] = bc[(size_t)(k0 + 4 * u) * MF_BINP];
+      fs[u] = bs[(size_t)(k0 + 4 * u) * MF_BINP];
+#pragma unroll
+      for (int rt = 0; rt < NRT; ++rt) fa[u][rt] = s_aud[arow[rt] + ks + 4 * u];
+    }
+    __builtin_amdgcn_sched_barrier(0);          // every operand request of the batch in front of its first MFMA
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+      for (int rt = 0; rt < NRT; ++rt) {
+        ac[rt] = mfma4(fa[u][rt], fc[u], ac[rt]);
+        as[rt] = mfma4(fa[u][rt], fs[u], as[rt]);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    completion_read(as[NRT - 1][0]);            // the youngest accumulator: the batch's registers are free again
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int rt = 0; rt < NRT; ++rt) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      s_pow[(16 * rt + 4 * lk + e) * MF_PS + 16 * wave + lr] = fmaf(ac[rt][e], ac[rt][e], as[rt][e] * as[rt][e]);
+  }
+}
+
+// c. mel projection of NT row tiles against mel columns 16 ct..: prow[i] is the LDS word of bin lk of row lr of tile i
+template <int NT>
+__device__ __forceinline__ void mfcc_mel(const float* s_pow, const float* tab, const int (&prow)[NT], int ct, int lr, int lk,
+                                         f32x4 (&acc)[NT]) {
+#pragma unroll
+  for (int i = 0; i < NT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float* bw = tab + TB_MEL + (size_t)lk * MF_MELS + 16 * ct + lr;
+  for (int k0 = 0; k0 < MF_BINP; k0 += 16) {
+    float fa[4][NT], fb[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      fb[u] = bw[(size_t)(k0 + 4 * u) * MF_MELS];
+#pragma unroll
+      for (int i = 0; i < NT; ++i) fa[u][i] = s_pow[prow[i] + k0 + 4 * u];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+      for (int i = 0; i < NT; ++i) acc[i] = mfma4(fa[u][i], fb[u], acc[i]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    completion_read(acc[NT - 1][0]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+__device__ __forceinline__ float mfcc_db(float mel) { return 10.0f * log10f(fmaxf(1e-10f, mel)); }
+
+// d. DCT-II of the dB image [112][MF_DS] into the coefficient image [112][MF_CS], the top_db clip applied to the A
+// operands on the way in: wave w owns coefficient columns 16 (w & 3).. and row tiles w >> 2, (w >> 2) + 4
+__device__ __forceinline__ void mfcc_dct(const float* s_db, float* s_coef, const float* tab, float floor_db, int wave,
+                                         int lr, int lk) {
+  const int ct = wave & 3, r0 = wave >> 2;
+  f32x4 acc[2];
+  int drow[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    drow[i] = (16 * min(r0 + 4 * i, 6) + lr) * MF_DS + lk;
+  }
+  const float* bd = tab + TB_DCT + (size_t)lk * MF_CMAX + 16 * ct + lr;
+  for (int k0 = 0; k0 < MF_MELS; k0 += 16) {
+    float fa[4][2], fb[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      fb[u] = bd[(size_t)(k0 + 4 * u) * MF_CMAX];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) fa[u][i] = fmaxf(s_db[drow[i] + k0 + 4 * u], floor_db);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) acc[i] = mfma4(fa[u][i], fb[u], acc[i]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    completion_read(acc[1][0]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int rt = r0 + 4 * i;
+    if (rt < 7) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s_coef[(16 * rt + 4 * lk + e) * MF_CS + 16 * ct + lr] = acc[i][e];
+    }
+  }
+}
+
+// e. deltas, pad / cut, normalisation, stores: element i of a clip's [max_len][F] block `out`, from its n frames of
+// coefficients
+__device__ __forceinline__ void mfcc_rows(const float* s_coef, const float* s_tap, int n, int C, int order, int width,
+                                          int max_len, const float* mean, const float* stdv, float* out, int tid) {
+  const int F = C * (order + 1), total = max_len * F, h = width >> 1;
+  const int last = max(n - 1 - h, h);             // (n >= width for every length the caller may pass; in bounds for any)
+  const bool norm = mean != nullptr;
+  for (int i = tid; i < total; i += MF_THREADS) {
+    const int t = i / F, f = i - t * F, o = f / C, c = f - o * C;
+    const int tt = min(t, n - 1);
+    const int tc = min(max(tt, h), last) - h;     // first row under the FIR; the interp edges are constant (deriv == polyorder)
+    float val = s_coef[tt * MF_CS + c], d = 0.f;
+    const float* tap = s_tap + (o == 2 ? 16 : 0);
+    for (int k = 0; k < width; ++k) d = fmaf(tap[k], s_coef[(tc + k) * MF_CS + c], d);
+    val = o == 0 ? val : d;
+    val = t < n ? val : 0.f;
+    if (norm) val = (val - mean[f]) / stdv[f];
+    out[i] = val;
+  }
+}
 
 template <typename AT, bool AUG, typename ARGS>
 __device__ __forceinline__ void mfcc_body(const ARGS& a) {
@@ -173,45 +312,11 @@ __device__ __forceinline__ void mfcc_body(const ARGS& a) {
 
   // ---- b. power spectrum: [112 frames] x [16 bins of this wave], cos and sin tiles side by side
   if (wave < 13) {                                // (wave-uniform, around the whole loop)
-    f32x4 ac[7], as[7];
     int arow[7];
 #pragma unroll
-    for (int rt = 0; rt < 7; ++rt) {
-      ac[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      as[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int rt = 0; rt < 7; ++rt)
       arow[rt] = min(16 * rt + lr, MF_FRAMES - 1) * MF_RS + lk;    // (rows 101..111 repeat frame 100; nothing reads them back)
-    }
-    const float* bc = a.tab + TB_COS + (size_t)lk * MF_BINP + 16 * wave + lr;
-    const float* bs = a.tab + TB_SIN + (size_t)lk * MF_BINP + 16 * wave + lr;
-    for (int k0 = 0; k0 < MF_NFFT; k0 += 16) {
-      const int ks = k0 + (k0 >= MF_HOP ? MF_SKEW : 0) + (k0 >= 2 * MF_HOP ? MF_SKEW : 0);   // (a batch never straddles a hop)
-      float fa[4][7], fc[4], fs[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        fc[u] = bc[(size_t)(k0 + 4 * u) * MF_BINP];
-        fs[u] = bs[(size_t)(k0 + 4 * u) * MF_BINP];
-#pragma unroll
-        for (int rt = 0; rt < 7; ++rt) fa[u][rt] = s_aud[arow[rt] + ks + 4 * u];
-      }
-      __builtin_amdgcn_sched_barrier(0);          // every operand request of the batch in front of its first MFMA
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-#pragma unroll
-        for (int rt = 0; rt < 7; ++rt) {
-          ac[rt] = mfma4(fa[u][rt], fc[u], ac[rt]);
-          as[rt] = mfma4(fa[u][rt], fs[u], as[rt]);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      completion_read(as[6][0]);                  // the youngest accumulator: the batch's registers are free again
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int rt = 0; rt < 7; ++rt) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        s_pow[(16 * rt + 4 * lk + e) * MF_PS + 16 * wave + lr] = fmaf(ac[rt][e], ac[rt][e], as[rt][e] * as[rt][e]);
-    }
+    mfcc_power<7>(s_aud, s_pow, a.tab, arow, wave, lr, lk);
   }
   __syncthreads();
 
@@ -222,29 +327,9 @@ __device__ __forceinline__ void mfcc_body(const ARGS& a) {
     f32x4 acc[4];
     int prow[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 4; ++i)
       prow[i] = (16 * min(r0 + 2 * i, 6) + lr) * MF_PS + lk;      // (a fourth tile of the odd waves repeats tile 6, unstored)
-    }
-    const float* bw = a.tab + TB_MEL + (size_t)lk * MF_MELS + 16 * ct + lr;
-    for (int k0 = 0; k0 < MF_BINP; k0 += 16) {
-      float fa[4][4], fb[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        fb[u] = bw[(size_t)(k0 + 4 * u) * MF_MELS];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa[u][i] = s_pow[prow[i] + k0 + 4 * u];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = mfma4(fa[u][i], fb[u], acc[i]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      completion_read(acc[3][0]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    mfcc_mel<4>(s_pow, a.tab, prow, ct, lr, lk, acc);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int rt = r0 + 2 * i;
@@ -252,7 +337,7 @@ __device__ __forceinline__ void mfcc_body(const ARGS& a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int row = 16 * rt + 4 * lk + e;
-          const float db = 10.0f * log10f(fmaxf(1e-10f, acc[i][e]));
+          const float db = mfcc_db(acc[i][e]);
           s_aud[row * MF_DS + 16 * ct + lr] = db;
           mx = row < n ? fmaxf(mx, db) : mx;
         }
@@ -267,63 +352,14 @@ __device__ __forceinline__ void mfcc_body(const ARGS& a) {
   for (int w = 1; w < 16; ++w) mx = fmaxf(mx, s_red[w]);
   const float floor_db = a.top_db >= 0.f ? mx - a.top_db : -INFINITY;
 
-  // ---- d. DCT-II: wave w owns coefficient columns 16 (w & 3).. and row tiles w >> 2, (w >> 2) + 4
-  {
-    const int ct = wave & 3, r0 = wave >> 2;
-    f32x4 acc[2];
-    int drow[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      drow[i] = (16 * min(r0 + 4 * i, 6) + lr) * MF_DS + lk;
-    }
-    const float* bd = a.tab + TB_DCT + (size_t)lk * MF_CMAX + 16 * ct + lr;
-    for (int k0 = 0; k0 < MF_MELS; k0 += 16) {
-      float fa[4][2], fb[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        fb[u] = bd[(size_t)(k0 + 4 * u) * MF_CMAX];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) fa[u][i] = fmaxf(s_aud[drow[i] + k0 + 4 * u], floor_db);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) acc[i] = mfma4(fa[u][i], fb[u], acc[i]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      completion_read(acc[1][0]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int rt = r0 + 4 * i;
-      if (rt < 7) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s_pow[(16 * rt + 4 * lk + e) * MF_CS + 16 * ct + lr] = acc[i][e];
-      }
-    }
-  }
+  // ---- d. DCT-II: the dB image in s_aud -> the coefficients in s_pow
+  mfcc_dct(s_aud, s_pow, a.tab, floor_db, wave, lr, lk);
   __syncthreads();
 
-  // ---- e. deltas, pad / cut, normalisation, stores: element i of the clip's [max_len][F] block
-  const int C = a.n_mfcc, F = C * (a.order + 1), total = a.max_len * F, h = a.width >> 1;
-  const int last = max(n - 1 - h, h);             // (n >= width for every length the caller may pass; in bounds for any)
-  float* out = a.feats + (size_t)blockIdx.x * (size_t)total;
-  const bool norm = a.mean != nullptr;
-  for (int i = tid; i < total; i += MF_THREADS) {
-    const int t = i / F, f = i - t * F, o = f / C, c = f - o * C;
-    const int tt = min(t, n - 1);
-    const int tc = min(max(tt, h), last) - h;     // first row under the FIR; the interp edges are constant (deriv == polyorder)
-    float val = s_pow[tt * MF_CS + c], d = 0.f;
-    const float* tap = s_tap + (o == 2 ? 16 : 0);
-    for (int k = 0; k < a.width; ++k) d = fmaf(tap[k], s_pow[(tc + k) * MF_CS + c], d);
-    val = o == 0 ? val : d;
-    val = t < n ? val : 0.f;
-    if (norm) val = (val - a.mean[f]) / a.stdv[f];
-    out[i] = val;
-  }
+  // ---- e. deltas, pad / cut, normalisation, stores
+  const int total = a.max_len * a.n_mfcc * (a.order + 1);
+  mfcc_rows(s_pow, s_tap, n, a.n_mfcc, a.order, a.width, a.max_len, a.mean, a.stdv,
+            a.feats + (size_t)blockIdx.x * (size_t)total, tid);
 }
 
 }  // namespace

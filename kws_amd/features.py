@@ -183,6 +183,96 @@ def mfcc_features(audio, lengths=None, *, n_mfcc=32, feature_type="delta", width
     return feats
 
 
+@functools.lru_cache(maxsize=256)
+def _stream_plan(N, hop, audio_dtype, clip0, B, n_mfcc, order, width, max_len, top_db, flags):
+    """``_mfcc_plan`` for the streamed calls: the descriptor and the bytes of the frames workspace (a function of N)."""
+    desc = _lib.MfccStreamDesc(N, hop, audio_dtype, clip0, B, n_mfcc, order, width, max_len, top_db, flags)
+    return desc, int(_lib.load().fastgrnn_hip_mfcc_stream_workspace_bytes(C.byref(desc)))
+
+
+def _check_stream_geometry(N, hop_samples, clip):
+    """The clip count of a recording of ``N`` samples, or the ``ValueError`` that names the broken rule."""
+    hop_samples, clip = int(hop_samples), int(clip)
+    if clip != _lib.MFCC_STREAM_CLIP:
+        raise ValueError("the streamed front end takes clips of exactly %d samples (got %d)" % (_lib.MFCC_STREAM_CLIP, clip))
+    if hop_samples < 1 or hop_samples % _lib.MFCC_STREAM_HOP_UNIT:
+        raise ValueError("the streamed front end takes hops that are a positive multiple of %d samples, the frame hop "
+                         "(got %d)" % (_lib.MFCC_STREAM_HOP_UNIT, hop_samples))
+    if N < clip:
+        raise ValueError("recording of %d samples is shorter than a clip of %d" % (N, clip))
+    if N >= 2 ** 31:
+        raise ValueError("recordings of fewer than 2^31 samples are supported (got %d)" % N)
+    return (N - clip) // hop_samples + 1
+
+
+def mfcc_stream_features(recording, hop_samples=800, *, clip0=0, num_clips=None, frames=None, return_frames=False,
+                         clip=16000, n_mfcc=32, feature_type="delta", width=9, max_len=99, top_db=80.0, mean=None,
+                         std=None, peak_normalize=False, tables=None):
+    """The features of the detector's overlapping clips of ONE 1-D ``recording`` (fp32 samples or int16 PCM on the
+    device, unit stride) -> ``[B, max_len, F]``: what ``mfcc_features(MFCCFrontend.clips_of(recording, hop_samples))``
+    returns for clips ``clip0 .. clip0 + num_clips - 1`` (``num_clips=None``: all from ``clip0`` on), with every 10 ms
+    frame of the recording taken through the DFT and the mel projection once instead of once per clip that contains it
+    (``fastgrnn_hip_mfcc_stream_frames`` / ``_clips``).  Without ``peak_normalize`` the result equals the per-clip
+    call's bit for bit; with it, by fp32 roundings of the interior frames' scaling only.
+
+    ``hop_samples`` is a multiple of 160 and ``clip`` is 16000: anything else is a ``ValueError`` -- there is no
+    fallback to the per-clip call.  ``frames``: the workspace of an earlier call on the same recording
+    (``return_frames=True`` returns ``(feats, frames)``); given it, the frames call is skipped and only the clips are
+    featurised, so a long recording is scored chunk by chunk in bounded memory.  The other settings are
+    ``mfcc_features``'s.  Two launches (one with ``frames``) on the current stream; nothing synchronises."""
+    lib = _lib.load()
+    order = _order_of(feature_type)
+    if not isinstance(recording, torch.Tensor):
+        raise TypeError("recording must be a torch.Tensor")
+    if not recording.is_cuda:
+        raise RuntimeError("recording must be a CUDA tensor")
+    if recording.dim() != 1:
+        raise ValueError("recording must be 1-D (got %d dimensions)" % recording.dim())
+    if recording.dtype not in _AUDIO_DTYPES:
+        raise RuntimeError("recording must be float32 samples or int16 PCM (got %s)" % recording.dtype)
+    N = recording.shape[0]
+    n_mfcc, width, max_len = _check_settings(n_mfcc, order, width, max_len)
+    total = _check_stream_geometry(N, hop_samples, clip)
+    if recording.stride(0) != 1:
+        raise RuntimeError("recording needs unit stride (got %d)" % recording.stride(0))
+    clip0 = int(clip0)
+    B = total - clip0 if num_clips is None else int(num_clips)
+    if clip0 < 0 or B < 1 or clip0 + B > total:
+        raise ValueError("clips %d .. %d lie outside the recording's %d clips" % (clip0, clip0 + B - 1, total))
+    dev = recording.device
+    F = n_mfcc * (order + 1)
+    if (mean is None) != (std is None):
+        raise RuntimeError("mean and std go together")
+    for t, name in ((mean, "mean"), (std, "std")):
+        if t is not None:
+            _check_input(t, name)
+            if t.dtype != torch.float32 or t.numel() != F or t.device != dev:
+                raise RuntimeError("%s must be float32 [%d] on %s" % (name, F, dev))
+    if tables is None:
+        tables = mfcc_tables(dev)
+    elif tables.device != dev or tables.dtype != torch.float32 or tables.numel() * 4 < lib.fastgrnn_hip_mfcc_tables_bytes():
+        raise RuntimeError("tables must be the float32 tensor of mfcc_tables() on %s" % dev)
+    top = -1.0 if top_db is None else float(top_db)
+    flags = _lib.MFCC_PEAK_NORMALIZE if peak_normalize else 0
+    desc, nbytes = _stream_plan(N, int(hop_samples), _AUDIO_DTYPES[recording.dtype], clip0, B, n_mfcc, order, width,
+                                max_len, top, flags)
+    with torch.cuda.device(dev):
+        if frames is None:
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+            _call(lib.fastgrnn_hip_mfcc_stream_frames, "fastgrnn mfcc_stream_frames", "mfcc_stream_frames", dev, None,
+                  C.byref(desc), _ptr(recording), _ptr(tables), _ptr(ws), nbytes)
+        else:
+            ws = frames
+            _check_input(ws, "frames")
+            if ws.dtype != torch.float32 or ws.device != dev or ws.numel() * 4 < nbytes or ws.data_ptr() % 256:
+                raise RuntimeError("frames must be the workspace an earlier call on this recording returned "
+                                   "(float32, %d bytes, on %s)" % (nbytes, dev))
+        feats = torch.empty((B, max_len, F), dtype=torch.float32, device=dev)
+        _call(lib.fastgrnn_hip_mfcc_stream_clips, "fastgrnn mfcc_stream_clips", "mfcc_stream_clips", dev, None,
+              C.byref(desc), _ptr(recording), _ptr(tables), _ptr(ws), nbytes, _ptr(mean), _ptr(std), _ptr(feats))
+    return (feats, ws) if return_frames else feats
+
+
 def _check_augment_operands(augment, noise, noise_lengths, audio):
     """The argument errors of the augmented call; ``(B, n_noise, noise_stride, noise_len_max)``."""
     dev = audio.device
@@ -265,6 +355,22 @@ class MFCCFrontend(nn.Module):
                              max_len=self.max_len, top_db=self.top_db, mean=mean, std=std,
                              peak_normalize=self.peak_normalize, tables=self.tables, augment=augment, noise=noise,
                              noise_lengths=noise_lengths, check=check)
+
+    def stream(self, recording, hop_samples=800, clip=16000, normalize=True, **chunk):
+        """``forward(clips_of(recording, hop_samples, clip))`` with the recording's frames computed once
+        (``mfcc_stream_features`` with this module's settings, normalisation and ``peak_normalize``): ``[B, max_len, F]``
+        for the 1-D ``recording`` on the device.  ``hop_samples`` must be a multiple of 160 and ``clip`` 16000
+        (``ValueError``).  ``chunk``: ``clip0`` / ``num_clips`` / ``frames`` / ``return_frames`` of
+        ``mfcc_stream_features``, to score a long recording piece by piece."""
+        if self.tables is None or self.tables.device != recording.device:
+            self.tables = mfcc_tables(recording.device)
+        use = normalize and self.mean is not None
+        if use and self.mean.device != recording.device:
+            self.mean, self.std = self.mean.to(recording.device), self.std.to(recording.device)
+        mean, std = (self.mean, self.std) if use else (None, None)
+        return mfcc_stream_features(recording, hop_samples, clip=clip, n_mfcc=self.n_mfcc, feature_type=self.feature_type,
+                                    width=self.width, max_len=self.max_len, top_db=self.top_db, mean=mean, std=std,
+                                    peak_normalize=self.peak_normalize, tables=self.tables, **chunk)
 
     @staticmethod
     def clips_of(recording, hop_samples=800, clip=16000):

@@ -208,7 +208,8 @@ class RNNClassifierModel(nn.Module):
         return pred, maj, event
 
     @torch.no_grad()
-    def detect_audio(self, recording, frontend, hop_samples=800, num_windows=10, majority=5, clip=16000):
+    def detect_audio(self, recording, frontend, hop_samples=800, num_windows=10, majority=5, clip=16000,
+                     shared_frames=False):
         """The reference's live loop (inferencetry.py:165-227) end to end on raw audio: every ``hop_samples`` (50 ms)
         the last ``clip`` samples of the 1-D ``recording`` (fp32 or int16 PCM) are peak-normalised and featurised by
         ``frontend`` (a ``kws_amd.MFCCFrontend``; its ``mean`` / ``std`` and ``max_len`` are the model's), the model
@@ -217,15 +218,20 @@ class RNNClassifierModel(nn.Module):
         windowed scans hold the cell (``forward_windows`` with ``starts = arange(B) * max_len``; gathered elsewhere),
         so nothing is copied between the samples and the vote.  Returns what ``detect_stream`` returns for one stream:
         ``(pred, majority, event)``, each ``[1, B]`` int32 on the device, ``B = (N - clip) // hop_samples + 1``.
-        ``hidden_states`` is neither read nor written.  Needs ``linear=True``; BatchNorm models: eval mode only."""
+        ``hidden_states`` is neither read nor written.  Needs ``linear=True``; BatchNorm models: eval mode only.
+        ``shared_frames=True`` featurises through ``frontend.stream``: every 10 ms frame of the recording goes through
+        the DFT and the mel projection once instead of once per clip that contains it (features equal up to the fp32
+        roundings of the peak scaling; everything behind the pool is unchanged).  It needs ``hop_samples`` a multiple
+        of 160 and ``clip == 16000`` and raises ``ValueError`` otherwise: it never falls back to the per-clip path."""
         if not self.linear:
             raise RuntimeError("detect_audio() needs the Linear head (linear=True)")
         if frontend.num_features != self.input_dim:
             raise ValueError("the front end gives %d features, the model takes %d" % (frontend.num_features, self.input_dim))
-        clips = frontend.clips_of(recording.to(self.rnn_list[0].device), hop_samples, clip)
+        recording = recording.to(self.rnn_list[0].device)
+        clips = None if shared_frames else frontend.clips_of(recording, hop_samples, clip)
         peak, frontend.peak_normalize = frontend.peak_normalize, True        # inferencetry.py:172-175
-        try:
-            feats = frontend(clips)                                          # [B, max_len, F]: the frame pool
+        try:                                                                 # [B, max_len, F]: the frame pool
+            feats = frontend.stream(recording, hop_samples, clip) if shared_frames else frontend(clips)
         finally:
             frontend.peak_normalize = peak
         h, B, _ = self._window_states(feats, 1, feats.shape[1])              # (one window per clip: starts = b * max_len)
